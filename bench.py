@@ -11,7 +11,20 @@ strong scaling.  Every transport of that sum is timed back to back -- shared mem
 partials), the in-kernel xGMI peer-write exchange, and RCCL's all-reduce -- and reported under
 config.reduce_variants; NDT_BENCH_REDUCE=shm|p2p|rccl pins one.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step` and
+what the timed steps themselves counted).  Everything measured beside the headline -- the instrumented
+repeat behind `roofline` / `roofline_build` and the build / align split, protocol variants, cadence,
+packed records, host clouds, the other configurations, the scaling probe, the CPU baseline and, with
+N > 1, the per-variant reduce timings -- runs only with --full.
+
+--dump-outputs DIR writes what the LAST timed step computed, as a caller of the step receives it, to
+DIR/<name>.npy (float64; rank 0): final_transformation (4x4), final_pose (6), hessian (6x6), the
+scalars iterations / n_evaluations / converged / score / transform_probability / nvtl / n_pairs
+(one element each), and the voxel grid the step built (leaf_cell, leaf_count, leaf_mean, leaf_cov,
+leaf_icov; rows in ascending voxel index).  The workload is seeded: the same arguments give the same
+inputs in every run.
 
 N > 1 runs either way: launched by `python -m torch.distributed.run --nproc-per-node N ...` (RANK /
 LOCAL_RANK / WORLD_SIZE from the environment), or as a plain `python bench.py --gpus N`, which then
@@ -61,7 +74,33 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="per CPU-baseline thread setting")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (roofline, side blocks, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, res):
+    """Writes the outputs of the last timed step (timed_region(capture=True)) to d/<name>.npy, float64."""
+    os.makedirs(d, exist_ok=True)
+    r, leaves = res["result"], res["leaves"]
+    arrays = {"final_transformation": r["T"], "final_pose": r["pose"], "hessian": r["hessian"]}
+    for k in ("iterations", "n_evaluations", "converged", "score", "transform_probability", "nvtl", "n_pairs"):
+        arrays[k] = np.array([r[k]])
+    grid = {"leaf_" + k: leaves[k] for k in ("cell", "count", "mean", "cov", "icov")}
+    n = len(grid["leaf_cell"])
+    row_bytes = sum(8 * a[0].size for a in grid.values()) if n else 0
+    if n * row_bytes > DUMP_LIMIT_BYTES // 2:
+        # (a fixed, seeded sample of the leaves keeps the files under the limit; C3 itself is ~2e4 leaves, 4 MB)
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // 2 // row_bytes, replace=False))
+        grid = {k: a[keep] for k, a in grid.items()}
+    arrays.update(grid)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def build_fast_oracle():
@@ -269,11 +308,12 @@ def main():
             board.barrier()
         hip.synchronize()
 
-    def timed_region(wake_steps=None):
+    def timed_region(wake_steps=None, capture=False):
         """W warm-up steps, then exactly K steps between two fences; max wall time over ranks.
         With several ranks an engine error (a reducer that stops answering) does not leave the other
         ranks stranded in a fence: the failing rank still walks through the same board calls and
-        reports an infinite time, so every rank sees the variant as failed and moves on."""
+        reports an infinite time, so every rank sees the variant as failed and moves on.
+        capture: also keep the voxel grid the last step built (for --dump-outputs)."""
         failed = None
         try:
             # (device wake-up, untimed, in front of the W warm-up steps: after an idle period -- the seconds of cloud
@@ -324,7 +364,8 @@ def main():
                                 struct.pack("<qq", iters, evals)).hexdigest()[:16]
         return dict(elapsed=elapsed, iters=iters, evals=evals, reused=reused, t_build=t_build, t_align=t_align,
                     prelaunched=pre1[0] - pre0[0], prelaunch_timeouts=pre1[2] - pre0[2], err_m=err_t, err_rad=err_r,
-                    digest=digest, lost_row_retries=ndt.lostRowRetries(), auto_streams=ndt.autoStreamPlacement())
+                    digest=digest, lost_row_retries=ndt.lostRowRetries(), auto_streams=ndt.autoStreamPlacement(),
+                    result=last, leaves=ndt.getLeaves() if capture else None)
 
     unavailable = {}
 
@@ -362,9 +403,32 @@ def main():
         ndt.setGlobalSourceSize(n_src_total)
         return True
 
-    def instrumented(res, reduce_mode, variants):
-        """Repeats the timed steps with HIP events around k_derivatives (engine's own stream)
-        and assembles rank 0's JSON line for the timed result `res`."""
+    def line(res, reduce_mode, variants):
+        """Rank 0's JSON line for the timed result `res`: only what the timed steps themselves gave."""
+        if rank != 0:
+            return None
+        gi = ndt.getGridInfo()
+        nbar = res["result"]["n_pairs"] / float(n_src_total)   # global pairs / global points (last evaluation)
+        return {
+            "metric": "ndt_align_iterations_per_sec", "value": 0.0, "unit": "iterations/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": 0.0, "higher_is_better": True, "scaling": "strong",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "C3 scan-to-map: 200k-pt source into 1M-pt voxelised submap, 0.5 m voxel, DIRECT7, "
+                                   "outlier 0.55, eps 1e-4, step 0.1, max 35 it; step = voxel-grid build + align",
+                       "handoff": "clouds resident in HBM as SoA: the target's build enqueued by ndt_set_target_device_deferred "
+                                  "and finished inside the step (the align's first evaluation is on the stream behind it), "
+                                  "source viewed in place (ndt_set_source_device_view: setInputSource's shared_ptr contract)",
+                       "n_source": n_src_total, "n_target": len(cfg["target"]), "voxels": int(gi["n_leaves"]),
+                       "grid_cells": int(gi["n_cells"]), "mean_neighbors": nbar, "sharding": "source/%d" % world,
+                       "reduce": reduce_mode, "reduce_variants": variants},
+            "device_wake_steps": WAKE_STEPS,   # untimed steps in front of the W warm-up steps of every timed region (clock ramp after idling)
+            "final_error_vs_ground_truth": {"m": res["err_m"], "rad": res["err_rad"]},
+        }
+
+    def instrumented(out):
+        """--full: repeats the timed steps with HIP events around k_derivatives and the build (engine's own
+        stream; every rank takes part) and adds the roofline figures and the build's device time to `out`."""
         ndt.enableKernelTiming(True)
         tm0 = ndt.getTiming()
         for _ in range(args.steps):
@@ -391,26 +455,10 @@ def main():
                 traffic_source = "static: profiles/traffic_k_derivatives.json (%s)" % tj.get("source", "rocprofv3 --pmc pass")
             except Exception:
                 traffic = None
-        final = ndt.getResult()
-        err_t, err_r = S.pose_error(final["T"], cfg["gt"])
-        if rank != 0:
-            return None
-        return {
-            "metric": "ndt_align_iterations_per_sec", "value": 0.0, "unit": "iterations/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 0.0, "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "C3 scan-to-map: 200k-pt source into 1M-pt voxelised submap, 0.5 m voxel, DIRECT7, "
-                                   "outlier 0.55, eps 1e-4, step 0.1, max 35 it; step = voxel-grid build + align",
-                       "handoff": "clouds resident in HBM as SoA: the target's build enqueued by ndt_set_target_device_deferred "
-                                  "and finished inside the step (the align's first evaluation is on the stream behind it), "
-                                  "source viewed in place (ndt_set_source_device_view: setInputSource's shared_ptr contract)",
-                       "n_source": n_src_total, "n_target": len(cfg["target"]), "voxels": int(gi["n_leaves"]),
-                       "grid_cells": int(gi["n_cells"]), "mean_neighbors": nbar, "sharding": "source/%d" % world,
-                       "reduce": reduce_mode, "reduce_variants": variants},
+        if out is None:
+            return
+        out.update({
             "ms_target_build_device": gi["ms_build"],
-            "device_wake_steps": WAKE_STEPS,   # untimed steps in front of the W warm-up steps of every timed region (clock ramp after idling)
-            "final_error_vs_ground_truth": {"m": err_t, "rad": err_r},
             # `bound`: what the evidence shows limits this launch (DESIGN 4.1 / HISTORY 4.1: half of the 200 k-point launch is a
             # fixed latency chain, the rest VALU issue); `roof`: the roofline `achieved` / `peak` / `frac` are
             # priced against, as the contract defines them (algorithmic bytes over the HBM peak)
@@ -435,7 +483,7 @@ def main():
                                if gi["ms_build"] > 0 else 0.0,
                                "frac": BUILD_BYTES(len(cfg["target"]), int(gi["n_leaves"])) / (gi["ms_build"] * 1e-3) / 1e9 / HBM_PEAK_GBS
                                if gi["ms_build"] > 0 else 0.0},
-        }
+        })
 
     def headline(out, res, reduce_mode):
         """Puts the timed result `res` into the JSON line (rank 0 only)."""
@@ -445,13 +493,8 @@ def main():
         out.update({
             "value": iters / elapsed, "ms_per_step": 1e3 * elapsed / args.steps,
             "ms_scan": 1e3 * elapsed / args.steps,
-            # Key meanings as in rounds 1-3: ms_target_build is the BUILD (device time; the set-target call
-            # only enqueues it since round 4 -- its host time is ms_target_build_enqueue), ms_align the align WITHOUT the
-            # build that now finishes inside it (ms_align_incl_build is what the call takes)
-            "ms_target_build": out.get("ms_target_build_device") or 0.0,
             "ms_target_build_enqueue": 1e3 * res["t_build"] / args.steps,
             "ms_align_incl_build": 1e3 * res["t_align"] / args.steps,
-            "ms_align": max(1e3 * res["t_align"] / args.steps - (out.get("ms_target_build_device") or 0.0), 0.0),
             "iterations_per_align": iters / args.steps, "evaluations_per_align": evals / args.steps,
             # line-search requests at the pose of the evaluation before them, answered without a launch
             "evaluations_reused_per_align": res["reused"] / args.steps,
@@ -459,12 +502,21 @@ def main():
             # previous evaluation ran); the rest went through an ordinary launch
             "evaluations_prelaunched_per_align": res["prelaunched"] / args.steps,
             "prelaunch_timeouts": res["prelaunch_timeouts"],
-            # (the build is enqueued by the set-target call and finishes inside the align: "align only" = the step
-            # without the build's own duration)
-            "align_only_iterations_per_sec": iters / max(elapsed - args.steps * 1e-3 * (out.get("ms_target_build_device") or 0.0), 1e-9),
-            "evaluations_per_sec": evals / max(elapsed - args.steps * 1e-3 * (out.get("ms_target_build_device") or 0.0), 1e-9),
             "prelaunch_auto": {"one_stream": res["auto_streams"][0], "switches": res["auto_streams"][1]},
         })
+        if "ms_target_build_device" in out:   # (--full: the build's device time of the instrumented repeat)
+            build_ms = out["ms_target_build_device"]
+            out.update({
+                # Key meanings as in rounds 1-3: ms_target_build is the BUILD (device time; the set-target call
+                # only enqueues it since round 4 -- its host time is ms_target_build_enqueue), ms_align the align WITHOUT the
+                # build that now finishes inside it (ms_align_incl_build is what the call takes)
+                "ms_target_build": build_ms,
+                "ms_align": max(1e3 * res["t_align"] / args.steps - build_ms, 0.0),
+                # (the build is enqueued by the set-target call and finishes inside the align: "align only" = the step
+                # without the build's own duration)
+                "align_only_iterations_per_sec": iters / max(elapsed - args.steps * 1e-3 * build_ms, 1e-9),
+                "evaluations_per_sec": evals / max(elapsed - args.steps * 1e-3 * build_ms, 1e-9),
+            })
         out["config"]["reduce"] = reduce_mode
 
     def host_cloud():
@@ -615,8 +667,12 @@ def main():
         return {"version": v, "library": path}
 
     if not multi:
-        res = timed_region()
-        out = instrumented(res, "none", variants)
+        res = timed_region(capture=args.dump_outputs is not None)
+        if args.dump_outputs is not None:
+            dump_outputs(args.dump_outputs, res)
+        out = line(res, "none", variants)
+        if args.full:
+            instrumented(out)
         headline(out, res, "none")
         # Not `value`: the same step on 48-byte voxel records (f64 mean, f32 inverse covariance; ndt_set_record_format):
         # three 16-byte fetches per neighbour instead of five.  The headline stays on the 80-byte f64 records, the
@@ -767,15 +823,16 @@ def main():
                 ndt.setKeepWarm(0)
             return v
 
-        side("protocol_variants", protocol_variants)
-        side("cadence", cadence)
-        side("packed_records", packed)
-        side("host_cloud", host_cloud)
-        side("configs", other_configs)
-        side("scaling_probe", scaling_probe)
+        if args.full:
+            side("protocol_variants", protocol_variants)
+            side("cadence", cadence)
+            side("packed_records", packed)
+            side("host_cloud", host_cloud)
+            side("configs", other_configs)
+            side("scaling_probe", scaling_probe)
         if out is not None:
             out["config"]["rccl"] = comm_record()
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             side("cpu_baseline", lambda: cpu_baseline(cfg, params, args.cpu_seconds))
     else:
         # Every transport of the 256-byte evaluation sum is timed back to back on the same workload
@@ -850,7 +907,7 @@ def main():
                         board.barrier()
                         dog.cancel()
                         continue
-                res = timed_region()
+                res = timed_region(capture=args.dump_outputs is not None)
                 if res is None:      # an engine error on some rank: the variant is reported as failed, the others stand
                     variants[mode] = "failed"
                     if out is not None:
@@ -889,42 +946,45 @@ def main():
                     # scaling curve then reads as "reduce-bound" or "fixed-chain-bound" from this one run:
                     # an instrumented repeat (ordinary launches, HIP events attached to the dispatch; host-side transports:
                     # wall time of the cross-rank sum; peer-write: the exchange's duration counted inside the kernel)
-                    try:
-                        if mode == "p2p":
-                            ndt.commP2pStats(reset=True)
-                        ndt.enableKernelTiming(True)
-                        tq0 = ndt.getTiming()
-                        for _ in range(max(2, args.steps // 4)):
-                            step()
-                        tq1 = ndt.getTiming()
-                        ndt.enableKernelTiming(False)
-                        nq = max(tq1["n_timed_evals"] - tq0["n_timed_evals"], 1)
-                        k_us = 1e3 * (tq1["ms_eval_kernel_total"] - tq0["ms_eval_kernel_total"]) / nq
-                        if mode == "p2p":
-                            ps = ndt.commP2pStats()
-                            r_us, r_max = ps["mean_us"], ps["max_us"]
-                        else:
-                            r_us, r_max = 1e3 * (tq1["ms_reduce_kernel_total"] - tq0["ms_reduce_kernel_total"]) / nq, None
-                        per_rank = [json.loads(b.decode()) for b in board.allgather(json.dumps([k_us, r_us]).encode())]
-                        variants[mode]["k_derivatives_us_per_rank"] = [round(p_[0], 2) for p_ in per_rank]
-                        variants[mode]["reduce_us_per_evaluation_per_rank"] = [round(p_[1], 2) for p_ in per_rank]
-                        variants[mode]["reduce_us_per_evaluation"] = max(p_[1] for p_ in per_rank)
-                        if r_max is not None:
-                            variants[mode]["reduce_us_longest_on_rank0"] = r_max
-                        variants[mode]["reduce_note"] = ("local sum in hand -> global sum in hand: " +
-                                                         {"shm": "host wall time of the shared-memory sum", "p2p": "own row published -> every rank's row read, inside the kernel's final sum",
-                                                          "rccl": "ncclAllReduce + read-back on the engine's stream (host wall time)"}[mode])
-                    except Exception as e:  # noqa: BLE001  (instrumentation must never cost the variant)
-                        variants[mode]["reduce_probe_error"] = "%s: %s" % (type(e).__name__, e)
+                    if args.full:
                         try:
+                            if mode == "p2p":
+                                ndt.commP2pStats(reset=True)
+                            ndt.enableKernelTiming(True)
+                            tq0 = ndt.getTiming()
+                            for _ in range(max(2, args.steps // 4)):
+                                step()
+                            tq1 = ndt.getTiming()
                             ndt.enableKernelTiming(False)
-                        except Exception:  # noqa: BLE001
-                            pass
+                            nq = max(tq1["n_timed_evals"] - tq0["n_timed_evals"], 1)
+                            k_us = 1e3 * (tq1["ms_eval_kernel_total"] - tq0["ms_eval_kernel_total"]) / nq
+                            if mode == "p2p":
+                                ps = ndt.commP2pStats()
+                                r_us, r_max = ps["mean_us"], ps["max_us"]
+                            else:
+                                r_us, r_max = 1e3 * (tq1["ms_reduce_kernel_total"] - tq0["ms_reduce_kernel_total"]) / nq, None
+                            per_rank = [json.loads(b.decode()) for b in board.allgather(json.dumps([k_us, r_us]).encode())]
+                            variants[mode]["k_derivatives_us_per_rank"] = [round(p_[0], 2) for p_ in per_rank]
+                            variants[mode]["reduce_us_per_evaluation_per_rank"] = [round(p_[1], 2) for p_ in per_rank]
+                            variants[mode]["reduce_us_per_evaluation"] = max(p_[1] for p_ in per_rank)
+                            if r_max is not None:
+                                variants[mode]["reduce_us_longest_on_rank0"] = r_max
+                            variants[mode]["reduce_note"] = ("local sum in hand -> global sum in hand: " +
+                                                             {"shm": "host wall time of the shared-memory sum", "p2p": "own row published -> every rank's row read, inside the kernel's final sum",
+                                                              "rccl": "ncclAllReduce + read-back on the engine's stream (host wall time)"}[mode])
+                        except Exception as e:  # noqa: BLE001  (instrumentation must never cost the variant)
+                            variants[mode]["reduce_probe_error"] = "%s: %s" % (type(e).__name__, e)
+                            try:
+                                ndt.enableKernelTiming(False)
+                            except Exception:  # noqa: BLE001
+                                pass
                     if out is None and sane:
-                        out = instrumented(res, mode, variants)
+                        out = line(res, mode, variants)
+                        if args.full:
+                            instrumented(out)
                         if rank != 0:
                             out = {"config": {"reduce_variants": variants}}  # placeholder: only rank 0 prints
-                        probe = scaling_probe()
+                        probe = scaling_probe() if args.full else None
                         if probe is not None:
                             probe["reduce"] = mode
                             out["scaling_probe"] = probe
@@ -938,6 +998,8 @@ def main():
             dog.cancel()
         if best is None:
             raise SystemExit("no cross-rank reducer could be created")
+        if args.dump_outputs is not None and rank == 0:
+            dump_outputs(args.dump_outputs, best)
         if out is not None and "config" in out:
             out["config"]["rccl"] = comm_record()
             out["config"]["launch"] = ("self-launched ranks" if "NDT_RANKS_BOARD" in os.environ else "external launcher") + \

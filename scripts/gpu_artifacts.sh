@@ -9,16 +9,16 @@ has() { [[ " $PARTS " == *" $1 "* ]]; }
 nolog() { grep -v amdgpu.ids; }
 if has bench; then   # the driver's N = 1 command
   nproc > $OUT/host.txt; cat /sys/fs/cgroup/cpu.max >> $OUT/host.txt 2>&1; lscpu | grep -E "Model name|^CPU\(s\)" >> $OUT/host.txt
-  timeout -k 10 500 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+  timeout -k 10 500 python bench.py --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 fi
 if has multi; then   # the multi-rank code path on a 1-GPU box: 2 and 4 ranks on the one device; one rank incl. RCCL
-  NDT_BENCH_SINGLE_DEVICE=1 NDT_BENCH_PROBE=0 timeout -k 10 400 python bench.py --gpus 2 --no-cpu-baseline > $OUT/bench_2on1.json 2> $OUT/bench_2on1.err; echo "2on1 rc=$?"
-  NDT_BENCH_SINGLE_DEVICE=1 NDT_BENCH_PROBE=0 timeout -k 10 400 python bench.py --gpus 4 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_4on1.json 2> $OUT/bench_4on1.err; echo "4on1 rc=$?"
-  NDT_BENCH_FORCE_DIST=1 NDT_BENCH_PROBE=0 timeout -k 10 400 python bench.py --gpus 1 --no-cpu-baseline > $OUT/bench_dist1.json 2> $OUT/bench_dist1.err; echo "dist1 rc=$?"
+  NDT_BENCH_SINGLE_DEVICE=1 NDT_BENCH_PROBE=0 timeout -k 10 400 python bench.py --gpus 2 --full --no-cpu-baseline > $OUT/bench_2on1.json 2> $OUT/bench_2on1.err; echo "2on1 rc=$?"
+  NDT_BENCH_SINGLE_DEVICE=1 NDT_BENCH_PROBE=0 timeout -k 10 400 python bench.py --gpus 4 --steps 10 --warmup 3 --full --no-cpu-baseline > $OUT/bench_4on1.json 2> $OUT/bench_4on1.err; echo "4on1 rc=$?"
+  NDT_BENCH_FORCE_DIST=1 NDT_BENCH_PROBE=0 timeout -k 10 400 python bench.py --gpus 1 --full --no-cpu-baseline > $OUT/bench_dist1.json 2> $OUT/bench_dist1.err; echo "dist1 rc=$?"
 fi
 if has prof; then    # rocprofv3 kernel stats of the bench command (headline workload only)
   ( cd /tmp && export TMPDIR=/tmp NDT_BENCH_PROBE=0 NDT_BENCH_HOST_CLOUD=0 NDT_BENCH_CONFIGS=0 NDT_BENCH_PACKED=0 NDT_BENCH_PROTOCOLS=0 NDT_BENCH_CADENCE=0
-    timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/prof -o r --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/prof.log 2>&1
+    timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/prof -o r --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $OUT/prof.log 2>&1
     cp $(find $OUT/prof -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv; rm -rf $OUT/prof/*/*trace* 2>/dev/null )
 fi
 if has pmc; then     # counters in their own passes, kernel-trace only (the pool refuses --pmc with other trace domains)

@@ -1,10 +1,12 @@
 """bench.py keeps its contract: one JSON line on stdout with the BASELINE.json metric, the
-whole-job value, and the roofline / cpu_baseline objects (short run: 2 steps, bounded CPU sample)."""
+whole-job value, and -- with --full -- the roofline / cpu_baseline objects (short run: 2 steps, bounded
+CPU sample).  A plain run is the headline alone and can dump what its last timed step computed."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -14,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_line_schema():
     env = dict(os.environ, NDT_BENCH_PROBE="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
-                        "--cpu-seconds", "1"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--full", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -74,6 +76,50 @@ def test_bench_line_schema():
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and cb["unit"] == "iterations/s" and cb["sample"]
     assert cb["nproc"] >= cb["cores"] and cb["cpus_usable"] >= 1 and "-O" in cb["build_flags"] and cb["threads_8"]["threads"] <= 8
     assert d["final_error_vs_ground_truth"]["m"] < 0.05
+
+
+DUMPED = {"final_transformation": (4, 4), "final_pose": (6,), "hessian": (6, 6), "iterations": (1,), "n_evaluations": (1,),
+          "converged": (1,), "score": (1,), "transform_probability": (1,), "nvtl": (1,), "n_pairs": (1,)}
+FULL_ONLY = ("roofline", "roofline_build", "ms_target_build", "ms_target_build_device", "ms_align", "protocol_variants",
+             "cadence", "packed_records", "host_cloud", "configs", "scaling_probe", "cpu_baseline")
+
+
+def _plain_run(out_dir):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path, S):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline keys, K timed steps, none of the side
+    measurements; --dump-outputs writes the last timed step's result and voxel grid as float64 .npy files, the same
+    bit for bit in a second run with the same arguments."""
+    d = _plain_run(tmp_path / "a")
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    assert "iterations" in d["metric"] and "iterations/sec" in base["metric"]
+    assert d["unit"] == "iterations/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["iterations_per_align"] * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert not [k for k in FULL_ONLY if k in d], [k for k in FULL_ONLY if k in d]
+    a = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    leaf_keys = {"leaf_cell", "leaf_count", "leaf_mean", "leaf_cov", "leaf_icov"}
+    assert set(a) == set(DUMPED) | leaf_keys
+    assert all(v.dtype == np.float64 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k, shape in DUMPED.items():
+        assert a[k].shape == shape, k
+    n = d["config"]["voxels"]
+    assert a["leaf_cell"].shape == (n,) and a["leaf_mean"].shape == (n, 3) and a["leaf_icov"].shape == (n, 3, 3)
+    assert np.all(np.diff(a["leaf_cell"]) > 0) and a["converged"][0] == 1.0
+    cfg = S.config_c3()
+    err_m, err_rad = S.pose_error(a["final_transformation"], cfg["gt"])
+    assert err_m == d["final_error_vs_ground_truth"]["m"] and err_rad == d["final_error_vs_ground_truth"]["rad"]
+    assert err_m < 0.05
+    _plain_run(tmp_path / "b")
+    for k in a:
+        assert np.array_equal(a[k], np.load(str(tmp_path / "b" / (k + ".npy")))), k
 
 
 def test_bench_gpus_2_from_a_plain_invocation():
