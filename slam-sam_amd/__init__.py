@@ -316,8 +316,65 @@ def lib():
             L.ndt_debug_handoff_counters.argtypes = [vp, C.POINTER(C.c_int64)]  # test seam, not in the header
         L.ndt_debug_set_speculation.argtypes = [vp, C.c_int]  # tuning aid, not in the header
         L.ndt_debug_sort_pairs.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, vp]  # test seam, not in the header
+        # test seams, not in the header: launch plans of k_derivatives, the XCD chunk map, the evaluation log
+        L.ndt_debug_launch_shape.argtypes = [C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.ndt_debug_launch_plan.argtypes = [C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.ndt_debug_xcd_chunk.argtypes = [C.c_int] * 5
+        L.ndt_debug_xcd_chunk_map.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int)]
+        L.ndt_debug_eval_log.argtypes = [vp, C.c_int]
+        L.ndt_debug_eval_log_read.argtypes = [vp, vp, C.c_int]
+        L.ndt_debug_eval_log_read.restype = C.c_int64
         _lib = L
     return _lib
+
+
+# DerivLaunchPlan (csrc/ndt_kernels.h): the shape of one k_derivatives launch, 16 ints in this order
+EVAL_DESC_FIELDS = ("batch", "mode", "nb", "mbox", "threads", "blocks", "point_blocks", "summers", "doubling_split",
+                    "xcd_count", "xcd_stripe", "two_level", "safe_sum", "dyn_lds", "cus", "spec")
+# EvalLogEntry (csrc/ndt_engine.h): one logged evaluation
+EVAL_LOG_DTYPE = np.dtype([("pose6", "<f8", 6), ("words", "<f8", EVAL_WORDS), ("T", "<f4", 16), ("launch", "<i8"),
+                           ("k", "<i4"), ("K", "<i4"), ("need_h", "<i4"), ("score_only", "<i4"), ("prelaunched", "<i4"),
+                           ("pad", "<i4"), ("plan", "<i4", len(EVAL_DESC_FIELDS))])
+assert EVAL_LOG_DTYPE.itemsize == 464
+
+
+def debug_launch_plan(n_src, K=1, cus=256, nb=1, mode=1, batched=None, mbox=False, safe_sum=False):
+    """Test seam: the plan of a k_derivatives launch (dict over EVAL_DESC_FIELDS) for n_src points and K poses on a
+    single-rank handle of `cus` compute units under the current ndt_tuning -- nb / mode: the template axes (NB 0 DIRECT1,
+    1 DIRECT7, 2 KDTREE, 3 DIRECT26, 4 multi-grid, 5 / 6 packed DIRECT1 / DIRECT7; MODE 0 gradient, 1 Hessian, 2 Gauss-
+    Newton, 3 score only).  batched defaults to K > 1."""
+    out = (C.c_int * len(EVAL_DESC_FIELDS))()
+    flags = (1 if (K > 1 if batched is None else batched) else 0) | (2 if mbox else 0) | (4 if safe_sum else 0)
+    rc = lib().ndt_debug_launch_plan(int(n_src), int(K), int(cus), int(nb), int(mode), flags, out)
+    if rc:
+        raise NdtError(rc, "ndt_debug_launch_plan")
+    return dict(zip(EVAL_DESC_FIELDS, out))
+
+
+def debug_launch_shape(n_src, K=1, cus=256):
+    """Test seam: (threads per block, point blocks, summing blocks, grid blocks per pose) of a k_derivatives launch."""
+    out = (C.c_int * 4)()
+    rc = lib().ndt_debug_launch_shape(int(n_src), int(K), int(cus), out)
+    if rc:
+        raise NdtError(rc, "ndt_debug_launch_shape")
+    return tuple(out)
+
+
+def debug_xcd_chunk(p, L, off, X, m):
+    """Test seam: xcd_chunk(p, L, off, X, m) of csrc/ndt_device.h, called on the host."""
+    r = lib().ndt_debug_xcd_chunk(int(p), int(L), int(off), int(X), int(m))
+    if r < 0:
+        raise NdtError(r, "ndt_debug_xcd_chunk")
+    return r
+
+
+def debug_xcd_chunk_map(L, off, X, m):
+    """Test seam: [xcd_chunk(p, L, off, X, m) for p in range(L)] in one call."""
+    out = np.zeros(int(L), np.int32)
+    rc = lib().ndt_debug_xcd_chunk_map(int(L), int(off), int(X), int(m), out.ctypes.data_as(C.POINTER(C.c_int)))
+    if rc:
+        raise NdtError(rc, "ndt_debug_xcd_chunk_map")
+    return out
 
 
 def default_params(preset=None, **kw):
@@ -812,6 +869,27 @@ class NormalDistributionsTransform:
 
     def enableKernelTiming(self, on=True):
         self._check(lib().ndt_enable_kernel_timing(self._h, int(on)))
+
+    def debugEvalLog(self, cap):
+        """Test seam: clear the evaluation log and keep the next `cap` evaluations (0: off)."""
+        rc = lib().ndt_debug_eval_log(self._h, int(cap))
+        if rc < 0:
+            raise NdtError(rc, "ndt_debug_eval_log")
+        assert rc == EVAL_LOG_DTYPE.itemsize, "EvalLogEntry layout differs from EVAL_LOG_DTYPE"
+
+    def debugEvalLogRead(self):
+        """Test seam: the logged evaluations as a list of dicts (pose6, T as a 4x4, words, need_h, score_only, prelaunched,
+        launch, k, K, desc: the launch's plan over EVAL_DESC_FIELDS).  Raises if the log overflowed."""
+        n = lib().ndt_debug_eval_log_read(self._h, None, 0)
+        if n < 0:
+            raise NdtError(int(n), "ndt_debug_eval_log_read")
+        a = np.zeros(n, EVAL_LOG_DTYPE)
+        kept = lib().ndt_debug_eval_log_read(self._h, a.ctypes.data if n else None, int(n))
+        assert kept == n
+        return [dict(pose6=e["pose6"].copy(), T=e["T"].reshape(4, 4).T.astype(np.float64), T32=e["T"].copy(),
+                     words=e["words"].copy(), need_h=bool(e["need_h"]), score_only=bool(e["score_only"]),
+                     prelaunched=bool(e["prelaunched"]), launch=int(e["launch"]), k=int(e["k"]), K=int(e["K"]),
+                     desc=dict(zip(EVAL_DESC_FIELDS, (int(v) for v in e["plan"])))) for e in a]
 
     def prelaunchCounters(self):
         """(evaluations served by a pre-launched kernel, pre-launched kernels told to leave, time-outs)."""

@@ -1543,8 +1543,11 @@ int derivs_block_threads(size_t n_src, int K, int cus) {
   const int g_compute_units = cus_or_default(cus);
   const int forced = tuning().deriv_block;  // multiple of 64, 64..1024 (checked by ndt_set_tuning)
   if (forced) return forced;
-  // (one compute unit is left to the dedicated summing block)
-  const size_t kCUs = (size_t)std::max(2, g_compute_units - (deriv_dedicated_enabled() && deriv_fixed_summer() ? 1 : 0));
+  // (one compute unit is left to the dedicated summing block -- whether or not ndt_tuning asks for one: the block shape
+  // decides the partition of the scan, hence the last bits of the sums, and deriv_summer / deriv_dedicated must not
+  // move it; with the unit's count taken from them, 146 881 points ran 640-thread blocks by default and 576 without
+  // the dedicated summer)
+  const size_t kCUs = (size_t)std::max(2, g_compute_units - 1);
   // (up to 512 points per compute unit the 512-thread shape stays: two such blocks share a CU, and a scan of exactly
   // 128 x 1024 points keeps the same partition -- hence the same sums, bit for bit -- single-pose and batched)
   if (K == 1 && n_src > (size_t)512 * (size_t)g_compute_units && n_src <= (size_t)MAX_BLOCK * kCUs) {
@@ -1639,23 +1642,18 @@ void derivs_item_owners(int threads, unsigned int* owners_out, unsigned int* fin
 
 int derivs_grid_blocks(size_t n_src, int K, int cus) { return derivs_point_blocks(n_src, K, cus) + derivs_dedicated_summer(n_src, K, cus); }
 
-void launch_derivatives(const float* sx, const float* sy, const float* sz, size_t n_src,
-                        const GridGeom& g, const int* cell2leaf, const VoxelRecord* rec, const float* cent4,
-                        const PoseConsts& pose, const PoseConsts* d_poses, int K,
-                        const EvalConsts& ec, double* d_partials, unsigned int* d_counters,
-                        double* d_out, hipStream_t s, unsigned long long* d_flag,
-                        unsigned long long seq, const PoseMailbox* d_mbox, const XchgInfo* d_xinfo,
-                        unsigned long long xround, unsigned int* d_arrive_ctr, unsigned long long* d_arrived_host,
-                        hipEvent_t ev_start, hipEvent_t ev_stop, const BuildGeom* d_geom) {
+DerivLaunchPlan plan_derivatives_launch(size_t n_src, int K, bool batched, bool mbox, bool xchg, const EvalConsts& ec,
+                                        EvalConsts* ecl_out) {
   const int cus = cus_or_default(ec.compute_units);
-  int blocks = derivs_grid_blocks(n_src, d_poses ? K : 1, cus);
-  const int threads = derivs_block_threads(n_src, d_poses ? K : 1, cus);
+  const int Kp = batched ? K : 1;
+  int blocks = derivs_grid_blocks(n_src, Kp, cus);
+  const int threads = derivs_block_threads(n_src, Kp, cus);
   const int mode = ec.score_only ? 3 : (!ec.need_hessian ? 0 : (ec.gauss_newton ? 2 : 1));
   EvalConsts ecl = ec;
   ecl.single_level_max = deriv_single_level_max();
   ecl.fixed_summer = deriv_fixed_summer();
-  ecl.dedicated_summer = derivs_dedicated_summer(n_src, d_poses ? K : 1, cus);
-  if (ecl.dedicated_summer > 1 && d_xinfo != nullptr) {   // the in-kernel cross-rank exchange is one block's (xchg_allsum)
+  ecl.dedicated_summer = derivs_dedicated_summer(n_src, Kp, cus);
+  if (ecl.dedicated_summer > 1 && xchg) {   // the in-kernel cross-rank exchange is one block's (xchg_allsum)
     blocks -= ecl.dedicated_summer - 1;
     ecl.dedicated_summer = 1;
   }
@@ -1665,7 +1663,7 @@ void launch_derivatives(const float* sx, const float* sy, const float* sz, size_
     // so nothing in the launch waits for a block that is not resident (a device shared with other processes).
     ecl.fixed_summer = 0;
     ecl.dedicated_summer = 0;
-    blocks = derivs_point_blocks(n_src, d_poses ? K : 1, cus);
+    blocks = derivs_point_blocks(n_src, Kp, cus);
   }
   // XCD-aware chunk assignment (xcd_chunk, ndt_device.h).  gfx950 has 32 compute units per XCD: 8 XCDs on a whole MI355X,
   // one in a CPX partition (nothing to do there).  Grids that are resident at once (at most one block per compute unit)
@@ -1678,15 +1676,15 @@ void launch_derivatives(const float* sx, const float* sy, const float* sz, size_
   const int nxcd = std::max(1, cus / 32);
   const int point_blocks = blocks - ecl.dedicated_summer;
   // no unit to spare for summing blocks (the 128 x 1024 scan): the blocks of rows 0 .. 3 add eight words each
-  if (!d_poses && d_xinfo == nullptr && !ec.safe_sum && ecl.dedicated_summer == 0 && ecl.fixed_summer != 0 && tuning().deriv_summer_split != 0 &&
+  if (!batched && !xchg && !ec.safe_sum && ecl.dedicated_summer == 0 && ecl.fixed_summer != 0 && tuning().deriv_summer_split != 0 &&
       point_blocks >= SUMMER_SPLIT && point_blocks <= ecl.single_level_max)
     ecl.doubling_split = 1;
   const int per_cu = std::max(1, 1024 / threads);
-  const bool resident = blocks <= cus * per_cu + 1 && !d_poses;
+  const bool resident = blocks <= cus * per_cu + 1 && !batched;
   ecl.xcd_count = 0;
   ecl.xcd_stripe = 0;
   if (nxcd > 1 && point_blocks >= 2 * nxcd && xcd_mode != 0) {
-    if (!d_poses && blocks <= cus + 1) {
+    if (!batched && blocks <= cus + 1) {
       ecl.xcd_count = nxcd;                 // the whole grid at once: one stripe (round 3's case)
     } else if (xcd_mode >= 2) {
       ecl.xcd_count = nxcd;
@@ -1707,8 +1705,43 @@ void launch_derivatives(const float* sx, const float* sy, const float* sz, size_
   // (tools/stamps_prelaunch.py, profiles/r05_c2_stragglers.txt).  A block that asks for more than half a unit's LDS has the unit to
   // itself; the kernel pre-launched for the next evaluation then moves in as this one's blocks leave, as it always has for the
   // 13-wave blocks of the 200 k-point scan.
-  if (!d_poses && ec.own_units && d_xinfo == nullptr && tuning().deriv_one_block_per_cu != 0 && blocks <= cus && dyn_lds <= (size_t)80 * 1024)
+  if (!batched && ec.own_units && !xchg && tuning().deriv_one_block_per_cu != 0 && blocks <= cus && dyn_lds <= (size_t)80 * 1024)
     dyn_lds = (size_t)80 * 1024 + 512;
+  DerivLaunchPlan pl{};
+  pl.batch = batched ? 1 : 0;
+  pl.mode = mode;
+  pl.nb = nb;
+  pl.mbox = !batched && mbox ? 1 : 0;   // (launch_derivatives: a batched launch never takes the mailbox)
+  pl.threads = threads;
+  pl.blocks = blocks;
+  pl.point_blocks = point_blocks;
+  pl.summers = ecl.dedicated_summer;
+  pl.doubling_split = ecl.doubling_split;
+  pl.xcd_count = ecl.xcd_count;
+  pl.xcd_stripe = ecl.xcd_stripe;
+  pl.two_level = point_blocks > ecl.single_level_max ? 1 : 0;
+  pl.safe_sum = ec.safe_sum ? 1 : 0;
+  pl.dyn_lds = (int)dyn_lds;
+  pl.cus = cus;
+  pl.spec = 0;
+  if (ecl_out != nullptr) *ecl_out = ecl;
+  return pl;
+}
+
+void launch_derivatives(const float* sx, const float* sy, const float* sz, size_t n_src,
+                        const GridGeom& g, const int* cell2leaf, const VoxelRecord* rec, const float* cent4,
+                        const PoseConsts& pose, const PoseConsts* d_poses, int K,
+                        const EvalConsts& ec, double* d_partials, unsigned int* d_counters,
+                        double* d_out, hipStream_t s, unsigned long long* d_flag,
+                        unsigned long long seq, const PoseMailbox* d_mbox, const XchgInfo* d_xinfo,
+                        unsigned long long xround, unsigned int* d_arrive_ctr, unsigned long long* d_arrived_host,
+                        hipEvent_t ev_start, hipEvent_t ev_stop, const BuildGeom* d_geom, DerivLaunchPlan* plan_out) {
+  EvalConsts ecl;
+  DerivLaunchPlan pl = plan_derivatives_launch(n_src, K, d_poses != nullptr, d_mbox != nullptr, d_xinfo != nullptr, ec, &ecl);
+  pl.spec = d_geom != nullptr ? 1 : 0;
+  if (plan_out != nullptr) *plan_out = pl;
+  const int blocks = pl.blocks, threads = pl.threads, mode = pl.mode, nb = pl.nb;
+  const size_t dyn_lds = (size_t)pl.dyn_lds;
   // ev_start / ev_stop: events attached to THIS dispatch (hipExtLaunchKernel): they carry the kernel's own begin and
   // end timestamps, what rocprofv3 reports -- events recorded around the launch include ~2.4 us of dispatch
 #define NDT_LAUNCH2(B, M, NBH, MB, GY, FLAG, SEQ)                                                            \

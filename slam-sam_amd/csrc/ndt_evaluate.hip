@@ -274,6 +274,26 @@ void quit_prelaunched(ndt_handle* h) {
   h->n_prelaunch_quit++;
 }
 
+void log_evals(ndt_handle* h, const DerivLaunchPlan& plan, const double* poses6, const float* T, const double* words, int K,
+               bool need_h, bool score_only, bool prelaunched) {
+  for (int k = 0; k < K; ++k, ++h->eval_log_total) {
+    if ((int64_t)h->eval_log.size() >= (int64_t)h->eval_log_cap) continue;
+    EvalLogEntry e{};
+    std::memcpy(e.pose6, poses6 + 6 * (size_t)k, sizeof(e.pose6));
+    std::memcpy(e.words, words + (size_t)k * EV_WORDS, sizeof(e.words));
+    std::memcpy(e.T, T + 16 * (size_t)k, sizeof(e.T));
+    e.launch = h->eval_log_launches;
+    e.k = k;
+    e.K = K;
+    e.need_h = need_h ? 1 : 0;
+    e.score_only = score_only ? 1 : 0;
+    e.prelaunched = prelaunched ? 1 : 0;
+    e.plan = plan;
+    h->eval_log.push_back(e);
+  }
+  ++h->eval_log_launches;
+}
+
 // one global evaluation at (p, T): local kernel + cross-rank sum
 int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, Eval* out, bool score_only,
              bool safe_retry) {
@@ -330,6 +350,7 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
                          h->prm.prelaunch != NDT_PRELAUNCH_OFF && ensure_mailbox(h);
   unsigned long long seq = 0;
   bool via_mailbox = false;
+  DerivLaunchPlan plan{};   // (the evaluation log's launch descriptor)
   // NDT_REDUCE_P2P: the kernel's final sum exchanges the evaluation with the other ranks itself, under
   // the tag "number of this global evaluation" (identical on every rank: all run the same host loop on
   // the same sums).  A pre-launched kernel got its tag when it was enqueued; one that is told to leave
@@ -347,6 +368,7 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
   if (h->pre_seq != 0) {
     if (prelaunch && h->pre_need_h == need_h) {  // the kernel for this evaluation is already waiting on the device
       seq = h->pre_seq;
+      plan = h->pre_plan;
       buf = h->pre_buf;
       xround = h->pre_round;
       h->cur_on2 = h->pre_on2;
@@ -381,7 +403,7 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
     launch_derivatives(px, py, pz, h->n_src, h->geom, h->cell2leaf.p, records, h->cent.p, pc, nullptr, 1, ec, h->partials.p,
                        h->counters.p, d_out, s, spin ? h->flag.d + (size_t)buf * 2 * EV_WORDS : nullptr, seq, nullptr,
                        xinfo, xround, nullptr, nullptr, h->timing && !bracket ? h->ev0 : nullptr,
-                       h->timing && !bracket ? h->ev1 : nullptr, speculate ? h->gd.p : nullptr);
+                       h->timing && !bracket ? h->ev1 : nullptr, speculate ? h->gd.p : nullptr, &plan);
     HIP_TRY(h, hipGetLastError());
     if (bracket) HIP_TRY(h, hipEventRecord(h->ev1, s));
   }
@@ -441,7 +463,8 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
     if (in_flight_resident) h->n_prelaunch_overlapped++;
     launch_derivatives(px, py, pz, h->n_src, h->geom, h->cell2leaf.p, records, h->cent.p, pc, nullptr, 1, ec, h->partials.p,
                        h->counters.p, d_out, h->pre_on2 ? h->stream2 : s, h->flag.d + (size_t)h->pre_buf * 2 * EV_WORDS,
-                       h->pre_seq, h->mbox, xinfo, h->pre_round, h->arrive_ctr.p + h->pre_buf, h->arrived.d + h->pre_buf);
+                       h->pre_seq, h->mbox, xinfo, h->pre_round, h->arrive_ctr.p + h->pre_buf, h->arrived.d + h->pre_buf,
+                       nullptr, nullptr, nullptr, &h->pre_plan);
     HIP_TRY(h, hipGetLastError());
   }
   if (dev_out) {
@@ -558,6 +581,7 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
     return fail(h, NDT_ERR_HIP, words[EV_FAIL] != 0.0 ? "derivative kernel: a partial row never arrived (hand-off lost)"
                                                       : "derivative kernel returned a non-finite score");
   }
+  if (h->eval_log_cap > 0) log_evals(h, plan, p, T, words, 1, need_h, score_only, via_mailbox);
   unpack_eval(words, out);
   if (!score_only) finish_eval(h->prm, h->have_reg ? h->reg_pose : nullptr, p, need_h, out);
   return NDT_OK;
@@ -754,11 +778,12 @@ static int eval_batch(ndt_handle* h, const double* poses6, const float* transfor
   const unsigned long long seq = g_launch_seq.fetch_add(1, std::memory_order_relaxed);
   const bool bracket = h->timing && timing_brackets_launch();
   if (bracket) HIP_TRY(h, hipEventRecord(h->ev0, s));
+  DerivLaunchPlan plan{};   // (the evaluation log's launch descriptor)
   launch_derivatives(h->src_sorted ? h->ox.p : h->vx, h->src_sorted ? h->oy.p : h->vy,
                      h->src_sorted ? h->oz.p : h->vz, h->n_src, h->geom, h->cell2leaf.p, records, h->cent.p,
                      h->hposes.h[0], fast ? h->bposes : h->dposes.p, K, ec, h->partials.p, h->counters.p, h->dres.p, s,
                      fast ? h->flag.d : nullptr, seq, nullptr, nullptr, 0ull, nullptr, nullptr,
-                     h->timing && !bracket ? h->ev0 : nullptr, h->timing && !bracket ? h->ev1 : nullptr);
+                     h->timing && !bracket ? h->ev0 : nullptr, h->timing && !bracket ? h->ev1 : nullptr, nullptr, &plan);
   HIP_TRY(h, hipGetLastError());
   if (bracket) HIP_TRY(h, hipEventRecord(h->ev1, s));
   if (overlap) overlap(overlap_ctx);
@@ -793,6 +818,14 @@ static int eval_batch(ndt_handle* h, const double* poses6, const float* transfor
   if (!h->red.wants_device_buffer() && h->red.mode() != NDT_REDUCE_NONE) {
     rc = h->red.allreduce_host_batch(out, K, &h->err);   // (P2P: one exchange round per 64 poses, not one per pose)
     if (rc) return rc;
+  }
+  if (h->eval_log_cap > 0) {
+    std::vector<float> Ts(16 * (size_t)K);
+    for (int k = 0; k < K; ++k) {
+      if (transforms) std::memcpy(&Ts[16 * (size_t)k], transforms + 16 * (size_t)k, 16 * sizeof(float));
+      else pose_to_matrix(poses6 + 6 * (size_t)k, &Ts[16 * (size_t)k]);
+    }
+    log_evals(h, plan, poses6, Ts.data(), out, K, compute_hessian != 0, score_only, false);
   }
   if (score_only) return NDT_OK;
   // ridge / regularisation / guards, then repack so callers see finished values

@@ -402,18 +402,80 @@ int ndt_debug_item_owners(int threads, unsigned int* owners, unsigned int* fin_w
   return NDT_OK;
 }
 
+// the EvalConsts of a handle with default parameters on a device of `cus` compute units, with the neighbourhood `nb` and
+// the mode `mode` of the k_derivatives instantiation asked for (ndt_debug_launch_plan's inverse of the NB / MODE mapping)
+static EvalConsts debug_eval_consts(int cus, int nb, int mode) {
+  EvalConsts ec{};
+  ec.compute_units = cus;
+  ec.own_units = 1;
+  ec.direct7 = (nb == 1 || nb == 6) ? 1 : 0;
+  ec.kdtree = nb == 2 ? 1 : 0;
+  ec.direct26 = nb == 3 ? 1 : 0;
+  ec.multigrid = nb == 4 ? 1 : 0;
+  ec.packed = (nb == 5 || nb == 6) ? 1 : 0;
+  ec.need_hessian = (mode == 1 || mode == 2) ? 1 : 0;
+  ec.gauss_newton = mode == 2 ? 1 : 0;
+  ec.score_only = mode == 3 ? 1 : 0;
+  return ec;
+}
+
 // test seam (not in the public header): the shape of a k_derivatives launch over n_src points and K poses on a device of `cus`
 // compute units -- {threads per block, blocks that own points, summing blocks in front of them, blocks of the grid (per pose)}
+// (K > 1: a batched launch; K = 1: a single-pose one -- the same shape as a batched launch of one pose)
 int ndt_debug_launch_shape(size_t n_src, int K, int cus, int out[4]) {
   if (!out || K < 1 || cus < 1) return NDT_ERR_INVALID_ARG;
-  const int threads = derivs_block_threads(n_src, K, cus);
-  const int grid = derivs_grid_blocks(n_src, K, cus);
-  const int pb = (int)std::max<size_t>(1, (n_src + (size_t)threads - 1) / (size_t)threads);
-  out[0] = threads;
-  out[1] = pb;
-  out[2] = grid - pb;
-  out[3] = grid;
+  const DerivLaunchPlan pl = plan_derivatives_launch(n_src, K, K > 1, false, false, debug_eval_consts(cus, 1, 1), nullptr);
+  out[0] = pl.threads;
+  out[1] = pl.point_blocks;
+  out[2] = pl.summers;
+  out[3] = pl.blocks;
   return NDT_OK;
+}
+
+// test seam (not in the public header): the whole plan of a k_derivatives launch (DerivLaunchPlan, 16 ints) on a single-rank
+// handle -- nb: the NB template axis (0 DIRECT1, 1 DIRECT7, 2 KDTREE, 3 DIRECT26, 4 multi-grid, 5 / 6 packed DIRECT1 /
+// DIRECT7), mode: the MODE axis (0 gradient, 1 Hessian, 2 Gauss-Newton, 3 score only), flags: 1 batched, 2 pre-launched,
+// 4 the ticketed re-evaluation (safe_sum)
+int ndt_debug_launch_plan(size_t n_src, int K, int cus, int nb, int mode, int flags, int out[16]) {
+  if (!out || K < 1 || cus < 1 || nb < 0 || nb > 6 || mode < 0 || mode > 3) return NDT_ERR_INVALID_ARG;
+  EvalConsts ec = debug_eval_consts(cus, nb, mode);
+  ec.safe_sum = (flags & 4) ? 1 : 0;
+  const DerivLaunchPlan pl = plan_derivatives_launch(n_src, K, (flags & 1) != 0, (flags & 2) != 0, false, ec, nullptr);
+  std::memcpy(out, &pl, sizeof(pl));
+  return NDT_OK;
+}
+
+// test seam (not in the public header): xcd_chunk (ndt_device.h), the chunk a block of an XCD-aware launch works on
+int ndt_debug_xcd_chunk(int p, int L, int off, int X, int m) {
+  if (L < 1 || p < 0 || p >= L || off < 0 || X < 1 || m < 0) return NDT_ERR_INVALID_ARG;
+  return xcd_chunk(p, L, off, X, m);
+}
+// ... the whole map: out[p] = xcd_chunk(p, L, off, X, m) for p in [0, L)
+int ndt_debug_xcd_chunk_map(int L, int off, int X, int m, int* out) {
+  if (L < 1 || off < 0 || X < 1 || m < 0 || !out) return NDT_ERR_INVALID_ARG;
+  for (int p = 0; p < L; ++p) out[p] = xcd_chunk(p, L, off, X, m);
+  return NDT_OK;
+}
+
+// test seam (not in the public header): the evaluation log of a handle (EvalLogEntry, ndt_engine.h).  cap > 0: clears it
+// and keeps the next `cap` evaluations; 0: clears and turns it off.  Returns sizeof(EvalLogEntry).
+int ndt_debug_eval_log(ndt_handle* h, int cap) {
+  if (!h || cap < 0) return NDT_ERR_INVALID_ARG;
+  h->eval_log.clear();
+  h->eval_log.shrink_to_fit();
+  h->eval_log.reserve((size_t)cap);
+  h->eval_log_cap = cap;
+  h->eval_log_total = 0;
+  h->eval_log_launches = 0;
+  return (int)sizeof(EvalLogEntry);
+}
+
+// copies up to `cap` entries to `out` (may be null); returns the evaluations logged since ndt_debug_eval_log, kept or not
+int64_t ndt_debug_eval_log_read(const ndt_handle* h, void* out, int cap) {
+  if (!h || cap < 0) return NDT_ERR_INVALID_ARG;
+  const size_t m = std::min(h->eval_log.size(), (size_t)cap);
+  if (out && m) std::memcpy(out, h->eval_log.data(), m * sizeof(EvalLogEntry));
+  return h->eval_log_total;
 }
 
 // test seam (not in the public header): the two-launch build's partition plan for a cloud of n points --

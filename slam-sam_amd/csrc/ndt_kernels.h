@@ -140,6 +140,22 @@ hipError_t sort_source_by_blocks(const float* x, const float* y, const float* z,
 // shaped one block per CU, and the XCD count follows from it
 int derivs_grid_blocks(size_t n_src, int K, int cus);
 int derivs_block_threads(size_t n_src, int K, int cus);
+// The shape of one k_derivatives launch, as launch_derivatives makes it (plan_derivatives_launch): the evaluation log
+// (ndt_debug_eval_log) records it per evaluation, ndt_debug_launch_plan computes it without a device.  Plain ints in this
+// order -- the Python binding reads them by position (EVAL_DESC_FIELDS, slam-sam_amd/__init__.py).
+struct DerivLaunchPlan {
+  int batch, mode, nb, mbox;                     // template axes <BATCH, MODE, NB, MBOX> of the instantiation
+  int threads, blocks, point_blocks, summers;    // per pose row: blocks = point_blocks + summers (dedicated summing blocks)
+  int doubling_split, xcd_count, xcd_stripe;     // EvalConsts fields of the same names
+  int two_level;                                 // point_blocks > single_level_max: the final sum goes through group rows
+  int safe_sum, dyn_lds, cus;                    // ticketed re-evaluation; dynamic LDS bytes per block; compute units
+  int spec;                                      // the first evaluation enqueued behind a build (d_geom), set by the caller
+};
+static_assert(sizeof(DerivLaunchPlan) == 16 * sizeof(int), "DerivLaunchPlan is 16 ints");
+// Everything launch_derivatives decides from the size, the pose count and the engine's consts: the plan and the EvalConsts
+// the kernel receives.  batched: d_poses != nullptr; mbox: a pre-launched launch; xchg: in-kernel cross-rank exchange.
+DerivLaunchPlan plan_derivatives_launch(size_t n_src, int K, bool batched, bool mbox, bool xchg, const EvalConsts& ec,
+                                        EvalConsts* ecl_out);
 size_t derivs_partials_words(size_t n_src, int K, int cus);  // doubles needed in d_partials
 int derivs_counters_per_pose();
 // which finishing wave expands which wave's points: 2 bits per wave (owning SIMD), 4 bits per SIMD (its finishing wave)
@@ -174,7 +190,9 @@ void launch_derivatives(const float* sx, const float* sy, const float* sz, size_
                         hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
                         // single-pose ordinary launches enqueued behind the build of their own grid: the geometry is read
                         // from the build's device-side BuildGeom (and nothing runs after a refused build), `g` is ignored
-                        const BuildGeom* d_geom = nullptr);
+                        const BuildGeom* d_geom = nullptr,
+                        // the shape of this launch (evaluation log), when not null
+                        DerivLaunchPlan* plan_out = nullptr);
 
 // The 80-byte records of leaf slots [0, n) as 48-byte PackedRecords (f64 mean, f32 inverse covariance); a launch
 // whose EvalConsts::packed is set takes that array in place of `rec`.

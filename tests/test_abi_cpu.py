@@ -442,3 +442,173 @@ def test_derivative_launch_shapes(pkg):
         assert shape(200000) == (832, 241, 8, 249)
     finally:
         pkg.set_tuning(**before)
+
+
+def test_xcd_chunk_is_a_bijection(pkg):
+    """xcd_chunk (ndt_device.h) maps the L positions of a row onto its L chunks; a map that were not one-to-one would
+    count some points twice and drop others -- only at the grid sizes where the XCD-aware order is on.  Every XCD count
+    of a device up to a whole MI355X (8), every offset up to three turns round, stripes of 0 (whole row) to 31 chunks per
+    XCD, rows of 1 .. 700 blocks."""
+    for X in range(1, 9):
+        for off in range(3 * X):
+            for m in (0, 1, 2, 3, 13, 31):
+                for L in range(1, 701):
+                    c = pkg.debug_xcd_chunk_map(L, off, X, m)
+                    assert np.array_equal(np.sort(c), np.arange(L)), (X, off, m, L, c)
+    # the single call is the map's
+    assert [pkg.debug_xcd_chunk(p, 245, 4, 8, 0) for p in range(245)] == list(pkg.debug_xcd_chunk_map(245, 4, 8, 0))
+    # with one XCD, or a stripe per position, nothing moves
+    assert np.array_equal(pkg.debug_xcd_chunk_map(300, 0, 1, 0), np.arange(300))
+
+
+def _derivative_kernel_static_lds():
+    """{(BATCH, NB): largest static LDS of the k_derivatives instantiations of that kind} as hipcc reports it
+    (-Rpass-analysis=kernel-resource-usage, what tools/kernel_resources.py reads)."""
+    import subprocess
+    import tempfile
+    src = os.path.join(ROOT, "slam-sam_amd", "csrc", "ndt_derivs.hip")
+    with tempfile.TemporaryDirectory() as d:
+        p = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
+                            "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.path.join(d, "d.o")],
+                           capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lds, name = {}, None
+    for ln in p.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", ln)
+        if m:
+            name = m.group(1)
+        m = re.search(r"LDS Size \[bytes/block\]: (\d+)", ln)
+        if m and name:
+            t = re.search(r"k_derivativesILb(\d)ELi(\d)ELi(\d)ELb(\d)E", name)
+            if t:
+                key = (int(t.group(1)), int(t.group(3)))
+                lds[key] = max(lds.get(key, 0), int(m.group(1)))
+    return lds
+
+
+def test_derivative_launch_lds_fits_a_compute_unit(pkg):
+    """Every block shape a launch can take (64 .. 1024 threads, through ndt_tuning::deriv_block), every neighbourhood and
+    both kinds of launch ask for dynamic LDS that, with the kernel's static LDS, fits the 160 KiB of a gfx950 compute
+    unit -- a launch that does not fit fails at dispatch, and only at that shape."""
+    static = _derivative_kernel_static_lds()
+    assert sorted(static) == [(b, nb) for b in (0, 1) for nb in range(7)], sorted(static)
+    before = pkg.get_tuning()
+    worst = 0
+    try:
+        for threads in range(64, 1025, 64):
+            pkg.set_tuning(deriv_block=threads)
+            for nb in range(7):
+                for K in (1, 20):
+                    for n in (1000, 100000, 200000, 1200000):   # (one block per compute unit asks for more LDS)
+                        for mbox in ((False, True) if K == 1 else (False,)):
+                            d = pkg.debug_launch_plan(n, K=K, nb=nb, mode=1, mbox=mbox)
+                            assert d["threads"] == threads and d["nb"] == nb and d["batch"] == (K > 1)
+                            total = d["dyn_lds"] + static[(d["batch"], nb)]
+                            worst = max(worst, total)
+                            assert total <= 160 * 1024, (threads, nb, K, n, d, static[(d["batch"], nb)])
+    finally:
+        pkg.set_tuning(**before)
+    assert worst > 80 * 1024   # (the one-block-per-unit request was among them)
+
+
+# sizes the GPU sweep (tests/test_gpu_launch_shapes.py) runs at, with the single-pose shape each must take on 256 compute
+# units: (n, threads, point blocks, summing blocks, doubling split, two-level)
+SWEEP_SHAPES = [
+    (20000, 256, 79, 4, 0, 0),          # 4 waves
+    (55000, 320, 172, 4, 0, 0),         # 5
+    (70000, 384, 183, 4, 0, 0),         # 6
+    (80000, 448, 179, 4, 0, 0),         # 7
+    (95000, 512, 186, 4, 0, 0),         # 8, small-source partition
+    (130000, 512, 254, 1, 0, 0),        # 8, one summing block (pb 253 .. 255)
+    (131072, 512, 256, 0, 1, 0),        # 8, no unit spare: the doubling split
+    (140000, 576, 244, 4, 0, 0),        # 9
+    (155000, 640, 243, 4, 0, 0),        # 10
+    (170000, 704, 242, 4, 0, 0),        # 11
+    (190000, 768, 248, 4, 0, 0),        # 12
+    (200000, 832, 241, 4, 0, 0),        # 13: C3
+    (220000, 896, 246, 4, 0, 0),        # 14
+    (235000, 960, 245, 4, 0, 0),        # 15
+    (250000, 1024, 245, 4, 0, 0),       # 16
+    (261000, 1024, 255, 1, 0, 0),       # 16, one summing block
+    (400000, 512, 782, 1, 0, 0),        # several residency rounds
+    (1200000, 512, 2344, 0, 0, 1),      # the two-level final sum
+]
+
+
+def test_derivative_launch_plans(pkg):
+    """plan_derivatives_launch (the host side of every k_derivatives launch) at the sizes of the GPU sweep and a few
+    edges: the shape, the summing arrangement, the XCD order and the template axes it picks; ndt_debug_launch_shape is
+    the same function's."""
+    for n, t, pb, ns, split, two in SWEEP_SHAPES:
+        d = pkg.debug_launch_plan(n)
+        got = (d["threads"], d["point_blocks"], d["summers"], d["doubling_split"], d["two_level"])
+        assert got == (t, pb, ns, split, two), (n, got)
+        assert d["blocks"] == pb + ns and pkg.debug_launch_shape(n) == (t, pb, ns, pb + ns)
+        # XCD-aware chunks on the resident single-pose grids only (ndt_tuning::deriv_xcd = 1)
+        assert (d["xcd_count"], d["xcd_stripe"]) == ((8, 0) if d["blocks"] <= 257 else (0, 0)), (n, d)
+        # one block per compute unit where the grid is at most one block per unit
+        assert (d["dyn_lds"] > 80 * 1024) == (d["blocks"] <= 256), (n, d)
+        # batched K = 1 has the single-pose partition; K = 20 keeps it up to 196 x 512 points and at 131072
+        b1 = pkg.debug_launch_plan(n, K=1, batched=True)
+        assert (b1["threads"], b1["point_blocks"]) == (t, pb) and b1["doubling_split"] == 0 and b1["xcd_count"] == 0
+        b20 = pkg.debug_launch_plan(n, K=20)
+        assert b20["batch"] == 1 and b20["summers"] in (0, 1) and b20["doubling_split"] == 0
+        assert (b20["threads"] == t) == (n <= 196 * 512 or t == 512), (n, b20)
+        # a pre-launched launch has the ordinary one's shape; the ticketed re-evaluation has no summing block
+        m = pkg.debug_launch_plan(n, mbox=True)
+        assert m["mbox"] == 1 and {k: v for k, v in m.items() if k != "mbox"} == {k: v for k, v in d.items() if k != "mbox"}
+        s = pkg.debug_launch_plan(n, safe_sum=True)
+        assert s["safe_sum"] == 1 and s["summers"] == 0 and s["doubling_split"] == 0 and s["blocks"] == pb
+    # the template axes: MODE from (score only, Hessian, Gauss-Newton), NB from the neighbourhood and record format
+    for nb in range(7):
+        for mode in range(4):
+            d = pkg.debug_launch_plan(20000, nb=nb, mode=mode)
+            assert (d["nb"], d["mode"], d["batch"], d["mbox"]) == (nb, mode, 0, 0)
+    assert pkg.debug_launch_plan(20000, mbox=True, batched=True)["mbox"] == 0   # a batched launch never takes the mailbox
+    before = pkg.get_tuning()
+    try:
+        for blk in (64, 128, 192):            # 1 .. 3 waves: only through ndt_tuning::deriv_block
+            pkg.set_tuning(deriv_block=blk)
+            d = pkg.debug_launch_plan(20000)
+            assert d["threads"] == blk and d["point_blocks"] == -(-20000 // blk)
+        pkg.set_tuning(**before)
+        pkg.set_tuning(deriv_single_level_max=8)   # a two-level sum over a few rows
+        d = pkg.debug_launch_plan(20000)
+        assert d["two_level"] == 1 and d["summers"] == 0 and d["doubling_split"] == 0
+        pkg.set_tuning(**before)
+        pkg.set_tuning(deriv_summer=0)             # ticket summer: no dedicated block, no split
+        d = pkg.debug_launch_plan(200000)
+        assert d["summers"] == 0 and d["doubling_split"] == 0 and d["threads"] == 832
+        pkg.set_tuning(**before)
+        pkg.set_tuning(deriv_dedicated=0)          # block 0 doubles as the summer: 1024-thread blocks over 256 units
+        d = pkg.debug_launch_plan(200000)
+        assert d["summers"] == 0 and d["threads"] == 832 and d["doubling_split"] == 1
+        pkg.set_tuning(**before)
+        pkg.set_tuning(deriv_xcd=2)                # stripes on grids of several residency rounds and batched launches
+        d = pkg.debug_launch_plan(400000)
+        assert d["xcd_count"] == 8 and d["xcd_stripe"] == 32 * 2
+        assert pkg.debug_launch_plan(200000, K=20)["xcd_count"] == 8
+        pkg.set_tuning(deriv_xcd=0)
+        assert pkg.debug_launch_plan(200000)["xcd_count"] == 0
+    finally:
+        pkg.set_tuning(**before)
+
+
+def test_summer_switches_keep_the_partition(pkg):
+    """include/ndt_hip.h: no ndt_tuning field but deriv_block / deriv_single_level_max changes a result bit.  The summing
+    arrangement (deriv_summer, deriv_dedicated, deriv_summer_split) must therefore leave the block shape -- the partition
+    of the scan -- alone at every size.  (It did not: the single-pose shape counted the dedicated summing block's unit
+    only when one was asked for, so 146 881 points ran 640-thread blocks by default and 576 with deriv_summer = 0.)"""
+    sizes = list(range(129000, 262000, 97)) + [146881, 163201, 179521, 195841, 212161, 228481, 244801, 261120, 261121]
+    base = {n: pkg.debug_launch_plan(n)["threads"] for n in sizes}
+    before = pkg.get_tuning()
+    try:
+        for kw in (dict(deriv_summer=0), dict(deriv_dedicated=0), dict(deriv_summer_split=0), dict(deriv_summer_split=8),
+                   dict(deriv_xcd=0), dict(deriv_xcd=2), dict(deriv_one_block_per_cu=0)):
+            pkg.set_tuning(**before)
+            pkg.set_tuning(**kw)
+            for n in sizes:
+                d = pkg.debug_launch_plan(n)
+                assert d["threads"] == base[n] and d["point_blocks"] == -(-n // base[n]), (kw, n, d, base[n])
+    finally:
+        pkg.set_tuning(**before)
