@@ -460,6 +460,28 @@ int ndt_result_covariance(const double hessian36[36], double eps, int gtsam_orde
 /* output cloud of align(): source transformed by T (device-side), packed xyz */
 int ndt_transform_source(ndt_handle* h, const float T_colmajor[16], float* out_xyz, size_t cap_points);
 
+/* getFitnessScore(max_range) [RECALLED: PCL 1.14 Registration::getFitnessScore, registration.hpp]: every source point
+ * is moved by T (the f32 arithmetic of ndt_transform_source, bit for bit), its squared distance d^2 to the NEAREST RAW
+ * target point is found (exactly: a point-level index over the target's points, not the voxel grid), and the mean of
+ * d^2 over the points with d^2 <= max_range (squared distance, inclusive) is the fitness.  Deviations: non-finite target
+ * points are not candidates; non-finite source points are skipped (neither counted nor summed).  The index is built
+ * by the first fitness call after the target changed and kept until the next ndt_set_target*, keyframe target or
+ * resolution-driven rebuild; targets consumed through ndt_set_target_device* (nothing retained) and multi-grid targets
+ * are NDT_ERR_UNSUPPORTED.  With a sharded source the result covers the local shard: ranks add sum_sq_dist and
+ * n_inliers themselves.  Results are bit-reproducible (fixed-order f64 sums, no float atomics). */
+typedef struct ndt_fitness {
+  double fitness_score;   /* sum_sq_dist / n_inliers, DBL_MAX when n_inliers == 0 */
+  double sum_sq_dist;     /* f64 sum of d^2 over the inliers */
+  int64_t n_inliers;      /* finite source points with d^2 <= max_range */
+  int64_t n_points;       /* finite source points queried */
+} ndt_fitness;
+/* sq_dists_out (nullable, host, cap >= n_source): per source point d^2 to its nearest target point;
+ * NaN for a non-finite source point, +INF where d^2 > max_range (not searched exactly) */
+int ndt_fitness_score(ndt_handle* h, const float T_colmajor[16], double max_range, ndt_fitness* out,
+                      float* sq_dists_out, size_t cap);
+/* K transforms (K x 16 floats, column-major) in one query launch; out[k] equals ndt_fitness_score at transform k */
+int ndt_fitness_scores(ndt_handle* h, const float* transforms_colmajor, int K, double max_range, ndt_fitness* out);
+
 /* ---- voxel grid accessors ------------------------------------------------ */
 int ndt_get_grid_info(const ndt_handle* h, ndt_grid_info* out);
 /* getTargetCells().getLeaves(): valid leaves sorted by ascending index; returns

@@ -35,6 +35,7 @@
 #include <array>
 #include <cstddef>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <memory>
 #include <string>
@@ -459,6 +460,19 @@ class NormalDistributionsTransform
   int getFinalNumIteration() const { return res_.iterations; }
   double getTransformationProbability() const { return res_.transform_probability; }
   double getNearestVoxelTransformationLikelihood() const { return res_.nearest_voxel_transformation_likelihood; }
+  // pcl::Registration::getFitnessScore(max_range) [RECALLED]: mean squared distance from the source, moved by the last
+  // align's final transformation (identity before any align), to the nearest raw target point, over the points with
+  // d^2 <= max_range (a squared distance) -- on the device (ndt_fitness_score).  PCL's own method is not virtual: it
+  // searches the kd-tree this adapter never lets PCL build, so call this one on the adapter type, not through a
+  // pcl::Registration pointer.  On error: DBL_MAX, and lastStatus() says why.
+  double getFitnessScore(double max_range = std::numeric_limits<double>::max()) {
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return std::numeric_limits<double>::max(); }
+    float T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    if (aligned_) std::memcpy(T, res_.final_transformation, sizeof(T));
+    ndt_fitness f;
+    status_ = ndt_fitness_score(h_, T, max_range, &f, nullptr, 0);
+    return status_ == NDT_OK ? f.fitness_score : std::numeric_limits<double>::max();
+  }
 
   // scoring-only calls of pclomp: score of `cloud` under transform T against the
   // current target, no gradient, nothing about the engine's source / result changes except the
@@ -654,6 +668,7 @@ class NormalDistributionsTransform
     return status_ == NDT_OK;
   }
   void run(const float* guess) {
+    aligned_ = true;
     std::memset(&res_, 0, sizeof(res_));
     std::memcpy(res_.final_transformation, guess, sizeof(float) * 16);
     if (!h_) { status_ = NDT_ERR_NO_DEVICE; return; }
@@ -678,6 +693,7 @@ class NormalDistributionsTransform
   ndt_params prm_{};
   ndt_handle* h_ = nullptr;
   ndt_result res_{};
+  bool aligned_ = false;   // res_ holds an align's outcome (getFitnessScore's transform; identity before)
   int status_ = NDT_OK;
   size_t n_src_ = 0;
   bool fill_output_ = false;

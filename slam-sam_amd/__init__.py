@@ -13,6 +13,7 @@ The directory name has a hyphen; load it with `__graft_entry__.load_package()`
 """
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 
@@ -75,6 +76,14 @@ class Score(C.Structure):
         ("nearest_voxel_transformation_likelihood", C.c_double), ("n_pairs", C.c_int64),
         ("n_points_with_neighbors", C.c_int64),
     ]
+
+
+class Fitness(C.Structure):
+    _fields_ = [("fitness_score", C.c_double), ("sum_sq_dist", C.c_double), ("n_inliers", C.c_int64),
+                ("n_points", C.c_int64)]
+
+
+DBL_MAX = sys.float_info.max
 
 
 class Leaf(C.Structure):
@@ -210,6 +219,7 @@ ABI_SYMBOLS = [
     "ndt_voxel_downsample_device", "ndt_voxel_downsample", "ndt_get_iteration_history",
     "ndt_get_tuning", "ndt_set_tuning", "ndt_set_keepwarm", "ndt_get_keepwarm",
     "ndt_comm_p2p_selftest", "ndt_comm_p2p_stats", "ndt_angle_tables", "ndt_gauss_constants", "ndt_svn_rbf_kernel",
+    "ndt_fitness_score", "ndt_fitness_scores",
 ]
 
 _lib = None
@@ -257,6 +267,8 @@ def lib():
         L.ndt_unpack_eval.restype = None
         L.ndt_unpack_eval.argtypes = [dp, dp, dp, dp]
         L.ndt_transform_source.argtypes = [vp, fp, fp, C.c_size_t]
+        L.ndt_fitness_score.argtypes = [vp, fp, C.c_double, C.POINTER(Fitness), fp, C.c_size_t]
+        L.ndt_fitness_scores.argtypes = [vp, fp, C.c_int, C.c_double, C.POINTER(Fitness)]
         L.ndt_get_grid_info.argtypes = [vp, C.POINTER(GridInfo)]
         L.ndt_export_leaves.restype = C.c_int64
         L.ndt_export_leaves.argtypes = [vp, C.POINTER(Leaf), C.c_size_t]
@@ -707,6 +719,39 @@ class NormalDistributionsTransform:
         return [dict(score=o.score, transform_probability=o.transform_probability,
                      nvtl=o.nearest_voxel_transformation_likelihood, n_pairs=o.n_pairs,
                      n_points_with_neighbors=o.n_points_with_neighbors) for o in out]
+
+    # --- getFitnessScore [RECALLED: PCL Registration::getFitnessScore] ---
+    def fitness(self, T, max_range=DBL_MAX, per_point=False):
+        """Nearest-point fitness of the current source under T against the raw target points: dict(fitness_score,
+        sum_sq_dist, n_inliers, n_points); with per_point=True also `sq_dists` (d^2 per source point, NaN for a
+        non-finite point, +inf where d^2 > max_range).  max_range is a SQUARED distance, as in PCL."""
+        a = _colmajor(T)
+        out = Fitness()
+        sq = None
+        if per_point:
+            sq = np.zeros(getattr(self, "_n_src", 0), np.float32)
+        self._check(lib().ndt_fitness_score(self._h, _fp(a), float(max_range), C.byref(out),
+                                            _fp(sq) if sq is not None else None, 0 if sq is None else len(sq)))
+        d = dict(fitness_score=out.fitness_score, sum_sq_dist=out.sum_sq_dist, n_inliers=out.n_inliers,
+                 n_points=out.n_points)
+        if sq is not None:
+            d["sq_dists"] = sq
+        return d
+
+    def fitnessMany(self, transforms, max_range=DBL_MAX):
+        """K transforms in one query launch: list of dicts like fitness()."""
+        t = np.ascontiguousarray(np.stack([_colmajor(T) for T in transforms]), dtype=np.float32)
+        K = len(t)
+        out = (Fitness * K)()
+        self._check(lib().ndt_fitness_scores(self._h, _fp(t), K, float(max_range), out))
+        return [dict(fitness_score=o.fitness_score, sum_sq_dist=o.sum_sq_dist, n_inliers=o.n_inliers,
+                     n_points=o.n_points) for o in out]
+
+    def getFitnessScore(self, max_range=DBL_MAX):
+        """PCL's getFitnessScore(max_range): the fitness at the last align's final transformation (identity before
+        any align)."""
+        T = self._result["T"] if self._raw is not None else np.eye(4)
+        return self.fitness(T, max_range)["fitness_score"]
 
     # --- 2-D covariance estimators of tier4 ndt_omp [RECALLED] (SURVEY 8f-4) ---
     def proposePosesToSearch(self, offsets_x, offsets_y):

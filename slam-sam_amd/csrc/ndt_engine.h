@@ -119,6 +119,47 @@ struct EvalLogEntry {
 };
 static_assert(sizeof(EvalLogEntry) == 464, "EvalLogEntry layout is read from Python");
 
+// Geometry of the point-level nearest-neighbour index (ndt_fitness.hip): cells of edge `c` on the bounding box of the
+// target's finite points, cell (i, j, k) = floor((p - lo) * inv_c) per axis in f32, key i + dims0 * (j + dims1 * k).
+struct FitGeom {
+  float lo[3];
+  float c, inv_c;
+  int dims[3];
+  uint32_t ncells;     // dims0 * dims1 * dims2 (< 2^30); also the key of a non-finite point
+  uint32_t hash_mask;  // open-addressing table of hash_mask + 1 slots
+  int n_finite;
+};
+
+// The index itself (built lazily by the first fitness call after the target changed; owns every buffer it uses --
+// the grid build's scratch is reused by ndt_voxel_downsample* and by builds).
+struct FitIndex {
+  uint64_t gen = 0;                  // ndt_handle::tgt_gen of the target it indexes
+  bool valid = false;
+  FitGeom g{};
+  DevBuf<float> pts;                 // the finite target points as float4, sorted by cell (stable)
+  DevBuf<uint32_t> tab;              // hash table, 4 words per slot: {cell key, first point, end point, 0}
+  DevBuf<uint32_t> keys, vals, keys2, vals2;
+  DevBuf<char> sort_tmp;
+  DevBuf<BuildGeom> plan;
+  BuildGeom plan_h{};
+  DevBuf<float> bslab;               // per-block bounds {min xyz, max xyz}
+  DevBuf<int> cslab;                 // ... and finite counts
+  PinBuf<float> bslab_h;
+  PinBuf<int> cslab_h;
+  // query
+  DevBuf<float> dist;                // K x n_src: d^2 (NaN / +INF as the C-ABI documents)
+  DevBuf<int> work;                  // [0] unresolved entries, then the entries (k * n_src + i)
+  DevBuf<float> poses;               // K x 12 floats {R row-major, t}
+  DevBuf<double> slab;               // K x blocks x 3: {sum d^2, inliers, finite points}
+  PinBuf<double> slab_h;
+  void release() {
+    pts.release(); tab.release(); keys.release(); vals.release(); keys2.release(); vals2.release(); sort_tmp.release();
+    plan.release(); bslab.release(); cslab.release(); bslab_h.release(); cslab_h.release(); dist.release(); work.release();
+    poses.release(); slab.release(); slab_h.release();
+    valid = false;
+  }
+};
+
 }  // namespace engine
 }  // namespace ndt
 
@@ -137,6 +178,8 @@ struct ndt_handle {
   // target
   DevBuf<float> tx, ty, tz;          // owned copy when the target came from the host
   size_t n_tgt = 0;
+  uint64_t tgt_gen = 0;              // counts target builds (build_begin): what the fitness index was built for
+  FitIndex fit;                      // point-level nearest-neighbour index of getFitnessScore (ndt_fitness.hip)
   bool have_grid = false;
   GridGeom geom{};
   int max_b[3] = {0, 0, 0};

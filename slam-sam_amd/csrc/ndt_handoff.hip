@@ -103,6 +103,7 @@ int build_begin(ndt_handle* h, const float* x, const float* y, const float* z, s
   h->multi_active = false;
   h->src_sorted = false;
   h->n_tgt = n;
+  ++h->tgt_gen;   // (the fitness index, if any, is rebuilt by the next fitness call)
   h->n_slots = h->n_valid = 0;
   br = ndt_handle::BuildRun{};
   br.x = x; br.y = y; br.z = z; br.n = n;
