@@ -497,6 +497,39 @@ int ndt_newton_align(const ndt_params* p, int64_t n_source_total,
                      const float guess_colmajor[16], const float* regularization_pose_or_null,
                      ndt_eval_fn fn, void* ctx, ndt_result* out);
 
+/* ---- multi-hypothesis align: K Newton loops in lockstep, one batched evaluation per round ---- */
+#define NDT_ALIGN_BATCH_MAX 256
+/* Host-only counterpart of ndt_newton_align for K guesses (K x 16 floats, column-major), 1 <= K <= NDT_ALIGN_BATCH_MAX.
+ * In every round each hypothesis still running advances on the host until it needs an evaluation or stops; fn then
+ * receives the requests of those K_round hypotheses, in hypothesis order (poses6: K_round x 6, T16: K_round x 16
+ * column-major, need_h: K_round flags), and fills out[K_round x NDT_EVAL_WORDS] with the GLOBAL evaluations.  Each
+ * hypothesis behaves as ndt_newton_align from its guess with the same evaluator (trials without the Hessian, one
+ * re-evaluation at the accepted step, no memo), so out[k] is what ndt_newton_align gives for guess k; ms_total is the
+ * wall time of the whole call.  A failing fn ends the call with its code.  NDT_ERR_INVALID_ARG for K outside the range
+ * or a NULL pointer (regularization_pose_or_null excepted). */
+typedef int (*ndt_eval_batch_fn)(void* ctx, int K, const double* poses6, const float* T16, const int* need_h,
+                                 double* out);
+int ndt_newton_align_batch(const ndt_params* p, int64_t n_source_total, const float* guesses16_colmajor, int K,
+                           const float* regularization_pose_or_null, ndt_eval_batch_fn fn, void* ctx, ndt_result* out);
+/* align(guess_k) for k < K against the handle's target, source, parameters and regularisation pose: K Newton /
+ * More-Thuente loops of the ndt_align product path (the Hessian in every trial, repeated requests answered without a
+ * launch) advanced in lockstep, the pending evaluations of one round in ONE batched kernel launch -- so a call costs
+ * max_k n_evaluations launches (ndt_timing.n_eval_launches), not their sum.
+ *  - arguments: 1 <= K <= NDT_ALIGN_BATCH_MAX and no NULL pointer, else NDT_ERR_INVALID_ARG (out untouched);
+ *  - out[k] is filled as ndt_align fills its result; n_evaluations / n_evaluations_reused are per hypothesis, ms_total
+ *    is the wall time of the call, ms_device the device time of its launches while kernel timing is on;
+ *  - without a target (or after a failed deferred build) every out[k] holds its guess with converged = 0, and the call
+ *    returns what ndt_align would; a reducer other than NDT_REDUCE_NONE is NDT_ERR_UNSUPPORTED (guesses in out);
+ *  - the handle's align state is left alone: ndt_get_iteration_history still reports the last ndt_align, the
+ *    pre-launch and stream-placement state is not touched, and an ndt_align after the call gives the bits it gave before;
+ *  - independence: out[k] depends on guess k alone -- not on the other guesses, their order or how many are still
+ *    running in a round -- as long as the source is evaluated in the order it was handed over (NDT_SOURCE_ORDER_KEEP, or
+ *    AUTO below its sort threshold).  A source the engine sorts is sorted once per (source, target), by the guess of
+ *    the first call that needs it (here guesses[0]), and every round of the call keeps that order;
+ *  - where the single-pose and batched launches partition the source alike (at most 512 points per compute unit:
+ *    131 072 on an MI355X), out[k] is bit-identical to ndt_align(guess k) but for the timings. */
+int ndt_align_batch(ndt_handle* h, const float* guesses16_colmajor, int K, ndt_result* out);
+
 /* ---- multi-GPU: one process per GPU, source sharded, target replicated ---- */
 /* contiguous shard of n items for rank r of nranks */
 void ndt_shard_range(size_t n, int rank, int nranks, size_t* begin, size_t* count);

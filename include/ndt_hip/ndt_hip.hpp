@@ -509,6 +509,31 @@ class NormalDistributionsTransform
     return r;
   }
 
+  // align() from each of K guesses (1 <= K <= 256) in shared launches (ndt_align_batch): one result per guess, its final
+  // transformation in `pose` as getResult().pose holds it after align().  The adapter's own result -- getFinalTransformation,
+  // hasConverged, getResult and its iteration arrays -- stays that of the last align(); the results here carry no iteration
+  // arrays.  lastStatus() reports this call; on an error every result holds its guess.
+  std::vector<NdtResult> alignMany(const std::vector<Matrix4f>& guesses) {
+    const size_t K = guesses.size();
+    std::vector<float> g(16 * (K ? K : 1));
+    for (size_t k = 0; k < K; ++k) detail::to_colmajor(guesses[k], 4, 4, &g[16 * k]);
+    std::vector<ndt_result> raw(K ? K : 1);
+    status_ = h_ ? ndt_align_batch(h_, g.data(), (int)K, raw.data()) : NDT_ERR_NO_DEVICE;
+    std::vector<NdtResult> out(K);
+    for (size_t k = 0; k < K; ++k) {
+      if (status_ != NDT_OK) {  // the reference returns the prior, not converged
+        std::memset(&raw[k], 0, sizeof(raw[k]));
+        std::memcpy(raw[k].final_transformation, &g[16 * k], sizeof(float) * 16);
+      }
+      out[k].pose = detail::from_colmajor<Matrix4f>(raw[k].final_transformation, 4, 4);
+      out[k].transform_probability = (float)raw[k].transform_probability;
+      out[k].nearest_voxel_transformation_likelihood = (float)raw[k].nearest_voxel_transformation_likelihood;
+      out[k].iteration_num = raw[k].iterations;
+      out[k].hessian = detail::from_rowmajor<Matrix6d>(raw[k].hessian, 6, 6);
+    }
+    return out;
+  }
+
   // ---- voxel grid (ref: include/pipeline.hpp:178-206) ----
   const TargetGrid& getTargetCells() {
     ndt_grid_info gi;

@@ -196,6 +196,9 @@ def apply_env_tuning(environ=None):
 EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_int,
                       C.POINTER(C.c_double))
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
+EVAL_BATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_float),
+                            C.POINTER(C.c_int), C.POINTER(C.c_double))
+ALIGN_BATCH_MAX = 256
 
 # every symbol include/ndt_hip.h declares
 ABI_SYMBOLS = [
@@ -219,7 +222,7 @@ ABI_SYMBOLS = [
     "ndt_voxel_downsample_device", "ndt_voxel_downsample", "ndt_get_iteration_history",
     "ndt_get_tuning", "ndt_set_tuning", "ndt_set_keepwarm", "ndt_get_keepwarm",
     "ndt_comm_p2p_selftest", "ndt_comm_p2p_stats", "ndt_angle_tables", "ndt_gauss_constants", "ndt_svn_rbf_kernel",
-    "ndt_fitness_score", "ndt_fitness_scores",
+    "ndt_fitness_score", "ndt_fitness_scores", "ndt_newton_align_batch", "ndt_align_batch",
 ]
 
 _lib = None
@@ -269,6 +272,9 @@ def lib():
         L.ndt_transform_source.argtypes = [vp, fp, fp, C.c_size_t]
         L.ndt_fitness_score.argtypes = [vp, fp, C.c_double, C.POINTER(Fitness), fp, C.c_size_t]
         L.ndt_fitness_scores.argtypes = [vp, fp, C.c_int, C.c_double, C.POINTER(Fitness)]
+        L.ndt_align_batch.argtypes = [vp, fp, C.c_int, C.POINTER(Result)]
+        L.ndt_newton_align_batch.argtypes = [C.POINTER(Params), C.c_int64, fp, C.c_int, fp, EVAL_BATCH_FN, vp,
+                                             C.POINTER(Result)]
         L.ndt_get_grid_info.argtypes = [vp, C.POINTER(GridInfo)]
         L.ndt_export_leaves.restype = C.c_int64
         L.ndt_export_leaves.argtypes = [vp, C.POINTER(Leaf), C.c_size_t]
@@ -687,6 +693,22 @@ class NormalDistributionsTransform:
 
     computeTransformation = align
 
+    def alignMany(self, guesses):
+        """align() from each of K guesses (1 <= K <= 256) in shared launches (ndt_align_batch): a list of
+        (final 4x4, result dict as getResult() gives it).  getResult() / getFinalTransformation() keep reporting the
+        last align()."""
+        g = np.ascontiguousarray(np.stack([x.a if isinstance(x, ColMajor4f) else _colmajor(x) for x in guesses]),
+                                 dtype=np.float32) if len(guesses) else np.zeros((0, 16), np.float32)
+        K = len(g)
+        out = (Result * max(K, 1))()
+        self._check(lib().ndt_align_batch(self._h, _fp(g), K, out))
+        res = []
+        for k in range(K):
+            d = result_to_dict(out[k])
+            d["iteration_num"] = d["iterations"]
+            res.append((d["T"], d))
+        return res
+
     @property
     def _result(self):
         if self._cooked is None and self._raw is not None:
@@ -1053,6 +1075,37 @@ def newton_align(params, n_source_total, guess, eval_fn, regularization_pose=Non
     if rc != 0:
         raise NdtError(rc, "ndt_newton_align")
     return result_to_dict(r)
+
+
+def newton_align_batch(params, n_source_total, guesses, batch_eval_fn, regularization_pose=None):
+    """K host Newton/More-Thuente loops in lockstep with an external batched evaluator (ndt_newton_align_batch).
+
+    batch_eval_fn(poses [n, 6], T [n, 4, 4], need_h [n] bool) -> [n, 32] packed doubles, called once per round with
+    the requests of the hypotheses still running.  Returns one result dict per guess, as newton_align() does.
+    """
+    def _cb(_ctx, n, pose_p, T_p, need_p, out_p):
+        try:
+            poses = np.ctypeslib.as_array(pose_p, shape=(n * 6,)).reshape(n, 6).copy()
+            T = np.ctypeslib.as_array(T_p, shape=(n * 16,)).reshape(n, 4, 4).transpose(0, 2, 1).copy()
+            need = np.ctypeslib.as_array(need_p, shape=(n,)).astype(bool)
+            w = np.asarray(batch_eval_fn(poses, T, need), dtype=np.float64).reshape(n, EVAL_WORDS)
+            np.ctypeslib.as_array(out_p, shape=(n * EVAL_WORDS,))[:] = w.ravel()
+            return 0
+        except Exception:  # never let an exception cross the C boundary
+            import traceback
+            traceback.print_exc()
+            return -1
+    cb = EVAL_BATCH_FN(_cb)
+    g = np.ascontiguousarray(np.stack([_colmajor(x) for x in guesses]), dtype=np.float32) if len(guesses) \
+        else np.zeros((0, 16), np.float32)
+    K = len(g)
+    reg = _colmajor(regularization_pose) if regularization_pose is not None else None
+    out = (Result * max(K, 1))()
+    rc = lib().ndt_newton_align_batch(C.byref(params), int(n_source_total), _fp(g), K,
+                                      _fp(reg) if reg is not None else None, cb, None, out)
+    if rc != 0:
+        raise NdtError(rc, "ndt_newton_align_batch")
+    return [result_to_dict(out[k]) for k in range(K)]
 
 
 def pack_eval(score, gradient, hessian, nvtl_sum=0.0, n_with=0, n_pairs=0):

@@ -1643,9 +1643,11 @@ void derivs_item_owners(int threads, unsigned int* owners_out, unsigned int* fin
 int derivs_grid_blocks(size_t n_src, int K, int cus) { return derivs_point_blocks(n_src, K, cus) + derivs_dedicated_summer(n_src, K, cus); }
 
 DerivLaunchPlan plan_derivatives_launch(size_t n_src, int K, bool batched, bool mbox, bool xchg, const EvalConsts& ec,
-                                        EvalConsts* ecl_out) {
+                                        EvalConsts* ecl_out, bool batched_shape) {
   const int cus = cus_or_default(ec.compute_units);
-  const int Kp = batched ? K : 1;
+  // (batched_shape: a batched launch of one pose takes the shape of a batched launch of several -- the partition, hence
+  // the bits, of a pose's sums then do not depend on how many poses share the launch)
+  const int Kp = batched ? (batched_shape && K == 1 ? 2 : K) : 1;
   int blocks = derivs_grid_blocks(n_src, Kp, cus);
   const int threads = derivs_block_threads(n_src, Kp, cus);
   const int mode = ec.score_only ? 3 : (!ec.need_hessian ? 0 : (ec.gauss_newton ? 2 : 1));
@@ -1735,9 +1737,11 @@ void launch_derivatives(const float* sx, const float* sy, const float* sz, size_
                         double* d_out, hipStream_t s, unsigned long long* d_flag,
                         unsigned long long seq, const PoseMailbox* d_mbox, const XchgInfo* d_xinfo,
                         unsigned long long xround, unsigned int* d_arrive_ctr, unsigned long long* d_arrived_host,
-                        hipEvent_t ev_start, hipEvent_t ev_stop, const BuildGeom* d_geom, DerivLaunchPlan* plan_out) {
+                        hipEvent_t ev_start, hipEvent_t ev_stop, const BuildGeom* d_geom, DerivLaunchPlan* plan_out,
+                        bool batched_shape) {
   EvalConsts ecl;
-  DerivLaunchPlan pl = plan_derivatives_launch(n_src, K, d_poses != nullptr, d_mbox != nullptr, d_xinfo != nullptr, ec, &ecl);
+  DerivLaunchPlan pl = plan_derivatives_launch(n_src, K, d_poses != nullptr, d_mbox != nullptr, d_xinfo != nullptr, ec, &ecl,
+                                               batched_shape);
   pl.spec = d_geom != nullptr ? 1 : 0;
   if (plan_out != nullptr) *plan_out = pl;
   const int blocks = pl.blocks, threads = pl.threads, mode = pl.mode, nb = pl.nb;

@@ -588,6 +588,13 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
 }
 
 
+// (the heartbeat pauses while an align runs, and counts its period from the align's end)
+struct AlignBusy {
+  KeepWarm& k;
+  explicit AlignBusy(KeepWarm& kw) : k(kw) { k.touch(); }
+  ~AlignBusy() { k.touch(); }
+};
+
 }  // namespace engine
 }  // namespace ndt
 
@@ -597,11 +604,7 @@ int ndt_align(ndt_handle* h, const float guess[16], ndt_result* out) {
   if (!h || !guess || !out) return NDT_ERR_INVALID_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  struct Busy {   // (the heartbeat pauses while an align runs, and counts its period from the align's end)
-    KeepWarm& k;
-    explicit Busy(KeepWarm& kw) : k(kw) { k.touch(); }
-    ~Busy() { k.touch(); }
-  } busy(h->keepwarm);
+  AlignBusy busy(h->keepwarm);
   h->spec_build_failed = false;
   h->spec_first = first_eval_behind_build(h);   // the build's verdict is then collected inside the first evaluation
   if (!h->spec_first) {
@@ -711,15 +714,19 @@ int ndt_comm_info(char* path_buf, size_t cap) { return Reducer::library_info(pat
 
 int ndt_comm_rank_count(const ndt_handle* h) { return h ? h->red.rank_count() : NDT_ERR_INVALID_ARG; }
 
-// overlap: host work that does not need this evaluation's results, run between the launch and the wait
+// overlap: host work that does not need this evaluation's results, run between the launch and the wait.
+// fixed_order: the source order was decided before this call (no sort by this batch's first pose); batched_shape: the
+// launch shape of K > 1 at every K (plan_derivatives_launch) -- the two together make a pose's result independent of
+// the other poses in the batch (the rounds of ndt_align_batch).
 static int eval_batch(ndt_handle* h, const double* poses6, const float* transforms, int K, int compute_hessian,
-                      bool score_only, double* out, void (*overlap)(void*) = nullptr, void* overlap_ctx = nullptr) {
+                      bool score_only, double* out, void (*overlap)(void*) = nullptr, void* overlap_ctx = nullptr,
+                      bool fixed_order = false, bool batched_shape = false) {
   if (!h || !poses6 || !out || K <= 0) return NDT_ERR_INVALID_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
   rc = ready_for_eval(h);
   if (rc) return rc;
-  {  // source ordering, by the first pose of the batch (the particles of an SVN iteration are close)
+  if (!fixed_order) {  // source ordering, by the first pose of the batch (the particles of an SVN iteration are close)
     float T0[16];
     if (!transforms) pose_to_matrix(poses6, T0);
     rc = maybe_sort_source(h, transforms ? transforms : T0);
@@ -763,7 +770,7 @@ static int eval_batch(ndt_handle* h, const double* poses6, const float* transfor
   const VoxelRecord* records = nullptr;
   rc = records_for_eval(h, &ec, &records);
   if (rc) return rc;
-  rc = ensure_partials(h, derivs_partials_words(h->n_src, K, h->n_cus));
+  rc = ensure_partials(h, derivs_partials_words(h->n_src, batched_shape ? std::max(K, 2) : K, h->n_cus));
   if (rc) return rc;
   HIP_TRY(h, h->result.ensure((size_t)K * EV_WORDS));
   HIP_TRY(h, h->dres.ensure((size_t)K * EV_WORDS));
@@ -783,7 +790,8 @@ static int eval_batch(ndt_handle* h, const double* poses6, const float* transfor
                      h->src_sorted ? h->oz.p : h->vz, h->n_src, h->geom, h->cell2leaf.p, records, h->cent.p,
                      h->hposes.h[0], fast ? h->bposes : h->dposes.p, K, ec, h->partials.p, h->counters.p, h->dres.p, s,
                      fast ? h->flag.d : nullptr, seq, nullptr, nullptr, 0ull, nullptr, nullptr,
-                     h->timing && !bracket ? h->ev0 : nullptr, h->timing && !bracket ? h->ev1 : nullptr, nullptr, &plan);
+                     h->timing && !bracket ? h->ev0 : nullptr, h->timing && !bracket ? h->ev1 : nullptr, nullptr, &plan,
+                     batched_shape);
   HIP_TRY(h, hipGetLastError());
   if (bracket) HIP_TRY(h, hipEventRecord(h->ev1, s));
   if (overlap) overlap(overlap_ctx);
@@ -929,6 +937,79 @@ int ndt_newton_align(const ndt_params* p, int64_t n_source_total, const float gu
     return 0;
   };
   return newton_align(prm, n_source_total, guess, wrap, out);
+}
+
+int ndt_newton_align_batch(const ndt_params* p, int64_t n_source_total, const float* guesses, int K,
+                           const float* reg_pose, ndt_eval_batch_fn fn, void* ctx, ndt_result* out) {
+  if (!p || !guesses || !fn || !out || K < 1 || K > NDT_ALIGN_BATCH_MAX) return NDT_ERR_INVALID_ARG;
+  const ndt_params prm = *p;
+  std::vector<double> poses, words;
+  std::vector<float> Ts;
+  std::vector<int> need;
+  BatchEvalFn wrap = [&](int n, const EvalRequest* const* rq, Eval* const* eo) -> int {
+    poses.resize(6 * (size_t)n);
+    Ts.resize(16 * (size_t)n);
+    need.resize((size_t)n);
+    words.assign((size_t)n * NDT_EVAL_WORDS, 0.0);
+    for (int i = 0; i < n; ++i) {
+      std::memcpy(&poses[6 * (size_t)i], rq[i]->p, 6 * sizeof(double));
+      std::memcpy(&Ts[16 * (size_t)i], rq[i]->T, 16 * sizeof(float));
+      need[(size_t)i] = rq[i]->need_h ? 1 : 0;
+    }
+    int rc = fn(ctx, n, poses.data(), Ts.data(), need.data(), words.data());
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i) {
+      unpack_eval(&words[(size_t)i * NDT_EVAL_WORDS], eo[i]);
+      finish_eval(prm, reg_pose, rq[i]->p, rq[i]->need_h, eo[i]);
+    }
+    return 0;
+  };
+  return newton_align_batch(prm, n_source_total, guesses, K, wrap, out);
+}
+
+int ndt_align_batch(ndt_handle* h, const float* guesses, int K, ndt_result* out) {
+  if (!h || !guesses || !out || K < 1 || K > NDT_ALIGN_BATCH_MAX) return NDT_ERR_INVALID_ARG;
+  for (int k = 0; k < K; ++k) {  // what every failure before the loop leaves: the guesses, not converged
+    std::memset(&out[k], 0, sizeof(out[k]));
+    std::memcpy(out[k].final_transformation, guesses + 16 * (size_t)k, sizeof(float) * 16);
+  }
+  if (h->red.mode() != NDT_REDUCE_NONE)
+    return fail(h, NDT_ERR_UNSUPPORTED, "ndt_align_batch: multi-rank batches are not supported");
+  int rc = bind_device(h);
+  if (rc) return rc;
+  AlignBusy busy(h->keepwarm);
+  rc = ready_for_eval(h);
+  if (rc) return rc;
+  // The source order of every round is decided here, once, by the first guess: a round never re-sorts by its own
+  // first pose (eval_batch, fixed_order), so no hypothesis's sums depend on which others are still live.
+  rc = maybe_sort_source(h, guesses);
+  if (rc) return rc;
+  const double dev_ms0 = h->tm.ms_eval_kernel_total;
+  const int64_t n_total = h->n_src_global >= 0 ? h->n_src_global : (int64_t)h->n_src;
+  std::vector<double> poses, words;
+  std::vector<float> Ts;
+  BatchEvalFn fn = [&](int n, const EvalRequest* const* rq, Eval* const* eo) -> int {
+    poses.resize(6 * (size_t)n);
+    Ts.resize(16 * (size_t)n);
+    words.resize((size_t)n * EV_WORDS);
+    int need_h = 0;
+    for (int i = 0; i < n; ++i) {
+      std::memcpy(&poses[6 * (size_t)i], rq[i]->p, 6 * sizeof(double));
+      std::memcpy(&Ts[16 * (size_t)i], rq[i]->T, 16 * sizeof(float));
+      need_h |= rq[i]->need_h ? 1 : 0;
+    }
+    // (finish_eval has been applied per pose: unpacking gives what evaluate() hands ndt_align's loop)
+    const int r = eval_batch(h, poses.data(), Ts.data(), n, need_h, false, words.data(), nullptr, nullptr,
+                             /*fixed_order=*/true, /*batched_shape=*/true);
+    if (r) return r;
+    for (int i = 0; i < n; ++i) unpack_eval(&words[(size_t)i * EV_WORDS], eo[i]);
+    return 0;
+  };
+  // the product path of ndt_align: the Hessian in every trial, the memo on; no iteration history
+  rc = newton_align_batch(h->prm, n_total, guesses, K, fn, out, /*hessian_in_trials=*/true);
+  const double dev_ms = h->tm.ms_eval_kernel_total - dev_ms0;
+  for (int k = 0; k < K; ++k) out[k].ms_device = dev_ms;
+  return rc;
 }
 
 

@@ -154,8 +154,10 @@ struct DerivLaunchPlan {
 static_assert(sizeof(DerivLaunchPlan) == 16 * sizeof(int), "DerivLaunchPlan is 16 ints");
 // Everything launch_derivatives decides from the size, the pose count and the engine's consts: the plan and the EvalConsts
 // the kernel receives.  batched: d_poses != nullptr; mbox: a pre-launched launch; xchg: in-kernel cross-rank exchange.
+// batched_shape: a batched launch keeps the block shape of K > 1 at K = 1 too (the rounds of ndt_align_batch: a pose's
+// sums do not depend on the number of poses in the launch); the same kernel instantiations either way.
 DerivLaunchPlan plan_derivatives_launch(size_t n_src, int K, bool batched, bool mbox, bool xchg, const EvalConsts& ec,
-                                        EvalConsts* ecl_out);
+                                        EvalConsts* ecl_out, bool batched_shape = false);
 size_t derivs_partials_words(size_t n_src, int K, int cus);  // doubles needed in d_partials
 int derivs_counters_per_pose();
 // which finishing wave expands which wave's points: 2 bits per wave (owning SIMD), 4 bits per SIMD (its finishing wave)
@@ -192,7 +194,9 @@ void launch_derivatives(const float* sx, const float* sy, const float* sz, size_
                         // from the build's device-side BuildGeom (and nothing runs after a refused build), `g` is ignored
                         const BuildGeom* d_geom = nullptr,
                         // the shape of this launch (evaluation log), when not null
-                        DerivLaunchPlan* plan_out = nullptr);
+                        DerivLaunchPlan* plan_out = nullptr,
+                        // batched launches: the shape of K > 1 at every K (plan_derivatives_launch)
+                        bool batched_shape = false);
 
 // The 80-byte records of leaf slots [0, n) as 48-byte PackedRecords (f64 mean, f32 inverse covariance); a launch
 // whose EvalConsts::packed is set takes that array in place of `rec`.

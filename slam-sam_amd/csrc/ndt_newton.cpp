@@ -272,10 +272,7 @@ void solve_sym6(const double Hin[36], const double b[6], double x[6]) {
   }
 }
 
-// state of one bracket end of the More-Thuente search
-struct End {
-  double a, f, g;
-};
+using End = SearchEnd;
 
 double cubic_step(const End& u, double a_t, double f_t, double g_t) {
   // minimiser of the cubic interpolating (u.a, u.f, u.g) and (a_t, f_t, g_t)
@@ -317,180 +314,261 @@ bool shrink(End& l, End& u, double a_t, double f_t, double g_t) {
   return true;
 }
 
-class Solver {
- public:
-  Solver(const ndt_params& prm, const EvalFn& fn, bool h_in_trials) : prm_(prm), fn_(fn), h_in_trials_(h_in_trials) {}
-
-  int evaluate(const double p[6], bool need_h) {
-    pose_to_matrix(p, T_);
-    return evaluate_with(p, T_, need_h);
-  }
-  int evaluate_with(const double p[6], const float T[16], bool need_h) {
-    if (T != T_) std::memcpy(T_, T, sizeof(T_));
-    // The evaluator is a pure, bit-reproducible function of (p, T): a repeated request -- the
-    // More-Thuente loop re-tries a step clamped to its lower bound up to 10 times, and the
-    // reference's loop re-evaluates at the accepted step to get the Hessian -- is answered
-    // from the last result instead of a launch.  Same numbers, fewer evaluations.
-    if (memo_ && have_last_ && (last_h_ || !need_h) && std::memcmp(last_p_, p, sizeof(last_p_)) == 0 &&
-        std::memcmp(last_T_, T_, sizeof(last_T_)) == 0) {
-      cur_ = last_;
-      ++n_reused_;
-      return 0;
-    }
-    ++n_evals_;
-    const int rc = fn_(p, T_, need_h, &cur_);
-    have_last_ = rc == 0;
-    if (have_last_) {
-      std::memcpy(last_p_, p, sizeof(last_p_));
-      std::memcpy(last_T_, T_, sizeof(last_T_));
-      last_h_ = need_h;
-      last_ = cur_;
-    }
-    return rc;
-  }
-
-  // Step length along `dir` from `x`.  phi(a) = -score(x + a dir).  On return
-  // cur_ holds score/gradient at the accepted point and H its Hessian.
-  int line_search(const double x[6], double dir[6], double a_init, double a_max, double a_min,
-                  double score0, const double g0[6], double H[36], double* a_out) {
-    const double phi0 = -score0;
-    double dphi0 = 0;
-    for (int i = 0; i < 6; ++i) dphi0 -= g0[i] * dir[i];
-    if (dphi0 >= 0) {
-      if (dphi0 == 0) { *a_out = 0; return 0; }
-      dphi0 = -dphi0;  // not an ascent direction of the score: search the other way
-      for (int i = 0; i < 6; ++i) dir[i] = -dir[i];
-    }
-    const double mu = 1e-4, nu = 0.9;
-    const int max_trials = 10;
-    End lo{0, 0, dphi0 - mu * dphi0}, up = lo;  // in terms of psi while the interval is open
-    bool collapsed = (a_max - a_min) < 0, open = true;
-    double a = std::fmax(std::fmin(a_init, a_max), a_min);
-    double xt[6];
-    auto probe = [&](bool need_h, double* phi, double* dphi) -> int {
-      for (int i = 0; i < 6; ++i) xt[i] = x[i] + dir[i] * a;
-      int rc = evaluate(xt, need_h);
-      *phi = -cur_.score;
-      *dphi = 0;
-      for (int i = 0; i < 6; ++i) *dphi -= cur_.g[i] * dir[i];
-      return rc;
-    };
-    double phi, dphi;
-    int rc = probe(true, &phi, &dphi);
-    if (rc) return rc;
-    std::memcpy(H, cur_.H, sizeof(double) * 36);
-    double psi = phi - phi0 - mu * dphi0 * a, dpsi = dphi - mu * dphi0;
-    int trials = 0;
-    while (prm_.use_line_search && !collapsed && trials < max_trials &&
-           !(psi <= 0 && dphi <= -nu * dphi0)) {
-      a = open ? next_trial(lo, up, a, psi, dpsi) : next_trial(lo, up, a, phi, dphi);
-      a = std::fmax(std::fmin(a, a_max), a_min);
-      rc = probe(h_in_trials_, &phi, &dphi);
-      if (rc) return rc;
-      psi = phi - phi0 - mu * dphi0 * a;
-      dpsi = dphi - mu * dphi0;
-      if (open && psi <= 0 && dpsi >= 0) {
-        open = false;  // switch the bracket from psi to phi
-        lo.f += phi0 - mu * dphi0 * lo.a; lo.g += mu * dphi0;
-        up.f += phi0 - mu * dphi0 * up.a; up.g += mu * dphi0;
-      }
-      collapsed = open ? shrink(lo, up, a, psi, dpsi) : shrink(lo, up, a, phi, dphi);
-      ++trials;
-    }
-    if (trials && h_in_trials_) {
-      std::memcpy(H, cur_.H, sizeof(double) * 36);  // the last trial IS the accepted point
-    } else if (trials) {  // the trial evaluations skipped the Hessian: get it at the accepted point
-      const double s = cur_.score;
-      double g[6];
-      std::memcpy(g, cur_.g, sizeof(g));
-      rc = evaluate(xt, true);
-      if (rc) return rc;
-      std::memcpy(H, cur_.H, sizeof(double) * 36);
-      cur_.score = s;
-      std::memcpy(cur_.g, g, sizeof(g));
-    }
-    *a_out = a;
-    return 0;
-  }
-
-  const ndt_params& prm_;
-  const EvalFn& fn_;
-  bool h_in_trials_;
-  Eval cur_;
-  float T_[16];
-  int n_evals_ = 0;
-  // memo of the last evaluation (see evaluate_with)
-  bool memo_ = false, have_last_ = false, last_h_ = false;
-  double last_p_[6];
-  float last_T_[16];
-  Eval last_;
-  int n_reused_ = 0;
-};
-
 }  // namespace
+
+NewtonMachine::NewtonMachine(const ndt_params& prm, int64_t n_source_total, const float guess[16],
+                             bool hessian_in_trials, IterHistory* history)
+    : prm_(prm), n_total_(n_source_total), h_in_trials_(hessian_in_trials),
+      memo_(hessian_in_trials),  // the product path; the plain driver keeps the reference's evaluation count
+      history_(history) {
+  if (history_) history_->clear();
+  std::memcpy(guess_, guess, sizeof(guess_));
+  std::memcpy(final_T_, guess, sizeof(final_T_));
+  std::memcpy(T_, guess, sizeof(T_));
+  matrix_to_pose(guess, p_);
+}
+
+void NewtonMachine::record(const float* T, const Eval& e) {
+  if (history_)
+    history_->push(T, n_total_ > 0 ? e.score / (double)n_total_ : 0.0, e.n_with > 0 ? e.nvtl_sum / e.n_with : 0.0);
+}
+
+void NewtonMachine::stop(int rc, bool converged) {
+  rc_ = rc;
+  converged_ = converged;
+  st_ = St::Done;
+}
+
+// An evaluation at (p, T) -- T = nullptr: the matrix built from p -- after which the machine continues in state `then`.
+// The evaluator is a pure, bit-reproducible function of (p, T): a repeated request -- the More-Thuente loop re-tries a
+// step clamped to its lower bound up to 10 times, and the reference's loop re-evaluates at the accepted step to get the
+// Hessian -- is answered from the last result instead of a launch (memo_).  Same numbers, fewer evaluations.
+// Returns true when the request has to be launched.
+bool NewtonMachine::ask(const double p[6], const float* T, bool need_h, St then) {
+  if (T) std::memcpy(T_, T, sizeof(T_));
+  else pose_to_matrix(p, T_);
+  if (memo_ && have_last_ && (last_h_ || !need_h) && std::memcmp(last_p_, p, sizeof(last_p_)) == 0 &&
+      std::memcmp(last_T_, T_, sizeof(last_T_)) == 0) {
+    cur_ = last_;
+    ++n_reused_;
+    st_ = then;
+    return false;
+  }
+  ++n_evals_;
+  std::memcpy(req_.p, p, sizeof(req_.p));
+  std::memcpy(req_.T, T_, sizeof(req_.T));
+  req_.need_h = need_h;
+  then_ = then;
+  st_ = St::Wait;
+  return true;
+}
+
+void NewtonMachine::deliver(int rc) {
+  if (st_ != St::Wait) return;
+  have_last_ = rc == 0;
+  if (rc) { stop(rc, false); return; }
+  std::memcpy(last_p_, req_.p, sizeof(last_p_));
+  std::memcpy(last_T_, req_.T, sizeof(last_T_));
+  last_h_ = req_.need_h;
+  last_ = cur_;
+  st_ = then_;
+}
+
+// Magnusson 2009, Algorithm 2: Newton steps on the pose, each followed by a More-Thuente line search along it
+// (phi(a) = -score(p + a dp), sufficient-decrease constant mu = 1e-4, curvature constant nu = 0.9, at most 10 trials;
+// psi = phi - phi0 - mu dphi0 a while the interval is open).  The states are the points where the loop waits for an
+// evaluation; the arithmetic between them is that of one uninterrupted loop.
+bool NewtonMachine::next(const EvalRequest** req) {
+  const double mu = 1e-4, nu = 0.9;
+  const int max_trials = 10;
+  auto probe = [&](bool need_h, St then) {
+    for (int i = 0; i < 6; ++i) xt_[i] = p_[i] + dp_[i] * a_;
+    return ask(xt_, nullptr, need_h, then);
+  };
+  auto take_probe = [&]() {  // phi, dphi of the evaluation just received
+    phi_ = -cur_.score;
+    dphi_ = 0;
+    for (int i = 0; i < 6; ++i) dphi_ -= cur_.g[i] * dp_[i];
+  };
+  for (;;) {
+    switch (st_) {
+      case St::Start:  // the first evaluation transforms the source by the guess matrix itself
+        if (ask(p_, guess_, true, St::First)) break;
+        continue;
+      case St::First:
+        score_ = cur_.score;
+        std::memcpy(g_, cur_.g, sizeof(g_));
+        std::memcpy(H_, cur_.H, sizeof(H_));
+        record(guess_, cur_);
+        st_ = St::Newton;
+        continue;
+      case St::Newton: {
+        double rhs[6];
+        for (int i = 0; i < 6; ++i) rhs[i] = -g_[i];
+        solve_sym6(H_, rhs, dp_);
+        double len = 0;
+        for (int i = 0; i < 6; ++i) len += dp_[i] * dp_[i];
+        len = std::sqrt(len);
+        if (len == 0 || len != len) {  // zero or NaN step: stop (converged only if not NaN)
+          stop(0, len == len);
+          continue;
+        }
+        for (int i = 0; i < 6; ++i) dp_[i] /= len;
+        // line search from p_ along dp_: a_init = len, a_max = step_size, a_min = trans_epsilon / 2
+        a_max_ = prm_.step_size;
+        a_min_ = prm_.trans_epsilon / 2;
+        phi0_ = -score_;
+        dphi0_ = 0;
+        for (int i = 0; i < 6; ++i) dphi0_ -= g_[i] * dp_[i];
+        if (dphi0_ >= 0) {
+          if (dphi0_ == 0) {
+            a_ = 0;
+            st_ = St::AfterLs;
+            continue;
+          }
+          dphi0_ = -dphi0_;  // not an ascent direction of the score: search the other way
+          for (int i = 0; i < 6; ++i) dp_[i] = -dp_[i];
+        }
+        lo_ = {0, 0, dphi0_ - mu * dphi0_};  // in terms of psi while the interval is open
+        up_ = lo_;
+        collapsed_ = (a_max_ - a_min_) < 0;
+        open_ = true;
+        a_ = std::fmax(std::fmin(len, a_max_), a_min_);
+        if (probe(true, St::LsFirst)) break;
+        continue;
+      }
+      case St::LsFirst:
+        take_probe();
+        std::memcpy(H_, cur_.H, sizeof(H_));
+        psi_ = phi_ - phi0_ - mu * dphi0_ * a_;
+        dpsi_ = dphi_ - mu * dphi0_;
+        trials_ = 0;
+        st_ = St::LsLoop;
+        continue;
+      case St::LsLoop:
+        if (prm_.use_line_search && !collapsed_ && trials_ < max_trials && !(psi_ <= 0 && dphi_ <= -nu * dphi0_)) {
+          a_ = open_ ? next_trial(lo_, up_, a_, psi_, dpsi_) : next_trial(lo_, up_, a_, phi_, dphi_);
+          a_ = std::fmax(std::fmin(a_, a_max_), a_min_);
+          if (probe(h_in_trials_, St::LsTrial)) break;
+          continue;
+        }
+        st_ = St::LsEnd;
+        continue;
+      case St::LsTrial:
+        take_probe();
+        psi_ = phi_ - phi0_ - mu * dphi0_ * a_;
+        dpsi_ = dphi_ - mu * dphi0_;
+        if (open_ && psi_ <= 0 && dpsi_ >= 0) {
+          open_ = false;  // switch the bracket from psi to phi
+          lo_.f += phi0_ - mu * dphi0_ * lo_.a; lo_.g += mu * dphi0_;
+          up_.f += phi0_ - mu * dphi0_ * up_.a; up_.g += mu * dphi0_;
+        }
+        collapsed_ = open_ ? shrink(lo_, up_, a_, psi_, dpsi_) : shrink(lo_, up_, a_, phi_, dphi_);
+        ++trials_;
+        st_ = St::LsLoop;
+        continue;
+      case St::LsEnd:
+        if (trials_ && h_in_trials_) {
+          std::memcpy(H_, cur_.H, sizeof(H_));  // the last trial IS the accepted point
+        } else if (trials_) {  // the trial evaluations skipped the Hessian: get it at the accepted point
+          s_keep_ = cur_.score;
+          std::memcpy(g_keep_, cur_.g, sizeof(g_keep_));
+          if (ask(xt_, nullptr, true, St::LsReeval)) break;
+          continue;
+        }
+        st_ = St::AfterLs;
+        continue;
+      case St::LsReeval:
+        std::memcpy(H_, cur_.H, sizeof(H_));
+        cur_.score = s_keep_;
+        std::memcpy(cur_.g, g_keep_, sizeof(g_keep_));
+        st_ = St::AfterLs;
+        continue;
+      case St::AfterLs: {
+        score_ = cur_.score;
+        std::memcpy(g_, cur_.g, sizeof(g_));
+        for (int i = 0; i < 6; ++i) p_[i] += dp_[i] * a_;
+        std::memcpy(final_T_, T_, sizeof(final_T_));
+        record(T_, cur_);
+        const bool last = iters_ > prm_.max_iterations || (iters_ && std::fabs(a_) < prm_.trans_epsilon);
+        ++iters_;
+        if (last) stop(0, true);
+        else st_ = St::Newton;
+        continue;
+      }
+      case St::Wait:
+        break;
+      case St::Done:
+        return false;
+    }
+    *req = &req_;
+    return true;
+  }
+}
+
+void NewtonMachine::result(ndt_result* out) const {
+  std::memset(out, 0, sizeof(*out));
+  std::memcpy(out->final_transformation, final_T_, sizeof(float) * 16);
+  if (rc_ != 0) return;
+  out->converged = converged_ ? 1 : 0;
+  out->iterations = iters_;
+  out->n_evaluations = n_evals_;
+  out->n_evaluations_reused = n_reused_;
+  std::memcpy(out->final_pose, p_, sizeof(p_));
+  std::memcpy(out->hessian, H_, sizeof(H_));
+  out->score = score_;
+  out->transform_probability = n_total_ > 0 ? score_ / (double)n_total_ : 0.0;
+  out->nearest_voxel_transformation_likelihood = cur_.n_with > 0 ? cur_.nvtl_sum / cur_.n_with : 0.0;
+  out->n_pairs = (int64_t)cur_.n_pairs;
+  out->n_points_with_neighbors = (int64_t)cur_.n_with;
+}
 
 int newton_align(const ndt_params& prm, int64_t n_source_total, const float guess[16],
                  const EvalFn& fn, ndt_result* out, bool hessian_in_trials, IterHistory* history) {
   const auto t0 = std::chrono::steady_clock::now();
-  if (history) history->clear();
-  auto record = [&](const float* T, const Eval& e) {
-    if (history)
-      history->push(T, n_source_total > 0 ? e.score / (double)n_source_total : 0.0, e.n_with > 0 ? e.nvtl_sum / e.n_with : 0.0);
-  };
-  std::memset(out, 0, sizeof(*out));
-  std::memcpy(out->final_transformation, guess, sizeof(float) * 16);
-  Solver sv(prm, fn, hessian_in_trials);
-  sv.memo_ = hessian_in_trials;  // the product path; the plain driver keeps the reference's evaluation count
-  double p[6];
-  matrix_to_pose(guess, p);
-  // the first evaluation transforms the source by the guess matrix itself
-  int rc = sv.evaluate_with(p, guess, true);
-  if (rc) return rc;
-  double score = sv.cur_.score, g[6], H[36];
-  std::memcpy(g, sv.cur_.g, sizeof(g));
-  std::memcpy(H, sv.cur_.H, sizeof(H));
-  record(guess, sv.cur_);
-
-  int iters = 0;
-  bool converged = false;
-  for (;;) {
-    double rhs[6], dp[6];
-    for (int i = 0; i < 6; ++i) rhs[i] = -g[i];
-    solve_sym6(H, rhs, dp);
-    double len = 0;
-    for (int i = 0; i < 6; ++i) len += dp[i] * dp[i];
-    len = std::sqrt(len);
-    if (len == 0 || len != len) {  // zero or NaN step: stop (converged only if not NaN)
-      converged = (len == len);
-      break;
-    }
-    for (int i = 0; i < 6; ++i) dp[i] /= len;
-    double a = 0;
-    rc = sv.line_search(p, dp, len, prm.step_size, prm.trans_epsilon / 2, score, g, H, &a);
-    if (rc) return rc;
-    score = sv.cur_.score;
-    std::memcpy(g, sv.cur_.g, sizeof(g));
-    for (int i = 0; i < 6; ++i) p[i] += dp[i] * a;
-    std::memcpy(out->final_transformation, sv.T_, sizeof(float) * 16);
-    record(sv.T_, sv.cur_);
-    const bool stop = iters > prm.max_iterations || (iters && std::fabs(a) < prm.trans_epsilon);
-    ++iters;
-    if (stop) { converged = true; break; }
-  }
-  out->converged = converged ? 1 : 0;
-  out->iterations = iters;
-  out->n_evaluations = sv.n_evals_;
-  out->n_evaluations_reused = sv.n_reused_;
-  std::memcpy(out->final_pose, p, sizeof(p));
-  std::memcpy(out->hessian, H, sizeof(H));
-  out->score = score;
-  out->transform_probability = n_source_total > 0 ? score / (double)n_source_total : 0.0;
-  out->nearest_voxel_transformation_likelihood =
-      sv.cur_.n_with > 0 ? sv.cur_.nvtl_sum / sv.cur_.n_with : 0.0;
-  out->n_pairs = (int64_t)sv.cur_.n_pairs;
-  out->n_points_with_neighbors = (int64_t)sv.cur_.n_with;
+  NewtonMachine m(prm, n_source_total, guess, hessian_in_trials, history);
+  const EvalRequest* rq = nullptr;
+  while (m.next(&rq)) m.deliver(fn(rq->p, rq->T, rq->need_h, m.slot()));
+  m.result(out);
+  if (m.status()) return m.status();
   out->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return 0;
+}
+
+int newton_align_batch(const ndt_params& prm, int64_t n_source_total, const float* guesses16, int K,
+                       const BatchEvalFn& fn, ndt_result* out, bool hessian_in_trials, int* rounds_out) {
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<NewtonMachine> ms;
+  ms.reserve((size_t)K);
+  for (int k = 0; k < K; ++k) ms.emplace_back(prm, n_source_total, guesses16 + 16 * (size_t)k, hessian_in_trials);
+  std::vector<int> live;
+  std::vector<const EvalRequest*> reqs;
+  std::vector<Eval*> outs;
+  int rounds = 0, rc = 0;
+  for (;;) {
+    live.clear();
+    reqs.clear();
+    outs.clear();
+    for (int k = 0; k < K; ++k) {
+      const EvalRequest* rq = nullptr;
+      if (!ms[(size_t)k].next(&rq)) continue;
+      live.push_back(k);
+      reqs.push_back(rq);
+      outs.push_back(ms[(size_t)k].slot());
+    }
+    if (live.empty()) break;
+    ++rounds;
+    rc = fn((int)live.size(), reqs.data(), outs.data());
+    for (int k : live) ms[(size_t)k].deliver(rc);
+    if (rc) break;
+  }
+  const double ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  for (int k = 0; k < K; ++k) {
+    ms[(size_t)k].result(&out[k]);
+    out[k].ms_total = ms_total;
+  }
+  if (rounds_out) *rounds_out = rounds;
+  return rc;
 }
 
 bool result_covariance(const double H[36], double eps, bool gtsam_order, double cov[36]) {
