@@ -37,6 +37,15 @@ def make_cloud(rng, kind, n, offset):
     return (p + offset).astype(np.float32)
 
 
+def cov_loss(OL):
+    """Per leaf, the relative covariance error two correct implementations may show.  The reference's single-pass
+    covariance (sum xx^T / n - mean mean^T) loses (|mean| / spread)^2 * eps to cancellation in BOTH implementations,
+    which sum in different orders: a millimetre-thin voxel 1.5 km from the origin keeps ~4 digits.  The inflated
+    inverse, and with it score / gradient / Hessian, inherit that: tolerances scale with it."""
+    spread = np.sqrt(np.maximum(np.abs(OL["cov"]).max(axis=(1, 2)), 1e-30))
+    return 1e-9 + 64 * np.finfo(np.float64).eps * (np.abs(OL["mean"]).max(axis=1) / spread) ** 2
+
+
 CASES = []
 _rng = np.random.default_rng(20241004)
 for i, kind in enumerate(["blobs", "planes", "lines", "dupes", "box"] * 20):
@@ -80,12 +89,7 @@ def test_random_cloud_parity(pkg, O, S, case):
     amp = 0.0
     if len(OL["cell"]):
         np.testing.assert_allclose(L["mean"], OL["mean"], rtol=1e-12, atol=0)
-        # The reference's single-pass covariance (sum xx^T / n - mean mean^T) loses
-        # (|mean| / spread)^2 * eps to cancellation in BOTH implementations, which sum in different
-        # orders: a millimetre-thin voxel 1.5 km from the origin keeps ~4 digits.  The inflated
-        # inverse, and with it score / gradient / Hessian, inherit that: tolerances scale with it.
-        spread = np.sqrt(np.maximum(np.abs(OL["cov"]).max(axis=(1, 2)), 1e-30))
-        loss = 1e-9 + 64 * np.finfo(np.float64).eps * (np.abs(OL["mean"]).max(axis=1) / spread) ** 2
+        loss = cov_loss(OL)
         scale = np.abs(OL["cov"]).max(axis=(1, 2))
         assert ((np.abs(L["cov"] - OL["cov"]).max(axis=(1, 2)) / scale) < loss).all()
         amp = float(loss.max())
