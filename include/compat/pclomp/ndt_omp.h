@@ -22,6 +22,8 @@ constexpr NeighborSearchMethod DIRECT1 = ndt_hip::DIRECT1;
 
 using NdtResult = ndt_hip::NdtResult;
 
+// (tier4's per-point scoring call, calculateNearestVoxelScoreEachPoint(cloud) [RECALLED], is a member of the engine
+// class under that name: the transformed cloud with intensity = the point's best per-voxel score)
 template <typename PointSource, typename PointTarget>
 using NormalDistributionsTransform = ndt_hip::NormalDistributionsTransform<PointSource, PointTarget>;
 

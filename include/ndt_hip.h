@@ -482,6 +482,45 @@ int ndt_fitness_score(ndt_handle* h, const float T_colmajor[16], double max_rang
 /* K transforms (K x 16 floats, column-major) in one query launch; out[k] equals ndt_fitness_score at transform k */
 int ndt_fitness_scores(ndt_handle* h, const float* transforms_colmajor, int K, double max_range, ndt_fitness* out);
 
+/* Per-point view of a scoring-only evaluation [RECALLED: tier4 ndt_omp's calculateNearestVoxelScoreEachPoint]: what
+ * ndt_score_transform adds up, kept per source point, in the order the source was handed over (whatever
+ * ndt_source_order says; viewed and keyframe sources included).  The point is moved by T with the f32 arithmetic of an
+ * evaluation, so it has exactly the neighbour voxels it has there.  Per point:
+ *   score                sum over its neighbour voxels of the pair score -d1 * exp(-d2/2 * q), the evaluation's guards
+ *   nearest_voxel_score  its largest pair score; 0 without a neighbour
+ *   n_neighbors          its (point, voxel) pairs, as counted for ndt_score.n_pairs
+ *   best_voxel           ndt_leaf.index of the voxel that gave nearest_voxel_score (multi-grid union: the cell's index);
+ *                        -1 without a contributing pair, i.e. exactly where nearest_voxel_score == 0; on equal scores
+ *                        the smallest index
+ * A source point that is not finite, or not finite after the transform, reports 0 / 0 / 0 / -1.  Hence, in either
+ * record format: sum(score) = ndt_score.score, sum(n_neighbors) = n_pairs, count(n_neighbors > 0) =
+ * n_points_with_neighbors, mean of nearest_voxel_score over those = NVTL (up to the order of the f64 additions).
+ * Any output may be NULL; cap >= n_source for those that are not (NDT_ERR_INVALID_ARG).  One plain launch on the
+ * engine's stream; a pending deferred build is settled first and the errors are those of ndt_score_transform.  The align
+ * state, the iteration history and the evaluation counters of the handle are left alone.  A sharded source reports its
+ * local shard. */
+int ndt_score_points(ndt_handle* h, const float T_colmajor[16], double* score, double* nearest_voxel_score,
+                     int32_t* n_neighbors, int64_t* best_voxel, size_t cap);
+/* the same into caller-owned DEVICE arrays; complete when the call returns */
+int ndt_score_points_device(ndt_handle* h, const float T_colmajor[16], double* d_score, double* d_nearest_voxel_score,
+                            int32_t* d_n_neighbors, int64_t* d_best_voxel, size_t cap);
+/* number of points of the current (local) source: the n_source the calls above size their outputs by; < 0 on error */
+int64_t ndt_source_size(const ndt_handle* h);
+
+/* Score-based filter of the source on the device.  Writes the source points (as handed over, NOT transformed) whose
+ * nearest_voxel_score under T is >= min_score (keep_below != 0: those below it, points without a neighbour included)
+ * to device SoA arrays, in input order -- the selection is exactly that comparison applied to what ndt_score_points
+ * returns for the same T.  At most cap points are written.  *n_out is the number selected.  NDT_ERR_INVALID_ARG if it
+ * exceeds cap (cap = n_source always suffices), or if min_score is NaN.  d_index_out (nullable) receives each selected
+ * point's position in the source.  Complete when the call returns: the arrays can go straight into
+ * ndt_set_target_device or ndt_set_source_device.  The handle's own source is unchanged.  Stable and deterministic:
+ * wave ballots, block scans and integer block offsets, no atomics. */
+int ndt_filter_source_device(ndt_handle* h, const float T_colmajor[16], double min_score, int keep_below,
+                             float* ox, float* oy, float* oz, int32_t* d_index_out, size_t cap, size_t* n_out);
+/* packed xyz and indices in host memory */
+int ndt_filter_source(ndt_handle* h, const float T_colmajor[16], double min_score, int keep_below,
+                      float* out_xyz, int32_t* index_out, size_t cap_points, size_t* n_out);
+
 /* ---- voxel grid accessors ------------------------------------------------ */
 int ndt_get_grid_info(const ndt_handle* h, ndt_grid_info* out);
 /* getTargetCells().getLeaves(): valid leaves sorted by ascending index; returns

@@ -488,6 +488,86 @@ class NormalDistributionsTransform
     return scoreCloud(cloud, T, &s) ? s.nearest_voxel_transformation_likelihood : 0.0;
   }
 
+  // ---- per-point scores (ndt_score_points) and the score-based source filter (ndt_filter_source) ----
+  // what a scoring-only evaluation of the CURRENT source under T adds up, per point in the order the source was handed
+  // over; best_voxel is a TargetGrid leaf index (-1: no voxel contributed).  On error: empty arrays, lastStatus() says why.
+  struct PointScores {
+    std::vector<double> score, nearest_voxel_score;
+    std::vector<int32_t> n_neighbors;
+    std::vector<int64_t> best_voxel;
+    size_t size() const { return score.size(); }
+  };
+  PointScores scorePoints(const Matrix4f& T = identity4f()) {
+    PointScores ps;
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return ps; }
+    const int64_t n = ndt_source_size(h_);
+    if (n < 0) { status_ = (int)n; return ps; }
+    float a[16];
+    detail::to_colmajor(T, 4, 4, a);
+    ps.score.resize((size_t)n); ps.nearest_voxel_score.resize((size_t)n); ps.n_neighbors.resize((size_t)n); ps.best_voxel.resize((size_t)n);
+    status_ = ndt_score_points(h_, a, ps.score.data(), ps.nearest_voxel_score.data(), ps.n_neighbors.data(), ps.best_voxel.data(), (size_t)n);
+    if (status_ != NDT_OK) ps = PointScores();
+    return ps;
+  }
+  // the current source moved by T (ndt_transform_source) with intensity = the point's nearest_voxel_score: the shape of
+  // tier4 ndt_omp's calculateNearestVoxelScoreEachPoint [RECALLED], which colours a scan by how well the map explains it
+  template <class PointOut = PointSource>
+  PointCloud<PointOut> nearestVoxelScoreEachPoint(const Matrix4f& T = identity4f()) {
+    PointCloud<PointOut> out;
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return out; }
+    const int64_t n = ndt_source_size(h_);
+    if (n < 0) { status_ = (int)n; return out; }
+    float a[16];
+    detail::to_colmajor(T, 4, 4, a);
+    std::vector<double> nvs((size_t)n);
+    std::vector<float> xyz(3 * (size_t)n);
+    status_ = ndt_score_points(h_, a, nullptr, nvs.data(), nullptr, nullptr, (size_t)n);
+    if (status_ == NDT_OK && n > 0) status_ = ndt_transform_source(h_, a, xyz.data(), (size_t)n);
+    if (status_ != NDT_OK) return out;
+    out.points.resize((size_t)n);
+    for (size_t i = 0; i < (size_t)n; ++i) {
+      out.points[i].x = xyz[3 * i];
+      out.points[i].y = xyz[3 * i + 1];
+      out.points[i].z = xyz[3 * i + 2];
+      out.points[i].intensity = (float)nvs[i];
+    }
+    return out;
+  }
+  // tier4's own signature [RECALLED]: `cloud` is already in the map frame; it becomes the engine's source, as with the
+  // other scoring-only calls above
+  template <class Cloud>
+  PointCloud<PointSource> calculateNearestVoxelScoreEachPoint(const Cloud& cloud) {
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return PointCloud<PointSource>(); }
+    uploadSource(&cloud);
+    if (status_ != NDT_OK) return PointCloud<PointSource>();
+    return nearestVoxelScoreEachPoint<PointSource>(identity4f());
+  }
+  // the source points (as handed over, not transformed) whose nearest_voxel_score under T is >= min_score (keep_below:
+  // those below it, points without a neighbour included), in input order; `index` (nullable) receives their positions
+  PointCloud<PointSource> filterSource(const Matrix4f& T, double min_score, bool keep_below = false,
+                                       std::vector<int32_t>* index = nullptr) {
+    PointCloud<PointSource> out;
+    if (index) index->clear();
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return out; }
+    const int64_t n = ndt_source_size(h_);
+    if (n < 0) { status_ = (int)n; return out; }
+    float a[16];
+    detail::to_colmajor(T, 4, 4, a);
+    std::vector<float> xyz(3 * (size_t)n + 3);
+    std::vector<int32_t> idx((size_t)n + 1);
+    size_t m = 0;
+    status_ = ndt_filter_source(h_, a, min_score, keep_below ? 1 : 0, xyz.data(), idx.data(), (size_t)n, &m);
+    if (status_ != NDT_OK) return out;
+    out.points.resize(m);   // value-initialised points: the fields the engine does not write keep their defaults
+    for (size_t i = 0; i < m; ++i) {
+      out.points[i].x = xyz[3 * i];
+      out.points[i].y = xyz[3 * i + 1];
+      out.points[i].z = xyz[3 * i + 2];
+    }
+    if (index) index->assign(idx.begin(), idx.begin() + (std::ptrdiff_t)m);
+    return out;
+  }
+
   NdtResult getResult() const {
     NdtResult r;
     r.pose = detail::from_colmajor<Matrix4f>(res_.final_transformation, 4, 4);

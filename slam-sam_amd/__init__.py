@@ -223,6 +223,7 @@ ABI_SYMBOLS = [
     "ndt_get_tuning", "ndt_set_tuning", "ndt_set_keepwarm", "ndt_get_keepwarm",
     "ndt_comm_p2p_selftest", "ndt_comm_p2p_stats", "ndt_angle_tables", "ndt_gauss_constants", "ndt_svn_rbf_kernel",
     "ndt_fitness_score", "ndt_fitness_scores", "ndt_newton_align_batch", "ndt_align_batch",
+    "ndt_score_points", "ndt_score_points_device", "ndt_source_size", "ndt_filter_source_device", "ndt_filter_source",
 ]
 
 _lib = None
@@ -273,6 +274,13 @@ def lib():
         L.ndt_fitness_score.argtypes = [vp, fp, C.c_double, C.POINTER(Fitness), fp, C.c_size_t]
         L.ndt_fitness_scores.argtypes = [vp, fp, C.c_int, C.c_double, C.POINTER(Fitness)]
         L.ndt_align_batch.argtypes = [vp, fp, C.c_int, C.POINTER(Result)]
+        L.ndt_score_points.argtypes = [vp, fp, vp, vp, vp, vp, C.c_size_t]
+        L.ndt_score_points_device.argtypes = [vp, fp, vp, vp, vp, vp, C.c_size_t]
+        L.ndt_source_size.restype = C.c_int64
+        L.ndt_source_size.argtypes = [vp]
+        L.ndt_filter_source_device.argtypes = [vp, fp, C.c_double, C.c_int, vp, vp, vp, vp, C.c_size_t,
+                                               C.POINTER(C.c_size_t)]
+        L.ndt_filter_source.argtypes = [vp, fp, C.c_double, C.c_int, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ndt_newton_align_batch.argtypes = [C.POINTER(Params), C.c_int64, fp, C.c_int, fp, EVAL_BATCH_FN, vp,
                                              C.POINTER(Result)]
         L.ndt_get_grid_info.argtypes = [vp, C.POINTER(GridInfo)]
@@ -774,6 +782,69 @@ class NormalDistributionsTransform:
         any align)."""
         T = self._result["T"] if self._raw is not None else np.eye(4)
         return self.fitness(T, max_range)["fitness_score"]
+
+    # --- per-point scores [RECALLED: tier4 ndt_omp calculateNearestVoxelScoreEachPoint] and the score-based filter ---
+    POINT_SCORE_FIELDS = (("score", np.float64), ("nearest_voxel_score", np.float64), ("n_neighbors", np.int32),
+                          ("best_voxel", np.int64))
+
+    def sourceSize(self):
+        """Points of the current (local) source, whichever call set it."""
+        n = int(lib().ndt_source_size(self._h))
+        if n < 0:
+            raise NdtError(n, "ndt_source_size")
+        return n
+
+    @staticmethod
+    def _T16(T):
+        a = _colmajor(T)
+        if a.shape != (16,) or not np.all(np.isfinite(a)):
+            raise ValueError("T must be a finite 4 x 4 transform")
+        return a
+
+    def scorePoints(self, T, fields=None):
+        """What scoreTransform(T) adds up, per source point in hand-over order: dict(score, nearest_voxel_score,
+        n_neighbors, best_voxel) of NumPy arrays (`fields`: a subset of those names -- the others are not computed back)."""
+        names = [f for f, _ in self.POINT_SCORE_FIELDS]
+        want = names if fields is None else list(fields)
+        for f in want:
+            if f not in names:
+                raise ValueError("unknown per-point field %r (one of %s)" % (f, ", ".join(names)))
+        a = self._T16(T)
+        n = self.sourceSize()
+        out = {f: np.zeros(n, dt) for f, dt in self.POINT_SCORE_FIELDS if f in want}
+        ptr = [out[f].ctypes.data if f in out else None for f in names]
+        self._check(lib().ndt_score_points(self._h, _fp(a), ptr[0], ptr[1], ptr[2], ptr[3], n))
+        return out
+
+    def scorePointsDevice(self, T, d_score, d_nearest_voxel_score, d_n_neighbors, d_best_voxel, cap):
+        """scorePoints into caller-owned device arrays (integer device addresses, None to skip one)."""
+        a = self._T16(T)
+        self._check(lib().ndt_score_points_device(self._h, _fp(a), d_score, d_nearest_voxel_score, d_n_neighbors,
+                                                  d_best_voxel, int(cap)))
+
+    def filterSource(self, T, min_score, keep_below=False):
+        """The source points (as handed over, not transformed) whose nearest_voxel_score under T is >= min_score
+        (keep_below: those below it), in input order: (xyz [m, 3] float32, index [m] int32)."""
+        a = self._T16(T)
+        if np.isnan(min_score):
+            raise ValueError("min_score must not be NaN")
+        n = self.sourceSize()
+        xyz, idx = np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+        m = C.c_size_t(0)
+        self._check(lib().ndt_filter_source(self._h, _fp(a), float(min_score), int(bool(keep_below)), xyz.ctypes.data,
+                                            idx.ctypes.data, n, C.byref(m)))
+        return xyz[:m.value].copy(), idx[:m.value].copy()
+
+    def filterSourceDevice(self, T, min_score, keep_below, ox, oy, oz, d_index, cap):
+        """filterSource into device SoA arrays (integer device addresses as setInputTargetDevice takes them; d_index may
+        be None); returns the number selected.  The arrays can go into setInputTargetDevice / setInputSourceDevice."""
+        a = self._T16(T)
+        m = C.c_size_t(0)
+        rc = lib().ndt_filter_source_device(self._h, _fp(a), float(min_score), int(bool(keep_below)), ox, oy, oz, d_index,
+                                            int(cap), C.byref(m))
+        self.last_filter_count = int(m.value)
+        self._check(rc)
+        return int(m.value)
 
     # --- 2-D covariance estimators of tier4 ndt_omp [RECALLED] (SURVEY 8f-4) ---
     def proposePosesToSearch(self, offsets_x, offsets_y):

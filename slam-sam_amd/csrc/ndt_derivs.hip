@@ -1482,6 +1482,132 @@ __global__ void __launch_bounds__(256) k_transform(const float* __restrict__ sx,
   out[3 * i + 2] = P.R[6] * x + (P.R[7] * y + (P.R[8] * z + P.t[2]));
 }
 
+// ---- per-point scores (ndt_score_points) ------------------------------------------------------------------------
+// What k_derivatives<.., 3, ..> adds up per point and throws away, kept: the point's score, its best pair score, its
+// pair count -- and the voxel that gave the best pair score, which needs an argmax beside PairAcc::best.  One pair at a
+// time goes through pair_update<3> on a fresh PairAcc (so guards, exp and rounding are the evaluation's own), and
+// PointAcc takes the pair's contribution together with the index of the CELL the leaf was found in.
+struct PointAcc {
+  double score, best;
+  int npairs;
+  int best_cell;   // -1: no pair has contributed
+};
+
+__device__ __forceinline__ void score_pair(PointAcc& p, const VoxelRecord& r, float xt, float yt, float zt,
+                                           const EvalConsts& ec, bool present, int cell) {
+  PairAcc t;
+  t.w[0] = t.w[1] = t.w[2] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) t.S[k] = 0.0;
+  t.score = 0.0; t.best = 0.0; t.npairs = 0;
+  pair_update<3>(t, r, xt, yt, zt, ec, present);
+  p.score += t.score;
+  p.npairs += t.npairs;
+  // (t.best = max(0, pair score): a pair that was masked or guarded away has 0 and never becomes the best voxel;
+  // on equal scores the smallest index)
+  const bool better = t.best > p.best || (t.best == p.best && t.best > 0.0 && cell < p.best_cell);
+  p.best_cell = better ? cell : p.best_cell;
+  p.best = fmax(p.best, t.best);
+}
+
+// NB as k_derivatives: 0 DIRECT1, 1 DIRECT7, 2 KDTREE, 3 DIRECT26, 4 multi-grid union, 5 / 6 DIRECT1 / DIRECT7 on packed
+// records.  The transform and the classification are point_pairs' / point_pairs_kd's, operation for operation, so a
+// point has the neighbours it has in an evaluation at the same R|t; the pairs are taken in the same (cell, chain) order.
+// The 27-cell neighbourhoods walk their cells without the LDS candidate list: a trip per cell that any lane of the wave
+// occupies, the radius test on the record's own mean (kd_within, as the union's unfiltered path).
+template <int NB>
+__global__ void __launch_bounds__(256)
+k_point_scores(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, int n, GridGeom g,
+               const int* __restrict__ cell2leaf, const VoxelRecord* __restrict__ rec, RigidRT P, EvalConsts ec,
+               double* __restrict__ o_score, double* __restrict__ o_best, int* __restrict__ o_npairs,
+               long long* __restrict__ o_cell) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const bool active = i < n;
+  float x = 0.0f, y = 0.0f, z = 0.0f;
+  if (active) { x = sx[i]; y = sy[i]; z = sz[i]; }
+  float xt = P.R[0] * x + (P.R[1] * y + (P.R[2] * z + P.t[0]));
+  float yt = P.R[3] * x + (P.R[4] * y + (P.R[5] * z + P.t[1]));
+  float zt = P.R[6] * x + (P.R[7] * y + (P.R[8] * z + P.t[2]));
+  const bool finite = active && isfinite(xt) && isfinite(yt) && isfinite(zt);
+  if (!finite) { xt = 0.0f; yt = 0.0f; zt = 0.0f; }
+  PointAcc p;
+  p.score = 0.0; p.best = 0.0; p.npairs = 0; p.best_cell = -1;
+  constexpr bool KD = NB >= 2 && NB <= 4;
+  if (!KD) {
+    constexpr bool D7 = NB == 1 || NB == 6, PACKED = NB >= 5;
+    const float w = g.leaf;
+    const float cx[3] = {xt, xt + w, xt - w}, cy[3] = {yt, yt + w, yt - w}, cz[3] = {zt, zt + w, zt - w};
+    bool inx[3], iny[3], inz[3];
+    unsigned int ix[3], iy[3], iz[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      inx[k] = cx[k] >= g.lo[0] && cx[k] < g.hi[0];
+      iny[k] = cy[k] >= g.lo[1] && cy[k] < g.hi[1];
+      inz[k] = cz[k] >= g.lo[2] && cz[k] < g.hi[2];
+      ix[k] = (unsigned int)(int)(floorf(cx[k] * g.inv_leaf) - (float)g.min_b[0]);
+      iy[k] = (unsigned int)(int)(floorf(cy[k] * g.inv_leaf) - (float)g.min_b[1]) * (unsigned int)g.mul1;
+      iz[k] = (unsigned int)(int)(floorf(cz[k] * g.inv_leaf) - (float)g.min_b[2]) * (unsigned int)g.mul2;
+    }
+    int cell[7];
+    {
+      const int idx0 = (int)(ix[0] + iy[0] + iz[0]);
+      cell[0] = (inx[0] && iny[0] && inz[0] && idx0 >= 0 && idx0 < g.ncells) ? idx0 : -1;
+    }
+#pragma unroll
+    for (int k = 1; k < 3; ++k) {
+      const int ax = (int)(ix[k] + iy[0] + iz[0]), ay = (int)(ix[0] + iy[k] + iz[0]), az = (int)(ix[0] + iy[0] + iz[k]);
+      cell[k] = (D7 && inx[k] && iny[0] && inz[0] && ax >= 0 && ax < g.ncells) ? ax : -1;
+      cell[2 + k] = (D7 && inx[0] && iny[k] && inz[0] && ay >= 0 && ay < g.ncells) ? ay : -1;
+      cell[4 + k] = (D7 && inx[0] && iny[0] && inz[k] && az >= 0 && az < g.ncells) ? az : -1;
+    }
+    int slot[7];
+#pragma unroll
+    for (int k = 0; k < (D7 ? 7 : 1); ++k) slot[k] = (finite && cell[k] >= 0) ? cell2leaf[cell[k]] : -1;
+#pragma unroll
+    for (int k = 0; k < (D7 ? 7 : 1); ++k) {
+      const VoxelRecord r = fetch_record(rec, slot[k] >= 0 ? slot[k] : 0, PACKED);
+      score_pair(p, r, xt, yt, zt, ec, slot[k] >= 0, cell[k]);
+    }
+  } else {
+    constexpr bool RADIUS = NB == 2 || NB == 4, CHAIN = NB == 4;
+    const int i0 = finite ? (int)(floorf(xt * g.inv_leaf) - (float)g.min_b[0]) : -4;
+    const int i1 = finite ? (int)(floorf(yt * g.inv_leaf) - (float)g.min_b[1]) : -4;
+    const int i2 = finite ? (int)(floorf(zt * g.inv_leaf) - (float)g.min_b[2]) : -4;
+    const unsigned int d0 = (unsigned int)g.div_b[0], d1 = (unsigned int)g.div_b[1], d2 = (unsigned int)g.div_b[2];
+    const bool xin[3] = {(unsigned int)(i0 - 1) < d0, (unsigned int)i0 < d0, (unsigned int)(i0 + 1) < d0};
+    const bool xany = xin[0] | xin[1] | xin[2];
+    const bool yin[3] = {(unsigned int)(i1 - 1) < d1, (unsigned int)i1 < d1, (unsigned int)(i1 + 1) < d1};
+    const bool zin[3] = {(unsigned int)(i2 - 1) < d2, (unsigned int)i2 < d2, (unsigned int)(i2 + 1) < d2};
+    const int base0 = (i0 - 1) + i1 * g.mul1 + i2 * g.mul2;
+    struct alignas(4) Int3 { int a, b, c; };
+    // (one row of three x-adjacent cells at a time: the index grid is readable four ints beyond either end)
+#pragma unroll
+    for (int r = 0; r < 9; ++r) {
+      const bool rowok = xany & yin[r % 3] & zin[r / 3];
+      if (__ballot(rowok) == 0ull) continue;   // wave-uniform
+      const int base = rowok ? base0 + ((r % 3) - 1) * g.mul1 + ((r / 3) - 1) * g.mul2 : 0;
+      const Int3 v = *reinterpret_cast<const Int3*>(cell2leaf + base);
+      const int rs[3] = {(rowok & xin[0]) ? v.a : -1, (rowok & xin[1]) ? v.b : -1, (rowok & xin[2]) ? v.c : -1};
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        int sl = rs[q];
+        while (__ballot(sl >= 0) != 0ull) {   // every lane of the wave leaves together; one trip without chains
+          const bool live = sl >= 0;
+          const VoxelRecord rr = rec[live ? sl : 0];
+          const bool present = live && (!RADIUS || kd_within(rr, xt, yt, zt, ec.kd_radius2));
+          score_pair(p, rr, xt, yt, zt, ec, present, base + q);
+          sl = (CHAIN && live) ? (int)rr.pad : -1;
+        }
+      }
+    }
+  }
+  if (!active) return;
+  if (o_score) o_score[i] = p.score;
+  if (o_best) o_best[i] = p.best;
+  if (o_npairs) o_npairs[i] = p.npairs;
+  if (o_cell) o_cell[i] = (long long)p.best_cell;
+}
+
 }  // namespace
 
 size_t derivs_partials_words(size_t n_src, int K, int cus) {
@@ -1812,6 +1938,31 @@ void launch_transform(const float* sx, const float* sy, const float* sz, size_t 
   if (n == 0) return;
   hipLaunchKernelGGL(k_transform, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sx, sy, sz,
                      (int)n, pose, out_xyz);
+}
+
+void launch_point_scores(const float* sx, const float* sy, const float* sz, size_t n, const GridGeom& g, const int* cell2leaf,
+                         const VoxelRecord* rec, const PoseConsts& pose, const EvalConsts& ec, double* d_score,
+                         double* d_best, int* d_npairs, long long* d_cell, hipStream_t s) {
+  if (n == 0) return;
+  RigidRT rt;
+  for (int k = 0; k < 9; ++k) rt.R[k] = pose.R[k];
+  for (int k = 0; k < 3; ++k) rt.t[k] = pose.t[k];
+  // the neighbourhood and the record format as plan_derivatives_launch chooses them
+  const bool packed = ec.packed && !(ec.multigrid || ec.kdtree || ec.direct26);
+  const int nb = ec.multigrid ? 4 : (ec.kdtree ? 2 : (ec.direct26 ? 3 : (ec.direct7 ? (packed ? 6 : 1) : (packed ? 5 : 0))));
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+#define NDT_PS(NBH) \
+  hipLaunchKernelGGL(k_point_scores<NBH>, grid, block, 0, s, sx, sy, sz, (int)n, g, cell2leaf, rec, rt, ec, d_score, d_best, d_npairs, d_cell)
+  switch (nb) {
+    case 0: NDT_PS(0); break;
+    case 1: NDT_PS(1); break;
+    case 2: NDT_PS(2); break;
+    case 3: NDT_PS(3); break;
+    case 4: NDT_PS(4); break;
+    case 5: NDT_PS(5); break;
+    default: NDT_PS(6); break;
+  }
+#undef NDT_PS
 }
 
 }  // namespace ndt

@@ -4,6 +4,7 @@
 //   ndt_handoff.hip    host hand-off (repack + pull kernels), the target voxel-grid build's orchestration, grid accessors
 //   ndt_evaluate.hip   derivative evaluations (ordinary, pre-launched, batched), align, scoring
 //   ndt_keyframes.hip  multi-grid targets, the device-resident keyframe archive, voxel downsample
+//   ndt_point_scores.hip  per-point scores and the score-based source filter (its compaction kernels included)
 // One handle = one engine instance = one HIP stream on one gfx950 device; it owns every device allocation.  There is no
 // CPU path: without a device every compute call fails with NDT_ERR_NO_DEVICE.
 #pragma once
@@ -160,6 +161,19 @@ struct FitIndex {
   }
 };
 
+// Scratch of the per-point scoring calls: the host forms' device-side outputs, the filter's predicate values, block
+// counts and (host form) compacted output.  Kept between calls.
+struct PointScoreBufs {
+  DevBuf<double> score, best;
+  DevBuf<int> npairs, index;
+  DevBuf<long long> cell;
+  DevBuf<unsigned int> counts;       // filter_blocks(n) block counts / offsets, then the total
+  DevBuf<float> out;                 // [x | y | z] of the selected points
+  void release() {
+    score.release(); best.release(); npairs.release(); index.release(); cell.release(); counts.release(); out.release();
+  }
+};
+
 }  // namespace engine
 }  // namespace ndt
 
@@ -285,6 +299,7 @@ struct ndt_handle {
   PinBuf<int> small;                 // bounds / counters read-back
   PinBuf<unsigned long long> flag;   // 32 result slots {seq, value} the single-pose kernel writes for the host
   DevBuf<double> partials, dres;
+  PointScoreBufs ps;                 // scratch of ndt_score_points / ndt_filter_source (ndt_point_scores.hip)
   DevBuf<unsigned int> counters;     // per-pose tickets of the in-kernel final reduction
   size_t counters_zeroed = 0;
   DevBuf<PoseConsts> dposes;

@@ -205,4 +205,21 @@ void launch_pack_records(const VoxelRecord* rec, PackedRecord* out, size_t n, hi
 void launch_transform(const float* sx, const float* sy, const float* sz, size_t n,
                       const PoseConsts& pose, float* out_xyz, hipStream_t s);
 
+// Per-point scores (k_point_scores): for point i of the source under pose.R|t its score, its best pair score, its pair
+// count and the cell index of the voxel that gave the best pair score (-1: none) -- what a score-only evaluation
+// adds up.  The neighbourhood and ec.packed (with `rec` the matching table) as for launch_derivatives; every output
+// may be null.  A plain launch: no partial rows, no tickets, no mailbox.
+void launch_point_scores(const float* sx, const float* sy, const float* sz, size_t n, const GridGeom& g, const int* cell2leaf,
+                         const VoxelRecord* rec, const PoseConsts& pose, const EvalConsts& ec, double* d_score,
+                         double* d_best, int* d_npairs, long long* d_cell, hipStream_t s);
+
+// ---- score-based source filter (ndt_point_scores.hip) -----------------------
+// Stable compaction of the points whose value passes  v >= thr  (keep_below: v < thr), in input order: per-block counts,
+// an exclusive scan of the counts by one block (*d_total receives the number selected), then the emit -- every block
+// recomputes its ballots and writes behind its offset; at most `cap` points are written.  Integer counters only.
+int filter_blocks(size_t n);
+void launch_filter_compact(const double* d_value, const float* sx, const float* sy, const float* sz, size_t n, double thr,
+                           int keep_below, unsigned int* d_block_counts /* filter_blocks(n) + 1 */, unsigned int* d_total,
+                           float* ox, float* oy, float* oz, int* o_index, size_t cap, hipStream_t s);
+
 }  // namespace ndt
