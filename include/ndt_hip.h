@@ -350,7 +350,12 @@ int ndt_multigrid_create_kdtree(ndt_handle* h);
  * keyframe's body-frame scan (pointsArchive, ref: run/pipeline.cpp:784) and rebuild the NDT
  * target per keyframe as the sum of <= 5 archived scans, each moved by its current pose
  * (ref: run/pipeline_ligo_tc.cpp:519-529; one scan in run/pipeline.cpp:554-557).  Here the
- * scans stay in HBM; only ids and 4x4 double poses cross the boundary per keyframe. */
+ * scans stay in HBM; only ids and 4x4 double poses cross the boundary per keyframe.
+ * Empty keyframes: ndt_keyframe_put accepts n = 0 (xyz may then be NULL).  In a window an empty keyframe adds no
+ * point.  A window whose keyframes hold no point at all is NDT_ERR_NO_TARGET, as an empty cloud is for
+ * ndt_set_target, and leaves the handle WITHOUT a target (the previous one is not kept).  Viewing an empty keyframe
+ * with ndt_set_source_from_keyframe succeeds and leaves the handle without a source, like ndt_set_source_device_view
+ * with n = 0: the next call that needs one returns NDT_ERR_NO_SOURCE. */
 int ndt_keyframe_put(ndt_handle* h, int64_t id, const float* xyz, size_t n, size_t stride_bytes);
 int ndt_keyframe_erase(ndt_handle* h, int64_t id);
 int64_t ndt_keyframe_count(const ndt_handle* h);

@@ -640,7 +640,9 @@ class NormalDistributionsTransform:
     # --- device-resident keyframe archive (ref: run/pipeline.cpp:784, run/pipeline_ligo_tc.cpp:519-529) ---
     def putKeyframe(self, kf_id, cloud):
         a = self._xyz(cloud)
-        self._check(lib().ndt_keyframe_put(self._h, int(kf_id), a.ctypes.data, len(a), a.strides[0]))
+        # (NumPy reports strides of 0 for an empty array; ndt_keyframe_put accepts n = 0 but checks the stride)
+        stride = a.strides[0] if len(a) else a.itemsize * a.shape[1]
+        self._check(lib().ndt_keyframe_put(self._h, int(kf_id), a.ctypes.data, len(a), stride))
 
     def setInputSourceFromKeyframe(self, kf_id):
         self._check(lib().ndt_set_source_from_keyframe(self._h, int(kf_id)))
