@@ -511,23 +511,16 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
       if (rc) return rc;
     }
     // (otherwise the words ARE the global sums already)
-  } else if (!dev_out) {
-    // (kernel timing on: the cross-rank sum's own wall time, from the local sum in hand to the global one -- what the
-    // --gpus N bench line reports per transport)
-    const auto t_red = std::chrono::steady_clock::now();
-    int rc = h->red.allreduce_host(words, EV_WORDS, &h->err);
-    if (rc) return rc;
-    if (h->timing && h->red.mode() != NDT_REDUCE_NONE) {
-      const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_red).count();
-      h->tm.ms_last_reduce_kernel = ms;
-      h->tm.ms_reduce_kernel_total += ms;
-    }
   }
   // word 31 is zero by construction; the in-kernel final sum raises it when it gave up waiting
   // for a partial row (a lost hand-off must not look like a converged result), and the kernel
   // never produces a non-finite score from finite records.  With several summing blocks (SUMMER_SPLIT) only one of them
-  // owns word 31: the others say "gave up" by publishing their words as NaN -- read here as a lost row, AFTER the
-  // cross-rank sum (a NaN goes through it: every rank sees it and repeats the evaluation).
+  // owns word 31: the others say "gave up" by publishing their words as NaN -- read here as a lost row.
+  // A host-side cross-rank sum (shm, hook) comes BEHIND the repeats below: a rank settles its own lost row or time-out
+  // first and then joins the round its peers are waiting in.  The codes of word 31 do not survive a sum -- one slow rank
+  // makes the kernels pre-launched on ALL its peers give up at once, and three ranks' 2 + 2 + 2 read as no code at all
+  // (the align ended with "a partial row never arrived" at 7 ranks; at 2 ranks the one peer's 2 came through as 2).
+  // Under RCCL the sum has been made on the device by now, and the repeats stay collective as before.
   if (words[EV_FAIL] == 0.0)
     for (int v = 0; v < EV_WORDS; ++v)
       if (std::isnan(words[v])) { words[EV_FAIL] = 1.0; break; }
@@ -575,6 +568,22 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
     HIP_TRY(h, hipStreamSynchronize(s));
     HIP_TRY(h, hipStreamSynchronize(h->stream2));
     return evaluate(h, p, T, need_h, out, score_only, /*safe_retry=*/true);
+  }
+  if (!p2p && !dev_out) {
+    // what is left of a failure here (a repeat that failed again) goes through the sum: every rank fails together
+    // (kernel timing on: the cross-rank sum's own wall time, from the local sum in hand to the global one -- what the
+    // --gpus N bench line reports per transport)
+    const auto t_red = std::chrono::steady_clock::now();
+    int rc = h->red.allreduce_host(words, EV_WORDS, &h->err);
+    if (rc) return rc;
+    if (h->timing && h->red.mode() != NDT_REDUCE_NONE) {
+      const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_red).count();
+      h->tm.ms_last_reduce_kernel = ms;
+      h->tm.ms_reduce_kernel_total += ms;
+    }
+    if (h->red.mode() != NDT_REDUCE_NONE && words[EV_FAIL] == 0.0)   // (a peer's failed repeat)
+      for (int v = 0; v < EV_WORDS; ++v)
+        if (std::isnan(words[v])) { words[EV_FAIL] = 1.0; break; }
   }
   if (words[EV_FAIL] != 0.0 || !std::isfinite(words[EV_SCORE])) {
     h->counters_zeroed = 0;  // the ticket words may be stale: re-zero them before the next launch
@@ -817,16 +826,19 @@ static int eval_batch(ndt_handle* h, const double* poses6, const float* transfor
     h->tm.ms_eval_kernel_total += ms;
     h->tm.n_timed_evals++;
   }
-  for (int k = 0; k < K; ++k)
-    if (h->result.h[(size_t)k * EV_WORDS + EV_FAIL] != 0.0 || !std::isfinite(h->result.h[(size_t)k * EV_WORDS + EV_SCORE])) {
-      h->counters_zeroed = 0;
-      return fail(h, NDT_ERR_HIP, "derivative kernel (batched): a partial row never arrived or the score is not finite");
-    }
   std::memcpy(out, h->result.h, (size_t)K * EV_WORDS * sizeof(double));
   if (!h->red.wants_device_buffer() && h->red.mode() != NDT_REDUCE_NONE) {
     rc = h->red.allreduce_host_batch(out, K, &h->err);   // (P2P: one exchange round per 64 poses, not one per pose)
     if (rc) return rc;
   }
+  // Checked BEHIND the cross-rank sum: a rank that left before the exchange would leave its peers waiting for its rows
+  // until the transport's time-out.  A raised word 31 (its values are positive) and a non-finite score both go through
+  // the sum, so every rank sees the failure of any one of them and all return together (as evaluate() does).
+  for (int k = 0; k < K; ++k)
+    if (out[(size_t)k * EV_WORDS + EV_FAIL] != 0.0 || !std::isfinite(out[(size_t)k * EV_WORDS + EV_SCORE])) {
+      h->counters_zeroed = 0;
+      return fail(h, NDT_ERR_HIP, "derivative kernel (batched): a partial row never arrived or the score is not finite");
+    }
   if (h->eval_log_cap > 0) {
     std::vector<float> Ts(16 * (size_t)K);
     for (int k = 0; k < K; ++k) {
