@@ -387,6 +387,65 @@ int ndt_voxel_downsample_device(ndt_handle* h, const float* dx, const float* dy,
 int ndt_voxel_downsample(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, long intensity_offset_bytes,
                          float leaf, float* out, size_t cap, size_t* n_out);
 
+/* Sparse voxel map accumulated scan by scan (ref: run/pipeline_ins_map_distribution.cpp:281-377: the map driver moves
+ * every keyframe scan into the map frame, keeps all of them, and at shutdown filters the concatenation with
+ * pcl::VoxelGrid(mapvoxelsize), builds the NDT grid from the result and exports the leaves).  Here one map per handle
+ * lives in device memory and holds, per occupied voxel, the float sums of x, y, z (and intensity) and an int32 count:
+ * the points are not kept, there is no dense index (ndt_voxel_downsample refuses a bounding box of more than INT32_MAX
+ * cells; the map does not care how far apart its voxels are), and the map built so far can be exported or made the
+ * target at any time.  The export is bit for bit what ndt_voxel_downsample returns for the concatenation of everything
+ * added, wherever that call is possible: a voxel is floor(p * inv_leaf) per axis in f32 (inv_leaf = 1.0f / leaf)
+ * whatever the bounding box is, a voxel's points are added one at a time in input order, continuing from the sums the
+ * map holds, and the output is in ascending (k, j, i) order, which is PCL's ascending voxel index.
+ *  - ndt_map_reset: a new, empty map (an existing one is freed).  leaf > 1e-6f; initial_capacity: table slots to start
+ *    with (rounded up to a power of two; 0: the default, 2^18).  The table grows by itself: after every add it holds at
+ *    most capacity / 2 voxels.
+ *  - ndt_map_clear frees the map; the other ndt_map_* calls and ndt_set_target_from_map then return
+ *    NDT_ERR_INVALID_ARG ("no map").
+ *  - ndt_map_add / _device / _keyframe: one cloud -- a strided host cloud (as ndt_voxel_downsample takes it), SoA arrays
+ *    in device memory, or an archived keyframe -- moved by a 4x4 double pose (column-major; NULL: as it is; f64 products
+ *    summed left to right, rounded to f32 once, as ndt_set_target_from_keyframes moves a scan).  Non-finite points,
+ *    before or after the pose, are skipped and counted.  Voxel coordinates are limited to |ijk| < 2^20 per axis: an add
+ *    with a finite point beyond is refused as a whole (NDT_ERR_GRID_OVERFLOW); so is one the table cannot grow for
+ *    (NDT_ERR_ALLOC).  Both are decided before anything is written: the map is unchanged.  n = 0 is a no-op.  A map
+ *    created with intensity needs it in every add (intensity_offset_bytes < 0, d_intensity == NULL or a keyframe, which
+ *    holds xyz only: NDT_ERR_INVALID_ARG); one created without ignores it.  The caller's arrays are free when the call
+ *    returns.
+ *  - ndt_map_export / _device: one point per voxel with count >= min_points (<= 1: all; PCL's
+ *    setMinimumPointsNumberPerVoxel), every field sum / (float)count.  At most `cap` points are written, *n_out
+ *    receives the number selected (NDT_ERR_INVALID_ARG naming it if it exceeds cap); o_intensity, o_count / count_out
+ *    may be NULL (count_out: `cap` contiguous int32).  Complete when it returns; the map is unchanged and can be added
+ *    to afterwards.
+ *  - ndt_set_target_from_map: the export with min_points becomes the target (the driver's line 368), without a host
+ *    round trip; the build is reported and deferred as ndt_set_target_from_keyframes' is.  An empty selection is
+ *    NDT_ERR_NO_TARGET and leaves the target as it was.
+ * Target grid, source, align state, iteration history, evaluation counters and the keyframe archive are left untouched
+ * by the ndt_map_* calls; the map survives ndt_set_target* and ndt_set_params and is freed by ndt_map_clear, a new
+ * ndt_map_reset or ndt_destroy. */
+typedef struct ndt_map_info {
+  float leaf;
+  int with_intensity;
+  int64_t n_voxels;          /* occupied voxels */
+  int64_t n_points;          /* finite points accumulated */
+  int64_t n_points_dropped;  /* non-finite points skipped */
+  int64_t capacity;          /* table slots (power of two) */
+  int min_ijk[3], max_ijk[3];/* absolute voxel coordinates; undefined when n_voxels == 0 */
+  int64_t n_adds, n_grows;
+} ndt_map_info;
+int ndt_map_reset(ndt_handle* h, float leaf, int with_intensity, int64_t initial_capacity);
+int ndt_map_clear(ndt_handle* h);
+int ndt_map_add(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, long intensity_offset_bytes,
+                const double* pose16_colmajor_or_null);
+int ndt_map_add_device(ndt_handle* h, const float* dx, const float* dy, const float* dz, const float* d_intensity,
+                       size_t n, const double* pose16_colmajor_or_null);
+int ndt_map_add_keyframe(ndt_handle* h, int64_t id, const double pose16_colmajor[16]);
+int ndt_map_get_info(const ndt_handle* h, ndt_map_info* out);
+int ndt_map_export_device(ndt_handle* h, int min_points, float* ox, float* oy, float* oz, float* o_intensity,
+                          int32_t* o_count, size_t cap, size_t* n_out);
+int ndt_map_export(ndt_handle* h, int min_points, float* out, size_t stride_bytes, long intensity_offset_bytes,
+                   int32_t* count_out, size_t cap, size_t* n_out);
+int ndt_set_target_from_map(ndt_handle* h, int min_points);
+
 /* setRegularizationPose (ref: run/pipeline_ligo_tc.cpp:531) */
 int ndt_set_regularization_pose(ndt_handle* h, const float pose_colmajor[16]);
 int ndt_clear_regularization_pose(ndt_handle* h);

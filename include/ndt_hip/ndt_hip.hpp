@@ -657,6 +657,60 @@ class NormalDistributionsTransform
     out.points.resize(status_ == NDT_OK ? m : 0);
   }
 
+  // ---- sparse voxel map accumulated scan by scan (ref: run/pipeline_ins_map_distribution.cpp:281-377: cumm_thread
+  // transforms every keyframe scan into the map frame and keeps it; the shutdown path filters the concatenation) ----
+  // not part of pclomp: the map keeps per-voxel sums in HBM instead of the points, mapExport returns what
+  // voxelDownsample returns for the concatenation of everything added (pose: 16 column-major doubles, or null)
+  void mapReset(float leaf, bool with_intensity = false, int64_t initial_capacity = 0) {
+    status_ = h_ ? ndt_map_reset(h_, leaf, with_intensity ? 1 : 0, initial_capacity) : NDT_ERR_NO_DEVICE;
+  }
+  void mapClear() { status_ = h_ ? ndt_map_clear(h_) : NDT_ERR_NO_DEVICE; }
+  template <class Cloud>
+  void mapAdd(const Cloud& cloud, const double* pose_colmajor = nullptr) {
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return; }
+    if (cloud.points.empty()) { status_ = ndt_map_add(h_, nullptr, 0, 12, -1, pose_colmajor); return; }
+    using P = typename std::decay<decltype(cloud.points[0])>::type;
+    status_ = ndt_map_add(h_, &cloud.points[0].x, cloud.points.size(), sizeof(P), intensity_offset_of<P>(0), pose_colmajor);
+  }
+  void mapAddDevice(const float* dx, const float* dy, const float* dz, const float* d_intensity, size_t n,
+                    const double* pose_colmajor = nullptr) {
+    status_ = h_ ? ndt_map_add_device(h_, dx, dy, dz, d_intensity, n, pose_colmajor) : NDT_ERR_NO_DEVICE;
+  }
+  void mapAddKeyframe(int64_t id, const double* pose_colmajor) {
+    status_ = h_ ? ndt_map_add_keyframe(h_, id, pose_colmajor) : NDT_ERR_NO_DEVICE;
+  }
+  ndt_map_info mapInfo() {
+    ndt_map_info mi{};
+    status_ = h_ ? ndt_map_get_info(h_, &mi) : NDT_ERR_NO_DEVICE;
+    return mi;
+  }
+  // one point per voxel with >= min_points points, ascending (k, j, i); counts: the voxels' point counts, if asked for
+  template <class Cloud>
+  void mapExport(Cloud& out, int min_points = 1, std::vector<int32_t>* counts = nullptr) {
+    out.points.clear();
+    if (counts) counts->clear();
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return; }
+    ndt_map_info mi{};
+    status_ = ndt_map_get_info(h_, &mi);
+    if (status_ != NDT_OK || mi.n_voxels == 0) return;
+    using P = typename std::decay<decltype(out.points[0])>::type;
+    out.points.resize((size_t)mi.n_voxels);
+    std::vector<int32_t> cnt((size_t)mi.n_voxels);
+    size_t m = 0;
+    status_ = ndt_map_export(h_, min_points, &out.points[0].x, sizeof(P), intensity_offset_of<P>(0), cnt.data(),
+                             out.points.size(), &m);
+    out.points.resize(status_ == NDT_OK ? m : 0);
+    if (counts && status_ == NDT_OK) counts->assign(cnt.begin(), cnt.begin() + (long)m);
+  }
+  size_t mapExportDevice(float* ox, float* oy, float* oz, float* o_intensity, int32_t* o_count, size_t cap, int min_points = 1) {
+    size_t m = 0;
+    status_ = h_ ? ndt_map_export_device(h_, min_points, ox, oy, oz, o_intensity, o_count, cap, &m) : NDT_ERR_NO_DEVICE;
+    return m;
+  }
+  void setInputTargetFromMap(int min_points = 1) {
+    status_ = h_ ? ndt_set_target_from_map(h_, min_points) : NDT_ERR_NO_DEVICE;
+  }
+
   // ---- device-resident keyframe archive (ref: run/pipeline_ligo_tc.cpp:519-529, run/pipeline.cpp:554-557,784) ----
   // not part of pclomp: the body-frame scans stay in HBM, the sliding-window target is assembled
   // there from ids + poses (column-major 4x4 doubles, e.g. gtsam::Pose3::matrix().data())

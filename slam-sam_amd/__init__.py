@@ -102,6 +102,12 @@ class GridInfo(C.Structure):
     ]
 
 
+class MapInfo(C.Structure):
+    _fields_ = [("leaf", C.c_float), ("with_intensity", C.c_int), ("n_voxels", C.c_int64), ("n_points", C.c_int64),
+                ("n_points_dropped", C.c_int64), ("capacity", C.c_int64), ("min_ijk", C.c_int * 3),
+                ("max_ijk", C.c_int * 3), ("n_adds", C.c_int64), ("n_grows", C.c_int64)]
+
+
 class Timing(C.Structure):
     _fields_ = [
         ("ms_last_eval_kernel", C.c_double), ("ms_last_reduce_kernel", C.c_double),
@@ -224,6 +230,8 @@ ABI_SYMBOLS = [
     "ndt_comm_p2p_selftest", "ndt_comm_p2p_stats", "ndt_angle_tables", "ndt_gauss_constants", "ndt_svn_rbf_kernel",
     "ndt_fitness_score", "ndt_fitness_scores", "ndt_newton_align_batch", "ndt_align_batch",
     "ndt_score_points", "ndt_score_points_device", "ndt_source_size", "ndt_filter_source_device", "ndt_filter_source",
+    "ndt_map_reset", "ndt_map_clear", "ndt_map_add", "ndt_map_add_device", "ndt_map_add_keyframe", "ndt_map_get_info",
+    "ndt_map_export_device", "ndt_map_export", "ndt_set_target_from_map",
 ]
 
 _lib = None
@@ -331,6 +339,15 @@ def lib():
         L.ndt_voxel_downsample.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_long, C.c_float, vp, C.c_size_t,
                                            C.POINTER(C.c_size_t)]
         L.ndt_get_iteration_history.argtypes = [vp, fp, dp, dp, C.c_int]
+        L.ndt_map_reset.argtypes = [vp, C.c_float, C.c_int, C.c_int64]
+        L.ndt_map_clear.argtypes = [vp]
+        L.ndt_map_add.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_long, dp]
+        L.ndt_map_add_device.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, dp]
+        L.ndt_map_add_keyframe.argtypes = [vp, C.c_int64, dp]
+        L.ndt_map_get_info.argtypes = [vp, C.POINTER(MapInfo)]
+        L.ndt_map_export_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ndt_map_export.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_long, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ndt_set_target_from_map.argtypes = [vp, C.c_int]
         L.ndt_set_handoff_mode.argtypes = [vp, C.c_int]
         L.ndt_get_handoff_mode.argtypes = [vp]
         L.ndt_wait.argtypes = [vp]
@@ -682,6 +699,81 @@ class NormalDistributionsTransform:
         self._check(lib().ndt_voxel_downsample(self._h, a.ctypes.data, len(a), a.strides[0], off, float(leaf),
                                                out.ctypes.data, len(out), C.byref(m)))
         return out[:m.value]
+
+    # --- sparse voxel map accumulated scan by scan (ref: run/pipeline_ins_map_distribution.cpp:281-377) ---
+    @staticmethod
+    def _pose16_or_none(pose):
+        if pose is None:
+            return None
+        p = np.asarray(pose, dtype=np.float64)
+        if p.shape != (4, 4):
+            raise ValueError("pose must be 4 x 4")
+        return np.ascontiguousarray(p.T).ravel()
+
+    def mapReset(self, leaf, with_intensity=False, initial_capacity=0):
+        """A new, empty voxel map of this leaf size (an existing one is freed)."""
+        self._check(lib().ndt_map_reset(self._h, float(leaf), int(bool(with_intensity)), int(initial_capacity)))
+
+    def mapClear(self):
+        self._check(lib().ndt_map_clear(self._h))
+
+    def mapAdd(self, cloud, intensity_column=None, pose=None):
+        """Host cloud (N x >= 3 float32; intensity_column as for voxelDownsample), moved by the 4x4 double `pose` if
+        one is given, accumulated into the map."""
+        a = np.ascontiguousarray(cloud, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] < 3:
+            raise ValueError("cloud must be N x >=3 float32")
+        p = self._pose16_or_none(pose)
+        off = -1 if intensity_column is None else 4 * int(intensity_column)
+        stride = a.strides[0] if len(a) else a.itemsize * a.shape[1]
+        self._check(lib().ndt_map_add(self._h, a.ctypes.data, len(a), stride, off, None if p is None else _dp(p)))
+
+    def mapAddDevice(self, dx, dy, dz, n, d_intensity=None, pose=None):
+        """SoA float32 arrays in device memory (integer addresses), as mapAdd."""
+        p = self._pose16_or_none(pose)
+        self._check(lib().ndt_map_add_device(self._h, dx, dy, dz, d_intensity, int(n), None if p is None else _dp(p)))
+
+    def mapAddKeyframe(self, kf_id, pose):
+        """An archived keyframe (putKeyframe) moved by its 4x4 double pose."""
+        p = self._pose16_or_none(pose)
+        if p is None:
+            raise ValueError("a keyframe is added under a pose")
+        self._check(lib().ndt_map_add_keyframe(self._h, int(kf_id), _dp(p)))
+
+    def mapInfo(self):
+        mi = MapInfo()
+        self._check(lib().ndt_map_get_info(self._h, C.byref(mi)))
+        return dict(leaf=mi.leaf, with_intensity=bool(mi.with_intensity), n_voxels=mi.n_voxels, n_points=mi.n_points,
+                    n_points_dropped=mi.n_points_dropped, capacity=mi.capacity, min_ijk=tuple(mi.min_ijk),
+                    max_ijk=tuple(mi.max_ijk), n_adds=mi.n_adds, n_grows=mi.n_grows)
+
+    def mapExport(self, min_points=1, columns=3, intensity_column=None, with_counts=False):
+        """The map's centroids (ascending (k, j, i)) as an M x `columns` float32 cloud in the layout mapAdd takes (other
+        columns zero); with_counts: (cloud, int32 counts)."""
+        columns = int(columns)
+        if columns < 3 or (intensity_column is not None and not 3 <= int(intensity_column) < columns):
+            raise ValueError("columns >= 3 and 3 <= intensity_column < columns")
+        off = -1 if intensity_column is None else 4 * int(intensity_column)
+        cap = self.mapInfo()["n_voxels"]              # (no selection holds more)
+        out = np.zeros((cap, columns), dtype=np.float32)
+        cnt = np.zeros(cap, dtype=np.int32)
+        m = C.c_size_t(0)
+        self._check(lib().ndt_map_export(self._h, int(min_points), out.ctypes.data if cap else None, 4 * columns, off,
+                                         cnt.ctypes.data if cap else None, cap, C.byref(m)))
+        out, cnt = out[:m.value], cnt[:m.value]
+        return (out, cnt) if with_counts else out
+
+    def mapExportDevice(self, ox, oy, oz, cap, min_points=1, o_intensity=None, o_count=None):
+        """Into SoA device arrays of `cap` elements (o_count: int32); returns the number of voxels.  The arrays can be
+        handed to setInputTargetDevice as they are."""
+        m = C.c_size_t(0)
+        self._check(lib().ndt_map_export_device(self._h, int(min_points), ox, oy, oz, o_intensity, o_count, int(cap),
+                                                C.byref(m)))
+        return int(m.value)
+
+    def setInputTargetFromMap(self, min_points=1):
+        """The map's centroids (voxels with >= min_points points) become the target, without leaving the device."""
+        self._check(lib().ndt_set_target_from_map(self._h, int(min_points)))
 
     def setGlobalSourceSize(self, n):
         self._check(lib().ndt_set_global_source_size(self._h, int(n)))

@@ -5,6 +5,7 @@
 //   ndt_evaluate.hip   derivative evaluations (ordinary, pre-launched, batched), align, scoring
 //   ndt_keyframes.hip  multi-grid targets, the device-resident keyframe archive, voxel downsample
 //   ndt_point_scores.hip  per-point scores and the score-based source filter (its compaction kernels included)
+//   ndt_map.hip        the sparse voxel map accumulated scan by scan (ndt_map_*), its kernels included
 // One handle = one engine instance = one HIP stream on one gfx950 device; it owns every device allocation.  There is no
 // CPU path: without a device every compute call fails with NDT_ERR_NO_DEVICE.
 #pragma once
@@ -174,6 +175,43 @@ struct PointScoreBufs {
   }
 };
 
+// The sparse voxel map of ndt_map_* (ndt_map.hip): an open-addressing table in HBM keyed by the 63-bit voxel key
+// (k, j, i), the table position being the voxel's slot -- float sums {x, y, z, intensity} and an int32 count per slot.
+// The host keeps the counters it knows when an add's range check returns; the number of voxels is counted on the
+// device by the insert launch and fetched under the next host wait (nvox_stale).
+struct VoxelMap {
+  float leaf = 0.0f, inv_leaf = 0.0f;
+  int with_intensity = 0;
+  unsigned long long* keys = nullptr;  // capacity words, ~0 = empty
+  float* sums = nullptr;               // capacity x float4
+  int* cnt = nullptr;                  // capacity
+  int64_t capacity = 0;
+  int64_t n_voxels = 0, n_points = 0, n_dropped = 0, n_adds = 0, n_grows = 0;
+  int mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
+  bool nvox_stale = false;             // the device's voxel counter is ahead of n_voxels
+  DevBuf<unsigned long long> pkey;     // the batch's voxel keys
+  DevBuf<float> px, py, pz;            // the batch moved by its pose
+  DevBuf<float> ux, uy, uz, ui;        // a host batch on the device
+  DevBuf<int> stats;                   // per add: {finite, out of range, min ijk, max ijk, probe failures}
+  DevBuf<unsigned long long> nvox;     // occupied slots (cumulative)
+  PinBuf<int> stats_h;                 // [0..15] read-back, [16..31] the neutral words
+  PinBuf<unsigned long long> nvox_h;
+  PinBuf<BuildGeom> plan_h;            // sort plans: [0] add, [1] / [2] export (low / high word)
+  DevBuf<unsigned int> xcounts;        // export: per-block counts / offsets, then the total
+  DevBuf<uint32_t> xslot, xslot2, xhi; // export: compacted slots (and in low-word order), high key words
+  DevBuf<float> xout;                  // host export: [x | y | z | intensity] ...
+  DevBuf<int32_t> xcnt;                // ... and counts
+  void release() {
+    if (keys) (void)hipFree(keys);
+    if (sums) (void)hipFree(sums);
+    if (cnt) (void)hipFree(cnt);
+    keys = nullptr; sums = nullptr; cnt = nullptr; capacity = 0;
+    pkey.release(); px.release(); py.release(); pz.release(); ux.release(); uy.release(); uz.release(); ui.release();
+    stats.release(); nvox.release(); stats_h.release(); nvox_h.release(); plan_h.release(); xcounts.release();
+    xslot.release(); xslot2.release(); xhi.release(); xout.release(); xcnt.release();
+  }
+};
+
 }  // namespace engine
 }  // namespace ndt
 
@@ -318,6 +356,8 @@ struct ndt_handle {
   // one per scan: hipMalloc / hipFree of three arrays each cost more than the upload they frame); at most 4 are kept
   std::vector<Keyframe> keyframe_pool;
 
+  VoxelMap* map = nullptr;            // ndt_map_reset .. ndt_map_clear (ndt_map.hip); survives target builds and ndt_set_params
+
   // multi-grid target [RECALLED] (tier4 MultiGridNormalDistributionsTransform): the valid leaves of
   // every separately voxelised cloud, on the host (adding a map tile is not a per-scan operation);
   // ndt_multigrid_create_kdtree assembles their union into the device table
@@ -429,6 +469,7 @@ int report_deferred(ndt_handle* h);
 int settle(ndt_handle* h);
 void settle_discard_keep_grid(ndt_handle* h);
 void settle_discard(ndt_handle* h);
+void map_release(ndt_handle* h);   // ndt_map.hip: frees the voxel map, if any (ndt_destroy)
 void fill_pose_consts(const double p[6], const float T[16], PoseConsts* pc);
 unsigned long long process_item_salt();
 EvalConsts make_eval_consts(const ndt_handle* h, bool need_h);

@@ -172,6 +172,7 @@ int ndt_destroy(ndt_handle* h) {
   h->keyframes.clear();
   for (auto& kf : h->keyframe_pool) { kf.x.release(); kf.y.release(); kf.z.release(); }
   h->keyframe_pool.clear();
+  map_release(h);
   h->sx.release(); h->sy.release(); h->sz.release();
   h->ox.release(); h->oy.release(); h->oz.release(); h->skeys.release(); h->skeys2.release();
   h->svals.release(); h->svals2.release(); h->ssort_tmp.release(); h->splan.release();

@@ -1,0 +1,792 @@
+// ndt_map.hip -- the sparse voxel map accumulated scan by scan (ndt_map_*, see ndt_engine.h: VoxelMap).
+// pcl::VoxelGrid centroids of EVERYTHING added so far, without keeping the points and without a dense index
+// (ref: run/pipeline_ins_map_distribution.cpp:281-377 keeps every scan until shutdown and filters the concatenation once).
+//   add      [transform] -> keys + range check (ONE host wait: refusal / growth are decided before anything is written)
+//            -> insert (atomicCAS on the key word; the table position is the slot) -> the build's stable radix sort of
+//            (slot, point index) and its run search -> one thread per run continues the voxel's float sums in input order
+//   export   compaction of the slots that pass min_points (ballots, integer block offsets) -> sort by the voxel key
+//            relative to the map's bounding box (one 32-bit sort, or two: low word then high word) -> centroids
+// Integer atomics only (the CAS, the block totals of the statistics); no kernel waits for another block, every probe loop
+// is bounded by the capacity.  Which slot a voxel gets depends on the race, on the hash and on the capacity -- what the
+// slot holds does not: a voxel's sums are ((old + p1) + p2) ... over its points in input order, and the export orders by key.
+#include "ndt_engine.h"
+
+namespace ndt {
+
+namespace {
+
+constexpr int MAP_THREADS = 256, MAP_WAVES = MAP_THREADS / 64;
+constexpr int MAP_SCAN_THREADS = 1024, MAP_SCAN_WAVES = MAP_SCAN_THREADS / 64;
+constexpr int MAP_XROUNDS = 4;                         // slots per thread of the export's compaction
+constexpr int MAP_XTILE = MAP_THREADS * MAP_XROUNDS;
+constexpr unsigned long long MAP_EMPTY = ~0ull;
+constexpr int MAP_BIAS = 1 << 20;                      // |ijk| < 2^20 per axis: 21 bits each once biased
+constexpr float MAP_LIMIT = 1048576.0f;
+// words of VoxelMap::stats
+enum { MS_FINITE = 0, MS_OOR = 1, MS_MIN = 2, MS_MAX = 5, MS_PROBE_FAIL = 8, MS_WORDS = 16 };
+
+__device__ __forceinline__ bool map_finite3(float a, float b, float c) {
+  return isfinite(a) && isfinite(b) && isfinite(c);
+}
+
+__device__ __forceinline__ unsigned long long map_hash(unsigned long long k) {  // splitmix64's finaliser
+  k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
+  k ^= k >> 27; k *= 0x94d049bb133111ebull;
+  k ^= k >> 31;
+  return k;
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off));
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
+  return v;
+}
+
+// Voxel key per point: floor(p * inv_leaf) per axis in f32 (the downsample's arithmetic), (k, j, i) biased into 21 bits
+// each -- a 63-bit key that orders as PCL's dense index does.  MAP_EMPTY for a non-finite point (skipped, counted) and
+// for a finite one outside the coordinate range (counted: the host refuses the whole add).  The batch's statistics go
+// to `stats` with one integer atomic per word and block.
+__global__ void __launch_bounds__(MAP_THREADS) k_map_keys(const float* __restrict__ x, const float* __restrict__ y,
+                                                         const float* __restrict__ z, int n, float inv_leaf,
+                                                         unsigned long long* __restrict__ pkey, int* __restrict__ stats) {
+  __shared__ int red[MAP_WAVES][8];
+  const int i = (int)(blockIdx.x * MAP_THREADS + threadIdx.x);
+  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+  int fin = 0, oor = 0;
+  int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
+  if (i < n) {
+    const float a = x[i], b = y[i], c = z[i];
+    unsigned long long key = MAP_EMPTY;
+    if (map_finite3(a, b, c)) {
+      fin = 1;
+      const float fi = floorf(a * inv_leaf), fj = floorf(b * inv_leaf), fk = floorf(c * inv_leaf);
+      if (fabsf(fi) < MAP_LIMIT && fabsf(fj) < MAP_LIMIT && fabsf(fk) < MAP_LIMIT) {
+        const int vi = (int)fi, vj = (int)fj, vk = (int)fk;
+        mn[0] = mx[0] = vi; mn[1] = mx[1] = vj; mn[2] = mx[2] = vk;
+        key = ((unsigned long long)(vk + MAP_BIAS) << 42) | ((unsigned long long)(vj + MAP_BIAS) << 21) |
+              (unsigned long long)(vi + MAP_BIAS);
+      } else {
+        oor = 1;
+      }
+    }
+    pkey[i] = key;
+  }
+  fin = wave_sum(fin);
+  oor = wave_sum(oor);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) { mn[a] = wave_min(mn[a]); mx[a] = wave_max(mx[a]); }
+  if (lane == 0) {
+    red[wave][0] = fin; red[wave][1] = oor;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { red[wave][2 + a] = mn[a]; red[wave][5 + a] = mx[a]; }
+  }
+  __syncthreads();
+  if (threadIdx.x < 8) {
+    const int t = (int)threadIdx.x;
+    int v = red[0][t];
+#pragma unroll
+    for (int w = 1; w < MAP_WAVES; ++w) v = t < 2 ? v + red[w][t] : t < 5 ? min(v, red[w][t]) : max(v, red[w][t]);
+    if (t < 2) { if (v) atomicAdd(stats + t, v); }
+    else if (t < 5) { if (v != INT_MAX) atomicMin(stats + t, v); }
+    else if (v != INT_MIN) atomicMax(stats + t, v);
+  }
+}
+
+// The slot of `key` in the table (linear probing from its hash): the position whose key word holds it, claimed with
+// atomicCAS if no position does yet.  *claimed: this call put the key there.  -1 if all `mask + 1` positions hold other
+// keys (cannot happen at a load of 1/2).  A plain load may show a stale EMPTY, never a wrong key (key words are written
+// once): the CAS then tells the truth.
+__device__ __forceinline__ long long map_slot_of(unsigned long long* __restrict__ tkeys, unsigned long long mask,
+                                                 unsigned long long key, bool* claimed) {
+  unsigned long long s = map_hash(key) & mask;
+  *claimed = false;
+  for (unsigned long long probe = 0; probe <= mask; ++probe) {
+    unsigned long long cur = tkeys[s];
+    if (cur == MAP_EMPTY) {
+      cur = atomicCAS(tkeys + s, MAP_EMPTY, key);
+      if (cur == MAP_EMPTY) { *claimed = true; return (long long)s; }
+    }
+    if (cur == key) return (long long)s;
+    s = (s + 1) & mask;
+  }
+  return -1;
+}
+
+// slot per point (the sort key of the grouping; `mask + 1`, the sentinel, for a skipped point) + the number of
+// voxels this batch created, added to *nvox
+__global__ void __launch_bounds__(MAP_THREADS) k_map_insert(const unsigned long long* __restrict__ pkey, int n,
+                                                           unsigned long long* __restrict__ tkeys, unsigned long long mask,
+                                                           uint32_t* __restrict__ slots, unsigned long long* __restrict__ nvox,
+                                                           int* __restrict__ stats) {
+  __shared__ int red[MAP_WAVES];
+  const int i = (int)(blockIdx.x * MAP_THREADS + threadIdx.x);
+  int fresh = 0;
+  if (i < n) {
+    const unsigned long long key = pkey[i];
+    uint32_t slot = (uint32_t)(mask + 1);
+    if (key != MAP_EMPTY) {
+      bool claimed;
+      const long long s = map_slot_of(tkeys, mask, key, &claimed);
+      if (s >= 0) slot = (uint32_t)s;
+      else atomicAdd(stats + MS_PROBE_FAIL, 1);
+      fresh = claimed ? 1 : 0;
+    }
+    slots[i] = slot;
+  }
+  fresh = wave_sum(fresh);
+  if ((threadIdx.x & 63u) == 0) red[threadIdx.x >> 6] = fresh;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int c = 0;
+#pragma unroll
+    for (int w = 0; w < MAP_WAVES; ++w) c += red[w];
+    if (c) atomicAdd(nvox, (unsigned long long)c);
+  }
+}
+
+// Run r of the slot-sorted batch = points vals_sorted[start .. start + cnt) of one voxel, in input order (the radix sort
+// is stable): its sums go on from what the map holds, one point at a time, as k_voxel_centroids adds them from zero.
+__global__ void __launch_bounds__(MAP_THREADS) k_map_accumulate(const int* __restrict__ d_nleaf, const int* __restrict__ leaf_start,
+                                                               const int* __restrict__ leaf_cnt,
+                                                               const uint32_t* __restrict__ keys_sorted,
+                                                               const uint32_t* __restrict__ vals_sorted,
+                                                               const float* __restrict__ px, const float* __restrict__ py,
+                                                               const float* __restrict__ pz, const float* __restrict__ pi,
+                                                               float4* __restrict__ sums, int* __restrict__ cnt) {
+  const int r = (int)(blockIdx.x * MAP_THREADS + threadIdx.x);
+  if (r >= d_nleaf[0]) return;
+  const int start = leaf_start[r], c = leaf_cnt[r];
+  const uint32_t slot = keys_sorted[start];
+  float4 s = sums[slot];
+  for (int j = 0; j < c; ++j) {
+    const uint32_t p = vals_sorted[start + j];
+    s.x += px[p]; s.y += py[p]; s.z += pz[p];
+    if (pi) s.w += pi[p];
+  }
+  sums[slot] = s;
+  cnt[slot] += c;
+}
+
+// growth: every occupied slot of the old table moves to the new one with its sums and its count as they are
+__global__ void __launch_bounds__(MAP_THREADS) k_map_rehash(const unsigned long long* __restrict__ okeys,
+                                                           const float4* __restrict__ osums, const int* __restrict__ ocnt,
+                                                           long long ocap, unsigned long long* __restrict__ tkeys,
+                                                           unsigned long long mask, float4* __restrict__ sums,
+                                                           int* __restrict__ cnt, int* __restrict__ stats) {
+  const long long i = (long long)blockIdx.x * MAP_THREADS + threadIdx.x;
+  if (i >= ocap) return;
+  const unsigned long long key = okeys[i];
+  if (key == MAP_EMPTY) return;
+  bool claimed;
+  const long long s = map_slot_of(tkeys, mask, key, &claimed);
+  if (s < 0) { atomicAdd(stats + MS_PROBE_FAIL, 1); return; }
+  sums[s] = osums[i];
+  cnt[s] = ocnt[i];
+}
+
+// ---- export ----
+__device__ __forceinline__ bool map_pass(const unsigned long long* __restrict__ tkeys, const int* __restrict__ cnt,
+                                         long long slot, long long cap, int min_points) {
+  return slot < cap && tkeys[slot] != MAP_EMPTY && cnt[slot] >= min_points;
+}
+
+__global__ void __launch_bounds__(MAP_THREADS) k_map_xcount(const unsigned long long* __restrict__ tkeys,
+                                                           const int* __restrict__ cnt, long long cap, int min_points,
+                                                           unsigned int* __restrict__ counts) {
+  __shared__ unsigned int s_w[MAP_WAVES];
+  unsigned int c = 0;
+#pragma unroll
+  for (int r = 0; r < MAP_XROUNDS; ++r) {
+    const long long slot = (long long)blockIdx.x * MAP_XTILE + r * MAP_THREADS + threadIdx.x;
+    c += (unsigned int)__popcll(__ballot(map_pass(tkeys, cnt, slot, cap, min_points)));
+  }
+  if ((threadIdx.x & 63u) == 0) s_w[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned int t = 0;
+#pragma unroll
+    for (int w = 0; w < MAP_WAVES; ++w) t += s_w[w];
+    counts[blockIdx.x] = t;
+  }
+}
+
+// counts[0 .. nb) -> their exclusive prefix sums, in place; counts[nb] receives the sum.  One block.
+__global__ void __launch_bounds__(MAP_SCAN_THREADS) k_map_xscan(unsigned int* __restrict__ counts, int nb) {
+  __shared__ unsigned int s_w[MAP_SCAN_WAVES];
+  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+  unsigned int carry = 0;   // block-uniform
+  for (int base = 0; base < nb; base += MAP_SCAN_THREADS) {
+    const int idx = base + (int)threadIdx.x;
+    const unsigned int c = idx < nb ? counts[idx] : 0u;
+    unsigned int incl = c;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const unsigned int v = __shfl_up(incl, off);
+      if (lane >= off) incl += v;
+    }
+    if (lane == 63) s_w[wave] = incl;
+    __syncthreads();
+    unsigned int wave_off = 0, chunk = 0;
+#pragma unroll
+    for (int w = 0; w < MAP_SCAN_WAVES; ++w) {
+      const unsigned int t = s_w[w];
+      wave_off += w < wave ? t : 0u;
+      chunk += t;
+    }
+    if (idx < nb) counts[idx] = carry + wave_off + incl - c;
+    carry += chunk;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) counts[nb] = carry;
+}
+
+// the key relative to the map's bounding box: (k - min_k, j - min_j, i - min_i) packed into bz + by + bx bits
+struct MapKeyBox {
+  int mn[3];
+  int bx, by;
+};
+
+// the selected slots, compacted (in table order: the sort that follows puts them in key order), and their relative keys
+__global__ void __launch_bounds__(MAP_THREADS) k_map_xemit(const unsigned long long* __restrict__ tkeys,
+                                                          const int* __restrict__ cnt, long long cap, int min_points,
+                                                          const unsigned int* __restrict__ offsets, MapKeyBox box,
+                                                          uint32_t* __restrict__ xslot, uint32_t* __restrict__ klo,
+                                                          uint32_t* __restrict__ khi) {
+  __shared__ unsigned int s_w[MAP_XROUNDS][MAP_WAVES];
+  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+  bool keep[MAP_XROUNDS];
+  unsigned long long bal[MAP_XROUNDS];
+#pragma unroll
+  for (int r = 0; r < MAP_XROUNDS; ++r) {
+    const long long slot = (long long)blockIdx.x * MAP_XTILE + r * MAP_THREADS + threadIdx.x;
+    keep[r] = map_pass(tkeys, cnt, slot, cap, min_points);
+    bal[r] = __ballot(keep[r]);
+    if (lane == 0) s_w[r][wave] = (unsigned int)__popcll(bal[r]);
+  }
+  __syncthreads();
+  unsigned int before = offsets[blockIdx.x];
+#pragma unroll
+  for (int r = 0; r < MAP_XROUNDS; ++r) {
+    unsigned int wave_off = 0, round_total = 0;
+#pragma unroll
+    for (int w = 0; w < MAP_WAVES; ++w) {
+      const unsigned int t = s_w[r][w];
+      wave_off += w < wave ? t : 0u;
+      round_total += t;
+    }
+    if (keep[r]) {
+      const long long slot = (long long)blockIdx.x * MAP_XTILE + r * MAP_THREADS + threadIdx.x;
+      const unsigned int pos = before + wave_off + (unsigned int)__popcll(bal[r] & ((1ull << lane) - 1ull));
+      const unsigned long long key = tkeys[slot];
+      const unsigned long long vi = (key & 0x1fffffull) - (unsigned long long)(box.mn[0] + MAP_BIAS);
+      const unsigned long long vj = ((key >> 21) & 0x1fffffull) - (unsigned long long)(box.mn[1] + MAP_BIAS);
+      const unsigned long long vk = (key >> 42) - (unsigned long long)(box.mn[2] + MAP_BIAS);
+      const unsigned long long rk = (vk << (box.bx + box.by)) | (vj << box.bx) | vi;
+      xslot[pos] = (uint32_t)slot;
+      klo[pos] = (uint32_t)rk;
+      if (khi) khi[pos] = (uint32_t)(rk >> 32);
+    }
+    before += round_total;
+  }
+}
+
+// between the two sorts: the high words and the slots in low-word order
+__global__ void __launch_bounds__(MAP_THREADS) k_map_xgather(const uint32_t* __restrict__ perm, const uint32_t* __restrict__ khi,
+                                                            const uint32_t* __restrict__ xslot, int m,
+                                                            uint32_t* __restrict__ khi2, uint32_t* __restrict__ xslot2) {
+  const int i = (int)(blockIdx.x * MAP_THREADS + threadIdx.x);
+  if (i >= m) return;
+  const uint32_t p = perm[i];
+  khi2[i] = khi[p];
+  xslot2[i] = xslot[p];
+}
+
+// output point r = the voxel slots[order[r]]: every field sum / (float)count, as k_voxel_centroids divides
+__global__ void __launch_bounds__(MAP_THREADS) k_map_xcentroids(const uint32_t* __restrict__ order, const uint32_t* __restrict__ slots,
+                                                               int m, const float4* __restrict__ sums, const int* __restrict__ cnt,
+                                                               float* __restrict__ ox, float* __restrict__ oy, float* __restrict__ oz,
+                                                               float* __restrict__ oi, int32_t* __restrict__ ocount) {
+  const int r = (int)(blockIdx.x * MAP_THREADS + threadIdx.x);
+  if (r >= m) return;
+  const uint32_t slot = slots[order[r]];
+  const float4 s = sums[slot];
+  const int c = cnt[slot];
+  const float nf = (float)c;
+  ox[r] = s.x / nf; oy[r] = s.y / nf; oz[r] = s.z / nf;
+  if (oi) oi[r] = s.w / nf;
+  if (ocount) ocount[r] = c;
+}
+
+int bits_for(long long v) {  // bits that hold 0 .. v
+  int b = 0;
+  while (b < 62 && (1ll << b) <= v) ++b;
+  return b;
+}
+
+}  // namespace
+
+namespace engine {
+namespace {
+
+constexpr int64_t MAP_DEFAULT_CAPACITY = 1ll << 18;
+constexpr int64_t MAP_MAX_CAPACITY = 1ll << 30;   // slots are 32-bit sort keys with one sentinel above them
+
+void free_table(unsigned long long* k, float* s, int* c) {
+  if (k) (void)hipFree(k);
+  if (s) (void)hipFree(s);
+  if (c) (void)hipFree(c);
+}
+
+// an empty table of `cap` slots (keys ~0, sums and counts zero), written on the engine's stream
+int alloc_table(ndt_handle* h, int64_t cap, unsigned long long** k, float** s, int** c) {
+  *k = nullptr; *s = nullptr; *c = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(k), (size_t)cap * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(s), (size_t)cap * 4 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(c), (size_t)cap * sizeof(int));
+  if (e == hipSuccess) e = hipMemsetAsync(*k, 0xFF, (size_t)cap * sizeof(unsigned long long), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(*s, 0, (size_t)cap * 4 * sizeof(float), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(*c, 0, (size_t)cap * sizeof(int), h->stream);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    free_table(*k, *s, *c);
+    *k = nullptr; *s = nullptr; *c = nullptr;
+    return fail(h, e == hipErrorOutOfMemory ? NDT_ERR_ALLOC : NDT_ERR_HIP, std::string("voxel map table: ") + hipGetErrorString(e));
+  }
+  return NDT_OK;
+}
+
+int64_t pow2_at_least(int64_t v) {
+  int64_t c = 64;
+  while (c < v) c <<= 1;
+  return c;
+}
+
+// the scratch of the build that the sort and the run search work in, for n pairs
+int ensure_sort_scratch(ndt_handle* h, size_t n) {
+  HIP_TRY(h, h->gd.ensure(1));
+  HIP_TRY(h, h->gdh.ensure(1));
+  if (!h->tickets.p) {
+    HIP_TRY(h, h->tickets.ensure(6));
+    HIP_TRY(h, hipMemsetAsync(h->tickets.p, 0, h->tickets.cap * sizeof(unsigned int), h->stream));
+  }
+  HIP_TRY(h, h->nleaf.ensure(4));
+  HIP_TRY(h, h->keys.ensure(n));
+  HIP_TRY(h, h->vals.ensure(n));
+  HIP_TRY(h, h->keys2.ensure(n));
+  HIP_TRY(h, h->vals2.ensure(n));
+  HIP_TRY(h, h->leaf_start.ensure(n + 1));
+  HIP_TRY(h, h->leaf_cnt.ensure(n + 1));
+  HIP_TRY(h, h->run_counts.ensure((size_t)runs_blocks(n)));
+  HIP_TRY(h, h->run_offsets.ensure((size_t)runs_blocks(n)));
+  HIP_TRY(h, h->sort_tmp.ensure(sort_temp_bytes(n)));
+  return NDT_OK;
+}
+
+// a sort plan for keys of `bits` bits in pinned slot `which`, copied to the build's device-side BuildGeom on the stream
+int put_plan(ndt_handle* h, int which, int bits, int ncells, int* passes) {
+  VoxelMap& m = *h->map;
+  BuildGeom& b = m.plan_h.h[which];
+  b = BuildGeom{};
+  fill_sort_plan(&b, bits);
+  b.g.ncells = ncells;
+  b.status = BG_OK;
+  *passes = b.passes;
+  HIP_TRY(h, hipMemcpyAsync(h->gd.p, &b, sizeof(BuildGeom), hipMemcpyHostToDevice, h->stream));
+  return NDT_OK;
+}
+
+// n_voxels as the device counts it (the insert launches before this point have run when the call returns)
+int refresh_voxel_count(ndt_handle* h) {
+  VoxelMap& m = *h->map;
+  if (!m.nvox_stale) return NDT_OK;
+  HIP_TRY(h, hipMemcpyAsync(m.nvox_h.h, m.nvox.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  m.n_voxels = (int64_t)m.nvox_h.h[0];
+  m.nvox_stale = false;
+  return NDT_OK;
+}
+
+int grow_table(ndt_handle* h, int64_t new_cap) {
+  VoxelMap& m = *h->map;
+  unsigned long long* nk; float* ns; int* nc;
+  int rc = alloc_table(h, new_cap, &nk, &ns, &nc);
+  if (rc) return rc;   // the map is as it was
+  hipLaunchKernelGGL(k_map_rehash, dim3((unsigned)((m.capacity + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0, h->stream,
+                     m.keys, reinterpret_cast<const float4*>(m.sums), m.cnt, (long long)m.capacity, nk,
+                     (unsigned long long)(new_cap - 1), reinterpret_cast<float4*>(ns), nc, m.stats.p);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // (growth is rare: the old table is freed behind its last reader)
+  if (e != hipSuccess) {
+    free_table(nk, ns, nc);
+    return fail(h, NDT_ERR_HIP, std::string("voxel map growth: ") + hipGetErrorString(e));
+  }
+  free_table(m.keys, m.sums, m.cnt);
+  m.keys = nk; m.sums = ns; m.cnt = nc;
+  m.capacity = new_cap;
+  ++m.n_grows;
+  return NDT_OK;
+}
+
+// One batch in device memory (di may be null in a map without intensity) under an optional pose.
+int map_add_device(ndt_handle* h, const float* dx, const float* dy, const float* dz, const float* di, size_t n,
+                   const double* pose16) {
+  VoxelMap& m = *h->map;
+  if (n == 0) return NDT_OK;
+  if (n > (size_t)std::numeric_limits<int>::max() / 2) return fail(h, NDT_ERR_INVALID_ARG, "cloud too large");
+  settle_discard_keep_grid(h);
+  hipStream_t s = h->stream;
+  // every allocation of the add except the table's growth, before anything is written
+  HIP_TRY(h, m.pkey.ensure(n));
+  if (pose16) {
+    HIP_TRY(h, m.px.ensure(n));
+    HIP_TRY(h, m.py.ensure(n));
+    HIP_TRY(h, m.pz.ensure(n));
+  }
+  int rc = ensure_sort_scratch(h, n);
+  if (rc) return rc;
+  const float *qx = dx, *qy = dy, *qz = dz;
+  if (pose16) {
+    launch_transform_append(dx, dy, dz, n, pose16, m.px.p, m.py.p, m.pz.p, s);
+    qx = m.px.p; qy = m.py.p; qz = m.pz.p;
+  }
+  const unsigned blocks = (unsigned)((n + MAP_THREADS - 1) / MAP_THREADS);
+  HIP_TRY(h, hipMemcpyAsync(m.stats.p, m.stats_h.h + MS_WORDS, MS_WORDS * sizeof(int), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_map_keys, dim3(blocks), dim3(MAP_THREADS), 0, s, qx, qy, qz, (int)n, m.inv_leaf, m.pkey.p, m.stats.p);
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipMemcpyAsync(m.stats_h.h, m.stats.p, MS_WORDS * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipMemcpyAsync(m.nvox_h.h, m.nvox.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));   // the add's one host wait: range check and growth decision
+  m.n_voxels = (int64_t)m.nvox_h.h[0];
+  m.nvox_stale = false;
+  const int* st = m.stats_h.h;
+  if (st[MS_OOR] > 0)
+    return fail(h, NDT_ERR_GRID_OVERFLOW, std::to_string(st[MS_OOR]) + " point(s) beyond the map's coordinate range (|voxel index| < 2^20 per axis); nothing was added");
+  const int64_t n_finite = st[MS_FINITE];
+  const int64_t want = pow2_at_least(2 * (m.n_voxels + (int64_t)n));
+  if (want > m.capacity) {
+    if (want > MAP_MAX_CAPACITY) return fail(h, NDT_ERR_ALLOC, "voxel map: more than 2^30 table slots needed");
+    rc = grow_table(h, want);
+    if (rc) return rc;
+  }
+  // from here on the map changes
+  ++m.n_adds;
+  m.n_dropped += (int64_t)n - n_finite;
+  if (n_finite == 0) return NDT_OK;
+  for (int a = 0; a < 3; ++a) {
+    m.mn[a] = m.n_points ? std::min(m.mn[a], st[MS_MIN + a]) : st[MS_MIN + a];
+    m.mx[a] = m.n_points ? std::max(m.mx[a], st[MS_MAX + a]) : st[MS_MAX + a];
+  }
+  m.n_points += n_finite;
+  m.nvox_stale = true;
+  hipLaunchKernelGGL(k_map_insert, dim3(blocks), dim3(MAP_THREADS), 0, s, m.pkey.p, (int)n, m.keys,
+                     (unsigned long long)(m.capacity - 1), h->keys.p, m.nvox.p, m.stats.p);
+  int passes = 0;
+  rc = put_plan(h, 0, bits_for(m.capacity), (int)m.capacity, &passes);   // (the sentinel `capacity` sorts behind every slot)
+  if (rc) return rc;
+  launch_sort_first_count(h->keys.p, n, h->gd.p, h->sort_tmp.p, s);
+  bool in_b = false;
+  HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, n, passes, h->gd.p, s, &in_b));
+  const uint32_t* keys_sorted = in_b ? h->keys2.p : h->keys.p;
+  const uint32_t* vals_sorted = in_b ? h->vals2.p : h->vals.p;
+  HIP_TRY(h, launch_find_runs(keys_sorted, n, h->gd.p, h->gdh.d, /*min_pts=*/1, h->nleaf.p, h->run_counts.p, h->run_offsets.p,
+                              h->tickets.p + 1, nullptr, 0, &h->run_seq, h->leaf_start.p, h->leaf_cnt.p, s));
+  hipLaunchKernelGGL(k_map_accumulate, dim3(blocks), dim3(MAP_THREADS), 0, s, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p,
+                     keys_sorted, vals_sorted, qx, qy, qz, m.with_intensity ? di : nullptr,
+                     reinterpret_cast<float4*>(m.sums), m.cnt);
+  HIP_TRY(h, hipGetLastError());
+  // the caller's arrays (and the engine's scratch) are free again when the call returns
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return NDT_OK;
+}
+
+// the voxels an export with min_points would write (count + scan, awaited); the block offsets stay in xcounts
+int map_export_count(ndt_handle* h, int min_points, size_t* total) {
+  VoxelMap& m = *h->map;
+  *total = 0;
+  int rc = refresh_voxel_count(h);
+  if (rc) return rc;
+  if (m.n_voxels == 0) return NDT_OK;
+  hipStream_t s = h->stream;
+  const int nb = (int)((m.capacity + MAP_XTILE - 1) / MAP_XTILE);
+  HIP_TRY(h, m.xcounts.ensure((size_t)nb + 1));
+  hipLaunchKernelGGL(k_map_xcount, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.keys, m.cnt, (long long)m.capacity, min_points,
+                     m.xcounts.p);
+  hipLaunchKernelGGL(k_map_xscan, dim3(1), dim3(MAP_SCAN_THREADS), 0, s, m.xcounts.p, nb);
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipMemcpyAsync(m.nvox_h.h + 1, m.xcounts.p + nb, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  *total = (size_t)*reinterpret_cast<const unsigned int*>(m.nvox_h.h + 1);
+  return NDT_OK;
+}
+
+// after map_export_count(min_points) = total > 0: the first min(total, cap) voxels in ascending (k, j, i) order
+int map_export_write(ndt_handle* h, int min_points, size_t total, float* ox, float* oy, float* oz, float* oi, int32_t* oc,
+                     size_t cap) {
+  VoxelMap& m = *h->map;
+  hipStream_t s = h->stream;
+  const size_t w = std::min(total, cap);
+  if (w == 0) return NDT_OK;
+  int rc = ensure_sort_scratch(h, total);
+  if (rc) return rc;
+  MapKeyBox box;
+  for (int a = 0; a < 3; ++a) box.mn[a] = m.mn[a];
+  box.bx = bits_for((long long)m.mx[0] - m.mn[0]);
+  box.by = bits_for((long long)m.mx[1] - m.mn[1]);
+  const int bits = box.bx + box.by + bits_for((long long)m.mx[2] - m.mn[2]);
+  const bool two_words = bits > 32;
+  HIP_TRY(h, m.xslot.ensure(total));
+  if (two_words) {
+    HIP_TRY(h, m.xhi.ensure(total));
+    HIP_TRY(h, m.xslot2.ensure(total));
+  }
+  const int nb = (int)((m.capacity + MAP_XTILE - 1) / MAP_XTILE);
+  hipLaunchKernelGGL(k_map_xemit, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.keys, m.cnt, (long long)m.capacity, min_points,
+                     m.xcounts.p, box, m.xslot.p, h->keys.p, two_words ? m.xhi.p : nullptr);
+  HIP_TRY(h, hipGetLastError());
+  int passes = 0;
+  rc = put_plan(h, 1, std::min(bits, 32), 0, &passes);
+  if (rc) return rc;
+  launch_sort_first_count(h->keys.p, total, h->gd.p, h->sort_tmp.p, s);
+  bool in_b = false;
+  HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, total, passes, h->gd.p, s, &in_b));
+  const uint32_t* order = in_b ? h->vals2.p : h->vals.p;
+  const uint32_t* slots = m.xslot.p;
+  const unsigned tb = (unsigned)((total + MAP_THREADS - 1) / MAP_THREADS);
+  if (two_words) {   // stable: the order of the low words survives among equal high words
+    hipLaunchKernelGGL(k_map_xgather, dim3(tb), dim3(MAP_THREADS), 0, s, order, m.xhi.p, m.xslot.p, (int)total, h->keys.p, m.xslot2.p);
+    HIP_TRY(h, hipGetLastError());
+    rc = put_plan(h, 2, bits - 32, 0, &passes);
+    if (rc) return rc;
+    launch_sort_first_count(h->keys.p, total, h->gd.p, h->sort_tmp.p, s);
+    HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, total, passes, h->gd.p, s, &in_b));
+    order = in_b ? h->vals2.p : h->vals.p;
+    slots = m.xslot2.p;
+  }
+  hipLaunchKernelGGL(k_map_xcentroids, dim3((unsigned)((w + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0, s, order, slots,
+                     (int)w, reinterpret_cast<const float4*>(m.sums), m.cnt, ox, oy, oz, m.with_intensity ? oi : nullptr, oc);
+  HIP_TRY(h, hipGetLastError());
+  if (oi && !m.with_intensity) HIP_TRY(h, hipMemsetAsync(oi, 0, w * sizeof(float), s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return NDT_OK;
+}
+
+int no_map(ndt_handle* h) { return fail(h, NDT_ERR_INVALID_ARG, "no map (ndt_map_reset creates one)"); }
+
+bool pose_finite(const double* p) {
+  for (int i = 0; i < 16; ++i)
+    if (!std::isfinite(p[i])) return false;
+  return true;
+}
+
+}  // namespace
+
+void map_release(ndt_handle* h) {
+  if (!h->map) return;
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  h->map->release();
+  delete h->map;
+  h->map = nullptr;
+}
+
+}  // namespace engine
+}  // namespace ndt
+
+extern "C" {
+
+int ndt_map_reset(ndt_handle* h, float leaf, int with_intensity, int64_t initial_capacity) {
+  if (!h || !(leaf > 1e-6f) || !std::isfinite(leaf) || initial_capacity < 0 || initial_capacity > MAP_MAX_CAPACITY)
+    return NDT_ERR_INVALID_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  map_release(h);
+  h->map = new VoxelMap();
+  VoxelMap& m = *h->map;
+  m.leaf = leaf;
+  m.inv_leaf = 1.0f / leaf;
+  m.with_intensity = with_intensity ? 1 : 0;
+  const int64_t cap = pow2_at_least(initial_capacity > 0 ? initial_capacity : MAP_DEFAULT_CAPACITY);
+  auto undo = [&](int code) { map_release(h); return code; };
+  rc = alloc_table(h, cap, &m.keys, &m.sums, &m.cnt);
+  if (rc) return undo(rc);
+  m.capacity = cap;
+  hipError_t e = m.stats.ensure(MS_WORDS);
+  if (e == hipSuccess) e = m.nvox.ensure(1);
+  if (e == hipSuccess) e = m.stats_h.ensure(2 * MS_WORDS);
+  if (e == hipSuccess) e = m.nvox_h.ensure(2);
+  if (e == hipSuccess) e = m.plan_h.ensure(3);
+  if (e == hipSuccess) e = hipMemsetAsync(m.nvox.p, 0, sizeof(unsigned long long), h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) return undo(fail(h, e == hipErrorOutOfMemory ? NDT_ERR_ALLOC : NDT_ERR_HIP, hipGetErrorString(e)));
+  int* neutral = m.stats_h.h + MS_WORDS;
+  for (int i = 0; i < MS_WORDS; ++i) neutral[i] = 0;
+  for (int a = 0; a < 3; ++a) { neutral[MS_MIN + a] = INT_MAX; neutral[MS_MAX + a] = INT_MIN; }
+  return NDT_OK;
+}
+
+int ndt_map_clear(ndt_handle* h) {
+  if (!h) return NDT_ERR_INVALID_ARG;
+  if (!h->map) return NDT_OK;
+  (void)hipSetDevice(h->device);
+  map_release(h);
+  return NDT_OK;
+}
+
+int ndt_map_add_device(ndt_handle* h, const float* dx, const float* dy, const float* dz, const float* d_intensity, size_t n,
+                       const double* pose16) {
+  if (!h || ((!dx || !dy || !dz) && n)) return NDT_ERR_INVALID_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  if (!h->map) return no_map(h);
+  if (h->map->with_intensity && !d_intensity && n) return fail(h, NDT_ERR_INVALID_ARG, "the map keeps intensity: every add must bring it");
+  if (pose16 && !pose_finite(pose16)) return fail(h, NDT_ERR_INVALID_ARG, "non-finite pose");
+  return map_add_device(h, dx, dy, dz, d_intensity, n, pose16);
+}
+
+int ndt_map_add(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, long intensity_offset_bytes, const double* pose16) {
+  if (!h || (!xyz && n) || stride_bytes < 12 || stride_bytes % 4 ||
+      (intensity_offset_bytes >= 0 && (intensity_offset_bytes % 4 || (size_t)intensity_offset_bytes + 4 > stride_bytes ||
+                                       intensity_offset_bytes < 12)))
+    return NDT_ERR_INVALID_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  if (!h->map) return no_map(h);
+  VoxelMap& m = *h->map;
+  const bool has_i = m.with_intensity != 0;
+  if (has_i && intensity_offset_bytes < 0) return fail(h, NDT_ERR_INVALID_ARG, "the map keeps intensity: every add must bring it");
+  if (pose16 && !pose_finite(pose16)) return fail(h, NDT_ERR_INVALID_ARG, "non-finite pose");
+  if (n == 0) return NDT_OK;
+  settle_discard_keep_grid(h);
+  rc = upload_soa(h, h->lane_t, h->stream, xyz, nullptr, nullptr, nullptr, n, stride_bytes, m.ux, m.uy, m.uz, true);
+  if (rc) return rc;
+  if (has_i) {
+    std::vector<float> tmp(n);
+    const char* base = reinterpret_cast<const char*>(xyz) + intensity_offset_bytes;
+    for (size_t i = 0; i < n; ++i) tmp[i] = *reinterpret_cast<const float*>(base + i * stride_bytes);
+    HIP_TRY(h, m.ui.ensure(n));
+    HIP_TRY(h, hipMemcpy(m.ui.p, tmp.data(), n * sizeof(float), hipMemcpyHostToDevice));
+  }
+  return map_add_device(h, m.ux.p, m.uy.p, m.uz.p, has_i ? m.ui.p : nullptr, n, pose16);
+}
+
+int ndt_map_add_keyframe(ndt_handle* h, int64_t id, const double pose16[16]) {
+  if (!h || !pose16) return NDT_ERR_INVALID_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  if (!h->map) return no_map(h);
+  if (h->map->with_intensity) return fail(h, NDT_ERR_INVALID_ARG, "the map keeps intensity: the keyframe archive holds xyz only");
+  if (!pose_finite(pose16)) return fail(h, NDT_ERR_INVALID_ARG, "non-finite pose");
+  auto it = h->keyframes.find(id);
+  if (it == h->keyframes.end()) return fail(h, NDT_ERR_INVALID_ARG, "unknown keyframe id");
+  const ndt_handle::Keyframe& kf = it->second;
+  return map_add_device(h, kf.x.p, kf.y.p, kf.z.p, nullptr, kf.n, pose16);
+}
+
+int ndt_map_get_info(const ndt_handle* h, ndt_map_info* out) {
+  if (!h || !out) return NDT_ERR_INVALID_ARG;
+  if (!h->map) return NDT_ERR_INVALID_ARG;
+  VoxelMap& m = *h->map;
+  if (m.nvox_stale) {   // (every add returns with its launches complete: a plain copy)
+    (void)hipSetDevice(h->device);
+    if (hipMemcpy(m.nvox_h.h, m.nvox.p, sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return NDT_ERR_HIP;
+    m.n_voxels = (int64_t)m.nvox_h.h[0];
+    m.nvox_stale = false;
+  }
+  *out = ndt_map_info{};
+  out->leaf = m.leaf;
+  out->with_intensity = m.with_intensity;
+  out->n_voxels = m.n_voxels;
+  out->n_points = m.n_points;
+  out->n_points_dropped = m.n_dropped;
+  out->capacity = m.capacity;
+  for (int a = 0; a < 3; ++a) { out->min_ijk[a] = m.mn[a]; out->max_ijk[a] = m.mx[a]; }
+  out->n_adds = m.n_adds;
+  out->n_grows = m.n_grows;
+  return NDT_OK;
+}
+
+int ndt_map_export_device(ndt_handle* h, int min_points, float* ox, float* oy, float* oz, float* o_intensity, int32_t* o_count,
+                          size_t cap, size_t* n_out) {
+  if (!h || !n_out || ((!ox || !oy || !oz) && cap)) return NDT_ERR_INVALID_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  if (!h->map) return no_map(h);
+  settle_discard_keep_grid(h);
+  size_t total = 0;
+  rc = map_export_count(h, min_points, &total);
+  if (rc) return rc;
+  *n_out = total;
+  if (total == 0) return NDT_OK;
+  rc = map_export_write(h, min_points, total, ox, oy, oz, o_intensity, o_count, cap);
+  if (rc) return rc;
+  if (total > cap) return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(total) + " voxels");
+  return NDT_OK;
+}
+
+int ndt_map_export(ndt_handle* h, int min_points, float* out, size_t stride_bytes, long intensity_offset_bytes, int32_t* count_out,
+                   size_t cap, size_t* n_out) {
+  if (!h || !n_out || (!out && cap) || stride_bytes < 12 || stride_bytes % 4 ||
+      (intensity_offset_bytes >= 0 && (intensity_offset_bytes % 4 || (size_t)intensity_offset_bytes + 4 > stride_bytes ||
+                                       intensity_offset_bytes < 12)))
+    return NDT_ERR_INVALID_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  if (!h->map) return no_map(h);
+  VoxelMap& m = *h->map;
+  settle_discard_keep_grid(h);
+  size_t total = 0;
+  rc = map_export_count(h, min_points, &total);
+  if (rc) return rc;
+  *n_out = total;
+  if (total == 0) return NDT_OK;
+  const size_t w = std::min(total, cap);
+  if (w) {
+    const bool has_i = intensity_offset_bytes >= 0;
+    HIP_TRY(h, m.xout.ensure(4 * w));
+    HIP_TRY(h, m.xcnt.ensure(w));
+    float* o = m.xout.p;
+    rc = map_export_write(h, min_points, total, o, o + w, o + 2 * w, has_i ? o + 3 * w : nullptr, m.xcnt.p, w);
+    if (rc) return rc;
+    std::vector<float> back(4 * w);
+    HIP_TRY(h, hipMemcpy(back.data(), o, (has_i ? 4 : 3) * w * sizeof(float), hipMemcpyDeviceToHost));
+    if (count_out) HIP_TRY(h, hipMemcpy(count_out, m.xcnt.p, w * sizeof(int32_t), hipMemcpyDeviceToHost));
+    char* ob = reinterpret_cast<char*>(out);
+    for (size_t i = 0; i < w; ++i) {
+      float* p = reinterpret_cast<float*>(ob + i * stride_bytes);
+      p[0] = back[i]; p[1] = back[w + i]; p[2] = back[2 * w + i];
+      if (has_i) *reinterpret_cast<float*>(ob + i * stride_bytes + intensity_offset_bytes) = back[3 * w + i];
+    }
+  }
+  if (total > cap) return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(total) + " voxels");
+  return NDT_OK;
+}
+
+int ndt_set_target_from_map(ndt_handle* h, int min_points) {
+  if (!h) return NDT_ERR_INVALID_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  if (!h->map) return no_map(h);
+  settle_discard(h);
+  size_t total = 0;
+  rc = map_export_count(h, min_points, &total);
+  if (rc) return rc;
+  if (total == 0) return fail(h, NDT_ERR_NO_TARGET, "the map holds no voxel with that many points");
+  HIP_TRY(h, h->tx.ensure(total));
+  HIP_TRY(h, h->ty.ensure(total));
+  HIP_TRY(h, h->tz.ensure(total));
+  rc = map_export_write(h, min_points, total, h->tx.p, h->ty.p, h->tz.p, nullptr, nullptr, total);
+  if (rc) return rc;
+  // (the centroids are the engine's own: the build may stay in flight like a host hand-off's)
+  return build_grid(h, h->tx.p, h->ty.p, h->tz.p, total, h->handoff_mode == NDT_HANDOFF_ASYNC);
+}
+
+}  // extern "C"
