@@ -446,6 +446,37 @@ int ndt_map_export(ndt_handle* h, int min_points, float* out, size_t stride_byte
                    int32_t* count_out, size_t cap, size_t* n_out);
 int ndt_set_target_from_map(ndt_handle* h, int min_points);
 
+/* Per-voxel moments and the NDT target made from them (the classical NDT map).  ndt_set_target_from_map builds the
+ * target from one centroid per map voxel, as the driver's shutdown code does: the distribution of the points inside a
+ * voxel is lost, and the whole map has to fit one dense index.  With moments on, the map keeps per voxel the nine sums
+ * the target build reduces a voxel's points to -- sum x, y, z and sum xx, xy, xz, yy, yz, zz, in f64 of the f32
+ * coordinates, one point at a time in input order, continuing from what the map holds (the order of the reference's
+ * own loop, so the sums do not depend on how the points were split into adds) -- and the leaves are made from them.
+ *  - ndt_map_enable_moments: allowed on a map that has accumulated no point yet (right after ndt_map_reset), once;
+ *    otherwise NDT_ERR_INVALID_ARG.  Every later add also accumulates the moments (72 more bytes per voxel).  A new
+ *    ndt_map_reset gives a map without moments.  ndt_map_has_moments: 1 / 0 (0 without a map).  The other ndt_map_*
+ *    calls and ndt_set_target_from_map behave, bit for bit, as on a map without moments.
+ *  - ndt_map_export_moments: host arrays (any may be NULL) of the voxels with count >= min_points in ascending
+ *    (k, j, i) order: ijk 3 ints, count, sums 9 doubles {x, y, z, xx, xy, xz, yy, yz, zz} per voxel.  Size protocol
+ *    as ndt_map_export.  NDT_ERR_INVALID_ARG on a map without moments.
+ *  - ndt_set_target_from_map_moments: box_min / box_max both NULL: the whole map; otherwise the voxels with
+ *    floor(box_min[a] * inv_leaf) <= ijk[a] <= floor(box_max[a] * inv_leaf) on every axis (the f32 floor of a point's
+ *    voxel).  The target becomes what ndt_set_target would build, under the handle's current ndt_params, from the
+ *    finite points ever added whose voxel is inside the box: the grid geometry is the ijk box of the occupied voxels
+ *    selected, the leaves are those with at least max(3, min_points_per_voxel) points, n_target_points is the sum of
+ *    the selected voxels' counts.  Leaf slots are handed out in ascending voxel order: two handles fed the same adds
+ *    hold the same table.  Refusals, each leaving the target exactly as it was: no map, no moments, a map leaf that is
+ *    not bit-equal to ndt_params::resolution, a box that is not finite or given by halves (NDT_ERR_INVALID_ARG); no
+ *    occupied voxel selected (NDT_ERR_NO_TARGET); a selected ijk box of INT32_MAX cells or more
+ *    (NDT_ERR_GRID_OVERFLOW).  The call completes before it returns.  Afterwards the handle is where
+ *    ndt_set_target_device leaves it: no target points are retained (ndt_fitness_score: NDT_ERR_UNSUPPORTED; an
+ *    ndt_set_params that changes the grid drops it until this function is called again -- the map is still there). */
+int ndt_map_enable_moments(ndt_handle* h);
+int ndt_map_has_moments(const ndt_handle* h);
+int ndt_map_export_moments(ndt_handle* h, int min_points, int32_t* ijk, int32_t* count, double* sums, size_t cap,
+                           size_t* n_out);
+int ndt_set_target_from_map_moments(ndt_handle* h, const float box_min[3], const float box_max[3]);
+
 /* setRegularizationPose (ref: run/pipeline_ligo_tc.cpp:531) */
 int ndt_set_regularization_pose(ndt_handle* h, const float pose_colmajor[16]);
 int ndt_clear_regularization_pose(ndt_handle* h);
@@ -717,7 +748,10 @@ typedef struct ndt_timing {
   double ms_last_eval_kernel;   /* HIP-event time of the last derivative kernel */
   double ms_last_reduce_kernel; /* round 5: wall time of the last CROSS-RANK sum on the host (shm / hook transports; 0 without
                                  * a reducer; the peer-write exchange runs inside the kernel: ndt_comm_p2p_stats) */
-  double ms_last_build;
+  double ms_last_build;         /* the last target build: HIP-event time of its launches while kernel timing is on, else wall time
+                                 * from its enqueue to its verdict.  ndt_set_target_from_map_moments and the multi-grid union
+                                 * always report the wall time of the whole call, its host waits included (so does
+                                 * ndt_grid_info::ms_build) */
   int64_t n_eval_launches;      /* since handle creation */
   double ms_eval_kernel_total;  /* summed HIP-event time of the accumulation kernel while timing is on */
   double ms_reduce_kernel_total;

@@ -710,6 +710,27 @@ class NormalDistributionsTransform
   void setInputTargetFromMap(int min_points = 1) {
     status_ = h_ ? ndt_set_target_from_map(h_, min_points) : NDT_ERR_NO_DEVICE;
   }
+  // per-voxel moments (the nine f64 sums of the target build) and the target made directly from them: right after
+  // mapReset; mapExportMoments fills ijk (3 per voxel), counts and sums (9 per voxel: x y z xx xy xz yy yz zz)
+  void mapEnableMoments() { status_ = h_ ? ndt_map_enable_moments(h_) : NDT_ERR_NO_DEVICE; }
+  bool mapHasMoments() const { return h_ && ndt_map_has_moments(h_) == 1; }
+  void mapExportMoments(std::vector<int32_t>& ijk, std::vector<int32_t>& counts, std::vector<double>& sums, int min_points = 1) {
+    ijk.clear(); counts.clear(); sums.clear();
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return; }
+    ndt_map_info mi{};
+    status_ = ndt_map_get_info(h_, &mi);
+    if (status_ != NDT_OK) return;
+    const size_t cap = (size_t)mi.n_voxels;
+    ijk.resize(3 * cap); counts.resize(cap); sums.resize(9 * cap);
+    size_t m = 0;
+    status_ = ndt_map_export_moments(h_, min_points, ijk.data(), counts.data(), sums.data(), cap, &m);
+    if (status_ != NDT_OK) m = 0;
+    ijk.resize(3 * m); counts.resize(m); sums.resize(9 * m);
+  }
+  // box_min / box_max: three floats each, or both null for the whole map
+  void setInputTargetFromMapMoments(const float* box_min = nullptr, const float* box_max = nullptr) {
+    status_ = h_ ? ndt_set_target_from_map_moments(h_, box_min, box_max) : NDT_ERR_NO_DEVICE;
+  }
 
   // ---- device-resident keyframe archive (ref: run/pipeline_ligo_tc.cpp:519-529, run/pipeline.cpp:554-557,784) ----
   // not part of pclomp: the body-frame scans stay in HBM, the sliding-window target is assembled

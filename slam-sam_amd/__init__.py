@@ -232,6 +232,7 @@ ABI_SYMBOLS = [
     "ndt_score_points", "ndt_score_points_device", "ndt_source_size", "ndt_filter_source_device", "ndt_filter_source",
     "ndt_map_reset", "ndt_map_clear", "ndt_map_add", "ndt_map_add_device", "ndt_map_add_keyframe", "ndt_map_get_info",
     "ndt_map_export_device", "ndt_map_export", "ndt_set_target_from_map",
+    "ndt_map_enable_moments", "ndt_map_has_moments", "ndt_map_export_moments", "ndt_set_target_from_map_moments",
 ]
 
 _lib = None
@@ -348,6 +349,10 @@ def lib():
         L.ndt_map_export_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ndt_map_export.argtypes = [vp, C.c_int, vp, C.c_size_t, C.c_long, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ndt_set_target_from_map.argtypes = [vp, C.c_int]
+        L.ndt_map_enable_moments.argtypes = [vp]
+        L.ndt_map_has_moments.argtypes = [vp]
+        L.ndt_map_export_moments.argtypes = [vp, C.c_int, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ndt_set_target_from_map_moments.argtypes = [vp, fp, fp]
         L.ndt_set_handoff_mode.argtypes = [vp, C.c_int]
         L.ndt_get_handoff_mode.argtypes = [vp]
         L.ndt_wait.argtypes = [vp]
@@ -774,6 +779,48 @@ class NormalDistributionsTransform:
     def setInputTargetFromMap(self, min_points=1):
         """The map's centroids (voxels with >= min_points points) become the target, without leaving the device."""
         self._check(lib().ndt_set_target_from_map(self._h, int(min_points)))
+
+    def mapEnableMoments(self):
+        """From now on the map also keeps, per voxel, the nine f64 moment sums the target build reduces to (allowed on
+        a map that has accumulated no point yet)."""
+        self._check(lib().ndt_map_enable_moments(self._h))
+
+    def mapHasMoments(self):
+        rc = lib().ndt_map_has_moments(self._h)
+        if rc < 0:
+            self._check(rc)
+        return bool(rc)
+
+    def mapExportMoments(self, min_points=1):
+        """(ijk [m, 3] int32, count [m] int32, sums [m, 9] float64: sum x, y, z, then xx xy xz yy yz zz) of the voxels
+        with >= min_points points, ascending (k, j, i): what a caller saves to disk."""
+        cap = self.mapInfo()["n_voxels"]              # (no selection holds more)
+        ijk = np.zeros((cap, 3), dtype=np.int32)
+        cnt = np.zeros(cap, dtype=np.int32)
+        sums = np.zeros((cap, 9), dtype=np.float64)
+        m = C.c_size_t(0)
+        self._check(lib().ndt_map_export_moments(self._h, int(min_points), ijk.ctypes.data if cap else None,
+                                                 cnt.ctypes.data if cap else None, sums.ctypes.data if cap else None, cap,
+                                                 C.byref(m)))
+        return ijk[:m.value], cnt[:m.value], sums[:m.value]
+
+    @staticmethod
+    def _box_corner(v, name):
+        a = np.ascontiguousarray(v, dtype=np.float32)
+        if a.shape != (3,) or not np.isfinite(a).all():
+            raise ValueError("%s must be three finite numbers" % name)
+        return a
+
+    def setInputTargetFromMapMoments(self, box_min=None, box_max=None):
+        """The NDT target made directly from the map's per-voxel moments: what setInputTarget would build from every
+        finite point ever added whose voxel lies inside the box (both corners None: the whole map)."""
+        if (box_min is None) != (box_max is None):
+            raise ValueError("box_min and box_max go together (both None: the whole map)")
+        if box_min is None:
+            self._check(lib().ndt_set_target_from_map_moments(self._h, None, None))
+            return
+        lo, hi = self._box_corner(box_min, "box_min"), self._box_corner(box_max, "box_max")
+        self._check(lib().ndt_set_target_from_map_moments(self._h, _fp(lo), _fp(hi)))
 
     def setGlobalSourceSize(self, n):
         self._check(lib().ndt_set_global_source_size(self._h, int(n)))

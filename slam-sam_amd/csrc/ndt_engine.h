@@ -176,7 +176,9 @@ struct PointScoreBufs {
 };
 
 // The sparse voxel map of ndt_map_* (ndt_map.hip): an open-addressing table in HBM keyed by the 63-bit voxel key
-// (k, j, i), the table position being the voxel's slot -- float sums {x, y, z, intensity} and an int32 count per slot.
+// (k, j, i), the table position being the voxel's slot -- float sums {x, y, z, intensity} and an int32 count per slot,
+// and with moments on (ndt_map_enable_moments) the nine f64 sums of the target build {x, y, z, xx, xy, xz, yy, yz, zz}:
+// 28 or 100 bytes per slot.
 // The host keeps the counters it knows when an add's range check returns; the number of voxels is counted on the
 // device by the insert launch and fetched under the next host wait (nvox_stale).
 struct VoxelMap {
@@ -185,6 +187,8 @@ struct VoxelMap {
   unsigned long long* keys = nullptr;  // capacity words, ~0 = empty
   float* sums = nullptr;               // capacity x float4
   int* cnt = nullptr;                  // capacity
+  double* mom = nullptr;               // capacity x 9 doubles; allocated only with moments on
+  bool moments = false;
   int64_t capacity = 0;
   int64_t n_voxels = 0, n_points = 0, n_dropped = 0, n_adds = 0, n_grows = 0;
   int mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
@@ -201,14 +205,20 @@ struct VoxelMap {
   DevBuf<uint32_t> xslot, xslot2, xhi; // export: compacted slots (and in low-word order), high key words
   DevBuf<float> xout;                  // host export: [x | y | z | intensity] ...
   DevBuf<int32_t> xcnt;                // ... and counts
+  DevBuf<int32_t> xijk;                // moments export: 3 ints per voxel ...
+  DevBuf<double> xmom;                 // ... and its 9 sums
+  DevBuf<int> tsel;                    // target from moments: what the selection pass reduces (TS_* words, ndt_map.hip)
+  PinBuf<int> tsel_h;                  // [0..15] read-back, [16..31] the neutral words
   void release() {
     if (keys) (void)hipFree(keys);
     if (sums) (void)hipFree(sums);
     if (cnt) (void)hipFree(cnt);
-    keys = nullptr; sums = nullptr; cnt = nullptr; capacity = 0;
+    if (mom) (void)hipFree(mom);
+    keys = nullptr; sums = nullptr; cnt = nullptr; mom = nullptr; moments = false; capacity = 0;
     pkey.release(); px.release(); py.release(); pz.release(); ux.release(); uy.release(); uz.release(); ui.release();
     stats.release(); nvox.release(); stats_h.release(); nvox_h.release(); plan_h.release(); xcounts.release();
-    xslot.release(); xslot2.release(); xhi.release(); xout.release(); xcnt.release();
+    xslot.release(); xslot2.release(); xhi.release(); xout.release(); xcnt.release(); xijk.release(); xmom.release();
+    tsel.release(); tsel_h.release();
   }
 };
 

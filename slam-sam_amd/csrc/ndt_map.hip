@@ -9,6 +9,10 @@
 // Integer atomics only (the CAS, the block totals of the statistics); no kernel waits for another block, every probe loop
 // is bounded by the capacity.  Which slot a voxel gets depends on the race, on the hash and on the capacity -- what the
 // slot holds does not: a voxel's sums are ((old + p1) + p2) ... over its points in input order, and the export orders by key.
+//   moments  (ndt_map_enable_moments) the same add also continues, per voxel, the nine f64 sums the target build reduces a
+//            voxel's points to; ndt_set_target_from_map_moments selects the voxels of a box with the export's count / scan /
+//            compaction / key sort under a predicate (ONE host wait: selection count, ijk box and point total decide the
+//            refusals and size the grid) and hands each to the ordinary build's finalize_leaf (launch_map_finalize).
 #include "ndt_engine.h"
 
 namespace ndt {
@@ -24,6 +28,9 @@ constexpr int MAP_BIAS = 1 << 20;                      // |ijk| < 2^20 per axis:
 constexpr float MAP_LIMIT = 1048576.0f;
 // words of VoxelMap::stats
 enum { MS_FINITE = 0, MS_OOR = 1, MS_MIN = 2, MS_MAX = 5, MS_PROBE_FAIL = 8, MS_WORDS = 16 };
+// words of VoxelMap::tsel: ijk box, number and point total (64 bits) of the occupied voxels a selection's box holds,
+// and the leaves its finalize launch accepted
+enum { TS_MIN = 0, TS_MAX = 3, TS_VOXELS = 6, TS_POINTS = 8, TS_VALID = 10, TS_WORDS = 16 };
 
 __device__ __forceinline__ bool map_finite3(float a, float b, float c) {
   return isfinite(a) && isfinite(b) && isfinite(c);
@@ -156,25 +163,45 @@ __global__ void __launch_bounds__(MAP_THREADS) k_map_insert(const unsigned long 
 
 // Run r of the slot-sorted batch = points vals_sorted[start .. start + cnt) of one voxel, in input order (the radix sort
 // is stable): its sums go on from what the map holds, one point at a time, as k_voxel_centroids adds them from zero.
+// MOM: so do its nine f64 moment sums -- a, b, c hold f32 values, so every product is exact in f64 and ss += a * b rounds
+// once whether or not it is contracted; the chains run in input order like the oracle's.
+template <bool MOM>
 __global__ void __launch_bounds__(MAP_THREADS) k_map_accumulate(const int* __restrict__ d_nleaf, const int* __restrict__ leaf_start,
                                                                const int* __restrict__ leaf_cnt,
                                                                const uint32_t* __restrict__ keys_sorted,
                                                                const uint32_t* __restrict__ vals_sorted,
                                                                const float* __restrict__ px, const float* __restrict__ py,
                                                                const float* __restrict__ pz, const float* __restrict__ pi,
-                                                               float4* __restrict__ sums, int* __restrict__ cnt) {
+                                                               float4* __restrict__ sums, int* __restrict__ cnt,
+                                                               double* __restrict__ mom) {
   const int r = (int)(blockIdx.x * MAP_THREADS + threadIdx.x);
   if (r >= d_nleaf[0]) return;
   const int start = leaf_start[r], c = leaf_cnt[r];
   const uint32_t slot = keys_sorted[start];
   float4 s = sums[slot];
+  double q[9];
+  if (MOM) {
+#pragma unroll
+    for (int a = 0; a < 9; ++a) q[a] = mom[(size_t)slot * 9 + a];
+  }
   for (int j = 0; j < c; ++j) {
     const uint32_t p = vals_sorted[start + j];
-    s.x += px[p]; s.y += py[p]; s.z += pz[p];
+    const float fx = px[p], fy = py[p], fz = pz[p];
+    s.x += fx; s.y += fy; s.z += fz;
     if (pi) s.w += pi[p];
+    if (MOM) {
+      const double a = (double)fx, b = (double)fy, d = (double)fz;
+      q[0] += a; q[1] += b; q[2] += d;
+      q[3] += a * a; q[4] += a * b; q[5] += a * d;
+      q[6] += b * b; q[7] += b * d; q[8] += d * d;
+    }
   }
   sums[slot] = s;
   cnt[slot] += c;
+  if (MOM) {
+#pragma unroll
+    for (int a = 0; a < 9; ++a) mom[(size_t)slot * 9 + a] = q[a];
+  }
 }
 
 // growth: every occupied slot of the old table moves to the new one with its sums and its count as they are
@@ -182,7 +209,8 @@ __global__ void __launch_bounds__(MAP_THREADS) k_map_rehash(const unsigned long 
                                                            const float4* __restrict__ osums, const int* __restrict__ ocnt,
                                                            long long ocap, unsigned long long* __restrict__ tkeys,
                                                            unsigned long long mask, float4* __restrict__ sums,
-                                                           int* __restrict__ cnt, int* __restrict__ stats) {
+                                                           int* __restrict__ cnt, int* __restrict__ stats,
+                                                           const double* __restrict__ omom, double* __restrict__ mom) {
   const long long i = (long long)blockIdx.x * MAP_THREADS + threadIdx.x;
   if (i >= ocap) return;
   const unsigned long long key = okeys[i];
@@ -192,31 +220,108 @@ __global__ void __launch_bounds__(MAP_THREADS) k_map_rehash(const unsigned long 
   if (s < 0) { atomicAdd(stats + MS_PROBE_FAIL, 1); return; }
   sums[s] = osums[i];
   cnt[s] = ocnt[i];
+  if (mom) {
+#pragma unroll
+    for (int a = 0; a < 9; ++a) mom[(size_t)s * 9 + a] = omom[(size_t)i * 9 + a];
+  }
 }
 
 // ---- export ----
-__device__ __forceinline__ bool map_pass(const unsigned long long* __restrict__ tkeys, const int* __restrict__ cnt,
-                                         long long slot, long long cap, int min_points) {
-  return slot < cap && tkeys[slot] != MAP_EMPTY && cnt[slot] >= min_points;
+// What a selection takes: the occupied slots with count >= min_points and, in the BOX instantiations, a voxel inside
+// lo <= ijk <= hi (absolute voxel coordinates, both ends included).
+struct MapSel {
+  int min_points;
+  int lo[3], hi[3];
+};
+
+__device__ __forceinline__ bool map_in_box(unsigned long long key, const MapSel& sel) {
+  const int vi = (int)(key & 0x1fffffull) - MAP_BIAS, vj = (int)((key >> 21) & 0x1fffffull) - MAP_BIAS,
+            vk = (int)(key >> 42) - MAP_BIAS;
+  return vi >= sel.lo[0] && vi <= sel.hi[0] && vj >= sel.lo[1] && vj <= sel.hi[1] && vk >= sel.lo[2] && vk <= sel.hi[2];
 }
 
+template <bool BOX>
+__device__ __forceinline__ bool map_pass(const unsigned long long* __restrict__ tkeys, const int* __restrict__ cnt,
+                                         long long slot, long long cap, const MapSel& sel) {
+  if (slot >= cap) return false;
+  const unsigned long long key = tkeys[slot];
+  if (key == MAP_EMPTY) return false;
+  if (BOX && !map_in_box(key, sel)) return false;
+  return cnt[slot] >= sel.min_points;
+}
+
+// BOX: the same pass reduces, over the OCCUPIED voxels inside the box whatever their count, the ijk box, their number
+// and their point total into tsel (TS_* words; one integer atomic per word and block, as k_map_keys)
+template <bool BOX>
 __global__ void __launch_bounds__(MAP_THREADS) k_map_xcount(const unsigned long long* __restrict__ tkeys,
-                                                           const int* __restrict__ cnt, long long cap, int min_points,
-                                                           unsigned int* __restrict__ counts) {
+                                                           const int* __restrict__ cnt, long long cap, MapSel sel,
+                                                           unsigned int* __restrict__ counts, int* __restrict__ tsel) {
   __shared__ unsigned int s_w[MAP_WAVES];
+  __shared__ int red[MAP_WAVES][8];
+  __shared__ unsigned long long red_pts[MAP_WAVES];
   unsigned int c = 0;
+  int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN}, nvox = 0;
+  unsigned long long pts = 0;
 #pragma unroll
   for (int r = 0; r < MAP_XROUNDS; ++r) {
     const long long slot = (long long)blockIdx.x * MAP_XTILE + r * MAP_THREADS + threadIdx.x;
-    c += (unsigned int)__popcll(__ballot(map_pass(tkeys, cnt, slot, cap, min_points)));
+    if (BOX) {
+      bool pass = false;
+      if (slot < cap) {
+        const unsigned long long key = tkeys[slot];
+        if (key != MAP_EMPTY && map_in_box(key, sel)) {
+          const int n = cnt[slot];
+          const int v[3] = {(int)(key & 0x1fffffull) - MAP_BIAS, (int)((key >> 21) & 0x1fffffull) - MAP_BIAS,
+                            (int)(key >> 42) - MAP_BIAS};
+#pragma unroll
+          for (int a = 0; a < 3; ++a) { mn[a] = min(mn[a], v[a]); mx[a] = max(mx[a], v[a]); }
+          ++nvox;
+          pts += (unsigned long long)n;
+          pass = n >= sel.min_points;
+        }
+      }
+      c += (unsigned int)__popcll(__ballot(pass));
+    } else {
+      c += (unsigned int)__popcll(__ballot(map_pass<false>(tkeys, cnt, slot, cap, sel)));
+    }
   }
-  if ((threadIdx.x & 63u) == 0) s_w[threadIdx.x >> 6] = c;
+  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+  if (BOX) {
+    nvox = wave_sum(nvox);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { mn[a] = wave_min(mn[a]); mx[a] = wave_max(mx[a]); }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) pts += __shfl_xor(pts, off);
+    if (lane == 0) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) { red[wave][TS_MIN + a] = mn[a]; red[wave][TS_MAX + a] = mx[a]; }
+      red[wave][TS_VOXELS] = nvox;
+      red_pts[wave] = pts;
+    }
+  }
+  if (lane == 0) s_w[wave] = c;
   __syncthreads();
   if (threadIdx.x == 0) {
     unsigned int t = 0;
 #pragma unroll
     for (int w = 0; w < MAP_WAVES; ++w) t += s_w[w];
     counts[blockIdx.x] = t;
+  }
+  if (BOX && threadIdx.x < 8) {
+    const int t = (int)threadIdx.x;
+    if (t < 7) {
+      int v = red[0][t];
+#pragma unroll
+      for (int w = 1; w < MAP_WAVES; ++w) v = t < TS_MAX ? min(v, red[w][t]) : t < TS_VOXELS ? max(v, red[w][t]) : v + red[w][t];
+      if (t < TS_MAX) { if (v != INT_MAX) atomicMin(tsel + t, v); }
+      else if (t < TS_VOXELS) { if (v != INT_MIN) atomicMax(tsel + t, v); }
+      else if (v) atomicAdd(tsel + t, v);
+    } else {
+      unsigned long long v = 0;
+#pragma unroll
+      for (int w = 0; w < MAP_WAVES; ++w) v += red_pts[w];
+      if (v) atomicAdd(reinterpret_cast<unsigned long long*>(tsel + TS_POINTS), v);
+    }
   }
 }
 
@@ -257,8 +362,9 @@ struct MapKeyBox {
 };
 
 // the selected slots, compacted (in table order: the sort that follows puts them in key order), and their relative keys
+template <bool BOX>
 __global__ void __launch_bounds__(MAP_THREADS) k_map_xemit(const unsigned long long* __restrict__ tkeys,
-                                                          const int* __restrict__ cnt, long long cap, int min_points,
+                                                          const int* __restrict__ cnt, long long cap, MapSel sel,
                                                           const unsigned int* __restrict__ offsets, MapKeyBox box,
                                                           uint32_t* __restrict__ xslot, uint32_t* __restrict__ klo,
                                                           uint32_t* __restrict__ khi) {
@@ -269,7 +375,7 @@ __global__ void __launch_bounds__(MAP_THREADS) k_map_xemit(const unsigned long l
 #pragma unroll
   for (int r = 0; r < MAP_XROUNDS; ++r) {
     const long long slot = (long long)blockIdx.x * MAP_XTILE + r * MAP_THREADS + threadIdx.x;
-    keep[r] = map_pass(tkeys, cnt, slot, cap, min_points);
+    keep[r] = map_pass<BOX>(tkeys, cnt, slot, cap, sel);
     bal[r] = __ballot(keep[r]);
     if (lane == 0) s_w[r][wave] = (unsigned int)__popcll(bal[r]);
   }
@@ -341,25 +447,28 @@ namespace {
 constexpr int64_t MAP_DEFAULT_CAPACITY = 1ll << 18;
 constexpr int64_t MAP_MAX_CAPACITY = 1ll << 30;   // slots are 32-bit sort keys with one sentinel above them
 
-void free_table(unsigned long long* k, float* s, int* c) {
+void free_table(unsigned long long* k, float* s, int* c, double* q) {
   if (k) (void)hipFree(k);
   if (s) (void)hipFree(s);
   if (c) (void)hipFree(c);
+  if (q) (void)hipFree(q);
 }
 
-// an empty table of `cap` slots (keys ~0, sums and counts zero), written on the engine's stream
-int alloc_table(ndt_handle* h, int64_t cap, unsigned long long** k, float** s, int** c) {
-  *k = nullptr; *s = nullptr; *c = nullptr;
+// an empty table of `cap` slots (keys ~0, sums, counts and -- with_moments -- moments zero), written on the engine's stream
+int alloc_table(ndt_handle* h, int64_t cap, bool with_moments, unsigned long long** k, float** s, int** c, double** q) {
+  *k = nullptr; *s = nullptr; *c = nullptr; *q = nullptr;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(k), (size_t)cap * sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(s), (size_t)cap * 4 * sizeof(float));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(c), (size_t)cap * sizeof(int));
+  if (e == hipSuccess && with_moments) e = hipMalloc(reinterpret_cast<void**>(q), (size_t)cap * 9 * sizeof(double));
   if (e == hipSuccess) e = hipMemsetAsync(*k, 0xFF, (size_t)cap * sizeof(unsigned long long), h->stream);
   if (e == hipSuccess) e = hipMemsetAsync(*s, 0, (size_t)cap * 4 * sizeof(float), h->stream);
   if (e == hipSuccess) e = hipMemsetAsync(*c, 0, (size_t)cap * sizeof(int), h->stream);
+  if (e == hipSuccess && with_moments) e = hipMemsetAsync(*q, 0, (size_t)cap * 9 * sizeof(double), h->stream);
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    free_table(*k, *s, *c);
-    *k = nullptr; *s = nullptr; *c = nullptr;
+    free_table(*k, *s, *c, *q);
+    *k = nullptr; *s = nullptr; *c = nullptr; *q = nullptr;
     return fail(h, e == hipErrorOutOfMemory ? NDT_ERR_ALLOC : NDT_ERR_HIP, std::string("voxel map table: ") + hipGetErrorString(e));
   }
   return NDT_OK;
@@ -418,20 +527,20 @@ int refresh_voxel_count(ndt_handle* h) {
 
 int grow_table(ndt_handle* h, int64_t new_cap) {
   VoxelMap& m = *h->map;
-  unsigned long long* nk; float* ns; int* nc;
-  int rc = alloc_table(h, new_cap, &nk, &ns, &nc);
+  unsigned long long* nk; float* ns; int* nc; double* nq;
+  int rc = alloc_table(h, new_cap, m.moments, &nk, &ns, &nc, &nq);
   if (rc) return rc;   // the map is as it was
   hipLaunchKernelGGL(k_map_rehash, dim3((unsigned)((m.capacity + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0, h->stream,
                      m.keys, reinterpret_cast<const float4*>(m.sums), m.cnt, (long long)m.capacity, nk,
-                     (unsigned long long)(new_cap - 1), reinterpret_cast<float4*>(ns), nc, m.stats.p);
+                     (unsigned long long)(new_cap - 1), reinterpret_cast<float4*>(ns), nc, m.stats.p, m.mom, nq);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // (growth is rare: the old table is freed behind its last reader)
   if (e != hipSuccess) {
-    free_table(nk, ns, nc);
+    free_table(nk, ns, nc, nq);
     return fail(h, NDT_ERR_HIP, std::string("voxel map growth: ") + hipGetErrorString(e));
   }
-  free_table(m.keys, m.sums, m.cnt);
-  m.keys = nk; m.sums = ns; m.cnt = nc;
+  free_table(m.keys, m.sums, m.cnt, m.mom);
+  m.keys = nk; m.sums = ns; m.cnt = nc; m.mom = nq;
   m.capacity = new_cap;
   ++m.n_grows;
   return NDT_OK;
@@ -500,17 +609,29 @@ int map_add_device(ndt_handle* h, const float* dx, const float* dy, const float*
   const uint32_t* vals_sorted = in_b ? h->vals2.p : h->vals.p;
   HIP_TRY(h, launch_find_runs(keys_sorted, n, h->gd.p, h->gdh.d, /*min_pts=*/1, h->nleaf.p, h->run_counts.p, h->run_offsets.p,
                               h->tickets.p + 1, nullptr, 0, &h->run_seq, h->leaf_start.p, h->leaf_cnt.p, s));
-  hipLaunchKernelGGL(k_map_accumulate, dim3(blocks), dim3(MAP_THREADS), 0, s, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p,
-                     keys_sorted, vals_sorted, qx, qy, qz, m.with_intensity ? di : nullptr,
-                     reinterpret_cast<float4*>(m.sums), m.cnt);
+  if (m.moments)
+    hipLaunchKernelGGL(k_map_accumulate<true>, dim3(blocks), dim3(MAP_THREADS), 0, s, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p,
+                       keys_sorted, vals_sorted, qx, qy, qz, m.with_intensity ? di : nullptr,
+                       reinterpret_cast<float4*>(m.sums), m.cnt, m.mom);
+  else
+    hipLaunchKernelGGL(k_map_accumulate<false>, dim3(blocks), dim3(MAP_THREADS), 0, s, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p,
+                       keys_sorted, vals_sorted, qx, qy, qz, m.with_intensity ? di : nullptr,
+                       reinterpret_cast<float4*>(m.sums), m.cnt, static_cast<double*>(nullptr));
   HIP_TRY(h, hipGetLastError());
   // the caller's arrays (and the engine's scratch) are free again when the call returns
   HIP_TRY(h, hipStreamSynchronize(s));
   return NDT_OK;
 }
 
-// the voxels an export with min_points would write (count + scan, awaited); the block offsets stay in xcounts
-int map_export_count(ndt_handle* h, int min_points, size_t* total) {
+MapSel sel_all(int min_points) {
+  MapSel sel{};
+  sel.min_points = min_points;
+  return sel;
+}
+
+// the voxels a selection takes (count + scan, awaited); the block offsets stay in xcounts.  box: the selection is
+// limited to sel.lo .. sel.hi, and tsel_h receives the TS_* words of the occupied voxels inside (same wait)
+int map_export_count(ndt_handle* h, const MapSel& sel, bool box, size_t* total) {
   VoxelMap& m = *h->map;
   *total = 0;
   int rc = refresh_voxel_count(h);
@@ -519,13 +640,72 @@ int map_export_count(ndt_handle* h, int min_points, size_t* total) {
   hipStream_t s = h->stream;
   const int nb = (int)((m.capacity + MAP_XTILE - 1) / MAP_XTILE);
   HIP_TRY(h, m.xcounts.ensure((size_t)nb + 1));
-  hipLaunchKernelGGL(k_map_xcount, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.keys, m.cnt, (long long)m.capacity, min_points,
-                     m.xcounts.p);
+  if (box) {
+    HIP_TRY(h, hipMemcpyAsync(m.tsel.p, m.tsel_h.h + TS_WORDS, TS_WORDS * sizeof(int), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_map_xcount<true>, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.keys, m.cnt, (long long)m.capacity, sel,
+                       m.xcounts.p, m.tsel.p);
+  } else {
+    hipLaunchKernelGGL(k_map_xcount<false>, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.keys, m.cnt, (long long)m.capacity, sel,
+                       m.xcounts.p, static_cast<int*>(nullptr));
+  }
   hipLaunchKernelGGL(k_map_xscan, dim3(1), dim3(MAP_SCAN_THREADS), 0, s, m.xcounts.p, nb);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(m.nvox_h.h + 1, m.xcounts.p + nb, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+  if (box) HIP_TRY(h, hipMemcpyAsync(m.tsel_h.h, m.tsel.p, TS_WORDS * sizeof(int), hipMemcpyDeviceToHost, s));
   HIP_TRY(h, hipStreamSynchronize(s));
   *total = (size_t)*reinterpret_cast<const unsigned int*>(m.nvox_h.h + 1);
+  return NDT_OK;
+}
+
+// after map_export_count(sel, box) = total > 0: the selected slots compacted and ordered by ascending (k, j, i) -- output
+// voxel r is table position (*slots)[(*order)[r]].  mn / mx: an ijk box that holds every selected voxel (the sort key is
+// relative to it).  Enqueued, not awaited.
+int map_export_order(ndt_handle* h, const MapSel& sel, bool box_sel, size_t total, const int mn[3], const int mx[3],
+                     const uint32_t** order_out, const uint32_t** slots_out) {
+  VoxelMap& m = *h->map;
+  hipStream_t s = h->stream;
+  int rc = ensure_sort_scratch(h, total);
+  if (rc) return rc;
+  MapKeyBox box;
+  for (int a = 0; a < 3; ++a) box.mn[a] = mn[a];
+  box.bx = bits_for((long long)mx[0] - mn[0]);
+  box.by = bits_for((long long)mx[1] - mn[1]);
+  const int bits = box.bx + box.by + bits_for((long long)mx[2] - mn[2]);
+  const bool two_words = bits > 32;
+  HIP_TRY(h, m.xslot.ensure(total));
+  if (two_words) {
+    HIP_TRY(h, m.xhi.ensure(total));
+    HIP_TRY(h, m.xslot2.ensure(total));
+  }
+  const int nb = (int)((m.capacity + MAP_XTILE - 1) / MAP_XTILE);
+  if (box_sel)
+    hipLaunchKernelGGL(k_map_xemit<true>, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.keys, m.cnt, (long long)m.capacity, sel,
+                       m.xcounts.p, box, m.xslot.p, h->keys.p, two_words ? m.xhi.p : nullptr);
+  else
+    hipLaunchKernelGGL(k_map_xemit<false>, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.keys, m.cnt, (long long)m.capacity, sel,
+                       m.xcounts.p, box, m.xslot.p, h->keys.p, two_words ? m.xhi.p : nullptr);
+  HIP_TRY(h, hipGetLastError());
+  int passes = 0;
+  rc = put_plan(h, 1, std::min(bits, 32), 0, &passes);
+  if (rc) return rc;
+  launch_sort_first_count(h->keys.p, total, h->gd.p, h->sort_tmp.p, s);
+  bool in_b = false;
+  HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, total, passes, h->gd.p, s, &in_b));
+  const uint32_t* order = in_b ? h->vals2.p : h->vals.p;
+  const uint32_t* slots = m.xslot.p;
+  if (two_words) {   // stable: the order of the low words survives among equal high words
+    const unsigned tb = (unsigned)((total + MAP_THREADS - 1) / MAP_THREADS);
+    hipLaunchKernelGGL(k_map_xgather, dim3(tb), dim3(MAP_THREADS), 0, s, order, m.xhi.p, m.xslot.p, (int)total, h->keys.p, m.xslot2.p);
+    HIP_TRY(h, hipGetLastError());
+    rc = put_plan(h, 2, bits - 32, 0, &passes);
+    if (rc) return rc;
+    launch_sort_first_count(h->keys.p, total, h->gd.p, h->sort_tmp.p, s);
+    HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, total, passes, h->gd.p, s, &in_b));
+    order = in_b ? h->vals2.p : h->vals.p;
+    slots = m.xslot2.p;
+  }
+  *order_out = order;
+  *slots_out = slots;
   return NDT_OK;
 }
 
@@ -536,42 +716,9 @@ int map_export_write(ndt_handle* h, int min_points, size_t total, float* ox, flo
   hipStream_t s = h->stream;
   const size_t w = std::min(total, cap);
   if (w == 0) return NDT_OK;
-  int rc = ensure_sort_scratch(h, total);
+  const uint32_t *order = nullptr, *slots = nullptr;
+  int rc = map_export_order(h, sel_all(min_points), false, total, m.mn, m.mx, &order, &slots);
   if (rc) return rc;
-  MapKeyBox box;
-  for (int a = 0; a < 3; ++a) box.mn[a] = m.mn[a];
-  box.bx = bits_for((long long)m.mx[0] - m.mn[0]);
-  box.by = bits_for((long long)m.mx[1] - m.mn[1]);
-  const int bits = box.bx + box.by + bits_for((long long)m.mx[2] - m.mn[2]);
-  const bool two_words = bits > 32;
-  HIP_TRY(h, m.xslot.ensure(total));
-  if (two_words) {
-    HIP_TRY(h, m.xhi.ensure(total));
-    HIP_TRY(h, m.xslot2.ensure(total));
-  }
-  const int nb = (int)((m.capacity + MAP_XTILE - 1) / MAP_XTILE);
-  hipLaunchKernelGGL(k_map_xemit, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.keys, m.cnt, (long long)m.capacity, min_points,
-                     m.xcounts.p, box, m.xslot.p, h->keys.p, two_words ? m.xhi.p : nullptr);
-  HIP_TRY(h, hipGetLastError());
-  int passes = 0;
-  rc = put_plan(h, 1, std::min(bits, 32), 0, &passes);
-  if (rc) return rc;
-  launch_sort_first_count(h->keys.p, total, h->gd.p, h->sort_tmp.p, s);
-  bool in_b = false;
-  HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, total, passes, h->gd.p, s, &in_b));
-  const uint32_t* order = in_b ? h->vals2.p : h->vals.p;
-  const uint32_t* slots = m.xslot.p;
-  const unsigned tb = (unsigned)((total + MAP_THREADS - 1) / MAP_THREADS);
-  if (two_words) {   // stable: the order of the low words survives among equal high words
-    hipLaunchKernelGGL(k_map_xgather, dim3(tb), dim3(MAP_THREADS), 0, s, order, m.xhi.p, m.xslot.p, (int)total, h->keys.p, m.xslot2.p);
-    HIP_TRY(h, hipGetLastError());
-    rc = put_plan(h, 2, bits - 32, 0, &passes);
-    if (rc) return rc;
-    launch_sort_first_count(h->keys.p, total, h->gd.p, h->sort_tmp.p, s);
-    HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, total, passes, h->gd.p, s, &in_b));
-    order = in_b ? h->vals2.p : h->vals.p;
-    slots = m.xslot2.p;
-  }
   hipLaunchKernelGGL(k_map_xcentroids, dim3((unsigned)((w + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0, s, order, slots,
                      (int)w, reinterpret_cast<const float4*>(m.sums), m.cnt, ox, oy, oz, m.with_intensity ? oi : nullptr, oc);
   HIP_TRY(h, hipGetLastError());
@@ -586,6 +733,132 @@ bool pose_finite(const double* p) {
   for (int i = 0; i < 16; ++i)
     if (!std::isfinite(p[i])) return false;
   return true;
+}
+
+int no_moments(ndt_handle* h) { return fail(h, NDT_ERR_INVALID_ARG, "the map keeps no moments (ndt_map_enable_moments right after ndt_map_reset)"); }
+
+// floor(v * inv_leaf) in f32 as a point's voxel coordinate is, held to the map's coordinate range
+int box_floor(float v, float inv_leaf) {
+  const float f = floorf(v * inv_leaf);
+  return f <= -MAP_LIMIT ? -MAP_BIAS : f >= MAP_LIMIT ? MAP_BIAS : (int)f;
+}
+
+// ndt_set_target_from_map_moments behind its argument checks.  Up to the one host wait nothing of the target is touched.
+int target_from_moments(ndt_handle* h, const float* box_min, const float* box_max) {
+  VoxelMap& m = *h->map;
+  settle_discard_keep_grid(h);   // (the pending build borrows the sort scratch; its verdict is dropped once this call replaces it)
+  const auto t0 = std::chrono::steady_clock::now();
+  MapSel sel{};
+  sel.min_points = std::max(3, h->prm.min_points_per_voxel);  // the ordinary build's rule (build_begin)
+  for (int a = 0; a < 3; ++a) {
+    sel.lo[a] = box_min ? box_floor(box_min[a], m.inv_leaf) : -MAP_BIAS;
+    sel.hi[a] = box_max ? box_floor(box_max[a], m.inv_leaf) : MAP_BIAS;
+  }
+  size_t total = 0;
+  int rc = map_export_count(h, sel, true, &total);
+  if (rc) return rc;
+  const int* ts = m.tsel_h.h;
+  if (m.n_voxels == 0 || ts[TS_VOXELS] == 0) return fail(h, NDT_ERR_NO_TARGET, "the map holds no occupied voxel inside the box");
+  unsigned long long n_points = 0;
+  std::memcpy(&n_points, ts + TS_POINTS, sizeof(n_points));
+  int mn[3], mx[3];
+  long long ncells = 1;
+  const long long lim = std::numeric_limits<int32_t>::max();
+  for (int a = 0; a < 3; ++a) {
+    mn[a] = ts[TS_MIN + a];
+    mx[a] = ts[TS_MAX + a];
+    if (ncells < lim) ncells *= (long long)mx[a] - mn[a] + 1;   // (each factor <= 2^21: no overflow below the limit)
+  }
+  if (ncells >= lim)
+    return fail(h, NDT_ERR_GRID_OVERFLOW, "the selected voxels span " + std::to_string(mx[0] - mn[0] + 1LL) + " x " +
+                                              std::to_string(mx[1] - mn[1] + 1LL) + " x " + std::to_string(mx[2] - mn[2] + 1LL) +
+                                              " cells (index overflow): select a box");
+  if (total >= (size_t)lim) return fail(h, NDT_ERR_GRID_OVERFLOW, "too many leaves");
+
+  // ---- from here on the target is replaced (what build_begin does for an ordinary build) ----
+  hipStream_t s = h->stream;
+  h->deferred_rc = 0;
+  h->deferred_msg.clear();
+  h->ms_settle_wait = 0;
+  h->prev_n_valid = h->have_grid && !h->multi_active ? h->n_valid : 0;
+  h->have_grid = false;
+  h->multi_active = false;
+  h->src_sorted = false;
+  h->n_tgt = (size_t)n_points;
+  ++h->tgt_gen;
+  h->n_slots = h->n_valid = 0;
+  const int dirty_slots = h->grid_dirty_slots;
+  const size_t clean_cap = h->grid_clean_cap;
+  h->grid_clean_cap = 0;
+  h->grid_dirty_slots = 0;
+  h->tx.release(); h->ty.release(); h->tz.release();   // no target points are retained
+
+  // the dense grid: -1 everywhere once per allocation, afterwards only the previous build's cells are reset
+  const size_t slots_needed = std::max<size_t>(total, 1);
+  const bool steady = clean_cap != 0 && clean_cap == h->cell2leaf.cap && (size_t)ncells <= h->cell2leaf.cap &&
+                      slots_needed <= h->stats.cap;
+  if (steady) {
+    if (dirty_slots > 0) {
+      launch_reset_cells(h->stats.p, dirty_slots, h->cell2leaf.p, h->cell2leaf.cap, s);
+      HIP_TRY(h, hipGetLastError());
+    }
+  } else {
+    HIP_TRY(h, hipStreamSynchronize(s));
+    HIP_TRY(h, h->cell2leaf.ensure((size_t)ncells));
+    HIP_TRY(h, hipMemsetAsync(h->cell2leaf.p, 0xFF, h->cell2leaf.cap * sizeof(int), s));
+    HIP_TRY(h, h->stats.ensure(slots_needed));
+  }
+  HIP_TRY(h, h->rec.ensure(slots_needed));
+  HIP_TRY(h, h->cent.ensure(slots_needed * 4));
+
+  GridGeom g{};
+  g.leaf = h->prm.resolution;
+  g.inv_leaf = 1.0f / h->prm.resolution;
+  for (int a = 0; a < 3; ++a) {
+    g.min_b[a] = mn[a];
+    g.div_b[a] = mx[a] - mn[a] + 1;
+    g.lo[a] = (float)mn[a] * g.leaf;
+    g.hi[a] = (float)(mx[a] + 1) * g.leaf;
+  }
+  g.mul1 = g.div_b[0];
+  g.mul2 = g.div_b[0] * g.div_b[1];
+  g.ncells = (int)ncells;
+
+  int n_valid = 0;
+  if (total > 0) {
+    const uint32_t *order = nullptr, *slots = nullptr;
+    rc = map_export_order(h, sel, true, total, mn, mx, &order, &slots);
+    if (rc) return rc;
+    const int key_min[3] = {mn[0] + MAP_BIAS, mn[1] + MAP_BIAS, mn[2] + MAP_BIAS};
+    FinalizeParams fp{h->prm.eig_inflation_ratio, h->prm.cov_mode};
+    launch_map_finalize(order, slots, total, m.keys, m.cnt, m.mom, key_min, g.mul1, g.mul2, fp, h->rec.p, h->cent.p, h->stats.p,
+                        h->cell2leaf.p, m.tsel.p + TS_VALID, s);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(m.tsel_h.h + TS_VALID, m.tsel.p + TS_VALID, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    n_valid = m.tsel_h.h[TS_VALID];
+  } else {
+    // (geometry without a leaf: the evaluation reads record 0 for an absent neighbour, so it has to be finite)
+    HIP_TRY(h, hipMemsetAsync(h->rec.p, 0, sizeof(VoxelRecord), s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+  }
+  // ---- publish (what build_collect / build_complete do) ----
+  h->geom = g;
+  for (int a = 0; a < 3; ++a) h->max_b[a] = mx[a];
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  h->ms_build = ms;
+  h->tm.ms_last_build = ms;
+  h->n_slots = (int)total;
+  h->n_valid = n_valid;
+  h->grid_clean_cap = h->cell2leaf.cap;
+  h->grid_dirty_slots = h->n_slots;
+  h->have_grid = true;
+  h->prec_valid = false;
+  if (h->record_format == NDT_RECORDS_PACKED48) {
+    rc = pack_records(h, false);
+    if (rc) return rc;
+  }
+  return NDT_OK;
 }
 
 }  // namespace
@@ -616,7 +889,7 @@ int ndt_map_reset(ndt_handle* h, float leaf, int with_intensity, int64_t initial
   m.with_intensity = with_intensity ? 1 : 0;
   const int64_t cap = pow2_at_least(initial_capacity > 0 ? initial_capacity : MAP_DEFAULT_CAPACITY);
   auto undo = [&](int code) { map_release(h); return code; };
-  rc = alloc_table(h, cap, &m.keys, &m.sums, &m.cnt);
+  rc = alloc_table(h, cap, false, &m.keys, &m.sums, &m.cnt, &m.mom);
   if (rc) return undo(rc);
   m.capacity = cap;
   hipError_t e = m.stats.ensure(MS_WORDS);
@@ -624,12 +897,17 @@ int ndt_map_reset(ndt_handle* h, float leaf, int with_intensity, int64_t initial
   if (e == hipSuccess) e = m.stats_h.ensure(2 * MS_WORDS);
   if (e == hipSuccess) e = m.nvox_h.ensure(2);
   if (e == hipSuccess) e = m.plan_h.ensure(3);
+  if (e == hipSuccess) e = m.tsel.ensure(TS_WORDS);
+  if (e == hipSuccess) e = m.tsel_h.ensure(2 * TS_WORDS);
   if (e == hipSuccess) e = hipMemsetAsync(m.nvox.p, 0, sizeof(unsigned long long), h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) return undo(fail(h, e == hipErrorOutOfMemory ? NDT_ERR_ALLOC : NDT_ERR_HIP, hipGetErrorString(e)));
   int* neutral = m.stats_h.h + MS_WORDS;
   for (int i = 0; i < MS_WORDS; ++i) neutral[i] = 0;
   for (int a = 0; a < 3; ++a) { neutral[MS_MIN + a] = INT_MAX; neutral[MS_MAX + a] = INT_MIN; }
+  int* tneutral = m.tsel_h.h + TS_WORDS;
+  for (int i = 0; i < TS_WORDS; ++i) tneutral[i] = 0;
+  for (int a = 0; a < 3; ++a) { tneutral[TS_MIN + a] = INT_MAX; tneutral[TS_MAX + a] = INT_MIN; }
   return NDT_OK;
 }
 
@@ -722,7 +1000,7 @@ int ndt_map_export_device(ndt_handle* h, int min_points, float* ox, float* oy, f
   if (!h->map) return no_map(h);
   settle_discard_keep_grid(h);
   size_t total = 0;
-  rc = map_export_count(h, min_points, &total);
+  rc = map_export_count(h, sel_all(min_points), false, &total);
   if (rc) return rc;
   *n_out = total;
   if (total == 0) return NDT_OK;
@@ -744,7 +1022,7 @@ int ndt_map_export(ndt_handle* h, int min_points, float* out, size_t stride_byte
   VoxelMap& m = *h->map;
   settle_discard_keep_grid(h);
   size_t total = 0;
-  rc = map_export_count(h, min_points, &total);
+  rc = map_export_count(h, sel_all(min_points), false, &total);
   if (rc) return rc;
   *n_out = total;
   if (total == 0) return NDT_OK;
@@ -777,7 +1055,7 @@ int ndt_set_target_from_map(ndt_handle* h, int min_points) {
   if (!h->map) return no_map(h);
   settle_discard(h);
   size_t total = 0;
-  rc = map_export_count(h, min_points, &total);
+  rc = map_export_count(h, sel_all(min_points), false, &total);
   if (rc) return rc;
   if (total == 0) return fail(h, NDT_ERR_NO_TARGET, "the map holds no voxel with that many points");
   HIP_TRY(h, h->tx.ensure(total));
@@ -787,6 +1065,80 @@ int ndt_set_target_from_map(ndt_handle* h, int min_points) {
   if (rc) return rc;
   // (the centroids are the engine's own: the build may stay in flight like a host hand-off's)
   return build_grid(h, h->tx.p, h->ty.p, h->tz.p, total, h->handoff_mode == NDT_HANDOFF_ASYNC);
+}
+
+int ndt_map_enable_moments(ndt_handle* h) {
+  if (!h) return NDT_ERR_INVALID_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  if (!h->map) return no_map(h);
+  VoxelMap& m = *h->map;
+  if (m.moments) return fail(h, NDT_ERR_INVALID_ARG, "the map keeps moments already");
+  if (m.n_points > 0 || m.n_voxels > 0 || m.nvox_stale)
+    return fail(h, NDT_ERR_INVALID_ARG, "the map holds points already: moments are enabled right after ndt_map_reset");
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&m.mom), (size_t)m.capacity * 9 * sizeof(double));
+  if (e == hipSuccess) e = hipMemsetAsync(m.mom, 0, (size_t)m.capacity * 9 * sizeof(double), h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (m.mom) (void)hipFree(m.mom);
+    m.mom = nullptr;
+    return fail(h, e == hipErrorOutOfMemory ? NDT_ERR_ALLOC : NDT_ERR_HIP, std::string("voxel map moments: ") + hipGetErrorString(e));
+  }
+  m.moments = true;
+  return NDT_OK;
+}
+
+int ndt_map_has_moments(const ndt_handle* h) {
+  if (!h) return NDT_ERR_INVALID_ARG;
+  return h->map && h->map->moments ? 1 : 0;
+}
+
+int ndt_map_export_moments(ndt_handle* h, int min_points, int32_t* ijk, int32_t* count, double* sums, size_t cap, size_t* n_out) {
+  if (!h || !n_out) return NDT_ERR_INVALID_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  if (!h->map) return no_map(h);
+  VoxelMap& m = *h->map;
+  if (!m.moments) return no_moments(h);
+  settle_discard_keep_grid(h);
+  size_t total = 0;
+  rc = map_export_count(h, sel_all(min_points), false, &total);
+  if (rc) return rc;
+  *n_out = total;
+  if (total == 0) return NDT_OK;
+  const size_t w = std::min(total, cap);
+  if (w && (ijk || count || sums)) {
+    HIP_TRY(h, m.xijk.ensure(3 * w));
+    HIP_TRY(h, m.xcnt.ensure(w));
+    HIP_TRY(h, m.xmom.ensure(9 * w));
+    const uint32_t *order = nullptr, *slots = nullptr;
+    rc = map_export_order(h, sel_all(min_points), false, total, m.mn, m.mx, &order, &slots);
+    if (rc) return rc;
+    launch_map_gather_moments(order, slots, w, m.keys, m.cnt, m.mom, MAP_BIAS, m.xijk.p, m.xcnt.p, m.xmom.p, h->stream);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (ijk) HIP_TRY(h, hipMemcpy(ijk, m.xijk.p, 3 * w * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (count) HIP_TRY(h, hipMemcpy(count, m.xcnt.p, w * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (sums) HIP_TRY(h, hipMemcpy(sums, m.xmom.p, 9 * w * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  if (total > cap) return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(total) + " voxels");
+  return NDT_OK;
+}
+
+int ndt_set_target_from_map_moments(ndt_handle* h, const float box_min[3], const float box_max[3]) {
+  if (!h || (box_min == nullptr) != (box_max == nullptr)) return NDT_ERR_INVALID_ARG;
+  int rc = bind_device(h);
+  if (rc) return rc;
+  if (!h->map) return no_map(h);
+  VoxelMap& m = *h->map;
+  if (!m.moments) return no_moments(h);
+  if (std::memcmp(&m.leaf, &h->prm.resolution, sizeof(float)) != 0)
+    return fail(h, NDT_ERR_INVALID_ARG, "the map's leaf size is not ndt_params::resolution: a voxel of the map is not a voxel of the grid");
+  if (box_min)
+    for (int a = 0; a < 3; ++a)
+      if (!std::isfinite(box_min[a]) || !std::isfinite(box_max[a])) return fail(h, NDT_ERR_INVALID_ARG, "non-finite box");
+  return target_from_moments(h, box_min, box_max);
 }
 
 }  // extern "C"

@@ -1222,6 +1222,64 @@ __device__ __forceinline__ bool finalize_leaf(int slot, int cell, int cnt, const
   return ok;
 }
 
+// The leaves of a target made from the voxel map's moments (launch_map_finalize): one thread per selected voxel, in
+// ascending key order, so slot order is cell order.  The sums were accumulated by the map; nothing is added here.
+struct MapCellDecode {
+  int key_min[3];  // min_b + the key's bias, per axis
+  int mul1, mul2;
+};
+__global__ void __launch_bounds__(256) k_map_finalize(const uint32_t* __restrict__ order, const uint32_t* __restrict__ slots,
+                                                     int m, const unsigned long long* __restrict__ tkeys,
+                                                     const int* __restrict__ tcnt, const double* __restrict__ tmom,
+                                                     MapCellDecode dc, FinalizeParams fp, VoxelRecord* __restrict__ rec,
+                                                     float4* __restrict__ cent, LeafStats* __restrict__ stats,
+                                                     int* __restrict__ cell2leaf, int* __restrict__ nvalid) {
+  __shared__ int s_ok[4];
+  const int r = (int)(blockIdx.x * 256 + threadIdx.x);
+  bool ok = false;
+  if (r < m) {
+    const uint32_t t = slots[order[r]];
+    const unsigned long long key = tkeys[t];
+    const int ci = (int)(key & 0x1fffffull) - dc.key_min[0];
+    const int cj = (int)((key >> 21) & 0x1fffffull) - dc.key_min[1];
+    const int ck = (int)(key >> 42) - dc.key_min[2];
+    ok = finalize_leaf(r, ci + cj * dc.mul1 + ck * dc.mul2, tcnt[t], tmom + (size_t)t * 9, fp, rec, cent, stats, cell2leaf);
+  }
+  const int wave_ok = __popcll(__ballot(ok));
+  if ((threadIdx.x & 63) == 0) s_ok[threadIdx.x >> 6] = wave_ok;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int t = s_ok[0] + s_ok[1] + s_ok[2] + s_ok[3];
+    if (t) atomicAdd(nvalid, t);
+  }
+}
+
+// output voxel r = table position slots[order[r]]: its absolute ijk, its count and its nine f64 sums as the map holds them
+__global__ void __launch_bounds__(256) k_map_gather_moments(const uint32_t* __restrict__ order, const uint32_t* __restrict__ slots,
+                                                           int m, const unsigned long long* __restrict__ tkeys,
+                                                           const int* __restrict__ tcnt, const double* __restrict__ tmom,
+                                                           int key_bias, int32_t* __restrict__ oijk,
+                                                           int32_t* __restrict__ ocount, double* __restrict__ osums) {
+  const int r = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (r >= m) return;
+  const uint32_t t = slots[order[r]];
+  const unsigned long long key = tkeys[t];
+  oijk[3 * r + 0] = (int)(key & 0x1fffffull) - key_bias;
+  oijk[3 * r + 1] = (int)((key >> 21) & 0x1fffffull) - key_bias;
+  oijk[3 * r + 2] = (int)(key >> 42) - key_bias;
+  ocount[r] = tcnt[t];
+#pragma unroll
+  for (int a = 0; a < 9; ++a) osums[(size_t)r * 9 + a] = tmom[(size_t)t * 9 + a];
+}
+
+__global__ void __launch_bounds__(256) k_reset_cells(const LeafStats* __restrict__ old_stats, int dirty_slots,
+                                                    int* __restrict__ cell2leaf, size_t c2l_cap) {
+  const int slot = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (slot >= dirty_slots) return;
+  const int cell = old_stats[slot].cell;
+  if (cell >= 0 && (size_t)cell < c2l_cap) cell2leaf[cell] = -1;
+}
+
 __global__ void __launch_bounds__(256) k_leaf_sums(const float4* __restrict__ xyz4, const uint32_t* __restrict__ vals,
                                                   const int* __restrict__ nleaf_p,
                                                   const int* __restrict__ leaf_start,
@@ -2679,6 +2737,33 @@ void launch_scatter_heads(const int* cells, const int* slots, size_t n, int* cel
 }
 
 int finalize_blocks(int max_leaves) { return (max_leaves + 63) / 64; }
+
+void launch_map_gather_moments(const uint32_t* order, const uint32_t* slots, size_t m, const unsigned long long* table_keys,
+                               const int* table_cnt, const double* table_mom, int key_bias, int32_t* oijk, int32_t* ocount,
+                               double* osums, hipStream_t s) {
+  if (m == 0) return;
+  hipLaunchKernelGGL(k_map_gather_moments, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, order, slots, (int)m, table_keys,
+                     table_cnt, table_mom, key_bias, oijk, ocount, osums);
+}
+
+void launch_reset_cells(const LeafStats* old_stats, int dirty_slots, int* cell2leaf, size_t c2l_cap, hipStream_t s) {
+  if (dirty_slots <= 0) return;
+  hipLaunchKernelGGL(k_reset_cells, dim3((unsigned)((dirty_slots + 255) / 256)), dim3(256), 0, s, old_stats, dirty_slots, cell2leaf,
+                     c2l_cap);
+}
+
+void launch_map_finalize(const uint32_t* order, const uint32_t* slots, size_t m, const unsigned long long* table_keys,
+                         const int* table_cnt, const double* table_mom, const int key_min[3], int mul1, int mul2,
+                         FinalizeParams fp, VoxelRecord* rec, float* cent4, LeafStats* stats, int* cell2leaf, int* d_nvalid,
+                         hipStream_t s) {
+  if (m == 0) return;
+  MapCellDecode dc;
+  for (int a = 0; a < 3; ++a) dc.key_min[a] = key_min[a];
+  dc.mul1 = mul1;
+  dc.mul2 = mul2;
+  hipLaunchKernelGGL(k_map_finalize, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, order, slots, (int)m, table_keys,
+                     table_cnt, table_mom, dc, fp, rec, reinterpret_cast<float4*>(cent4), stats, cell2leaf, d_nvalid);
+}
 
 void launch_finalize_leaves(const float* xyz4, const uint32_t* keys_sorted, const uint32_t* vals_sorted,
                             int* d_nleaf, const int* leaf_start, const int* leaf_cnt, int max_leaves,
