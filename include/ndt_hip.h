@@ -236,8 +236,12 @@ typedef enum ndt_handoff_mode { NDT_HANDOFF_ASYNC = 0, NDT_HANDOFF_SYNC = 1 } nd
  * linked into somebody else's process is not steered by variables that process never heard of.  The environment is
  * left with four documented OPERATIONAL knobs: NDT_HANDOFF=sync (blocking hand-off), NDT_UPLOAD_THREADS (repack
  * workers), NDT_COMM_TIMEOUT_S (multi-rank reduce time-out), NDT_PRELAUNCH=0 (no pre-launched kernels).  Everything
- * else is this struct: process-wide, read at the launches and handle creations that FOLLOW the call; every field has
- * the default ndt_get_tuning() reports in a fresh process.  Results do not depend on any of them (same rows, same
+ * else is this struct: process-wide; every field has the default ndt_get_tuning() reports in a fresh process.
+ * ndt_set_tuning may be called from any thread at any time: a target build and an evaluation (every evaluation of an
+ * align, a batched evaluation) each take ONE copy of the struct when they begin and size and launch everything from
+ * that copy, so a call takes effect at the next build / evaluation and never in the middle of one; a kernel
+ * pre-launched for the next evaluation keeps the shape it was enqueued with.  mbox_tagged, mbox_preload and
+ * prelaunch_streams are read once per handle, at ndt_create.  Results do not depend on any field (same rows, same
  * order, same bits), only timings do -- except deriv_block / deriv_single_level_max, which change the partition of
  * the scan and with it the last bits of the floating-point sums.
  * (The diagnostic library variants -- make VARIANT=ab|seams|stamps -- still take the historical NDT_* variables as

@@ -175,7 +175,7 @@ def get_tuning():
 
 
 def set_tuning(**fields):
-    """ndt_set_tuning with the named fields changed; applies to the handles created and the launches made afterwards."""
+    """ndt_set_tuning with the named fields changed; applies to the handles created and the builds / evaluations begun afterwards."""
     t = Tuning()
     rc = lib().ndt_get_tuning(C.byref(t))
     if rc:

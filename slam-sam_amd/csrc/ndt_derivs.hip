@@ -20,7 +20,6 @@
 // Compiled with -ffp-contract=off; the transform and the index arithmetic must
 // round exactly as written to classify points into the same voxels as the ref.
 #include "ndt_kernels.h"
-#include "ndt_tuning.h"
 
 #include <hip/hip_ext.h>
 
@@ -1610,9 +1609,7 @@ k_point_scores(const float* __restrict__ sx, const float* __restrict__ sy, const
 
 }  // namespace
 
-size_t derivs_partials_words(size_t n_src, int K, int cus) {
-  return (size_t)K * ((size_t)derivs_grid_blocks(n_src, K, cus) + NGROUPS) * ROW_WORDS;
-}
+size_t derivs_partials_words(const DerivLaunchPlan& pl, int K) { return (size_t)K * ((size_t)pl.blocks + NGROUPS) * ROW_WORDS; }
 int derivs_counters_per_pose() { return COUNTERS_PER_POSE; }
 
 int derivs_read_stamps(unsigned long long* out, int nblocks) {
@@ -1653,21 +1650,15 @@ int derivs_read_wave_stamps(unsigned long long* out, int nblocks) {
 // the grid is at most one block per CU (256 CUs) -- 200 000 points: 832 threads, 241 blocks --
 // which keeps every CU at <= 4 waves/SIMD and leaves <= 256 rows for the final sum
 // (profiles/r02_block_sweep.txt: 16.6 us at 832, 17.2 at 1024, 20.3 at 512).
-// ndt_tuning::deriv_block overrides it for tuning.
+// ndt_tuning::deriv_block overrides it for tuning.  (`tn`, here and below: the caller's snapshot of ndt_tuning -- A/B
+// switches, include/ndt_hip.h; nothing in this file reads the process-wide struct.)
 // (the compute units of the handle's device come in as `cus`: two engines on differently partitioned devices in one
 // process must not share a block shape)
 static inline int cus_or_default(int cus) { return cus > 0 ? cus : 256; }
 
-namespace {
-// (ndt_tuning, include/ndt_hip.h: A/B switches, none of them read from the environment by the production library)
-int deriv_single_level_max() { return tuning().deriv_single_level_max; }
-int deriv_fixed_summer() { return tuning().deriv_summer; }       // 0 = ticket + last block, 1 = a fixed block polls the rows
-bool deriv_dedicated_enabled() { return tuning().deriv_dedicated != 0; }
-}  // namespace
-
-int derivs_block_threads(size_t n_src, int K, int cus) {
+static int derivs_block_threads(const ndt_tuning& tn, size_t n_src, int K, int cus) {
   const int g_compute_units = cus_or_default(cus);
-  const int forced = tuning().deriv_block;  // multiple of 64, 64..1024 (checked by ndt_set_tuning)
+  const int forced = tn.deriv_block;  // multiple of 64, 64..1024 (checked by ndt_set_tuning)
   if (forced) return forced;
   // (one compute unit is left to the dedicated summing block -- whether or not ndt_tuning asks for one: the block shape
   // decides the partition of the scan, hence the last bits of the sums, and deriv_summer / deriv_dedicated must not
@@ -1693,23 +1684,15 @@ int derivs_block_threads(size_t n_src, int K, int cus) {
   return 512;
 }
 
-// blocks that own points
-static int derivs_point_blocks(size_t n_src, int K, int cus) {
-  const size_t bt = (size_t)derivs_block_threads(n_src, K, cus);
-  size_t blocks = (n_src + bt - 1) / bt;  // one point per thread
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
-
-// 1: block 0 of the grid owns no points and adds the rows (single-level grids with the fixed summer)
-static int derivs_dedicated_summer(size_t n_src, int K, int cus) {
-  if (!deriv_dedicated_enabled() || deriv_fixed_summer() == 0) return 0;
-  const int pb = derivs_point_blocks(n_src, K, cus);
-  if (pb > deriv_single_level_max()) return 0;
+// blocks in front of the `pb` blocks that own points, which own none and add the rows (single-level grids with the
+// fixed summer: deriv_summer = 1 -- a fixed block polls the rows; 0 -- ticket + last block)
+static int derivs_dedicated_summer(const ndt_tuning& tn, int pb, int K, int cus) {
+  if (tn.deriv_dedicated == 0 || tn.deriv_summer == 0) return 0;
+  if (pb > tn.deriv_single_level_max) return 0;
   // SUMMER_SPLIT of them where the point blocks leave that many compute units (the 200 k-point scan: 241 + 4 of 256),
   // single-pose launches only: each polls one 128-byte line of every row (summer_finish)
   {
-    const int want = tuning().deriv_summer_split == 1 ? SUMMER_SPLIT : tuning().deriv_summer_split;   // (4 | 8: A/B)
+    const int want = tn.deriv_summer_split == 1 ? SUMMER_SPLIT : tn.deriv_summer_split;   // (4 | 8: A/B)
     if (K == 1 && want > 1 && pb + want <= cus_or_default(cus)) return want;
   }
   // The summing block needs a compute unit of its own.  A single-pose grid whose point blocks fill the machine EXACTLY
@@ -1766,21 +1749,30 @@ void derivs_item_owners(int threads, unsigned int* owners_out, unsigned int* fin
   }
 }
 
-int derivs_grid_blocks(size_t n_src, int K, int cus) { return derivs_point_blocks(n_src, K, cus) + derivs_dedicated_summer(n_src, K, cus); }
+// The NB template axis of k_derivatives and k_point_scores for an engine's consts.  The packed record format (5 / 6) is
+// for DIRECT1 / DIRECT7 only: the union's leaves are chained through VoxelRecord::pad, and in the 27-cell neighbourhoods
+// the format (as a run-time flag) cost more than the shorter fetch gave back (KDTREE 21.9 -> 22.5 us, DIRECT26 29.1 -> 29.7)
+static int neighbourhood_axis(const EvalConsts& ec) {
+  if (ec.multigrid) return 4;
+  if (ec.kdtree) return 2;
+  if (ec.direct26) return 3;
+  return ec.direct7 ? (ec.packed ? 6 : 1) : (ec.packed ? 5 : 0);
+}
 
-DerivLaunchPlan plan_derivatives_launch(size_t n_src, int K, bool batched, bool mbox, bool xchg, const EvalConsts& ec,
+DerivLaunchPlan plan_derivatives_launch(const ndt_tuning& tn, size_t n_src, int K, bool batched, bool xchg, const EvalConsts& ec,
                                         EvalConsts* ecl_out, bool batched_shape) {
   const int cus = cus_or_default(ec.compute_units);
   // (batched_shape: a batched launch of one pose takes the shape of a batched launch of several -- the partition, hence
   // the bits, of a pose's sums then do not depend on how many poses share the launch)
   const int Kp = batched ? (batched_shape && K == 1 ? 2 : K) : 1;
-  int blocks = derivs_grid_blocks(n_src, Kp, cus);
-  const int threads = derivs_block_threads(n_src, Kp, cus);
+  const int threads = derivs_block_threads(tn, n_src, Kp, cus);
+  const int point_blocks = (int)std::max<size_t>(1, (n_src + (size_t)threads - 1) / (size_t)threads);  // one point per thread
   const int mode = ec.score_only ? 3 : (!ec.need_hessian ? 0 : (ec.gauss_newton ? 2 : 1));
   EvalConsts ecl = ec;
-  ecl.single_level_max = deriv_single_level_max();
-  ecl.fixed_summer = deriv_fixed_summer();
-  ecl.dedicated_summer = derivs_dedicated_summer(n_src, Kp, cus);
+  ecl.single_level_max = tn.deriv_single_level_max;
+  ecl.fixed_summer = tn.deriv_summer;
+  ecl.dedicated_summer = derivs_dedicated_summer(tn, point_blocks, Kp, cus);
+  int blocks = point_blocks + ecl.dedicated_summer;
   if (ecl.dedicated_summer > 1 && xchg) {   // the in-kernel cross-rank exchange is one block's (xchg_allsum)
     blocks -= ecl.dedicated_summer - 1;
     ecl.dedicated_summer = 1;
@@ -1791,7 +1783,7 @@ DerivLaunchPlan plan_derivatives_launch(size_t n_src, int K, bool batched, bool 
     // so nothing in the launch waits for a block that is not resident (a device shared with other processes).
     ecl.fixed_summer = 0;
     ecl.dedicated_summer = 0;
-    blocks = derivs_point_blocks(n_src, Kp, cus);
+    blocks = point_blocks;
   }
   // XCD-aware chunk assignment (xcd_chunk, ndt_device.h).  gfx950 has 32 compute units per XCD: 8 XCDs on a whole MI355X,
   // one in a CPX partition (nothing to do there).  Grids that are resident at once (at most one block per compute unit)
@@ -1800,11 +1792,10 @@ DerivLaunchPlan plan_derivatives_launch(size_t n_src, int K, bool batched, bool 
   // per CU).  Measured in round 4 (profiles/r04_xcd_stripes_ab.txt): the stripes LOSE -- C3 400 k / 800 k points 25.8 /
   // 40.7 us against 24.1 / 39.1 with chunk = block id, C3-wide 30.0 / 48.9 against 28.1 / 46.1, the SVN Stage-1 launch
   // (20 poses x 131 k points) 87.7 against 83.3 -- so they stay a knob.
-  const int xcd_mode = tuning().deriv_xcd;
+  const int xcd_mode = tn.deriv_xcd;
   const int nxcd = std::max(1, cus / 32);
-  const int point_blocks = blocks - ecl.dedicated_summer;
   // no unit to spare for summing blocks (the 128 x 1024 scan): the blocks of rows 0 .. 3 add eight words each
-  if (!batched && !xchg && !ec.safe_sum && ecl.dedicated_summer == 0 && ecl.fixed_summer != 0 && tuning().deriv_summer_split != 0 &&
+  if (!batched && !xchg && !ec.safe_sum && ecl.dedicated_summer == 0 && ecl.fixed_summer != 0 && tn.deriv_summer_split != 0 &&
       point_blocks >= SUMMER_SPLIT && point_blocks <= ecl.single_level_max)
     ecl.doubling_split = 1;
   const int per_cu = std::max(1, 1024 / threads);
@@ -1819,10 +1810,8 @@ DerivLaunchPlan plan_derivatives_launch(size_t n_src, int K, bool batched, bool 
       ecl.xcd_stripe = resident ? 0 : std::max(1, (cus / nxcd) * per_cu);
     }
   }
-  // DIRECT7 / DIRECT1 only: the union's leaves are chained through VoxelRecord::pad, and in the 27-cell neighbourhoods
-  // the format (as a run-time flag) cost more than the shorter fetch gave back (KDTREE 21.9 -> 22.5 us, DIRECT26 29.1 -> 29.7)
-  if (ec.multigrid || ec.kdtree || ec.direct26) ecl.packed = 0;
-  const int nb = ec.multigrid ? 4 : (ec.kdtree ? 2 : (ec.direct26 ? 3 : (ec.direct7 ? (ecl.packed ? 6 : 1) : (ecl.packed ? 5 : 0))));
+  const int nb = neighbourhood_axis(ec);
+  ecl.packed = nb >= 5 ? 1 : 0;
   derivs_item_owners(threads, &ecl.item_owner, &ecl.fin_waves, &ecl.lone_wave);
   // one LDS region per wave: the 27-cell modes' candidate list, then the wave's hand-over to the finishing waves
   // (the summing stage's 4 KB of scratch lie over them)
@@ -1833,13 +1822,13 @@ DerivLaunchPlan plan_derivatives_launch(size_t n_src, int K, bool batched, bool 
   // (tools/stamps_prelaunch.py, profiles/r05_c2_stragglers.txt).  A block that asks for more than half a unit's LDS has the unit to
   // itself; the kernel pre-launched for the next evaluation then moves in as this one's blocks leave, as it always has for the
   // 13-wave blocks of the 200 k-point scan.
-  if (!batched && ec.own_units && !xchg && tuning().deriv_one_block_per_cu != 0 && blocks <= cus && dyn_lds <= (size_t)80 * 1024)
+  if (!batched && ec.own_units && !xchg && tn.deriv_one_block_per_cu != 0 && blocks <= cus && dyn_lds <= (size_t)80 * 1024)
     dyn_lds = (size_t)80 * 1024 + 512;
   DerivLaunchPlan pl{};
   pl.batch = batched ? 1 : 0;
   pl.mode = mode;
   pl.nb = nb;
-  pl.mbox = !batched && mbox ? 1 : 0;   // (launch_derivatives: a batched launch never takes the mailbox)
+  pl.mbox = 0;   // (set by the caller, like spec: the shape does not depend on it)
   pl.threads = threads;
   pl.blocks = blocks;
   pl.point_blocks = point_blocks;
@@ -1856,20 +1845,13 @@ DerivLaunchPlan plan_derivatives_launch(size_t n_src, int K, bool batched, bool 
   return pl;
 }
 
-void launch_derivatives(const float* sx, const float* sy, const float* sz, size_t n_src,
-                        const GridGeom& g, const int* cell2leaf, const VoxelRecord* rec, const float* cent4,
-                        const PoseConsts& pose, const PoseConsts* d_poses, int K,
-                        const EvalConsts& ec, double* d_partials, unsigned int* d_counters,
+void launch_derivatives(const DerivLaunchPlan& pl, const EvalConsts& ecl, const float* sx, const float* sy, const float* sz,
+                        size_t n_src, const GridGeom& g, const int* cell2leaf, const VoxelRecord* rec, const float* cent4,
+                        const PoseConsts& pose, const PoseConsts* d_poses, int K, double* d_partials, unsigned int* d_counters,
                         double* d_out, hipStream_t s, unsigned long long* d_flag,
                         unsigned long long seq, const PoseMailbox* d_mbox, const XchgInfo* d_xinfo,
                         unsigned long long xround, unsigned int* d_arrive_ctr, unsigned long long* d_arrived_host,
-                        hipEvent_t ev_start, hipEvent_t ev_stop, const BuildGeom* d_geom, DerivLaunchPlan* plan_out,
-                        bool batched_shape) {
-  EvalConsts ecl;
-  DerivLaunchPlan pl = plan_derivatives_launch(n_src, K, d_poses != nullptr, d_mbox != nullptr, d_xinfo != nullptr, ec, &ecl,
-                                               batched_shape);
-  pl.spec = d_geom != nullptr ? 1 : 0;
-  if (plan_out != nullptr) *plan_out = pl;
+                        hipEvent_t ev_start, hipEvent_t ev_stop, const BuildGeom* d_geom) {
   const int blocks = pl.blocks, threads = pl.threads, mode = pl.mode, nb = pl.nb;
   const size_t dyn_lds = (size_t)pl.dyn_lds;
   // ev_start / ev_stop: events attached to THIS dispatch (hipExtLaunchKernel): they carry the kernel's own begin and
@@ -1947,9 +1929,7 @@ void launch_point_scores(const float* sx, const float* sy, const float* sz, size
   RigidRT rt;
   for (int k = 0; k < 9; ++k) rt.R[k] = pose.R[k];
   for (int k = 0; k < 3; ++k) rt.t[k] = pose.t[k];
-  // the neighbourhood and the record format as plan_derivatives_launch chooses them
-  const bool packed = ec.packed && !(ec.multigrid || ec.kdtree || ec.direct26);
-  const int nb = ec.multigrid ? 4 : (ec.kdtree ? 2 : (ec.direct26 ? 3 : (ec.direct7 ? (packed ? 6 : 1) : (packed ? 5 : 0))));
+  const int nb = neighbourhood_axis(ec);   // (as plan_derivatives_launch chooses it)
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
 #define NDT_PS(NBH) \
   hipLaunchKernelGGL(k_point_scores<NBH>, grid, block, 0, s, sx, sy, sz, (int)n, g, cell2leaf, rec, rt, ec, d_score, d_best, d_npairs, d_cell)

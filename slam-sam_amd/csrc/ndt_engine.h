@@ -323,6 +323,7 @@ struct ndt_handle {
     const float* y = nullptr;
     const float* z = nullptr;
     size_t n = 0;
+    ndt_tuning tn{};             // build_begin's snapshot: every size and launch shape of this build, all attempts, follows it
     int dirty_slots = 0;
     size_t clean_cap = 0;
     bool fused = false, fused_sort = false, bucketed_ok = false;
@@ -462,8 +463,6 @@ int lane_wait(ndt_handle* h, ndt_handle::UploadLane& lane);
 int upload_soa(ndt_handle* h, ndt_handle::UploadLane& lane, hipStream_t stream, const float* xyz, const float* x,
                const float* y, const float* z, size_t n, size_t stride, DevBuf<float>& dx, DevBuf<float>& dy,
                DevBuf<float>& dz, bool sync, const std::function<void(size_t /* points on the device so far */, bool /* last chunk */)>* after_chunk = nullptr);
-bool timing_brackets_launch();
-bool auto_probe_enabled();
 int pack_records(ndt_handle* h, bool wait);
 int records_for_eval(ndt_handle* h, EvalConsts* ec, const VoxelRecord** rec);
 int neutral_bounds(ndt_handle* h);
@@ -488,7 +487,7 @@ int ready_for_eval(ndt_handle* h);
 int ensure_flag_slots(ndt_handle* h, size_t K);
 int maybe_sort_source(ndt_handle* h, const float T[16]);
 bool source_sort_wanted(const ndt_handle* h, int n_valid);
-bool first_eval_behind_build(const ndt_handle* h);
+bool first_eval_behind_build(const ndt_tuning& tn, const ndt_handle* h);
 int ensure_partials(ndt_handle* h, size_t words);
 bool slots_complete(const volatile unsigned long long* slots, unsigned long long seq);
 int wait_slots(ndt_handle* h, unsigned long long seq, int K = 1, int first = 0);

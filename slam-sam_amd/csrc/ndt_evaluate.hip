@@ -4,13 +4,11 @@
 namespace ndt {
 namespace engine {
 
+// Every evaluation (evaluate(), eval_batch()) and every align takes ONE snapshot of ndt_tuning at its top: the partial
+// rows, the launch plan, the timing bracket and the speculation decision of that call all follow it.
 // Kernel timing (ndt_enable_kernel_timing): the two events are attached to the derivative kernel's dispatch, so their
 // difference is the kernel's own duration -- the figure rocprofv3 reports.  ndt_tuning::timing_bracket = 1 records them
 // around the launch call instead, as rounds 1-2 did (adds the dispatch, ~2.4 us: the tuning scripts' older numbers).
-bool timing_brackets_launch() { return tuning().timing_bracket != 0; }
-
-// ndt_tuning::prelaunch_probe = 0: the automatic stream placement never probes the other placement (A/B aid)
-bool auto_probe_enabled() { return tuning().prelaunch_probe != 0; }
 
 // (re)writes the packed copy of the record table; `wait`: the caller is about to launch on another stream
 int pack_records(ndt_handle* h, bool wait) {
@@ -155,8 +153,8 @@ bool source_sort_wanted(const ndt_handle* h, int n_valid) {
 // polled from pinned slots, f64 records, no cross-rank exchange inside the kernel, a source that needs no re-ordering
 // for a grid of the size of the previous one (checked again once the verdict is in: a mismatch discards the launch).
 // ndt_tuning::speculate_first = 0: off.
-bool first_eval_behind_build(const ndt_handle* h) {
-  return tuning().speculate_first != 0 && h->spec_enabled && h->build_pending && h->prev_n_valid > 0 && h->n_src > 0 && !h->timing &&
+bool first_eval_behind_build(const ndt_tuning& tn, const ndt_handle* h) {
+  return tn.speculate_first != 0 && h->spec_enabled && h->build_pending && h->prev_n_valid > 0 && h->n_src > 0 && !h->timing &&
          h->prm.wait_mode == NDT_WAIT_SPIN && !h->red.wants_device_buffer() && h->red.mode() != NDT_REDUCE_P2P &&
          h->record_format != NDT_RECORDS_PACKED48 && !source_sort_wanted(h, h->prev_n_valid);
 }
@@ -190,8 +188,6 @@ bool slots_complete(const volatile unsigned long long* slots, unsigned long long
 // "late" -- the kernel is queued behind foreign work, or it is gone.  hipStreamSynchronize is always
 // safe (it loses nothing): afterwards the slots are either there or the launch has failed.
 constexpr auto kHostSpinLimit = std::chrono::microseconds(3 * (MBOX_TIMEOUT_TICKS / 100));
-
-void quit_prelaunched(ndt_handle* h);
 
 int wait_slots(ndt_handle* h, unsigned long long seq, int K, int first) {
   const volatile unsigned long long* f = h->flag.h + (size_t)first * 2 * EV_WORDS;
@@ -297,11 +293,12 @@ void log_evals(ndt_handle* h, const DerivLaunchPlan& plan, const double* poses6,
 // one global evaluation at (p, T): local kernel + cross-rank sum
 int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, Eval* out, bool score_only,
              bool safe_retry) {
+  const ndt_tuning tn = tuning_snapshot();
   hipStream_t s = h->stream;
   bool speculate = false;
   if (h->spec_first) {   // ndt_align left the pending build's verdict to this call
     h->spec_first = false;
-    speculate = first_eval_behind_build(h) && !score_only && !safe_retry && h->pre_seq == 0;
+    speculate = first_eval_behind_build(tn, h) && !score_only && !safe_retry && h->pre_seq == 0;
     if (!speculate) {
       int rc = ready_for_eval(h);
       if (rc) { h->spec_build_failed = true; return rc; }
@@ -323,11 +320,10 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
     if (mute_at >= 0 && !safe_retry && h->tm.n_eval_launches == mute_at) ec.mute_row = 3;
   }
 #endif
+  const bool p2p = h->red.mode() == NDT_REDUCE_P2P;
   const VoxelRecord* records = nullptr;
   {
     int rc = records_for_eval(h, &ec, &records);
-    if (rc) return rc;
-    rc = ensure_partials(h, derivs_partials_words(h->n_src, 1, h->n_cus));
     if (rc) return rc;
   }
   HIP_TRY(h, h->result.ensure(EV_WORDS));
@@ -355,7 +351,6 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
   // the tag "number of this global evaluation" (identical on every rank: all run the same host loop on
   // the same sums).  A pre-launched kernel got its tag when it was enqueued; one that is told to leave
   // has consumed none.
-  const bool p2p = h->red.mode() == NDT_REDUCE_P2P;
   const XchgInfo* xinfo = p2p ? h->red.p2p_info() : nullptr;
   unsigned long long xround = p2p ? h->red.p2p_round() + 1 : 0;
   // Consecutive single-pose launches write their results to ALTERNATING host buffers: a pre-launched
@@ -394,16 +389,25 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
       std::this_thread::sleep_for(std::chrono::milliseconds(late_ms));
   }
 #endif
+  // The shape of this evaluation's launch and of the one pre-launched for the next, and the rows that shape writes.
+  // Planned only here: a kernel that was waiting has its pose by now and runs while the host plans.
+  EvalConsts ecl;   // the consts as planned: what the kernel receives
+  const DerivLaunchPlan pl = plan_derivatives_launch(tn, h->n_src, 1, false, p2p, ec, &ecl);
+  const size_t rows = derivs_partials_words(pl, 1);
   if (!via_mailbox) {
+    int rc = ensure_partials(h, rows);   // (no kernel of this handle waits for a pose now)
+    if (rc) return rc;
     seq = g_launch_seq.fetch_add(1, std::memory_order_relaxed);
     buf = (h->flag_toggle ^= 1);
     h->cur_on2 = 0;
-    const bool bracket = h->timing && timing_brackets_launch();
+    const bool bracket = h->timing && tn.timing_bracket != 0;
     if (bracket) HIP_TRY(h, hipEventRecord(h->ev0, s));
-    launch_derivatives(px, py, pz, h->n_src, h->geom, h->cell2leaf.p, records, h->cent.p, pc, nullptr, 1, ec, h->partials.p,
+    plan = pl;
+    plan.spec = speculate ? 1 : 0;
+    launch_derivatives(plan, ecl, px, py, pz, h->n_src, h->geom, h->cell2leaf.p, records, h->cent.p, pc, nullptr, 1, h->partials.p,
                        h->counters.p, d_out, s, spin ? h->flag.d + (size_t)buf * 2 * EV_WORDS : nullptr, seq, nullptr,
                        xinfo, xround, nullptr, nullptr, h->timing && !bracket ? h->ev0 : nullptr,
-                       h->timing && !bracket ? h->ev1 : nullptr, speculate ? h->gd.p : nullptr, &plan);
+                       h->timing && !bracket ? h->ev1 : nullptr, speculate ? h->gd.p : nullptr);
     HIP_TRY(h, hipGetLastError());
     if (bracket) HIP_TRY(h, hipEventRecord(h->ev1, s));
   }
@@ -427,7 +431,9 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
     ++h->n_spec_used;
   }
   if (p2p) h->red.p2p_set_round(xround);  // this evaluation's tag is spent (a fallback below gives it back)
-  if (prelaunch) {
+  // (rows > cap: the tuning changed since the kernel in flight was enqueued and the new shape writes more rows than
+  // there are -- they grow at the next evaluation's ordinary launch, when nothing reads them)
+  if (prelaunch && rows <= h->partials.cap) {
     // the next evaluation's kernel goes onto the stream now, behind the one in flight; it will
     // start when that one has finished and wait for its pose (or for the order to leave)
     h->pre_seq = g_launch_seq.fetch_add(1, std::memory_order_relaxed);
@@ -461,10 +467,12 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
     }
     h->pre_on2 = in_flight_resident ? (h->cur_on2 ^ 1) : h->cur_on2;
     if (in_flight_resident) h->n_prelaunch_overlapped++;
-    launch_derivatives(px, py, pz, h->n_src, h->geom, h->cell2leaf.p, records, h->cent.p, pc, nullptr, 1, ec, h->partials.p,
-                       h->counters.p, d_out, h->pre_on2 ? h->stream2 : s, h->flag.d + (size_t)h->pre_buf * 2 * EV_WORDS,
-                       h->pre_seq, h->mbox, xinfo, h->pre_round, h->arrive_ctr.p + h->pre_buf, h->arrived.d + h->pre_buf,
-                       nullptr, nullptr, nullptr, &h->pre_plan);
+    h->pre_plan = pl;   // (planned from this evaluation's snapshot; the kernel keeps it whatever the tuning is when its pose comes)
+    h->pre_plan.mbox = 1;
+    launch_derivatives(h->pre_plan, ecl, px, py, pz, h->n_src, h->geom, h->cell2leaf.p, records, h->cent.p, pc, nullptr, 1,
+                       h->partials.p, h->counters.p, d_out, h->pre_on2 ? h->stream2 : s,
+                       h->flag.d + (size_t)h->pre_buf * 2 * EV_WORDS, h->pre_seq, h->mbox, xinfo, h->pre_round,
+                       h->arrive_ctr.p + h->pre_buf, h->arrived.d + h->pre_buf);
     HIP_TRY(h, hipGetLastError());
   }
   if (dev_out) {
@@ -615,7 +623,8 @@ int ndt_align(ndt_handle* h, const float guess[16], ndt_result* out) {
   if (rc) return rc;
   AlignBusy busy(h->keepwarm);
   h->spec_build_failed = false;
-  h->spec_first = first_eval_behind_build(h);   // the build's verdict is then collected inside the first evaluation
+  const ndt_tuning tn = tuning_snapshot();   // (this align's: the decision below and the probe; each evaluation takes its own)
+  h->spec_first = first_eval_behind_build(tn, h);   // the build's verdict is then collected inside the first evaluation
   if (!h->spec_first) {
     rc = ready_for_eval(h);
     if (rc) {
@@ -644,7 +653,8 @@ int ndt_align(ndt_handle* h, const float guess[16], ndt_result* out) {
   // placement of the waiting kernels for this align (see auto_one_stream)
   const bool auto_mode = h->two_streams && h->prm.prelaunch == NDT_PRELAUNCH_AUTO;
   ++h->n_auto_aligns;   // (probes: the 6th and 14th align of a handle, so that a shared device is noticed early, then every 32nd)
-  h->probing = auto_mode && auto_probe_enabled() && (h->n_auto_aligns == 6 || h->n_auto_aligns == 14 || h->n_auto_aligns % 32 == 0);
+  // (ndt_tuning::prelaunch_probe = 0: the automatic placement never probes the other one, an A/B aid)
+  h->probing = auto_mode && tn.prelaunch_probe != 0 && (h->n_auto_aligns == 6 || h->n_auto_aligns == 14 || h->n_auto_aligns % 32 == 0);
   h->streams_this_align = auto_mode && (h->auto_one_stream == h->probing);   // two streams unless AUTO settled on one (probe: the other)
   const int64_t used0 = h->n_prelaunch_used, launches0 = h->tm.n_eval_launches;
   rc = newton_align(h->prm, n_total, guess, fn, out, /*hessian_in_trials=*/true, &h->history);
@@ -731,6 +741,7 @@ static int eval_batch(ndt_handle* h, const double* poses6, const float* transfor
                       bool score_only, double* out, void (*overlap)(void*) = nullptr, void* overlap_ctx = nullptr,
                       bool fixed_order = false, bool batched_shape = false) {
   if (!h || !poses6 || !out || K <= 0) return NDT_ERR_INVALID_ARG;
+  const ndt_tuning tn = tuning_snapshot();
   int rc = bind_device(h);
   if (rc) return rc;
   rc = ready_for_eval(h);
@@ -779,7 +790,9 @@ static int eval_batch(ndt_handle* h, const double* poses6, const float* transfor
   const VoxelRecord* records = nullptr;
   rc = records_for_eval(h, &ec, &records);
   if (rc) return rc;
-  rc = ensure_partials(h, derivs_partials_words(h->n_src, batched_shape ? std::max(K, 2) : K, h->n_cus));
+  EvalConsts ecl;   // the consts as planned: what the kernel receives
+  const DerivLaunchPlan plan = plan_derivatives_launch(tn, h->n_src, K, true, false, ec, &ecl, batched_shape);
+  rc = ensure_partials(h, derivs_partials_words(plan, K));
   if (rc) return rc;
   HIP_TRY(h, h->result.ensure((size_t)K * EV_WORDS));
   HIP_TRY(h, h->dres.ensure((size_t)K * EV_WORDS));
@@ -792,15 +805,13 @@ static int eval_batch(ndt_handle* h, const double* poses6, const float* transfor
     HIP_TRY(h, hipMemcpyAsync(h->dposes.p, h->hposes.h, (size_t)K * sizeof(PoseConsts), hipMemcpyHostToDevice, s));
   }
   const unsigned long long seq = g_launch_seq.fetch_add(1, std::memory_order_relaxed);
-  const bool bracket = h->timing && timing_brackets_launch();
+  const bool bracket = h->timing && tn.timing_bracket != 0;
   if (bracket) HIP_TRY(h, hipEventRecord(h->ev0, s));
-  DerivLaunchPlan plan{};   // (the evaluation log's launch descriptor)
-  launch_derivatives(h->src_sorted ? h->ox.p : h->vx, h->src_sorted ? h->oy.p : h->vy,
+  launch_derivatives(plan, ecl, h->src_sorted ? h->ox.p : h->vx, h->src_sorted ? h->oy.p : h->vy,
                      h->src_sorted ? h->oz.p : h->vz, h->n_src, h->geom, h->cell2leaf.p, records, h->cent.p,
-                     h->hposes.h[0], fast ? h->bposes : h->dposes.p, K, ec, h->partials.p, h->counters.p, h->dres.p, s,
+                     h->hposes.h[0], fast ? h->bposes : h->dposes.p, K, h->partials.p, h->counters.p, h->dres.p, s,
                      fast ? h->flag.d : nullptr, seq, nullptr, nullptr, 0ull, nullptr, nullptr,
-                     h->timing && !bracket ? h->ev0 : nullptr, h->timing && !bracket ? h->ev1 : nullptr, nullptr, &plan,
-                     batched_shape);
+                     h->timing && !bracket ? h->ev0 : nullptr, h->timing && !bracket ? h->ev1 : nullptr);
   HIP_TRY(h, hipGetLastError());
   if (bracket) HIP_TRY(h, hipEventRecord(h->ev1, s));
   if (overlap) overlap(overlap_ctx);

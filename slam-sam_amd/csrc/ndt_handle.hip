@@ -122,7 +122,7 @@ int ndt_create(const ndt_params* p, ndt_handle** out) {
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) h->n_cus = cus;
   }
   {  // A/B switches of the pose hand-over to pre-launched kernels (ndt_tuning; profiles/r02_mailbox_ab.txt)
-    const ndt_tuning& tn = tuning();
+    const ndt_tuning tn = tuning_snapshot();
     h->mbox_tagged = tn.mbox_tagged != 0;
     h->mbox_preload = tn.mbox_preload != 0;
     h->two_streams = tn.prelaunch_streams != 1;
@@ -427,7 +427,7 @@ static EvalConsts debug_eval_consts(int cus, int nb, int mode) {
 // (K > 1: a batched launch; K = 1: a single-pose one -- the same shape as a batched launch of one pose)
 int ndt_debug_launch_shape(size_t n_src, int K, int cus, int out[4]) {
   if (!out || K < 1 || cus < 1) return NDT_ERR_INVALID_ARG;
-  const DerivLaunchPlan pl = plan_derivatives_launch(n_src, K, K > 1, false, false, debug_eval_consts(cus, 1, 1), nullptr);
+  const DerivLaunchPlan pl = plan_derivatives_launch(tuning_snapshot(), n_src, K, K > 1, false, debug_eval_consts(cus, 1, 1), nullptr);
   out[0] = pl.threads;
   out[1] = pl.point_blocks;
   out[2] = pl.summers;
@@ -443,7 +443,8 @@ int ndt_debug_launch_plan(size_t n_src, int K, int cus, int nb, int mode, int fl
   if (!out || K < 1 || cus < 1 || nb < 0 || nb > 6 || mode < 0 || mode > 3) return NDT_ERR_INVALID_ARG;
   EvalConsts ec = debug_eval_consts(cus, nb, mode);
   ec.safe_sum = (flags & 4) ? 1 : 0;
-  const DerivLaunchPlan pl = plan_derivatives_launch(n_src, K, (flags & 1) != 0, (flags & 2) != 0, false, ec, nullptr);
+  DerivLaunchPlan pl = plan_derivatives_launch(tuning_snapshot(), n_src, K, (flags & 1) != 0, false, ec, nullptr);
+  pl.mbox = (flags & 2) != 0 && !pl.batch ? 1 : 0;   // (a batched launch never takes the mailbox)
   std::memcpy(out, &pl, sizeof(pl));
   return NDT_OK;
 }
@@ -485,10 +486,11 @@ int64_t ndt_debug_eval_log_read(const ndt_handle* h, void* out, int cap) {
 // {fits (0 / 1), points per tile, tiles, words of the column table}
 int ndt_debug_bucket_plan(size_t n, long long out[4]) {
   if (!out) return NDT_ERR_INVALID_ARG;
+  const ndt_tuning tn = tuning_snapshot();
   const bool fits = bucket_build_fits(n, 0);
   out[0] = fits ? 1 : 0;
-  out[1] = fits ? (long long)bucket_tile_points(n) : 0;
-  out[2] = fits ? bucket_build_tiles(n) : 0;
+  out[1] = fits ? (long long)bucket_tile_points(tn, n) : 0;
+  out[2] = fits ? bucket_build_tiles(tn, n) : 0;
   out[3] = (long long)bucket_table_words();
   return NDT_OK;
 }

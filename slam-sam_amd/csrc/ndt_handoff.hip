@@ -106,6 +106,7 @@ int build_begin(ndt_handle* h, const float* x, const float* y, const float* z, s
   ++h->tgt_gen;   // (the fitness index, if any, is rebuilt by the next fitness call)
   h->n_slots = h->n_valid = 0;
   br = ndt_handle::BuildRun{};
+  br.tn = tuning_snapshot();   // the one read of ndt_tuning of this build: everything below and every later step reads br.tn
   br.x = x; br.y = y; br.z = z; br.n = n;
   br.dirty_slots = h->grid_dirty_slots;
   br.clean_cap = h->grid_clean_cap;
@@ -114,7 +115,6 @@ int build_begin(ndt_handle* h, const float* x, const float* y, const float* z, s
   if (n == 0) return fail(h, NDT_ERR_NO_TARGET, "empty target cloud");
   if (n > (size_t)std::numeric_limits<int>::max() / 2) return fail(h, NDT_ERR_INVALID_ARG, "target too large");
   hipStream_t s = h->stream;
-  const int nrows = bounds_rows(n);
   br.min_pts = std::max(3, h->prm.min_points_per_voxel);  // ref: voxel_grid_covariance.h:176-184
   br.max_leaves = (int)(n / (size_t)br.min_pts) + 1;
   const int max_leaves = br.max_leaves;
@@ -122,7 +122,7 @@ int build_begin(ndt_handle* h, const float* x, const float* y, const float* z, s
   br.inv_leaf = 1.0f / h->prm.resolution;
 
   HIP_TRY(h, h->small.ensure(16));
-  HIP_TRY(h, h->brows.ensure(8 * (size_t)std::max(nrows, bucket_build_tiles(n))));
+  HIP_TRY(h, h->brows.ensure(8 * (size_t)std::max(bounds_rows(br.tn, n), bucket_build_tiles(br.tn, n))));
   HIP_TRY(h, h->bucket_tab.ensure(bucket_table_words()));
   if (!h->bnd.p) {
     HIP_TRY(h, h->bnd.ensure(8));
@@ -153,10 +153,10 @@ int build_begin(ndt_handle* h, const float* x, const float* y, const float* z, s
   HIP_TRY(h, h->fin_counts.ensure((size_t)finalize_blocks(max_leaves)));
   HIP_TRY(h, h->sort_tmp.ensure(sort_temp_bytes(n)));
   // fused = launches that wait, inside the kernel, for sibling blocks (k_sort_pass, k_runs<RUNS_FUSED>)
-  br.fused = fused_build_enabled();
+  br.fused = br.tn.fused_sort != 0;
   br.fused_sort = br.fused && fused_sort_fits(n, h->n_cus);
   // the two-launch build: steady state only (decided per attempt below)
-  br.bucketed_ok = bucket_build_enabled() && bucket_build_fits(n, h->n_cus);
+  br.bucketed_ok = br.tn.bucket_build != 0 && bucket_build_fits(n, h->n_cus);
   // A cloud the two-launch build declined (BG_BUCKET: a bucket beyond a block's LDS or hash table, far-away coordinates)
   // is usually followed by more of its kind (the same map, the next keyframe): the attempt costs two launches and, for a
   // late decline, a full clear of the index grid, so after a decline the next 8 builds go sort-based straight away, 16 after
@@ -179,11 +179,10 @@ int build_begin(ndt_handle* h, const float* x, const float* y, const float* z, s
   // device time of the build by HIP events when kernel timing is on (ndt_enable_kernel_timing; bench.py's
   // instrumented pass); otherwise ms_build is the wall time from the build's enqueue to its verdict and the two
   // event records, the event query and the elapsed-time call (3-4 us of host time) are saved
-  const int events_tuned = tuning().build_events;
-  br.build_events = events_tuned >= 0 ? events_tuned != 0 : h->timing;
+  br.build_events = br.tn.build_events >= 0 ? br.tn.build_events != 0 : h->timing;
   br.t0 = std::chrono::steady_clock::now();
   if (br.build_events) HIP_TRY(h, hipEventRecord(h->ev0, s));
-  br.poll_done = tuning().build_wait_sync == 0 && h->prm.wait_mode == NDT_WAIT_SPIN;
+  br.poll_done = br.tn.build_wait_sync == 0 && h->prm.wait_mode == NDT_WAIT_SPIN;
   br.attempt = 0;
   return NDT_OK;
 }
@@ -214,20 +213,20 @@ int build_enqueue(ndt_handle* h, ndt_handle::BuildRun& br) {
   if (br.bucketed) {
     // bounds, partition, sort, sums and statistics in two launches (k_bucket_pass, k_bucket_leaves)
     FinalizeParams fpb{h->prm.eig_inflation_ratio, h->prm.cov_mode};
-    if (br.pass_chunked && br.attempt == 0 && br.pass_tiles == bucket_build_tiles(n)) {
+    if (br.pass_chunked && br.attempt == 0 && br.pass_tiles == bucket_build_tiles(br.tn, n)) {
       // the partition ran under the transfer (chunked_pass_hook): only the leaves launch is left, and the build's clock
       // starts here
       br.t0 = std::chrono::steady_clock::now();
       if (br.build_events) HIP_TRY(h, hipEventRecord(h->ev0, s));
     } else {
-      HIP_TRY(h, launch_bucket_pass_tiles(x, y, z, n, br.inv_leaf, h->bucket_tab.p, h->stats.p, br.dirty_slots, h->cell2leaf.p,
-                                          h->cell2leaf.cap, h->bnd.p, h->nleaf.p, h->xyz4.p, 0, bucket_build_tiles(n), s));
+      HIP_TRY(h, launch_bucket_pass_tiles(br.tn, x, y, z, n, br.inv_leaf, h->bucket_tab.p, h->stats.p, br.dirty_slots, h->cell2leaf.p,
+                                          h->cell2leaf.cap, h->bnd.p, h->nleaf.p, h->xyz4.p, 0, bucket_build_tiles(br.tn, n), s));
     }
-    HIP_TRY(h, launch_bucket_leaves(n, br.leaf, br.inv_leaf, cap_cells, min_pts, fpb, h->gd.p, h->gdh.d, h->bucket_tab.p,
+    HIP_TRY(h, launch_bucket_leaves(br.tn, n, br.leaf, br.inv_leaf, cap_cells, min_pts, fpb, h->gd.p, h->gdh.d, h->bucket_tab.p,
                                     h->cell2leaf.p, h->bnd.p, h->nleaf.p, h->tickets.p + 4, h->xyz4.p, h->leaf_sums.p, h->rec.p,
                                     h->cent.p, h->stats.p, max_leaves, h->small.d + 8, done_tag, s));
   } else {
-    launch_bounds_geometry(x, y, z, n, br.leaf, br.inv_leaf, cap_cells, passes, h->brows.p, h->tickets.p, h->gd.p, h->gdh.d,
+    launch_bounds_geometry(br.tn, x, y, z, n, br.leaf, br.inv_leaf, cap_cells, passes, h->brows.p, h->tickets.p, h->gd.p, h->gdh.d,
                            optimistic ? h->stats.p : nullptr, optimistic ? br.dirty_slots : 0, h->cell2leaf.p,
                            h->cell2leaf.cap, h->nleaf.p, s);
     if (!optimistic) {
@@ -255,7 +254,7 @@ int build_enqueue(ndt_handle* h, ndt_handle::BuildRun& br) {
                                 h->tickets.p + 1, br.fused ? h->run_tags.p : nullptr, h->run_tags.cap, &h->run_seq,
                                 h->leaf_start.p, h->leaf_cnt.p, s));
     FinalizeParams fp{h->prm.eig_inflation_ratio, h->prm.cov_mode};
-    launch_finalize_leaves(h->xyz4.p, keys_sorted, vals_sorted, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p, max_leaves,
+    launch_finalize_leaves(br.tn, h->xyz4.p, keys_sorted, vals_sorted, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p, max_leaves,
                            fp, h->leaf_sums.p, h->rec.p, h->cent.p, h->stats.p, h->cell2leaf.p, h->fin_counts.p, h->tickets.p + 2,
                            h->small.d + 8, done_tag, s);
   }  // (sort-based pipeline)
@@ -413,11 +412,11 @@ int build_grid_handoff(ndt_handle* h, const float* xyz, const float* x, const fl
   int rc = build_begin(h, h->tx.p, h->ty.p, h->tz.p, n, br);
   if (rc) return rc;
   const bool steady = br.clean_cap != 0 && br.clean_cap == h->cell2leaf.cap;   // (build_enqueue's `optimistic`)
-  br.pass_chunked = br.bucketed_ok && steady && tuning().handoff_chunk_pass != 0;
+  br.pass_chunked = br.bucketed_ok && steady && br.tn.handoff_chunk_pass != 0;
   br.pass_tiles = 0;
   hipError_t hook_err = hipSuccess;
-  const size_t tile = br.pass_chunked ? bucket_tile_points(n) : 1;
-  const int ntiles = br.pass_chunked ? bucket_build_tiles(n) : 0;
+  const size_t tile = br.pass_chunked ? bucket_tile_points(br.tn, n) : 1;
+  const int ntiles = br.pass_chunked ? bucket_build_tiles(br.tn, n) : 0;
   // The partition launches go to a stream of their own, each behind its chunk's pull kernel by an event: on the pull
   // kernels' stream they would stand between two transfers (measured: PCIe idle for every partition launch, the scan
   // 0.84 -> 0.92 ms); the leaves launch joins them below.
@@ -434,7 +433,7 @@ int build_grid_handoff(ndt_handle* h, const float* xyz, const float* x, const fl
     hipEvent_t e = h->pass_ev[ev_used++];
     if ((hook_err = hipEventRecord(e, h->stream)) != hipSuccess) return;
     if ((hook_err = hipStreamWaitEvent(h->pstream, e, 0)) != hipSuccess) return;
-    hook_err = launch_bucket_pass_tiles(h->tx.p, h->ty.p, h->tz.p, n, br.inv_leaf, h->bucket_tab.p, h->stats.p, br.dirty_slots,
+    hook_err = launch_bucket_pass_tiles(br.tn, h->tx.p, h->ty.p, h->tz.p, n, br.inv_leaf, h->bucket_tab.p, h->stats.p, br.dirty_slots,
                                         h->cell2leaf.p, h->cell2leaf.cap, h->bnd.p, h->nleaf.p, h->xyz4.p, br.pass_tiles, upto,
                                         h->pstream);
     br.pass_tiles = upto;

@@ -1,6 +1,7 @@
 // ndt_kernels.h -- launch wrappers of the HIP kernels (internal).
 #pragma once
 
+#include "../../include/ndt_hip.h"
 #include "ndt_device.h"
 
 namespace ndt {
@@ -10,17 +11,19 @@ struct FinalizeParams {
   double eig_ratio;
   int cov_mode;  // 0 svn, 1 pcl (recalled)
 };
-// One launch: per-block bounds rows (device memory, bounds_rows(n) x 8 ints), the fold of the
+// One launch: per-block bounds rows (device memory, bounds_rows(tn, n) x 8 ints), the fold of the
 // rows + the grid geometry + the sort plan by the block that draws the last ticket (into *gd,
 // device memory, and *gd_host, a pinned copy for the host to read at the end of the build),
 // the reset of the cells the previous build published (old_stats / dirty_slots), and the
 // zeroing of d_nleaf[0..1].  cell_capacity: cells the dense grid can hold (BG_CAPACITY beyond);
 // planned_passes: digit passes the host has enqueued (0 = the device decides, host reads it).
 // *ticket: zero-initialised, left at zero.
-int bounds_rows(size_t n);
+// Every function below that takes `tn` follows ndt_tuning in what it sizes or launches: the caller passes the ONE snapshot
+// its build took when it began (ndt_handle::BuildRun::tn), so that sizes and launches of one build cannot disagree.
+int bounds_rows(const ndt_tuning& tn, size_t n);
 int sort_passes_for_cells(long long ncells);
-void launch_bounds_geometry(const float* x, const float* y, const float* z, size_t n, float leaf, float inv_leaf,
-                            long long cell_capacity, int planned_passes, int* rows, unsigned int* ticket,
+void launch_bounds_geometry(const ndt_tuning& tn, const float* x, const float* y, const float* z, size_t n, float leaf,
+                            float inv_leaf, long long cell_capacity, int planned_passes, int* rows, unsigned int* ticket,
                             BuildGeom* gd, BuildGeom* gd_host, const LeafStats* old_stats, int dirty_slots,
                             int* cell2leaf, size_t c2l_cap, int* d_nleaf, hipStream_t s);
 
@@ -42,8 +45,8 @@ void launch_sort_first_count(const uint32_t* keys, size_t n, const BuildGeom* gd
 
 // One launch per digit, straight from the cloud (no launch_cell_keys): see k_sort_pass.  Only for
 // clouds with fused_sort_fits(n, CUs of the device); `table`: fused_table_words() words, zero at allocation; a build
-// that had to give up waiting leaves BG_SPIN in *gd / *gd_host (repeat it with the classic passes).
-bool fused_build_enabled();  // NDT_FUSED_SORT != 0 (default): fused sort passes and the fused run search
+// that had to give up waiting leaves BG_SPIN in *gd / *gd_host (repeat it with the classic passes).  On while
+// ndt_tuning::fused_sort = 1 (the default): fused sort passes and the fused run search.
 bool fused_sort_fits(size_t n, int compute_units);
 int fused_tile_for(size_t n, int compute_units);  // pairs per tile (8192 up to 2 M points on 256 CUs, 16384 up to 4 M), 0 = classic passes
 size_t fused_table_words();
@@ -58,31 +61,25 @@ hipError_t sort_cloud_fused(const float* x, const float* y, const float* z, size
 // tags, no initial state); pts4: n float4 (the cloud, tile by tile, each tile in bucket order); sums: 9 doubles
 // per leaf slot.  Neither launch waits for sibling blocks.  Refusals leave BG_BUCKET / BG_CAPACITY / ... in
 // *gd_host: decided before anything is written, except a bucket beyond a block's LDS or hash table (late BG_BUCKET).
-bool bucket_build_enabled();                            // NDT_BUCKET_BUILD != 0 (default on)
+// On while ndt_tuning::bucket_build = 1 (the default).
 // the 8 bounds words {min xyz, max xyz, #finite, unused} between two builds (host copy for (re)initialisation;
 // the launch pair leaves them neutral again whenever it runs to its end)
 void bucket_bounds_neutral(int out[8]);
 bool bucket_build_fits(size_t n, int compute_units);
-int bucket_build_tiles(size_t n);
+int bucket_build_tiles(const ndt_tuning& tn, size_t n);
 size_t bucket_table_words();
 // ... or piecewise (the asynchronous host hand-off runs the partition under the transfer, chunk by chunk, and only the
-// leaves launch behind the last chunk): tiles [tile_first, tile_end) of bucket_build_tiles(n), each of
-// bucket_tile_points(n) points; every tile exactly once, tile 0's launch first (it resets the previous build's cells)
-size_t bucket_tile_points(size_t n);
-hipError_t launch_bucket_pass_tiles(const float* x, const float* y, const float* z, size_t n, float inv_leaf, uint32_t* tab,
-                                    const LeafStats* old_stats, int dirty_slots, int* cell2leaf, size_t c2l_cap, int* bnd,
-                                    int* d_nleaf, float* pts4, int tile_first, int tile_end, hipStream_t s);
-hipError_t launch_bucket_leaves(size_t n, float leaf, float inv_leaf, long long cell_capacity, int min_pts, FinalizeParams fp,
+// leaves launch behind the last chunk): tiles [tile_first, tile_end) of bucket_build_tiles(tn, n), each of
+// bucket_tile_points(tn, n) points; every tile exactly once, tile 0's launch first (it resets the previous build's cells)
+size_t bucket_tile_points(const ndt_tuning& tn, size_t n);
+hipError_t launch_bucket_pass_tiles(const ndt_tuning& tn, const float* x, const float* y, const float* z, size_t n, float inv_leaf,
+                                    uint32_t* tab, const LeafStats* old_stats, int dirty_slots, int* cell2leaf, size_t c2l_cap,
+                                    int* bnd /* 8 ints, see bucket_bounds_neutral */, int* d_nleaf, float* pts4, int tile_first,
+                                    int tile_end, hipStream_t s);
+hipError_t launch_bucket_leaves(const ndt_tuning& tn, size_t n, float leaf, float inv_leaf, long long cell_capacity, int min_pts, FinalizeParams fp,
                                 BuildGeom* gd, BuildGeom* gd_host, const uint32_t* tab, int* cell2leaf, int* bnd, int* d_nleaf,
                                 unsigned int* ticket, const float* pts4, double* sums, VoxelRecord* rec, float* cent4,
                                 LeafStats* stats, int max_leaves, int* nleaf_host, int done_tag, hipStream_t s);
-hipError_t launch_bucket_build(const float* x, const float* y, const float* z, size_t n, float leaf, float inv_leaf,
-                               long long cell_capacity, int min_pts, FinalizeParams fp, BuildGeom* gd, BuildGeom* gd_host,
-                               uint32_t* tab, const LeafStats* old_stats, int dirty_slots, int* cell2leaf,
-                               size_t c2l_cap, int* bnd /* 8 ints, see bucket_bounds_neutral */, int* d_nleaf,
-                               unsigned int* ticket, float* pts4,
-                               double* sums, VoxelRecord* rec, float* cent4 /* 4 floats per leaf slot: f32 centroid + chain link */,
-                               LeafStats* stats, int max_leaves, int* nleaf_host, int done_tag, hipStream_t s);
 
 // runs of equal cell key with >= min_pts points get a leaf slot (ascending cell order);
 // block_counts / block_offsets: runs_blocks(n) ints each; d_nleaf[0] receives the total
@@ -108,7 +105,7 @@ void launch_scatter_heads(const int* cells, const int* slots, size_t n, int* cel
 int finalize_blocks(int max_leaves);
 int build_read_stamps(unsigned long long* out /* 4 x 512 x 8 */);  // -DNDT_STAMPS builds only; else 0
 // per-leaf sums, then per-leaf statistics; sums: 9 doubles per leaf slot (scratch)
-void launch_finalize_leaves(const float* xyz4, const uint32_t* keys_sorted, const uint32_t* vals_sorted,
+void launch_finalize_leaves(const ndt_tuning& tn, const float* xyz4, const uint32_t* keys_sorted, const uint32_t* vals_sorted,
                             int* d_nleaf /* [0]=slots, [1]=valid */, const int* leaf_start, const int* leaf_cnt,
                             int max_leaves, FinalizeParams fp, double* sums, VoxelRecord* rec,
                             float* cent4 /* 4 floats per leaf slot: the f32 centroid the radius search tests + chain link */,
@@ -154,13 +151,9 @@ hipError_t sort_source_by_blocks(const float* x, const float* y, const float* z,
                                  float* oz, hipStream_t s);
 
 // ---- derivative evaluation (ndt_derivs.hip) ---------------------------------
-// cus: compute units of the handle's device (EvalConsts::compute_units): single-pose launches of mid-sized scans are
-// shaped one block per CU, and the XCD count follows from it
-int derivs_grid_blocks(size_t n_src, int K, int cus);
-int derivs_block_threads(size_t n_src, int K, int cus);
-// The shape of one k_derivatives launch, as launch_derivatives makes it (plan_derivatives_launch): the evaluation log
-// (ndt_debug_eval_log) records it per evaluation, ndt_debug_launch_plan computes it without a device.  Plain ints in this
-// order -- the Python binding reads them by position (EVAL_DESC_FIELDS, slam-sam_amd/__init__.py).
+// The shape of one k_derivatives launch, as plan_derivatives_launch decides it and launch_derivatives makes it: the
+// evaluation log (ndt_debug_eval_log) records it per evaluation, ndt_debug_launch_plan computes it without a device.
+// Plain ints in this order -- the Python binding reads them by position (EVAL_DESC_FIELDS, slam-sam_amd/__init__.py).
 struct DerivLaunchPlan {
   int batch, mode, nb, mbox;                     // template axes <BATCH, MODE, NB, MBOX> of the instantiation
   int threads, blocks, point_blocks, summers;    // per pose row: blocks = point_blocks + summers (dedicated summing blocks)
@@ -170,19 +163,23 @@ struct DerivLaunchPlan {
   int spec;                                      // the first evaluation enqueued behind a build (d_geom), set by the caller
 };
 static_assert(sizeof(DerivLaunchPlan) == 16 * sizeof(int), "DerivLaunchPlan is 16 ints");
-// Everything launch_derivatives decides from the size, the pose count and the engine's consts: the plan and the EvalConsts
-// the kernel receives.  batched: d_poses != nullptr; mbox: a pre-launched launch; xchg: in-kernel cross-rank exchange.
+// Everything about a launch that follows from the caller's snapshot of ndt_tuning, the size, the pose count and the
+// engine's consts -- a pure function of its arguments: the plan and the EvalConsts the kernel receives.  The compute
+// units of the handle's device come in as ec.compute_units: single-pose launches of mid-sized scans are shaped one block
+// per CU, and the XCD count follows from it.  batched: d_poses != nullptr; xchg: in-kernel cross-rank exchange.
+// mbox and spec say how the launch is made, not what shape it has: they are left 0 for the caller to set.
 // batched_shape: a batched launch keeps the block shape of K > 1 at K = 1 too (the rounds of ndt_align_batch: a pose's
 // sums do not depend on the number of poses in the launch); the same kernel instantiations either way.
-DerivLaunchPlan plan_derivatives_launch(size_t n_src, int K, bool batched, bool mbox, bool xchg, const EvalConsts& ec,
+DerivLaunchPlan plan_derivatives_launch(const ndt_tuning& tn, size_t n_src, int K, bool batched, bool xchg, const EvalConsts& ec,
                                         EvalConsts* ecl_out, bool batched_shape = false);
-size_t derivs_partials_words(size_t n_src, int K, int cus);  // doubles needed in d_partials
+size_t derivs_partials_words(const DerivLaunchPlan& pl, int K);  // doubles a launch of that plan and K poses needs in d_partials
 int derivs_counters_per_pose();
 // which finishing wave expands which wave's points: 2 bits per wave (owning SIMD), 4 bits per SIMD (its finishing wave)
 void derivs_item_owners(int threads, unsigned int* owners_out, unsigned int* fin_waves_out, int* lone_out = nullptr);
 int derivs_read_wave_stamps(unsigned long long* out, int nblocks);  // diagnostic builds only: per-wave stamps, see ndt_derivs.hip
 int derivs_read_stamps(unsigned long long* out, int nblocks);  // diagnostic builds (-DNDT_STAMPS) only                     // ticket words per pose in d_counters
-// d_partials: derivs_partials_words() doubles, ZEROED when allocated (rows of tagged slots);
+// pl, ecl: what plan_derivatives_launch returned for this launch (the caller sets pl.mbox and pl.spec).
+// d_partials: derivs_partials_words(pl, K) doubles, ZEROED when allocated (rows of tagged slots);
 // d_counters: K * derivs_counters_per_pose() zero-initialised ticket words (left at zero again
 // by every launch).  `seq`: a sequence number no earlier launch IN THIS PROCESS has used (it
 // tags every partial slot).  If d_poses is null the single pose `pose` is passed as a kernel
@@ -192,11 +189,10 @@ int derivs_read_stamps(unsigned long long* out, int nblocks);  // diagnostic bui
 // {seq, value} per pose for the host to poll, d_out unused.
 // d_mbox != nullptr (single-pose only): a PRE-LAUNCHED evaluation -- `pose` is ignored, the kernel
 // waits for the pose to appear in *d_mbox under its sequence number (PoseMailbox in ndt_device.h).
-void launch_derivatives(const float* sx, const float* sy, const float* sz, size_t n_src,
-                        const GridGeom& g, const int* cell2leaf /* readable 4 ints beyond either end */,
+void launch_derivatives(const DerivLaunchPlan& pl, const EvalConsts& ecl, const float* sx, const float* sy, const float* sz,
+                        size_t n_src, const GridGeom& g, const int* cell2leaf /* readable 4 ints beyond either end */,
                         const VoxelRecord* rec, const float* cent4 /* per-leaf f32 centroid + chain link (KDTREE, multi-grid) */,
-                        const PoseConsts& pose, const PoseConsts* d_poses, int K,
-                        const EvalConsts& ec, double* d_partials, unsigned int* d_counters,
+                        const PoseConsts& pose, const PoseConsts* d_poses, int K, double* d_partials, unsigned int* d_counters,
                         double* d_out, hipStream_t s, unsigned long long* d_host_slots,
                         unsigned long long seq, const PoseMailbox* d_mbox = nullptr,
                         // NDT_REDUCE_P2P (single-pose launches): the block that finishes the local sum
@@ -210,11 +206,7 @@ void launch_derivatives(const float* sx, const float* sy, const float* sz, size_
                         hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
                         // single-pose ordinary launches enqueued behind the build of their own grid: the geometry is read
                         // from the build's device-side BuildGeom (and nothing runs after a refused build), `g` is ignored
-                        const BuildGeom* d_geom = nullptr,
-                        // the shape of this launch (evaluation log), when not null
-                        DerivLaunchPlan* plan_out = nullptr,
-                        // batched launches: the shape of K > 1 at every K (plan_derivatives_launch)
-                        bool batched_shape = false);
+                        const BuildGeom* d_geom = nullptr);
 
 // The 80-byte records of leaf slots [0, n) as 48-byte PackedRecords (f64 mean, f32 inverse covariance); a launch
 // whose EvalConsts::packed is set takes that array in place of `rec`.

@@ -262,7 +262,8 @@ static int voxel_downsample_device_impl(ndt_handle* h, const float* dx, const fl
   if (n > (size_t)std::numeric_limits<int>::max() / 2) return fail(h, NDT_ERR_INVALID_ARG, "cloud too large");
   settle_discard_keep_grid(h);
   hipStream_t s = h->stream;
-  HIP_TRY(h, h->brows.ensure(8 * (size_t)std::max(bounds_rows(n), bucket_build_tiles(n))));
+  const ndt_tuning tn = tuning_snapshot();   // (the bounds launch below and the rows it writes: one configuration)
+  HIP_TRY(h, h->brows.ensure(8 * (size_t)std::max(bounds_rows(tn, n), bucket_build_tiles(tn, n))));
   HIP_TRY(h, h->gd.ensure(1));
   HIP_TRY(h, h->gdh.ensure(1));
   if (!h->tickets.p) {
@@ -284,7 +285,7 @@ static int voxel_downsample_device_impl(ndt_handle* h, const float* dx, const fl
   h->gdh.h->status = -1;
   // the geometry is awaited (its pass count sizes the sort): a full, launch-per-phase pipeline that never waits
   // inside a kernel; no cell of the handle's index grid is touched (old_stats = null, no dirty slots)
-  launch_bounds_geometry(dx, dy, dz, n, leaf, 1.0f / leaf, (long long)std::numeric_limits<int32_t>::max(), 0, h->brows.p,
+  launch_bounds_geometry(tn, dx, dy, dz, n, leaf, 1.0f / leaf, (long long)std::numeric_limits<int32_t>::max(), 0, h->brows.p,
                          h->tickets.p, h->gd.p, h->gdh.d, nullptr, 0, nullptr, 0, h->nleaf.p, s);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipStreamSynchronize(s));

@@ -22,7 +22,6 @@
 //                      cell -> leaf index.
 // Compiled with -ffp-contract=off: f32 index arithmetic must round as written.
 #include "ndt_kernels.h"
-#include "ndt_tuning.h"
 
 #include <climits>
 #include <cstdlib>
@@ -2403,30 +2402,13 @@ void launch_transform_append(const float* x, const float* y, const float* z, siz
                      ox, oy, oz);
 }
 
-// Launch shapes of the build kernels that end in a "last block finishes the job" ticket: A/B switches of ndt_tuning
-// (include/ndt_hip.h; profiles/r02_build_tickets.txt), none of them read from the environment by the production library.
-struct BuildTuning {
-  int bounds_blocks;     // <= BOUNDS_BLOCKS
-  int bounds_unroll;     // 4 | 8 (16 measured: no change)
-  int finalize_threads;  // 64 | 256
-  int fused_sort;        // 0 | 1: one launch per sort digit where the cloud allows it
-};
-BuildTuning build_tuning() {
-  const ndt_tuning& t = tuning();
-  BuildTuning b;
-  b.bounds_blocks = t.bounds_blocks;
-  if (b.bounds_blocks < 1 || b.bounds_blocks > BOUNDS_BLOCKS) b.bounds_blocks = BOUNDS_BLOCKS;
-  b.bounds_unroll = t.bounds_unroll == 4 ? 4 : 8;
-  b.finalize_threads = t.finalize_threads == 64 ? 64 : 256;
-  b.fused_sort = t.fused_sort != 0 ? 1 : 0;
-  return b;
-}
-
-int bounds_rows(size_t n) {
-  size_t blocks = (n + 255) / 256;
-  if (blocks > (size_t)build_tuning().bounds_blocks) blocks = build_tuning().bounds_blocks;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
+// Launch shapes of the build kernels that end in a "last block finishes the job" ticket are A/B switches of ndt_tuning
+// (include/ndt_hip.h; profiles/r02_build_tickets.txt): bounds_blocks (<= BOUNDS_BLOCKS), bounds_unroll (4 | 8; 16 measured:
+// no change), finalize_threads (64 | 256).  `tn`, here and below: the snapshot the build took when it began
+// (ndt_handle::BuildRun) -- nothing in this file reads the process-wide struct.
+int bounds_rows(const ndt_tuning& tn, size_t n) {
+  const size_t most = tn.bounds_blocks < 1 || tn.bounds_blocks > BOUNDS_BLOCKS ? BOUNDS_BLOCKS : tn.bounds_blocks;
+  return (int)std::max<size_t>(1, std::min(most, (n + 255) / 256));
 }
 
 int sort_passes_for_cells(long long ncells) {
@@ -2435,16 +2417,16 @@ int sort_passes_for_cells(long long ncells) {
   return (bits + 7) / 8;
 }
 
-void launch_bounds_geometry(const float* x, const float* y, const float* z, size_t n, float leaf, float inv_leaf,
-                            long long cell_capacity, int planned_passes, int* rows, unsigned int* ticket,
+void launch_bounds_geometry(const ndt_tuning& tn, const float* x, const float* y, const float* z, size_t n, float leaf,
+                            float inv_leaf, long long cell_capacity, int planned_passes, int* rows, unsigned int* ticket,
                             BuildGeom* gd, BuildGeom* gd_host, const LeafStats* old_stats, int dirty_slots,
                             int* cell2leaf, size_t c2l_cap, int* d_nleaf, hipStream_t s) {
-  if (build_tuning().bounds_unroll == 8)
-    hipLaunchKernelGGL(k_bounds<8>, dim3((unsigned)bounds_rows(n)), dim3(256), 0, s, x, y, z, n, rows, ticket, leaf,
+  if (tn.bounds_unroll != 4)
+    hipLaunchKernelGGL(k_bounds<8>, dim3((unsigned)bounds_rows(tn, n)), dim3(256), 0, s, x, y, z, n, rows, ticket, leaf,
                        inv_leaf, cell_capacity, planned_passes, gd, gd_host, old_stats, dirty_slots, cell2leaf, c2l_cap,
                        d_nleaf);
   else
-    hipLaunchKernelGGL(k_bounds<4>, dim3((unsigned)bounds_rows(n)), dim3(256), 0, s, x, y, z, n, rows, ticket, leaf,
+    hipLaunchKernelGGL(k_bounds<4>, dim3((unsigned)bounds_rows(tn, n)), dim3(256), 0, s, x, y, z, n, rows, ticket, leaf,
                        inv_leaf, cell_capacity, planned_passes, gd, gd_host, old_stats, dirty_slots, cell2leaf, c2l_cap,
                        d_nleaf);
 }
@@ -2523,7 +2505,6 @@ int fused_tile_for(size_t n, int compute_units) {
   if (fused_tiles(n, FUSED_BIG_TILE) <= cap) return FUSED_BIG_TILE;
   return 0;
 }
-bool fused_build_enabled() { return build_tuning().fused_sort != 0; }
 // every block of a fused pass waits for all the others: one tile per compute unit at most (a
 // partitioned device -- CPX mode: 32 CUs -- takes the classic passes for anything above 256 k points)
 bool fused_sort_fits(size_t n, int compute_units) {
@@ -2586,11 +2567,10 @@ hipError_t sort_cloud_fused(const float* x, const float* y, const float* z, size
 }
 
 // ---- bucketed build (two launches) ----
-bool bucket_build_enabled() { return tuning().bucket_build != 0; }
 // points per thread of the partition launch: the smallest tile of >= 2048 points that keeps the launch at <= BK_MAX_TILES tiles
 // (a 131 k-point scan: 64 tiles of 2048 points, the 1 M-point map: 245 tiles of 4096); ndt_tuning::bucket_tile forces a size that fits
-static int bucket_rounds_for(size_t n) {
-  const int forced = tuning().bucket_tile;
+static int bucket_rounds_for(const ndt_tuning& tn, size_t n) {
+  const int forced = tn.bucket_tile;
   if (forced != 0 && (n + (size_t)forced - 1) / (size_t)forced <= (size_t)BK_MAX_TILES) return forced / BK_THREADS;
   // (1024-point tiles are compiled and measured: C2's 131 k points, 128 tiles, 40.4 us against 38.8 with 64 tiles of 2048 --
   // a bucket's segments of 4 points are half a cache line)
@@ -2598,8 +2578,9 @@ static int bucket_rounds_for(size_t n) {
     if ((n + (size_t)(BK_THREADS * r) - 1) / (size_t)(BK_THREADS * r) <= (size_t)BK_MAX_TILES) return r;
   return BK_ROUNDS;
 }
-int bucket_build_tiles(size_t n) {
-  const size_t tile = (size_t)BK_THREADS * bucket_rounds_for(n);
+size_t bucket_tile_points(const ndt_tuning& tn, size_t n) { return (size_t)BK_THREADS * bucket_rounds_for(tn, n); }
+int bucket_build_tiles(const ndt_tuning& tn, size_t n) {
+  const size_t tile = bucket_tile_points(tn, n);
   return (int)((n + tile - 1) / tile);
 }
 size_t bucket_table_words() { return (size_t)BK_BUCKETS * BK_MAX_TILES; }
@@ -2625,18 +2606,16 @@ static void launch_bucket_pass(int tile0, int ntiles, hipStream_t s, const float
                      dirty_slots, cell2leaf, c2l_cap, bnd, d_nleaf, pts4);
 }
 
-size_t bucket_tile_points(size_t n) { return (size_t)BK_THREADS * bucket_rounds_for(n); }
-
-hipError_t launch_bucket_pass_tiles(const float* x, const float* y, const float* z, size_t n, float inv_leaf, uint32_t* tab,
-                                    const LeafStats* old_stats, int dirty_slots, int* cell2leaf, size_t c2l_cap, int* bnd,
-                                    int* d_nleaf, float* pts4, int tile_first, int tile_end, hipStream_t s) {
-  if (n == 0 || !bucket_build_fits(n, 0) || tile_first < 0 || tile_end > bucket_build_tiles(n) || tile_end > BK_MAX_TILES)
+hipError_t launch_bucket_pass_tiles(const ndt_tuning& tn, const float* x, const float* y, const float* z, size_t n, float inv_leaf,
+                                    uint32_t* tab, const LeafStats* old_stats, int dirty_slots, int* cell2leaf, size_t c2l_cap,
+                                    int* bnd, int* d_nleaf, float* pts4, int tile_first, int tile_end, hipStream_t s) {
+  if (n == 0 || !bucket_build_fits(n, 0) || tile_first < 0 || tile_end > bucket_build_tiles(tn, n) || tile_end > BK_MAX_TILES)
     return hipErrorInvalidValue;
   if (tile_end <= tile_first) return hipSuccess;
   float4* p4 = reinterpret_cast<float4*>(pts4);
   const int nt = tile_end - tile_first;
   const int dirty = tile_first == 0 ? dirty_slots : 0;   // the launch that holds tile 0 resets the previous build's cells
-  switch (bucket_rounds_for(n)) {
+  switch (bucket_rounds_for(tn, n)) {
     case 1: launch_bucket_pass<1>(tile_first, nt, s, x, y, z, (int)n, inv_leaf, tab, old_stats, dirty, cell2leaf, c2l_cap, bnd, d_nleaf, p4); break;
     case 2: launch_bucket_pass<2>(tile_first, nt, s, x, y, z, (int)n, inv_leaf, tab, old_stats, dirty, cell2leaf, c2l_cap, bnd, d_nleaf, p4); break;
     case 4: launch_bucket_pass<4>(tile_first, nt, s, x, y, z, (int)n, inv_leaf, tab, old_stats, dirty, cell2leaf, c2l_cap, bnd, d_nleaf, p4); break;
@@ -2645,33 +2624,20 @@ hipError_t launch_bucket_pass_tiles(const float* x, const float* y, const float*
   return hipGetLastError();
 }
 
-hipError_t launch_bucket_leaves(size_t n, float leaf, float inv_leaf, long long cell_capacity, int min_pts, FinalizeParams fp,
+hipError_t launch_bucket_leaves(const ndt_tuning& tn, size_t n, float leaf, float inv_leaf, long long cell_capacity, int min_pts, FinalizeParams fp,
                                 BuildGeom* gd, BuildGeom* gd_host, const uint32_t* tab, int* cell2leaf, int* bnd, int* d_nleaf,
                                 unsigned int* ticket, const float* pts4, double* sums, VoxelRecord* rec, float* cent4,
                                 LeafStats* stats, int max_leaves, int* nleaf_host, int done_tag, hipStream_t s) {
   if (n == 0 || !bucket_build_fits(n, 0)) return hipErrorInvalidValue;
-  const int ntiles = bucket_build_tiles(n);
+  const int ntiles = bucket_build_tiles(tn, n);
   if (ntiles > BK_MAX_TILES) return hipErrorInvalidValue;
   int tile_shift = 10;
-  while (((size_t)1 << tile_shift) < bucket_tile_points(n)) ++tile_shift;
+  while (((size_t)1 << tile_shift) < bucket_tile_points(tn, n)) ++tile_shift;
   hipLaunchKernelGGL(k_bucket_leaves, dim3(BK_BUCKETS), dim3(BK_THREADS), 0, s, reinterpret_cast<const float4*>(pts4),
                      tab, ntiles, tile_shift, bnd, leaf, inv_leaf, cell_capacity, min_pts, fp, gd, gd_host, d_nleaf,
                      reinterpret_cast<unsigned long long*>(ticket) /* 8-byte aligned, zero between builds */, sums,
                      rec, reinterpret_cast<float4*>(cent4), stats, cell2leaf, max_leaves, nleaf_host, done_tag);
   return hipGetLastError();
-}
-
-hipError_t launch_bucket_build(const float* x, const float* y, const float* z, size_t n, float leaf, float inv_leaf,
-                               long long cell_capacity, int min_pts, FinalizeParams fp, BuildGeom* gd, BuildGeom* gd_host,
-                               uint32_t* tab, const LeafStats* old_stats, int dirty_slots, int* cell2leaf,
-                               size_t c2l_cap, int* bnd, int* d_nleaf, unsigned int* ticket, float* pts4,
-                               double* sums, VoxelRecord* rec, float* cent4, LeafStats* stats, int max_leaves, int* nleaf_host,
-                               int done_tag, hipStream_t s) {
-  hipError_t e = launch_bucket_pass_tiles(x, y, z, n, inv_leaf, tab, old_stats, dirty_slots, cell2leaf, c2l_cap, bnd, d_nleaf, pts4,
-                                          0, bucket_build_tiles(n), s);
-  if (e != hipSuccess) return e;
-  return launch_bucket_leaves(n, leaf, inv_leaf, cell_capacity, min_pts, fp, gd, gd_host, tab, cell2leaf, bnd, d_nleaf, ticket, pts4,
-                              sums, rec, cent4, stats, max_leaves, nleaf_host, done_tag, s);
 }
 
 int runs_blocks(size_t n) { return (int)((n + 256 * 8 - 1) / (256 * 8)); }
@@ -2765,7 +2731,7 @@ void launch_map_finalize(const uint32_t* order, const uint32_t* slots, size_t m,
                      table_cnt, table_mom, dc, fp, rec, reinterpret_cast<float4*>(cent4), stats, cell2leaf, d_nvalid);
 }
 
-void launch_finalize_leaves(const float* xyz4, const uint32_t* keys_sorted, const uint32_t* vals_sorted,
+void launch_finalize_leaves(const ndt_tuning& tn, const float* xyz4, const uint32_t* keys_sorted, const uint32_t* vals_sorted,
                             int* d_nleaf, const int* leaf_start, const int* leaf_cnt, int max_leaves,
                             FinalizeParams fp, double* sums, VoxelRecord* rec, float* cent4, LeafStats* stats, int* cell2leaf,
                             int* block_ok, unsigned int* ticket, int* nleaf_host, int done_tag, hipStream_t s) {
@@ -2774,7 +2740,7 @@ void launch_finalize_leaves(const float* xyz4, const uint32_t* keys_sorted, cons
   if (blocks > (size_t)SUMS_BLOCKS_MAX) blocks = SUMS_BLOCKS_MAX;
   hipLaunchKernelGGL(k_leaf_sums, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<const float4*>(xyz4),
                      vals_sorted, d_nleaf, leaf_start, leaf_cnt, sums);
-  if (build_tuning().finalize_threads == 256)
+  if (tn.finalize_threads != 64)
     hipLaunchKernelGGL(k_leaf_finalize<256>, dim3((unsigned)((max_leaves + 255) / 256)), dim3(256), 0, s, keys_sorted,
                        d_nleaf, leaf_start, leaf_cnt, sums, fp, rec, reinterpret_cast<float4*>(cent4), stats, cell2leaf, block_ok, ticket, nleaf_host, done_tag);
   else

@@ -57,8 +57,8 @@ bool valid(const ndt_tuning& t) {
   return true;
 }
 
-// Written rarely (a tuning program between two runs), read at every launch: the struct is copied under a mutex on both
-// sides -- 128 bytes, no launch path takes it more than once.
+// Written rarely (a tuning program between two runs), read once per build / evaluation / handle creation: the struct is
+// copied under a mutex on both sides -- 128 bytes.
 std::mutex g_mu;
 ndt_tuning g_tuning;
 std::once_flag g_once;
@@ -102,13 +102,10 @@ void init_once() {
 
 }  // namespace
 
-const ndt_tuning& tuning() {
-  // (a thread-local snapshot: callers keep the reference for the length of a call)
-  static thread_local ndt_tuning snap;
+ndt_tuning tuning_snapshot() {
   init_once();
   std::lock_guard<std::mutex> lk(g_mu);
-  snap = g_tuning;
-  return snap;
+  return g_tuning;
 }
 
 int tuning_set(const ndt_tuning* t) {
@@ -125,7 +122,7 @@ extern "C" {
 
 int ndt_get_tuning(ndt_tuning* out) {
   if (!out) return NDT_ERR_INVALID_ARG;
-  *out = ndt::tuning();
+  *out = ndt::tuning_snapshot();
   return NDT_OK;
 }
 

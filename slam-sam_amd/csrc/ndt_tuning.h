@@ -7,7 +7,10 @@
 
 namespace ndt {
 
-const ndt_tuning& tuning();
+// The one read of the process-wide struct, by value.  A build, an evaluation, an align and a handle creation each take
+// ONE snapshot when they begin and pass it down: everything they size and launch follows that one configuration,
+// whatever ndt_set_tuning() does on another thread meanwhile.
+ndt_tuning tuning_snapshot();
 void tuning_defaults(ndt_tuning* t);
 int tuning_set(const ndt_tuning* t);  // NDT_OK | NDT_ERR_INVALID_ARG
 

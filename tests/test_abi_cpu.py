@@ -594,6 +594,81 @@ def test_derivative_launch_plans(pkg):
         pkg.set_tuning(**before)
 
 
+def test_plans_under_concurrent_set_tuning_are_never_a_mixture(pkg):
+    """ndt_set_tuning may be called from any thread at any time; a launch plan is made from ONE snapshot of ndt_tuning.
+    While a second thread alternates two tunings that differ in block size, summing arrangement and partition tile,
+    every plan the two seams return is exactly the plan of one of the two -- all 16 ints, (tile points, tiles) for the
+    partition -- never threads of one and blocks or summing blocks of the other.  (ctypes.CDLL releases the GIL around
+    every foreign call, so the two threads do overlap inside the library.)"""
+    import threading
+    import time
+    L = pkg.lib()
+    L.ndt_debug_bucket_plan.argtypes = [C.c_size_t, C.POINTER(C.c_longlong)]
+    before = pkg.get_tuning()
+    # A: the defaults of include/ndt_hip.h in the five fields B changes (the library exports no call that returns its
+    # defaults); every other field is the same in both and plays no part in the comparison
+    A = dict(before, deriv_block=0, deriv_dedicated=1, deriv_summer_split=1, deriv_single_level_max=2048, bucket_tile=0)
+    B = dict(A, deriv_block=256, deriv_dedicated=0, deriv_summer_split=0, deriv_single_level_max=64, bucket_tile=1024)
+    cases = [(n, K, flags) for flags, K in ((0, 1), (1, 4)) for n in (131072, 150000, 200000)]   # single-pose, batched
+
+    def launch_plan(n, K, flags):
+        out = (C.c_int * 16)()
+        assert L.ndt_debug_launch_plan(n, K, 256, 1, 1, flags, out) == 0
+        return tuple(out)
+
+    def bucket_plan():
+        out = (C.c_longlong * 4)()
+        assert L.ndt_debug_bucket_plan(100000, out) == 0
+        return (out[1], out[2])
+
+    def struct_of(fields):
+        t = pkg.Tuning()
+        for k, v in fields.items():
+            setattr(t, k, v)
+        return t
+
+    try:
+        pure = []
+        for t in (A, B):
+            pkg.set_tuning(**t)
+            pure.append(({c: launch_plan(*c) for c in cases}, bucket_plan()))
+        (PA, bucket_a), (PB, bucket_b) = pure
+        threads_at, blocks_at = pkg.EVAL_DESC_FIELDS.index("threads"), pkg.EVAL_DESC_FIELDS.index("blocks")
+        for c in cases:   # (or the test could not tell the two apart)
+            assert PA[c][threads_at] != PB[c][threads_at] and PA[c][blocks_at] != PB[c][blocks_at], (c, PA[c], PB[c])
+        assert bucket_a[0] != bucket_b[0] and bucket_a[1] != bucket_b[1], (bucket_a, bucket_b)
+
+        stop, refused = threading.Event(), []
+        ta, tb = struct_of(A), struct_of(B)
+
+        def alternate():
+            while not stop.is_set():
+                for t in (ta, tb):
+                    if L.ndt_set_tuning(C.byref(t)) != 0:
+                        refused.append(1)
+
+        setter = threading.Thread(target=alternate)
+        setter.start()
+        try:
+            calls, seen, t_end = 0, set(), time.monotonic() + 1.0
+            # (at least 10 000 calls and one second; on a host that starves one of the two threads, up to ten more
+            # seconds until both tunings have been seen in force)
+            while calls < 10000 or time.monotonic() < t_end or (len(seen) < 2 and time.monotonic() < t_end + 10.0):
+                c = cases[calls % len(cases)]
+                p, b = launch_plan(*c), bucket_plan()
+                assert p == PA[c] or p == PB[c], (c, dict(zip(pkg.EVAL_DESC_FIELDS, p)), PA[c], PB[c])
+                assert b == bucket_a or b == bucket_b, (b, bucket_a, bucket_b)
+                seen.add(p == PA[c])
+                calls += 1
+        finally:
+            stop.set()
+            setter.join()
+        assert not refused
+        assert seen == {True, False}   # both tunings were in force at some call: the two threads did interleave
+    finally:
+        pkg.set_tuning(**before)
+
+
 def test_summer_switches_keep_the_partition(pkg):
     """include/ndt_hip.h: no ndt_tuning field but deriv_block / deriv_single_level_max changes a result bit.  The summing
     arrangement (deriv_summer, deriv_dedicated, deriv_summer_split) must therefore leave the block shape -- the partition
