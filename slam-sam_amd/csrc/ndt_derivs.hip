@@ -1845,31 +1845,25 @@ DerivLaunchPlan plan_derivatives_launch(const ndt_tuning& tn, size_t n_src, int 
   return pl;
 }
 
-void launch_derivatives(const DerivLaunchPlan& pl, const EvalConsts& ecl, const float* sx, const float* sy, const float* sz,
-                        size_t n_src, const GridGeom& g, const int* cell2leaf, const VoxelRecord* rec, const float* cent4,
-                        const PoseConsts& pose, const PoseConsts* d_poses, int K, double* d_partials, unsigned int* d_counters,
-                        double* d_out, hipStream_t s, unsigned long long* d_flag,
-                        unsigned long long seq, const PoseMailbox* d_mbox, const XchgInfo* d_xinfo,
-                        unsigned long long xround, unsigned int* d_arrive_ctr, unsigned long long* d_arrived_host,
-                        hipEvent_t ev_start, hipEvent_t ev_stop, const BuildGeom* d_geom) {
+void launch_derivatives(const DerivLaunchPlan& pl, const EvalConsts& ecl, const DerivLaunchArgs& a) {
   const int blocks = pl.blocks, threads = pl.threads, mode = pl.mode, nb = pl.nb;
   const size_t dyn_lds = (size_t)pl.dyn_lds;
   // ev_start / ev_stop: events attached to THIS dispatch (hipExtLaunchKernel): they carry the kernel's own begin and
   // end timestamps, what rocprofv3 reports -- events recorded around the launch include ~2.4 us of dispatch
 #define NDT_LAUNCH2(B, M, NBH, MB, GY, FLAG, SEQ)                                                            \
   do {                                                                                                       \
-    if (ev_start != nullptr)                                                                                 \
-      hipExtLaunchKernelGGL((k_derivatives<B, M, NBH, MB>), dim3(blocks, GY), dim3(threads), (std::uint32_t)dyn_lds, s, ev_start, ev_stop, 0u, sx, sy, sz,  \
-                            (int)n_src, g, cell2leaf, rec, reinterpret_cast<const float4*>(cent4), pose, d_poses, ecl, d_partials, d_counters, d_out,         \
-                            FLAG, SEQ, d_mbox, d_xinfo, xround, d_arrive_ctr, d_arrived_host, d_geom);        \
+    if (a.ev_start != nullptr)                                                                               \
+      hipExtLaunchKernelGGL((k_derivatives<B, M, NBH, MB>), dim3(blocks, GY), dim3(threads), (std::uint32_t)dyn_lds, a.stream, a.ev_start, a.ev_stop, 0u,  \
+                            a.sx, a.sy, a.sz, (int)a.n_src, *a.geom, a.cell2leaf, a.rec, reinterpret_cast<const float4*>(a.cent4), *a.pose, a.d_poses, ecl,  \
+                            a.d_partials, a.d_counters, a.d_out, FLAG, SEQ, a.d_mbox, a.d_xinfo, a.xround, a.d_arrive_ctr, a.d_arrived_host, a.d_geom);      \
     else                                                                                                     \
-      hipLaunchKernelGGL((k_derivatives<B, M, NBH, MB>), dim3(blocks, GY), dim3(threads), dyn_lds, s, sx, sy, sz,  \
-                         (int)n_src, g, cell2leaf, rec, reinterpret_cast<const float4*>(cent4), pose, d_poses, ecl, d_partials, d_counters, d_out,         \
-                         FLAG, SEQ, d_mbox, d_xinfo, xround, d_arrive_ctr, d_arrived_host, d_geom);           \
+      hipLaunchKernelGGL((k_derivatives<B, M, NBH, MB>), dim3(blocks, GY), dim3(threads), dyn_lds, a.stream,  \
+                         a.sx, a.sy, a.sz, (int)a.n_src, *a.geom, a.cell2leaf, a.rec, reinterpret_cast<const float4*>(a.cent4), *a.pose, a.d_poses, ecl,  \
+                         a.d_partials, a.d_counters, a.d_out, FLAG, SEQ, a.d_mbox, a.d_xinfo, a.xround, a.d_arrive_ctr, a.d_arrived_host, a.d_geom);      \
   } while (0)
 #define NDT_LAUNCH(B, M, NBH, GY, FLAG, SEQ)                                  \
   do {                                                                         \
-    if (!B && d_mbox != nullptr) NDT_LAUNCH2(false, M, NBH, true, GY, FLAG, SEQ);  \
+    if (!B && a.d_mbox != nullptr) NDT_LAUNCH2(false, M, NBH, true, GY, FLAG, SEQ);  \
     else NDT_LAUNCH2(B, M, NBH, false, GY, FLAG, SEQ);                         \
   } while (0)
 #define NDT_LAUNCH_MODE(B, NBH, GY, FLAG, SEQ)                 \
@@ -1889,8 +1883,8 @@ void launch_derivatives(const DerivLaunchPlan& pl, const EvalConsts& ecl, const 
     else if (nb == 5) NDT_LAUNCH_MODE(B, 5, GY, FLAG, SEQ);     \
     else NDT_LAUNCH_MODE(B, 6, GY, FLAG, SEQ);                  \
   } while (0)
-  if (d_poses) NDT_LAUNCH_NB(true, K, d_flag, seq);
-  else NDT_LAUNCH_NB(false, 1, d_flag, seq);
+  if (a.d_poses) NDT_LAUNCH_NB(true, a.K, a.d_host_slots, a.seq);
+  else NDT_LAUNCH_NB(false, 1, a.d_host_slots, a.seq);
 #undef NDT_LAUNCH_NB
 #undef NDT_LAUNCH_MODE
 #undef NDT_LAUNCH

@@ -391,9 +391,14 @@ struct ndt_handle {
   bool mbox_tagged = true;            // the pose is published as tagged 8-byte granules
   bool mbox_preload = false;          // the waiting kernel fetches its points before the pose arrives (measured: no gain)
   bool prelaunch_armed = false;       // inside ndt_align
-  unsigned long long pre_seq = 0;     // sequence number of the kernel that is waiting, 0 = none
-  unsigned long long pre_round = 0;   // ... and the cross-rank round it will exchange under (NDT_REDUCE_P2P)
-  int pre_on2 = 0;                    // ... and the stream it is on (0: stream, 1: stream2)
+  struct Waiting {                    // the kernel enqueued for the NEXT evaluation: set together, claimed together (evaluate())
+    unsigned long long seq = 0;       // sequence number of the kernel that is waiting, 0 = none
+    unsigned long long round = 0;     // ... and the cross-rank round it will exchange under (NDT_REDUCE_P2P)
+    int on2 = 0;                      // ... and the stream it is on (0: stream, 1: stream2)
+    int buf = 0;                      // ... and the result buffer (0 / 1) it will write
+    bool need_h = false;              // ... and whether it computes the Hessian (an evaluation that differs sends it away)
+    DerivLaunchPlan plan{};           // the shape of the waiting kernel's launch (evaluation log)
+  } pre;
   int cur_on2 = 0;                    // stream of the evaluation in flight
   bool two_streams = true;            // NDT_PRELAUNCH_STREAMS != 1
   // NDT_PRELAUNCH_AUTO decides between the two-stream and the one-stream placement of the waiting kernel BY MEASUREMENT:
@@ -409,13 +414,11 @@ struct ndt_handle {
   int64_t n_auto_aligns = 0, n_auto_switches = 0;
   DevBuf<unsigned int> arrive_ctr;    // [2] blocks of a pre-launched launch that have started (per result buffer)
   PinBuf<unsigned long long> arrived; // [2] sequence number of the launch whose blocks are all resident
-  int pre_buf = 0;                    // ... and the result buffer (0 / 1) it will write
   int prelaunch_strikes = 0;          // consecutive aligns in which a waiting kernel gave up
   bool prelaunch_suspended = false;   // three such aligns in a row (a chronically starved host): no more pre-launching
                                       // on this handle until ndt_set_params is called -- the caller's ndt_params
                                       // are never rewritten
   int flag_toggle = 0;                // result buffer of the latest single-pose launch
-  bool pre_need_h = false;
   int64_t n_prelaunch_used = 0, n_prelaunch_quit = 0, n_prelaunch_timeouts = 0;
   int64_t n_lost_row_retries = 0;      // evaluations repeated through the ticketed final sum after a row was lost
   // The first evaluation of an align that follows a DEFERRED build is enqueued behind that build, before its verdict is
@@ -427,7 +430,6 @@ struct ndt_handle {
   int64_t n_spec_used = 0, n_spec_discarded = 0;
   int64_t n_p2p_host_finishes = 0;     // peer-write evaluations whose exchange the host finished (a peer was late)
   int64_t n_prelaunch_overlapped = 0; // pre-launches that went to the other stream (resident before their predecessor ended)
-  DerivLaunchPlan pre_plan{};         // the shape of the waiting kernel's launch (evaluation log)
 
   // evaluation log (ndt_debug_eval_log): off (cap 0) by default; entries beyond cap are counted, not kept
   int eval_log_cap = 0;

@@ -31,8 +31,8 @@ int records_for_eval(ndt_handle* h, EvalConsts* ec, const VoxelRecord** rec) {
       (h->prm.search_method != NDT_DIRECT7 && h->prm.search_method != NDT_DIRECT1))
     return NDT_OK;  // (an empty table: slot 0 of the f64 one is what absent neighbours read)
   if (!h->prec_valid) {
-    int rc = pack_records(h, true);  // (the format was selected after the build, or the table came from another path)
-    if (rc) return rc;
+    // (the format was selected after the build, or the table came from another path)
+    if (int rc = pack_records(h, true)) return rc;
   }
   ec->packed = 1;
   *rec = reinterpret_cast<const VoxelRecord*>(h->prec.p);
@@ -89,8 +89,7 @@ int ensure_counters(ndt_handle* h, size_t k) {
 }
 
 int ready_for_eval(ndt_handle* h) {
-  int rc = settle(h);
-  if (rc) return rc;
+  if (int rc = settle(h)) return rc;
   if (!h->have_grid || h->n_valid <= 0) return fail(h, NDT_ERR_NO_TARGET, "no target voxel grid (setInputTarget first)");
   if (h->n_src == 0 && h->red.mode() == NDT_REDUCE_NONE) return fail(h, NDT_ERR_NO_SOURCE, "no source cloud (setInputSource first)");
   return NDT_OK;
@@ -109,12 +108,7 @@ int ensure_flag_slots(ndt_handle* h, size_t K) {
 // (NDT_SOURCE_ORDER_*).  Done once per (source, target): the copy stays a valid permutation of the
 // source whatever the later poses are.
 int maybe_sort_source(ndt_handle* h, const float T[16]) {
-  if (h->src_sorted || h->n_src == 0 || !h->have_grid) return NDT_OK;
-  const int mode = h->prm.source_order;
-  if (mode == NDT_SOURCE_ORDER_KEEP) return NDT_OK;
-  if (mode == NDT_SOURCE_ORDER_AUTO &&
-      ((size_t)h->n_valid * sizeof(VoxelRecord) <= (size_t)6 << 20 || h->n_src < 32768))
-    return NDT_OK;
+  if (!h->have_grid || !source_sort_wanted(h, h->n_valid)) return NDT_OK;
   const size_t n = h->n_src;
   HIP_TRY(h, h->ox.ensure(n));
   HIP_TRY(h, h->oy.ensure(n));
@@ -262,11 +256,11 @@ void publish_pose(ndt_handle* h, unsigned long long seq, const PoseConsts& pc) {
 
 // tells a waiting pre-launched kernel to leave (stream order does the rest)
 void quit_prelaunched(ndt_handle* h) {
-  if (h->pre_seq == 0) return;
-  if (h->mbox_tagged) mbox_store_granule(h->mbox, MBOX_GRANULES - 1, mbox_tag32(h->pre_seq), MBOX_CTRL_QUIT);
-  else *reinterpret_cast<volatile unsigned long long*>(&h->mbox->seq) = h->pre_seq | MBOX_QUIT;
+  if (h->pre.seq == 0) return;
+  if (h->mbox_tagged) mbox_store_granule(h->mbox, MBOX_GRANULES - 1, mbox_tag32(h->pre.seq), MBOX_CTRL_QUIT);
+  else *reinterpret_cast<volatile unsigned long long*>(&h->mbox->seq) = h->pre.seq | MBOX_QUIT;
   _mm_sfence();
-  h->pre_seq = 0;
+  h->pre.seq = 0;
   h->n_prelaunch_quit++;
 }
 
@@ -290,6 +284,108 @@ void log_evals(ndt_handle* h, const DerivLaunchPlan& plan, const double* poses6,
   ++h->eval_log_launches;
 }
 
+// What every k_derivatives launch of a handle shares; a call site adds what is particular to it, by name.  (Read when
+// the partial rows have their size for this launch: ensure_partials may move them.)
+static DerivLaunchArgs shared_launch_args(const ndt_handle* h, const VoxelRecord* records) {
+  DerivLaunchArgs a;
+  a.sx = h->src_sorted ? h->ox.p : h->vx;
+  a.sy = h->src_sorted ? h->oy.p : h->vy;
+  a.sz = h->src_sorted ? h->oz.p : h->vz;
+  a.n_src = h->n_src;
+  a.geom = &h->geom;
+  a.cell2leaf = h->cell2leaf.p;
+  a.rec = records;   // (records_for_eval's choice)
+  a.cent4 = h->cent.p;
+  a.d_partials = h->partials.p;
+  a.d_counters = h->counters.p;
+  a.stream = h->stream;
+  return a;
+}
+
+// kernel-timing bookkeeping of the launch that ev0 / ev1 belong to
+static int note_kernel_time(ndt_handle* h) {
+  if (!h->timing) return NDT_OK;
+  float ms = 0;
+  HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  h->tm.ms_last_eval_kernel = ms;
+  h->tm.ms_eval_kernel_total += ms;
+  h->tm.n_timed_evals++;
+  return NDT_OK;
+}
+
+// the values of the pinned result slots {seq, value} of K poses, from slot buffer `first` on, as plain words
+static void copy_slot_values(const ndt_handle* h, int first, int K, double* words) {
+  const unsigned long long* f = h->flag.h + (size_t)first * 2 * EV_WORDS;
+  for (size_t i = 0; i < (size_t)K * EV_WORDS; ++i) std::memcpy(&words[i], &f[2 * i + 1], sizeof(double));
+}
+
+// The next evaluation's kernel goes onto the stream now, behind the one in flight (seq, buf, xround; via_mailbox: it was
+// itself pre-launched); it will start when that one has finished and wait for its pose (or for the order to leave).
+// `a`: what the launches of the evaluation in flight share -- its pose is ignored by a kernel that waits for its own.
+static int prelaunch_next(ndt_handle* h, const DerivLaunchPlan& pl, const EvalConsts& ecl, DerivLaunchArgs a, bool need_h,
+                          unsigned long long seq, int buf, unsigned long long xround, bool via_mailbox) {
+  h->pre.seq = g_launch_seq.fetch_add(1, std::memory_order_relaxed);
+  h->pre.need_h = need_h;
+  h->pre.buf = (h->flag_toggle ^= 1);
+  h->pre.round = xround + 1;
+  // Which stream: behind the evaluation in flight (same stream: starts when that launch has ENDED), or on the
+  // other stream, where its blocks take compute units as the blocks of the launch in flight leave -- resident
+  // and polling by the time the host has the next pose (the end-of-launch barrier, the dispatch and the cold
+  // start of a kernel are 2-3 us of every evaluation otherwise).  Only when the launch in flight needs no
+  // more compute units itself (its last-arriving block has said so): the two must never wait for each other.
+  // An ordinary launch (first evaluation of an align) never qualifies.
+  if (!h->arrive_ctr.p) {
+    HIP_TRY(h, h->arrive_ctr.ensure(2));
+    HIP_TRY(h, hipMemsetAsync(h->arrive_ctr.p, 0, h->arrive_ctr.cap * sizeof(unsigned int), h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, h->arrived.ensure(2));
+    h->arrived.h[0] = h->arrived.h[1] = 0;
+  }
+  // (The launch in flight has just been given its pose; if it was queued behind its predecessor it is only now
+  // starting.  The next kernel is not needed for another ~10 us, so the host can afford to watch the arrival
+  // word for a few microseconds before it decides.)
+  bool in_flight_resident = false;
+  if (h->streams_this_align && via_mailbox) {
+    const auto t_arr = std::chrono::steady_clock::now();
+    for (unsigned spins = 0;; ++spins) {
+      if (__atomic_load_n(&h->arrived.h[buf], __ATOMIC_ACQUIRE) == seq) { in_flight_resident = true; break; }
+      if ((spins & 63) == 63 && std::chrono::steady_clock::now() - t_arr > std::chrono::microseconds(6)) break;
+      _mm_pause();
+    }
+  }
+  h->pre.on2 = in_flight_resident ? (h->cur_on2 ^ 1) : h->cur_on2;
+  if (in_flight_resident) h->n_prelaunch_overlapped++;
+  h->pre.plan = pl;   // (planned from this evaluation's snapshot; the kernel keeps it whatever the tuning is when its pose comes)
+  h->pre.plan.mbox = 1;
+  if (h->pre.on2) a.stream = h->stream2;
+  a.d_host_slots = h->flag.d + (size_t)h->pre.buf * 2 * EV_WORDS;
+  a.seq = h->pre.seq;
+  a.d_mbox = h->mbox;
+  a.xround = h->pre.round;
+  a.d_arrive_ctr = h->arrive_ctr.p + h->pre.buf;
+  a.d_arrived_host = h->arrived.d + h->pre.buf;
+  launch_derivatives(h->pre.plan, ecl, a);
+  HIP_TRY(h, hipGetLastError());
+  return NDT_OK;
+}
+
+// The common part of evaluate()'s repeats (a pre-launched kernel that gave up, a lost row): the waiting kernel is told to
+// leave, the cross-rank round is given back -- nothing was exchanged under this tag (a sum that missed rows is never
+// published, sum_rows): the re-evaluation uses it --, ordinary launches for the rest of this align (the next align tries
+// again), the ticket words of the abandoned launch re-zeroed before the next launch.  Every block of a pre-launched
+// kernel times out on its own clock: block 0 wrote the notice, blocks whose deadline comes microseconds later may still
+// see the late pose and compute -- rows (and tickets) tagged with the abandoned sequence number.  With two streams
+// nothing orders the re-launch behind them: both are drained before the rows are reused.
+static int abandon_evaluation(ndt_handle* h, bool p2p, unsigned long long xround) {
+  quit_prelaunched(h);
+  if (p2p) h->red.p2p_set_round(xround - 1);
+  h->prelaunch_armed = false;
+  h->counters_zeroed = 0;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream2));
+  return NDT_OK;
+}
+
 // one global evaluation at (p, T): local kernel + cross-rank sum
 int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, Eval* out, bool score_only,
              bool safe_retry) {
@@ -298,15 +394,12 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
   bool speculate = false;
   if (h->spec_first) {   // ndt_align left the pending build's verdict to this call
     h->spec_first = false;
-    speculate = first_eval_behind_build(tn, h) && !score_only && !safe_retry && h->pre_seq == 0;
+    speculate = first_eval_behind_build(tn, h) && !score_only && !safe_retry && h->pre.seq == 0;
     if (!speculate) {
-      int rc = ready_for_eval(h);
-      if (rc) { h->spec_build_failed = true; return rc; }
-      rc = maybe_sort_source(h, T);
-      if (rc) return rc;
-    } else {
-      int rc = settle_source(h);   // the engine's streams ordered behind the source's transfer
-      if (rc) return rc;
+      if (int rc = ready_for_eval(h)) { h->spec_build_failed = true; return rc; }
+      if (int rc = maybe_sort_source(h, T)) return rc;
+    } else if (int rc = settle_source(h)) {   // the engine's streams ordered behind the source's transfer
+      return rc;
     }
   }
   PoseConsts pc;
@@ -322,26 +415,13 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
 #endif
   const bool p2p = h->red.mode() == NDT_REDUCE_P2P;
   const VoxelRecord* records = nullptr;
-  {
-    int rc = records_for_eval(h, &ec, &records);
-    if (rc) return rc;
-  }
+  if (int rc = records_for_eval(h, &ec, &records)) return rc;
   HIP_TRY(h, h->result.ensure(EV_WORDS));
-  {
-    int rc = ensure_flag_slots(h, 2);  // two result buffers, used in turn (below)
-    if (rc) return rc;
-  }
+  if (int rc = ensure_flag_slots(h, 2)) return rc;  // two result buffers, used in turn (below)
   const bool dev_out = h->red.wants_device_buffer();
   if (dev_out) HIP_TRY(h, h->dres.ensure(EV_WORDS));
-  {
-    int rc = ensure_counters(h, (size_t)derivs_counters_per_pose());
-    if (rc) return rc;
-  }
-  double* d_out = dev_out ? h->dres.p : h->result.d;
+  if (int rc = ensure_counters(h, (size_t)derivs_counters_per_pose())) return rc;
   const bool spin = !dev_out && !h->timing && h->prm.wait_mode == NDT_WAIT_SPIN;
-  const float* px = h->src_sorted ? h->ox.p : h->vx;
-  const float* py = h->src_sorted ? h->oy.p : h->vy;
-  const float* pz = h->src_sorted ? h->oz.p : h->vz;
   const bool prelaunch = spin && !score_only && !safe_retry && h->prelaunch_armed && !h->prelaunch_suspended &&
                          h->prm.prelaunch != NDT_PRELAUNCH_OFF && ensure_mailbox(h);
   unsigned long long seq = 0;
@@ -351,7 +431,6 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
   // the tag "number of this global evaluation" (identical on every rank: all run the same host loop on
   // the same sums).  A pre-launched kernel got its tag when it was enqueued; one that is told to leave
   // has consumed none.
-  const XchgInfo* xinfo = p2p ? h->red.p2p_info() : nullptr;
   unsigned long long xround = p2p ? h->red.p2p_round() + 1 : 0;
   // Consecutive single-pose launches write their results to ALTERNATING host buffers: a pre-launched
   // kernel runs ahead of the host, and one that gives up waiting for its pose (this thread frozen for
@@ -360,14 +439,14 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
   // result and the host waited for tags that were gone ("finished without publishing", found by the
   // soak under host contention, tests/gpu_mbox_stress.py).
   int buf = 0;
-  if (h->pre_seq != 0) {
-    if (prelaunch && h->pre_need_h == need_h) {  // the kernel for this evaluation is already waiting on the device
-      seq = h->pre_seq;
-      plan = h->pre_plan;
-      buf = h->pre_buf;
-      xround = h->pre_round;
-      h->cur_on2 = h->pre_on2;
-      h->pre_seq = 0;
+  if (h->pre.seq != 0) {
+    if (prelaunch && h->pre.need_h == need_h) {  // the kernel for this evaluation is already waiting on the device
+      seq = h->pre.seq;
+      plan = h->pre.plan;
+      buf = h->pre.buf;
+      xround = h->pre.round;
+      h->cur_on2 = h->pre.on2;
+      h->pre.seq = 0;
 #ifdef NDT_TEST_SEAMS
       {  // test seam (libndt_hip_seams.so only): hold the pose back so that the waiting kernel gives up
         static const int delay_ms = [] { const char* e = getenv("NDT_DEBUG_PUBLISH_DELAY_MS"); return e ? atoi(e) : 0; }();
@@ -394,9 +473,13 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
   EvalConsts ecl;   // the consts as planned: what the kernel receives
   const DerivLaunchPlan pl = plan_derivatives_launch(tn, h->n_src, 1, false, p2p, ec, &ecl);
   const size_t rows = derivs_partials_words(pl, 1);
+  if (!via_mailbox)   // (no kernel of this handle waits for a pose now)
+    if (int rc = ensure_partials(h, rows)) return rc;
+  DerivLaunchArgs la = shared_launch_args(h, records);   // ... and what both launches of this evaluation share
+  la.pose = &pc;
+  la.d_out = dev_out ? h->dres.p : h->result.d;
+  if (p2p) la.d_xinfo = h->red.p2p_info();
   if (!via_mailbox) {
-    int rc = ensure_partials(h, rows);   // (no kernel of this handle waits for a pose now)
-    if (rc) return rc;
     seq = g_launch_seq.fetch_add(1, std::memory_order_relaxed);
     buf = (h->flag_toggle ^= 1);
     h->cur_on2 = 0;
@@ -404,10 +487,13 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
     if (bracket) HIP_TRY(h, hipEventRecord(h->ev0, s));
     plan = pl;
     plan.spec = speculate ? 1 : 0;
-    launch_derivatives(plan, ecl, px, py, pz, h->n_src, h->geom, h->cell2leaf.p, records, h->cent.p, pc, nullptr, 1, h->partials.p,
-                       h->counters.p, d_out, s, spin ? h->flag.d + (size_t)buf * 2 * EV_WORDS : nullptr, seq, nullptr,
-                       xinfo, xround, nullptr, nullptr, h->timing && !bracket ? h->ev0 : nullptr,
-                       h->timing && !bracket ? h->ev1 : nullptr, speculate ? h->gd.p : nullptr);
+    DerivLaunchArgs a = la;
+    if (spin) a.d_host_slots = h->flag.d + (size_t)buf * 2 * EV_WORDS;
+    a.seq = seq;
+    a.xround = xround;
+    if (h->timing && !bracket) { a.ev_start = h->ev0; a.ev_stop = h->ev1; }
+    if (speculate) a.d_geom = h->gd.p;
+    launch_derivatives(plan, ecl, a);
     HIP_TRY(h, hipGetLastError());
     if (bracket) HIP_TRY(h, hipEventRecord(h->ev1, s));
   }
@@ -422,10 +508,8 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
       HIP_TRY(h, hipStreamSynchronize(s));
       h->counters_zeroed = 0;
       if (rs) { h->spec_build_failed = true; return rs; }
-      int rc = ready_for_eval(h);
-      if (rc) { h->spec_build_failed = true; return rc; }
-      rc = maybe_sort_source(h, T);
-      if (rc) return rc;
+      if (int rc = ready_for_eval(h)) { h->spec_build_failed = true; return rc; }
+      if (int rc = maybe_sort_source(h, T)) return rc;
       return evaluate(h, p, T, need_h, out, score_only);
     }
     ++h->n_spec_used;
@@ -433,93 +517,35 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
   if (p2p) h->red.p2p_set_round(xround);  // this evaluation's tag is spent (a fallback below gives it back)
   // (rows > cap: the tuning changed since the kernel in flight was enqueued and the new shape writes more rows than
   // there are -- they grow at the next evaluation's ordinary launch, when nothing reads them)
-  if (prelaunch && rows <= h->partials.cap) {
-    // the next evaluation's kernel goes onto the stream now, behind the one in flight; it will
-    // start when that one has finished and wait for its pose (or for the order to leave)
-    h->pre_seq = g_launch_seq.fetch_add(1, std::memory_order_relaxed);
-    h->pre_need_h = need_h;
-    h->pre_buf = (h->flag_toggle ^= 1);
-    h->pre_round = xround + 1;
-    // Which stream: behind the evaluation in flight (same stream: starts when that launch has ENDED), or on the
-    // other stream, where its blocks take compute units as the blocks of the launch in flight leave -- resident
-    // and polling by the time the host has the next pose (the end-of-launch barrier, the dispatch and the cold
-    // start of a kernel are 2-3 us of every evaluation otherwise).  Only when the launch in flight needs no
-    // more compute units itself (its last-arriving block has said so): the two must never wait for each other.
-    // An ordinary launch (first evaluation of an align) never qualifies.
-    if (!h->arrive_ctr.p) {
-      HIP_TRY(h, h->arrive_ctr.ensure(2));
-      HIP_TRY(h, hipMemsetAsync(h->arrive_ctr.p, 0, h->arrive_ctr.cap * sizeof(unsigned int), s));
-      HIP_TRY(h, hipStreamSynchronize(s));
-      HIP_TRY(h, h->arrived.ensure(2));
-      h->arrived.h[0] = h->arrived.h[1] = 0;
-    }
-    // (The launch in flight has just been given its pose; if it was queued behind its predecessor it is only now
-    // starting.  The next kernel is not needed for another ~10 us, so the host can afford to watch the arrival
-    // word for a few microseconds before it decides.)
-    bool in_flight_resident = false;
-    if (h->streams_this_align && via_mailbox) {
-      const auto t_arr = std::chrono::steady_clock::now();
-      for (unsigned spins = 0;; ++spins) {
-        if (__atomic_load_n(&h->arrived.h[buf], __ATOMIC_ACQUIRE) == seq) { in_flight_resident = true; break; }
-        if ((spins & 63) == 63 && std::chrono::steady_clock::now() - t_arr > std::chrono::microseconds(6)) break;
-        _mm_pause();
-      }
-    }
-    h->pre_on2 = in_flight_resident ? (h->cur_on2 ^ 1) : h->cur_on2;
-    if (in_flight_resident) h->n_prelaunch_overlapped++;
-    h->pre_plan = pl;   // (planned from this evaluation's snapshot; the kernel keeps it whatever the tuning is when its pose comes)
-    h->pre_plan.mbox = 1;
-    launch_derivatives(h->pre_plan, ecl, px, py, pz, h->n_src, h->geom, h->cell2leaf.p, records, h->cent.p, pc, nullptr, 1,
-                       h->partials.p, h->counters.p, d_out, h->pre_on2 ? h->stream2 : s,
-                       h->flag.d + (size_t)h->pre_buf * 2 * EV_WORDS, h->pre_seq, h->mbox, xinfo, h->pre_round,
-                       h->arrive_ctr.p + h->pre_buf, h->arrived.d + h->pre_buf);
-    HIP_TRY(h, hipGetLastError());
-  }
+  if (prelaunch && rows <= h->partials.cap)
+    if (int rc = prelaunch_next(h, pl, ecl, la, need_h, seq, buf, xround, via_mailbox)) return rc;
   if (dev_out) {
-    int rc = h->red.allreduce_device(h->dres.p, EV_WORDS, s, &h->err);
-    if (rc) return rc;
+    if (int rc = h->red.allreduce_device(h->dres.p, EV_WORDS, s, &h->err)) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->result.h, h->dres.p, EV_WORDS * sizeof(double), hipMemcpyDeviceToHost, s));
     if (h->timing && h->ev2) HIP_TRY(h, hipEventRecord(h->ev2, s));
   }
-  if (spin) {
-    int rc = wait_slots(h, seq, 1, buf);
-    if (rc) return rc;
-  } else {
-    HIP_TRY(h, hipStreamSynchronize(s));
-  }
+  if (!spin) HIP_TRY(h, hipStreamSynchronize(s));
+  else if (int rc = wait_slots(h, seq, 1, buf)) return rc;
   h->tm.n_eval_launches++;
-  if (h->timing) {
-    float ms = 0;
-    HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->tm.ms_last_eval_kernel = ms;
-    h->tm.ms_eval_kernel_total += ms;
-    h->tm.n_timed_evals++;
-    if (dev_out && h->ev2) {   // RCCL: the all-reduce and the read-back behind the kernel, device time
-      float mr = 0;
-      if (hipEventElapsedTime(&mr, h->ev1, h->ev2) == hipSuccess) {
-        h->tm.ms_last_reduce_kernel = mr;
-        h->tm.ms_reduce_kernel_total += mr;
-      } else {
-        (void)hipGetLastError();
-      }
+  if (int rc = note_kernel_time(h)) return rc;
+  if (h->timing && dev_out && h->ev2) {   // RCCL: the all-reduce and the read-back behind the kernel, device time
+    float mr = 0;
+    if (hipEventElapsedTime(&mr, h->ev1, h->ev2) == hipSuccess) {
+      h->tm.ms_last_reduce_kernel = mr;
+      h->tm.ms_reduce_kernel_total += mr;
+    } else {
+      (void)hipGetLastError();
     }
   }
   double words[EV_WORDS];
-  if (spin) {
-    for (int v = 0; v < EV_WORDS; ++v) std::memcpy(&words[v], &h->flag.h[((size_t)buf * EV_WORDS + v) * 2 + 1], sizeof(double));
-  } else {
-    std::memcpy(words, h->result.h, sizeof(words));
-  }
-  if (p2p) {
-    if (words[EV_FAIL] == 3.0) {
-      h->n_p2p_host_finishes++;
-      // this rank's sum is published, a peer was more than 20 ms late (a starved host over there):
-      // the kernel is gone, the host finishes the same exchange -- same rows, same rank order
-      int rc = h->red.p2p_finish_on_host(xround, words, EV_WORDS, &h->err);
-      if (rc) return rc;
-    }
-    // (otherwise the words ARE the global sums already)
-  }
+  if (spin) copy_slot_values(h, buf, 1, words);
+  else std::memcpy(words, h->result.h, sizeof(words));
+  if (p2p && words[EV_FAIL] == 3.0) {
+    h->n_p2p_host_finishes++;
+    // this rank's sum is published, a peer was more than 20 ms late (a starved host over there):
+    // the kernel is gone, the host finishes the same exchange -- same rows, same rank order
+    if (int rc = h->red.p2p_finish_on_host(xround, words, EV_WORDS, &h->err)) return rc;
+  }  // (otherwise the words of a peer-write job ARE the global sums already)
   // word 31 is zero by construction; the in-kernel final sum raises it when it gave up waiting
   // for a partial row (a lost hand-off must not look like a converged result), and the kernel
   // never produces a non-finite score from finite records.  With several summing blocks (SUMMER_SPLIT) only one of them
@@ -529,69 +555,42 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
   // makes the kernels pre-launched on ALL its peers give up at once, and three ranks' 2 + 2 + 2 read as no code at all
   // (the align ended with "a partial row never arrived" at 7 ranks; at 2 ranks the one peer's 2 came through as 2).
   // Under RCCL the sum has been made on the device by now, and the repeats stay collective as before.
-  if (words[EV_FAIL] == 0.0)
-    for (int v = 0; v < EV_WORDS; ++v)
-      if (std::isnan(words[v])) { words[EV_FAIL] = 1.0; break; }
-  if (words[EV_FAIL] == 2.0 && via_mailbox) {
+  mark_lost_rows(words);
+  switch (recovery_for(words[EV_FAIL], via_mailbox, safe_retry, dev_out)) {
+    case Recovery::None: break;
     // the pre-launched kernel gave up waiting for its pose (this thread was away for > 20 ms):
     // nothing was evaluated.  Evaluate the ordinary way, and stop pre-launching for this align.
-    h->n_prelaunch_timeouts++;
-    quit_prelaunched(h);
-    if (p2p) h->red.p2p_set_round(xround - 1);  // nothing was exchanged under this tag: the re-evaluation uses it
-    h->prelaunch_armed = false;  // ordinary launches for the rest of this align; the next align tries again
-    // Every block times out on its own clock: block 0 wrote the notice, blocks whose deadline comes microseconds later
-    // may still see the late pose and compute -- rows (and tickets) tagged with the abandoned sequence number.  With
-    // two streams nothing orders the re-launch behind them: drain both before the rows are reused.
-    h->counters_zeroed = 0;
-    HIP_TRY(h, hipStreamSynchronize(s));
-    HIP_TRY(h, hipStreamSynchronize(h->stream2));
-    if (++h->prelaunch_strikes >= 3) h->prelaunch_suspended = true;  // three aligns in a row: a chronically starved host
-    return evaluate(h, p, T, need_h, out, score_only);
-  }
-  if (words[EV_FAIL] == 1.0 && via_mailbox) {
+    case Recovery::RelaunchPoseTimeout:
     // Every block of a pre-launched kernel times out on its OWN clock: when the pose lands near the
     // deadline (or the grid is larger than the machine, so that late blocks start after the first
     // wave's 20 ms) some blocks compute while others have left, and the final sum then misses rows.
     // Nothing usable was evaluated -- same remedy as a time-out: an ordinary launch of the same pose.
-    h->n_prelaunch_timeouts++;
-    quit_prelaunched(h);
-    if (p2p) h->red.p2p_set_round(xround - 1);  // a sum that missed rows is never published (sum_rows)
-    h->prelaunch_armed = false;
-    h->counters_zeroed = 0;  // ticket mode: the partial tickets of the abandoned launch are not zero
-    HIP_TRY(h, hipStreamSynchronize(s));  // the abandoned grid has drained before its rows are reused
-    HIP_TRY(h, hipStreamSynchronize(h->stream2));
-    if (++h->prelaunch_strikes >= 3) h->prelaunch_suspended = true;
-    return evaluate(h, p, T, need_h, out, score_only);
-  }
-  if (words[EV_FAIL] == 1.0 && !via_mailbox && !safe_retry && !dev_out) {
+    case Recovery::RelaunchMissingRows:
+      h->n_prelaunch_timeouts++;
+      if (int rc = abandon_evaluation(h, p2p, xround)) return rc;
+      if (++h->prelaunch_strikes >= 3) h->prelaunch_suspended = true;  // three aligns in a row: a chronically starved host
+      return evaluate(h, p, T, need_h, out, score_only);
     // An ordinary launch whose summing block gave up waiting for a row (its blocks were not all resident within
     // SUM_TIMEOUT_TICKS: a device shared with other processes).  Nothing usable was evaluated and nothing was
     // exchanged: once more, stream-synchronised, with the final sum made by the block that draws the last ticket --
     // a launch in which no block waits for another.  Only if THAT fails is the evaluation an error.
-    h->n_lost_row_retries++;
-    quit_prelaunched(h);
-    if (p2p) h->red.p2p_set_round(xround - 1);
-    h->prelaunch_armed = false;
-    h->counters_zeroed = 0;
-    HIP_TRY(h, hipStreamSynchronize(s));
-    HIP_TRY(h, hipStreamSynchronize(h->stream2));
-    return evaluate(h, p, T, need_h, out, score_only, /*safe_retry=*/true);
+    case Recovery::TicketedRetry:
+      h->n_lost_row_retries++;
+      if (int rc = abandon_evaluation(h, p2p, xround)) return rc;
+      return evaluate(h, p, T, need_h, out, score_only, /*safe_retry=*/true);
   }
   if (!p2p && !dev_out) {
     // what is left of a failure here (a repeat that failed again) goes through the sum: every rank fails together
     // (kernel timing on: the cross-rank sum's own wall time, from the local sum in hand to the global one -- what the
     // --gpus N bench line reports per transport)
     const auto t_red = std::chrono::steady_clock::now();
-    int rc = h->red.allreduce_host(words, EV_WORDS, &h->err);
-    if (rc) return rc;
+    if (int rc = h->red.allreduce_host(words, EV_WORDS, &h->err)) return rc;
     if (h->timing && h->red.mode() != NDT_REDUCE_NONE) {
       const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_red).count();
       h->tm.ms_last_reduce_kernel = ms;
       h->tm.ms_reduce_kernel_total += ms;
     }
-    if (h->red.mode() != NDT_REDUCE_NONE && words[EV_FAIL] == 0.0)   // (a peer's failed repeat)
-      for (int v = 0; v < EV_WORDS; ++v)
-        if (std::isnan(words[v])) { words[EV_FAIL] = 1.0; break; }
+    if (h->red.mode() != NDT_REDUCE_NONE) mark_lost_rows(words);   // (a peer's failed repeat)
   }
   if (words[EV_FAIL] != 0.0 || !std::isfinite(words[EV_SCORE])) {
     h->counters_zeroed = 0;  // the ticket words may be stale: re-zero them before the next launch
@@ -711,15 +710,12 @@ int ndt_get_iteration_history(const ndt_handle* h, float* transforms16, double* 
 int ndt_score_transform(ndt_handle* h, const float T[16], ndt_score* out) {
   if (!h || !T || !out) return NDT_ERR_INVALID_ARG;
   std::memset(out, 0, sizeof(*out));
-  int rc = bind_device(h);
-  if (rc) return rc;
-  rc = ready_for_eval(h);
-  if (rc) return rc;
+  if (int rc = bind_device(h)) return rc;
+  if (int rc = ready_for_eval(h)) return rc;
   double p[6];
   matrix_to_pose(T, p);  // only feeds the (unused) angle tables
   Eval e;
-  rc = evaluate(h, p, T, false, &e, /*score_only=*/true);
-  if (rc) return rc;
+  if (int rc = evaluate(h, p, T, false, &e, /*score_only=*/true)) return rc;
   const int64_t n_total = h->n_src_global >= 0 ? h->n_src_global : (int64_t)h->n_src;
   out->score = e.score;
   out->transform_probability = n_total > 0 ? e.score / (double)n_total : 0.0;
@@ -742,15 +738,12 @@ static int eval_batch(ndt_handle* h, const double* poses6, const float* transfor
                       bool fixed_order = false, bool batched_shape = false) {
   if (!h || !poses6 || !out || K <= 0) return NDT_ERR_INVALID_ARG;
   const ndt_tuning tn = tuning_snapshot();
-  int rc = bind_device(h);
-  if (rc) return rc;
-  rc = ready_for_eval(h);
-  if (rc) return rc;
+  if (int rc = bind_device(h)) return rc;
+  if (int rc = ready_for_eval(h)) return rc;
   if (!fixed_order) {  // source ordering, by the first pose of the batch (the particles of an SVN iteration are close)
     float T0[16];
     if (!transforms) pose_to_matrix(poses6, T0);
-    rc = maybe_sort_source(h, transforms ? transforms : T0);
-    if (rc) return rc;
+    if (int rc = maybe_sort_source(h, transforms ? transforms : T0)) return rc;
   }
   hipStream_t s = h->stream;
   HIP_TRY(h, h->hposes.ensure((size_t)K));
@@ -788,60 +781,47 @@ static int eval_batch(ndt_handle* h, const double* poses6, const float* transfor
   EvalConsts ec = make_eval_consts(h, compute_hessian != 0);
   ec.score_only = score_only ? 1 : 0;
   const VoxelRecord* records = nullptr;
-  rc = records_for_eval(h, &ec, &records);
-  if (rc) return rc;
+  if (int rc = records_for_eval(h, &ec, &records)) return rc;
   EvalConsts ecl;   // the consts as planned: what the kernel receives
   const DerivLaunchPlan plan = plan_derivatives_launch(tn, h->n_src, K, true, false, ec, &ecl, batched_shape);
-  rc = ensure_partials(h, derivs_partials_words(plan, K));
-  if (rc) return rc;
+  if (int rc = ensure_partials(h, derivs_partials_words(plan, K))) return rc;
   HIP_TRY(h, h->result.ensure((size_t)K * EV_WORDS));
   HIP_TRY(h, h->dres.ensure((size_t)K * EV_WORDS));
-  rc = ensure_counters(h, (size_t)K * derivs_counters_per_pose());
-  if (rc) return rc;
+  if (int rc = ensure_counters(h, (size_t)K * derivs_counters_per_pose())) return rc;
   if (fast) {
-    rc = ensure_flag_slots(h, (size_t)K);
-    if (rc) return rc;
+    if (int rc = ensure_flag_slots(h, (size_t)K)) return rc;
   } else {
     HIP_TRY(h, hipMemcpyAsync(h->dposes.p, h->hposes.h, (size_t)K * sizeof(PoseConsts), hipMemcpyHostToDevice, s));
   }
   const unsigned long long seq = g_launch_seq.fetch_add(1, std::memory_order_relaxed);
   const bool bracket = h->timing && tn.timing_bracket != 0;
   if (bracket) HIP_TRY(h, hipEventRecord(h->ev0, s));
-  launch_derivatives(plan, ecl, h->src_sorted ? h->ox.p : h->vx, h->src_sorted ? h->oy.p : h->vy,
-                     h->src_sorted ? h->oz.p : h->vz, h->n_src, h->geom, h->cell2leaf.p, records, h->cent.p,
-                     h->hposes.h[0], fast ? h->bposes : h->dposes.p, K, h->partials.p, h->counters.p, h->dres.p, s,
-                     fast ? h->flag.d : nullptr, seq, nullptr, nullptr, 0ull, nullptr, nullptr,
-                     h->timing && !bracket ? h->ev0 : nullptr, h->timing && !bracket ? h->ev1 : nullptr);
+  DerivLaunchArgs a = shared_launch_args(h, records);
+  a.pose = &h->hposes.h[0];
+  a.d_poses = fast ? h->bposes : h->dposes.p;
+  a.K = K;
+  a.d_out = h->dres.p;
+  if (fast) a.d_host_slots = h->flag.d;
+  a.seq = seq;
+  if (h->timing && !bracket) { a.ev_start = h->ev0; a.ev_stop = h->ev1; }
+  launch_derivatives(plan, ecl, a);
   HIP_TRY(h, hipGetLastError());
   if (bracket) HIP_TRY(h, hipEventRecord(h->ev1, s));
   if (overlap) overlap(overlap_ctx);
   if (fast) {
-    rc = wait_slots(h, seq, K);
-    if (rc) return rc;
-    for (int k = 0; k < K; ++k)
-      for (int v = 0; v < EV_WORDS; ++v)
-        std::memcpy(&h->result.h[(size_t)k * EV_WORDS + v], &h->flag.h[((size_t)k * EV_WORDS + v) * 2 + 1], sizeof(double));
+    if (int rc = wait_slots(h, seq, K)) return rc;
+    copy_slot_values(h, 0, K, h->result.h);
   } else {
-    if (dev_red) {
-      rc = h->red.allreduce_device(h->dres.p, K * EV_WORDS, s, &h->err);
-      if (rc) return rc;
-    }
+    if (dev_red)
+      if (int rc = h->red.allreduce_device(h->dres.p, K * EV_WORDS, s, &h->err)) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->result.h, h->dres.p, (size_t)K * EV_WORDS * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
   }
   h->tm.n_eval_launches++;
-  if (h->timing) {
-    float ms = 0;
-    HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->tm.ms_last_eval_kernel = ms;
-    h->tm.ms_eval_kernel_total += ms;
-    h->tm.n_timed_evals++;
-  }
+  if (int rc = note_kernel_time(h)) return rc;
   std::memcpy(out, h->result.h, (size_t)K * EV_WORDS * sizeof(double));
-  if (!h->red.wants_device_buffer() && h->red.mode() != NDT_REDUCE_NONE) {
-    rc = h->red.allreduce_host_batch(out, K, &h->err);   // (P2P: one exchange round per 64 poses, not one per pose)
-    if (rc) return rc;
-  }
+  if (!dev_red && h->red.mode() != NDT_REDUCE_NONE)   // (P2P: one exchange round per 64 poses, not one per pose)
+    if (int rc = h->red.allreduce_host_batch(out, K, &h->err)) return rc;
   // Checked BEHIND the cross-rank sum: a rank that left before the exchange would leave its peers waiting for its rows
   // until the transport's time-out.  A raised word 31 (its values are positive) and a non-finite score both go through
   // the sum, so every rank sees the failure of any one of them and all return together (as evaluate() does).
@@ -889,8 +869,7 @@ int ndt_eval_derivatives_overlapped(ndt_handle* h, const double* poses6, const f
 int ndt_score_transforms(ndt_handle* h, const float* transforms, int K, ndt_score* out) {
   if (!h || !transforms || !out || K <= 0) return NDT_ERR_INVALID_ARG;
   std::vector<double> poses6(6 * (size_t)K, 0.0), words((size_t)K * EV_WORDS);  // the angle tables are not used
-  int rc = eval_batch(h, poses6.data(), transforms, K, 0, true, words.data());
-  if (rc) return rc;
+  if (int rc = eval_batch(h, poses6.data(), transforms, K, 0, true, words.data())) return rc;
   const int64_t n_total = h->n_src_global >= 0 ? h->n_src_global : (int64_t)h->n_src;
   for (int k = 0; k < K; ++k) {
     const double* w = &words[(size_t)k * EV_WORDS];
@@ -925,12 +904,10 @@ int ndt_gauss_constants(double resolution, double outlier_ratio, double* d1, dou
 
 int ndt_transform_source(ndt_handle* h, const float T[16], float* out_xyz, size_t cap_points) {
   if (!h || !T || !out_xyz) return NDT_ERR_INVALID_ARG;
-  int rc = bind_device(h);
-  if (rc) return rc;
+  if (int rc = bind_device(h)) return rc;
   if (cap_points < h->n_src) return fail(h, NDT_ERR_INVALID_ARG, "output buffer too small");
   if (h->n_src == 0) return NDT_OK;
-  rc = settle_source(h);
-  if (rc) return rc;
+  if (int rc = settle_source(h)) return rc;
   PoseConsts pc{};
   for (int i = 0; i < 3; ++i) {
     for (int j = 0; j < 3; ++j) pc.R[3 * i + j] = T[4 * j + i];
@@ -953,8 +930,7 @@ int ndt_newton_align(const ndt_params* p, int64_t n_source_total, const float gu
   EvalFn wrap = [&](const double* pose, const float* T, bool need_h, Eval* e) -> int {
     double words[NDT_EVAL_WORDS];
     std::memset(words, 0, sizeof(words));
-    int rc = fn(ctx, pose, T, need_h ? 1 : 0, words);
-    if (rc) return rc;
+    if (int rc = fn(ctx, pose, T, need_h ? 1 : 0, words)) return rc;
     unpack_eval(words, e);
     finish_eval(prm, reg_pose, pose, need_h, e);
     return 0;
@@ -979,8 +955,7 @@ int ndt_newton_align_batch(const ndt_params* p, int64_t n_source_total, const fl
       std::memcpy(&Ts[16 * (size_t)i], rq[i]->T, 16 * sizeof(float));
       need[(size_t)i] = rq[i]->need_h ? 1 : 0;
     }
-    int rc = fn(ctx, n, poses.data(), Ts.data(), need.data(), words.data());
-    if (rc) return rc;
+    if (int rc = fn(ctx, n, poses.data(), Ts.data(), need.data(), words.data())) return rc;
     for (int i = 0; i < n; ++i) {
       unpack_eval(&words[(size_t)i * NDT_EVAL_WORDS], eo[i]);
       finish_eval(prm, reg_pose, rq[i]->p, rq[i]->need_h, eo[i]);
@@ -998,15 +973,12 @@ int ndt_align_batch(ndt_handle* h, const float* guesses, int K, ndt_result* out)
   }
   if (h->red.mode() != NDT_REDUCE_NONE)
     return fail(h, NDT_ERR_UNSUPPORTED, "ndt_align_batch: multi-rank batches are not supported");
-  int rc = bind_device(h);
-  if (rc) return rc;
+  if (int rc = bind_device(h)) return rc;
   AlignBusy busy(h->keepwarm);
-  rc = ready_for_eval(h);
-  if (rc) return rc;
+  if (int rc = ready_for_eval(h)) return rc;
   // The source order of every round is decided here, once, by the first guess: a round never re-sorts by its own
   // first pose (eval_batch, fixed_order), so no hypothesis's sums depend on which others are still live.
-  rc = maybe_sort_source(h, guesses);
-  if (rc) return rc;
+  if (int rc = maybe_sort_source(h, guesses)) return rc;
   const double dev_ms0 = h->tm.ms_eval_kernel_total;
   const int64_t n_total = h->n_src_global >= 0 ? h->n_src_global : (int64_t)h->n_src;
   std::vector<double> poses, words;
@@ -1022,14 +994,14 @@ int ndt_align_batch(ndt_handle* h, const float* guesses, int K, ndt_result* out)
       need_h |= rq[i]->need_h ? 1 : 0;
     }
     // (finish_eval has been applied per pose: unpacking gives what evaluate() hands ndt_align's loop)
-    const int r = eval_batch(h, poses.data(), Ts.data(), n, need_h, false, words.data(), nullptr, nullptr,
-                             /*fixed_order=*/true, /*batched_shape=*/true);
-    if (r) return r;
+    if (int r = eval_batch(h, poses.data(), Ts.data(), n, need_h, false, words.data(), nullptr, nullptr,
+                           /*fixed_order=*/true, /*batched_shape=*/true))
+      return r;
     for (int i = 0; i < n; ++i) unpack_eval(&words[(size_t)i * EV_WORDS], eo[i]);
     return 0;
   };
   // the product path of ndt_align: the Hessian in every trial, the memo on; no iteration history
-  rc = newton_align_batch(h->prm, n_total, guesses, K, fn, out, /*hessian_in_trials=*/true);
+  const int rc = newton_align_batch(h->prm, n_total, guesses, K, fn, out, /*hessian_in_trials=*/true);
   const double dev_ms = h->tm.ms_eval_kernel_total - dev_ms0;
   for (int k = 0; k < K; ++k) out[k].ms_device = dev_ms;
   return rc;

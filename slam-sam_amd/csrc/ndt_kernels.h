@@ -173,40 +173,51 @@ static_assert(sizeof(DerivLaunchPlan) == 16 * sizeof(int), "DerivLaunchPlan is 1
 DerivLaunchPlan plan_derivatives_launch(const ndt_tuning& tn, size_t n_src, int K, bool batched, bool xchg, const EvalConsts& ec,
                                         EvalConsts* ecl_out, bool batched_shape = false);
 size_t derivs_partials_words(const DerivLaunchPlan& pl, int K);  // doubles a launch of that plan and K poses needs in d_partials
-int derivs_counters_per_pose();
+int derivs_counters_per_pose();                                  // ticket words per pose in d_counters
 // which finishing wave expands which wave's points: 2 bits per wave (owning SIMD), 4 bits per SIMD (its finishing wave)
 void derivs_item_owners(int threads, unsigned int* owners_out, unsigned int* fin_waves_out, int* lone_out = nullptr);
 int derivs_read_wave_stamps(unsigned long long* out, int nblocks);  // diagnostic builds only: per-wave stamps, see ndt_derivs.hip
-int derivs_read_stamps(unsigned long long* out, int nblocks);  // diagnostic builds (-DNDT_STAMPS) only                     // ticket words per pose in d_counters
+int derivs_read_stamps(unsigned long long* out, int nblocks);  // diagnostic builds (-DNDT_STAMPS) only
+// The arguments of one k_derivatives launch.  One launch: the last block to finish adds the per-block rows in fixed order.
+struct DerivLaunchArgs {
+  const float *sx = nullptr, *sy = nullptr, *sz = nullptr;
+  size_t n_src = 0;
+  const GridGeom* geom = nullptr;
+  // single-pose ordinary launches enqueued behind the build of their own grid: the geometry is read
+  // from the build's device-side BuildGeom (and nothing runs after a refused build), `geom` is ignored
+  const BuildGeom* d_geom = nullptr;
+  const int* cell2leaf = nullptr;   // readable 4 ints beyond either end
+  const VoxelRecord* rec = nullptr;
+  const float* cent4 = nullptr;     // per-leaf f32 centroid + chain link (KDTREE, multi-grid)
+  // If d_poses is null the single pose `*pose` is passed as a kernel argument.
+  const PoseConsts *pose = nullptr, *d_poses = nullptr;
+  int K = 1;
+  // d_partials: derivs_partials_words(pl, K) doubles, ZEROED when allocated (rows of tagged slots);
+  // d_counters: K * derivs_counters_per_pose() zero-initialised ticket words (left at zero again
+  // by every launch).
+  double* d_partials = nullptr;
+  unsigned int* d_counters = nullptr;
+  // Result: d_host_slots == nullptr -> K * EV_WORDS plain doubles in d_out (device memory);
+  // d_host_slots != nullptr (device-mapped pinned host memory, K * 2 * EV_WORDS words) -> 32 slots
+  // {seq, value} per pose for the host to poll, d_out unused.
+  double* d_out = nullptr; unsigned long long* d_host_slots = nullptr;
+  unsigned long long seq = 0;   // a sequence number no earlier launch IN THIS PROCESS has used (it tags every partial slot)
+  // d_mbox != nullptr (single-pose only): a PRE-LAUNCHED evaluation -- `pose` is ignored, the kernel
+  // waits for the pose to appear in *d_mbox under its sequence number (PoseMailbox in ndt_device.h).
+  const PoseMailbox* d_mbox = nullptr;
+  // NDT_REDUCE_P2P (single-pose launches): the block that finishes the local sum
+  // exchanges it with the other ranks under the tag `xround` (XchgInfo, ndt_device.h)
+  const XchgInfo* d_xinfo = nullptr; unsigned long long xround = 0ull;
+  // pre-launched launches: a zeroed device counter and a pinned host word that receives
+  // `seq` once every block of the launch is resident
+  unsigned int* d_arrive_ctr = nullptr; unsigned long long* d_arrived_host = nullptr;
+  // kernel timing: events attached to the dispatch itself (begin / end of the kernel, as rocprofv3
+  // reports it); both or neither
+  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+  hipStream_t stream = nullptr;
+};
 // pl, ecl: what plan_derivatives_launch returned for this launch (the caller sets pl.mbox and pl.spec).
-// d_partials: derivs_partials_words(pl, K) doubles, ZEROED when allocated (rows of tagged slots);
-// d_counters: K * derivs_counters_per_pose() zero-initialised ticket words (left at zero again
-// by every launch).  `seq`: a sequence number no earlier launch IN THIS PROCESS has used (it
-// tags every partial slot).  If d_poses is null the single pose `pose` is passed as a kernel
-// argument.  One launch: the last block to finish adds the per-block rows in fixed order.
-// Result: d_host_slots == nullptr -> K * EV_WORDS plain doubles in d_out (device memory);
-// d_host_slots != nullptr (device-mapped pinned host memory, K * 2 * EV_WORDS words) -> 32 slots
-// {seq, value} per pose for the host to poll, d_out unused.
-// d_mbox != nullptr (single-pose only): a PRE-LAUNCHED evaluation -- `pose` is ignored, the kernel
-// waits for the pose to appear in *d_mbox under its sequence number (PoseMailbox in ndt_device.h).
-void launch_derivatives(const DerivLaunchPlan& pl, const EvalConsts& ecl, const float* sx, const float* sy, const float* sz,
-                        size_t n_src, const GridGeom& g, const int* cell2leaf /* readable 4 ints beyond either end */,
-                        const VoxelRecord* rec, const float* cent4 /* per-leaf f32 centroid + chain link (KDTREE, multi-grid) */,
-                        const PoseConsts& pose, const PoseConsts* d_poses, int K, double* d_partials, unsigned int* d_counters,
-                        double* d_out, hipStream_t s, unsigned long long* d_host_slots,
-                        unsigned long long seq, const PoseMailbox* d_mbox = nullptr,
-                        // NDT_REDUCE_P2P (single-pose launches): the block that finishes the local sum
-                        // exchanges it with the other ranks under the tag `xround` (XchgInfo, ndt_device.h)
-                        const XchgInfo* d_xinfo = nullptr, unsigned long long xround = 0ull,
-                        // pre-launched launches: a zeroed device counter and a pinned host word that receives
-                        // `seq` once every block of the launch is resident
-                        unsigned int* d_arrive_ctr = nullptr, unsigned long long* d_arrived_host = nullptr,
-                        // kernel timing: events attached to the dispatch itself (begin / end of the kernel, as rocprofv3
-                        // reports it); both or neither
-                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
-                        // single-pose ordinary launches enqueued behind the build of their own grid: the geometry is read
-                        // from the build's device-side BuildGeom (and nothing runs after a refused build), `g` is ignored
-                        const BuildGeom* d_geom = nullptr);
+void launch_derivatives(const DerivLaunchPlan& pl, const EvalConsts& ecl, const DerivLaunchArgs& a);
 
 // The 80-byte records of leaf slots [0, n) as 48-byte PackedRecords (f64 mean, f32 inverse covariance); a launch
 // whose EvalConsts::packed is set takes that array in place of `rec`.

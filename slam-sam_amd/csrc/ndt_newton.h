@@ -3,6 +3,7 @@
 // (the HIP kernels in production).  Internal header.
 #pragma once
 
+#include <cmath>
 #include <functional>
 #include <vector>
 
@@ -30,6 +31,22 @@ void gauss_constants(double resolution, double outlier_ratio, double* d1, double
 void angle_tables(const double p[6], float jang[24], float hang[45]);
 // expands NDT_EVAL_WORDS packed words into an Eval
 void unpack_eval(const double* w, Eval* e);
+// Word 31 of the packed words (EV_FAIL, ndt_device.h): with several summing blocks only one of them owns it, the others say
+// "gave up" by publishing their words as NaN -- read as a lost row, code 1 (a word 31 that is raised already stays as it is).
+inline void mark_lost_rows(double* w) {
+  if (w[NDT_EVAL_WORDS - 1] != 0.0) return;   // (a NaN there compares unequal too)
+  for (int v = 0; v < NDT_EVAL_WORDS; ++v)
+    if (std::isnan(w[v])) { w[NDT_EVAL_WORDS - 1] = 1.0; return; }
+}
+// What evaluate() does about a raised word 31 before a host-side cross-rank sum (the reasons stand there); whatever it
+// does not repeat -- 3 has been finished by the host before this is asked -- is left to the final failure check.
+enum class Recovery { None, RelaunchPoseTimeout, RelaunchMissingRows, TicketedRetry };
+inline Recovery recovery_for(double fail_word, bool via_mailbox, bool safe_retry, bool dev_out) {
+  if (fail_word == 2.0 && via_mailbox) return Recovery::RelaunchPoseTimeout;
+  if (fail_word == 1.0 && via_mailbox) return Recovery::RelaunchMissingRows;
+  if (fail_word == 1.0 && !via_mailbox && !safe_retry && !dev_out) return Recovery::TicketedRetry;
+  return Recovery::None;
+}
 // adds the ridge / regularisation terms and applies the non-finite guards
 void finish_eval(const ndt_params& prm, const float* reg_pose, const double p[6], bool need_h, Eval* e);
 

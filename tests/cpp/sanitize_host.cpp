@@ -6,6 +6,7 @@
 //   * the 6x6 solve (Cholesky fast path and eigen route), result_covariance, pose <-> matrix;
 //   * the shared-memory reducer with 4 threads x 2000 rounds (bit-identical sums on every rank);
 //   * SE(3) exp / log round trips;
+//   * what evaluate() does about word 31 of an evaluation (recovery_for, mark_lost_rows), every combination;
 //   * the upload path's worker pool growing between two jobs whose captures live on dead frames;
 //   * the host half of the asynchronous cloud hand-off (stage_cloud): every layout and stride against a scalar
 //     restatement, the caller's cloud in an exactly-sized heap block (no byte beyond the last point's z is read)
@@ -321,6 +322,46 @@ int main() {
       }
       CHECK(same);
     }
+  }
+
+  // ---- what evaluate() does about word 31 (recovery_for, mark_lost_rows: ndt_newton.h) ----------------------------
+  // Every combination, against the if chain written out: NO = no recovery (the final check fails the evaluation, or
+  // there was nothing to recover), PT = relaunch after a pose time-out, MR = relaunch after missing rows, TR = ticketed retry.
+  {
+    using R = ndt::Recovery;
+    const R NO = R::None, PT = R::RelaunchPoseTimeout, MR = R::RelaunchMissingRows, TR = R::TicketedRetry;
+    // index: [word 31][via_mailbox][safe_retry][dev_out]
+    const R want[4][2][2][2] = {
+        /* 0 */ {{{NO, NO}, {NO, NO}}, {{NO, NO}, {NO, NO}}},
+        /* 1 */ {{{TR, NO}, {NO, NO}}, {{MR, MR}, {MR, MR}}},   // ordinary: only a first, host-summed launch; pre-launched: always
+        /* 2 */ {{{NO, NO}, {NO, NO}}, {{PT, PT}, {PT, PT}}},   // only a pre-launched kernel waits for a pose
+        /* 3 */ {{{NO, NO}, {NO, NO}}, {{NO, NO}, {NO, NO}}},   // the host has finished that exchange before this is asked
+    };
+    for (int w = 0; w < 4; ++w)
+      for (int mb = 0; mb < 2; ++mb)
+        for (int sr = 0; sr < 2; ++sr)
+          for (int dv = 0; dv < 2; ++dv) CHECK(ndt::recovery_for((double)w, mb != 0, sr != 0, dv != 0) == want[w][mb][sr][dv]);
+    const double nan = std::nan("");
+    auto words = [](int at, double v, double w31) {
+      std::vector<double> w(NDT_EVAL_WORDS);
+      for (int i = 0; i < NDT_EVAL_WORDS; ++i) w[(size_t)i] = 0.5 * i;
+      w[NDT_EVAL_WORDS - 1] = w31;
+      if (at >= 0) w[(size_t)at] = v;
+      return w;
+    };
+    struct Case { int at; double w31, want31; };   // a NaN at word `at` (-1: none) beside word 31 = w31
+    const Case cases[] = {{0, 0.0, 1.0}, {30, 0.0, 1.0}, {-1, 0.0, 0.0}, {0, 2.0, 2.0}, {30, 3.0, 3.0}, {5, 1.0, 1.0}};
+    for (const Case& c : cases) {
+      std::vector<double> w = words(c.at, nan, c.w31), before = w;
+      ndt::mark_lost_rows(w.data());
+      CHECK(w[NDT_EVAL_WORDS - 1] == c.want31);
+      w[NDT_EVAL_WORDS - 1] = before[NDT_EVAL_WORDS - 1];   // nothing else is touched
+      CHECK(std::memcmp(w.data(), before.data(), sizeof(double) * NDT_EVAL_WORDS) == 0);
+    }
+    // a NaN in word 31 itself is not zero: it stays (and fails the evaluation as a raised word does)
+    std::vector<double> w = words(NDT_EVAL_WORDS - 1, nan, 0.0);
+    ndt::mark_lost_rows(w.data());
+    CHECK(std::isnan(w[NDT_EVAL_WORDS - 1]));
   }
 
   // ---- SE(3) ---------------------------------------------------------------------------------------
