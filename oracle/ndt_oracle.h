@@ -189,6 +189,11 @@ void oracle_svn_align(const oracle_grid* g, const float* src_xyz, size_t n, size
 void oracle_svn_sample_particles(const double prior16[16], int K, uint64_t seed, double* particles);
 /* SE(3) helpers exported for tests: xi = [omega, v] (GTSAM order) */
 void oracle_se3_expmap(const double xi[6], double T16[16]);
+// Limit of the logarithm (gtsam's formulas, restated as they are): the generic branch divides by 2 sin(theta), so its
+// error grows as 1e-16 pi / sin(theta)^2 (1e-9 at pi - 1e-3); where trace + 1 < 1e-10 (within 1e-5 rad of pi) it
+// returns the angle pi itself and an axis whose sign is fixed by convention, not by R - R^T: off by pi - theta, and
+// by the sign for half of the axes.  Nothing the SVN loop feeds it comes near pi (particle pairs are centimetres and
+// milliradians apart); tests/test_attitudes_cpu.py pins the size of the limit.
 void oracle_se3_logmap(const double T16[16], double xi[6]);
 
 #ifdef __cplusplus

@@ -329,6 +329,8 @@ def se3_expmap(xi):
 
 
 def se3_logmap(T):
+    """gtsam's Logmap restated; exact to 1e-12 up to rotations of ~3 rad, 1e-9 at pi - 1e-3, and within 1e-5 rad of pi
+    only to pi - theta with a conventional axis sign (see ndt_oracle.h)."""
     L = _svn_protos()
     xi = np.zeros(6)
     L.oracle_se3_logmap(_dp(_pose16(T)), _dp(xi))

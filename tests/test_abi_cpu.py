@@ -321,15 +321,17 @@ def test_quoted_hbm_traffic_matches_the_newest_pmc_summary():
     assert os.path.basename(mod.newest_summary()) in have["source"]
 
 
-def test_angle_tables_are_the_derivatives_of_the_rotation(pkg):
-    """ndt_angle_tables (host arithmetic, no device): the eight rows of j_ang are d(R x)/d(roll, pitch, yaw) and the fifteen
-    rows of h_ang the second derivatives, in the reference's row order (svn_ndt_impl.hpp:270-331) -- checked against central
-    differences of R = Rx(roll) Ry(pitch) Rz(yaw) (ref: the pose-to-matrix convention of :761); ndt_gauss_constants against
-    the closed form of :90-130."""
-    L = pkg.lib()
+def angle_tables(L, pose6):
+    """ndt_angle_tables at pose6: (j_ang [8, 3], h_ang [15, 3]) as float32"""
     L.ndt_angle_tables.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.ndt_gauss_constants.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    j, h = (C.c_float * 24)(), (C.c_float * 45)()
+    assert L.ndt_angle_tables((C.c_double * 6)(*pose6), j, h) == 0
+    return np.array(j, dtype=np.float32).reshape(8, 3), np.array(h, dtype=np.float32).reshape(15, 3)
 
+
+def check_angle_tables(L, ang):
+    """The tables at the angles `ang` against central differences of R = Rx(roll) Ry(pitch) Rz(yaw) (shared with
+    tests/test_attitudes_cpu.py, which runs it all over SO(3))."""
     def rot(a):
         cx, sx, cy, sy, cz, sz = np.cos(a[0]), np.sin(a[0]), np.cos(a[1]), np.sin(a[1]), np.cos(a[2]), np.sin(a[2])
         rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
@@ -337,11 +339,9 @@ def test_angle_tables_are_the_derivatives_of_the_rotation(pkg):
         rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
         return rx @ ry @ rz
 
-    ang = np.array([0.31, -0.22, 0.47])
-    pose = (C.c_double * 6)(1.0, 2.0, 3.0, *ang)
-    j, h = (C.c_float * 24)(), (C.c_float * 45)()
-    assert L.ndt_angle_tables(pose, j, h) == 0
-    j, h = np.array(j, dtype=np.float64).reshape(8, 3), np.array(h, dtype=np.float64).reshape(15, 3)
+    ang = np.asarray(ang, dtype=np.float64)
+    j, h = angle_tables(L, [1.0, 2.0, 3.0, *ang])
+    j, h = j.astype(np.float64), h.astype(np.float64)
     e = 1e-5
 
     def d1(k):
@@ -363,6 +363,16 @@ def test_angle_tables_are_the_derivatives_of_the_rotation(pkg):
         if row == 6:   # the reference's table has +sin(pitch) where d2 x'/dpitch^2 has -sin(pitch) (kept: svn_ndt_impl.hpp:312)
             want = want * np.array([1.0, 1.0, -1.0])
         np.testing.assert_allclose(h[row], want, atol=2e-4)
+
+
+def test_angle_tables_are_the_derivatives_of_the_rotation(pkg):
+    """ndt_angle_tables (host arithmetic, no device): the eight rows of j_ang are d(R x)/d(roll, pitch, yaw) and the fifteen
+    rows of h_ang the second derivatives, in the reference's row order (svn_ndt_impl.hpp:270-331) -- checked against central
+    differences of R = Rx(roll) Ry(pitch) Rz(yaw) (ref: the pose-to-matrix convention of :761); ndt_gauss_constants against
+    the closed form of :90-130."""
+    L = pkg.lib()
+    L.ndt_gauss_constants.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    check_angle_tables(L, [0.31, -0.22, 0.47])
     d1c, d2c = C.c_double(), C.c_double()
     assert L.ndt_gauss_constants(1.0, 0.55, C.byref(d1c), C.byref(d2c)) == 0
     c1, c2 = 10.0 * (1 - 0.55), 0.55
