@@ -481,6 +481,49 @@ int ndt_map_export_moments(ndt_handle* h, int min_points, int32_t* ijk, int32_t*
                            size_t* n_out);
 int ndt_set_target_from_map_moments(ndt_handle* h, const float box_min[3], const float box_max[3]);
 
+/* Bound, keep and combine a map: remove voxels by box, hand out and take back the complete state of its voxels.  A box
+ * is what ndt_set_target_from_map_moments takes: a voxel is inside when floor(box_min[a] * inv_leaf) <= ijk[a] <=
+ * floor(box_max[a] * inv_leaf) on every axis (f32 floor, held to the map's coordinate range); box_min[a] > box_max[a]
+ * on an axis is an empty box and valid.  File formats stay the caller's business.
+ *  - ndt_map_crop: remove_inside == 0 keeps the voxels inside the box and drops the rest (a sliding window around the
+ *    vehicle; an empty box empties the map), != 0 drops the voxels inside (erase a region).  *n_removed (nullable):
+ *    voxels dropped.  Nothing to drop: NDT_OK, the table untouched.  Otherwise the survivors move, bit for bit, into a
+ *    fresh table of the smallest power-of-two capacity >= 2 x kept that is not below the capacity ndt_map_reset gave
+ *    the map, and the old table is freed; an allocation failure is NDT_ERR_ALLOC and leaves the map as it was.
+ *    Afterwards ndt_map_get_info reports n_voxels and n_points of what was kept, the TIGHT min_ijk / max_ijk of the kept
+ *    voxels and the new capacity; n_points_dropped, n_adds and n_grows are unchanged.  An emptied map still exists and
+ *    keeps its moments setting.  Both box pointers are needed and every value finite (NDT_ERR_INVALID_ARG).
+ *  - ndt_map_export_state / _device: every OCCUPIED voxel of the map (both box pointers NULL) or of a box, in ascending
+ *    (k, j, i) order: ijk 3 x int32, count int32, sums4 4 x float {sum x, sum y, sum z, sum intensity (0 in a map
+ *    without)} exactly as the table holds them (NOT divided by the count), moments9 9 x double as
+ *    ndt_map_export_moments gives them.  Any output may be NULL; moments9 != NULL on a map without moments, half a box
+ *    or a non-finite box is NDT_ERR_INVALID_ARG.  Size protocol of ndt_map_export.  Complete when it returns; the map is
+ *    unchanged.
+ *  - ndt_map_import_state / _device: n such records are merged into the map through the add's own pipeline.  Per voxel,
+ *    for its records in input order: every sum = what the map holds + the record's sum, rounded once (f32 for sums4,
+ *    intensity only in a map with intensity; f64 for moments9), count += the record's count.  A voxel new to the map
+ *    starts from +0 and so receives its record bit for bit (0 + s is s for every value but -0.0, which a map never
+ *    holds and never exports): export -> import into an empty map restores the state exactly, and a map that is saved,
+ *    loaded and continued holds what it would hold had it never stopped.  For a voxel both sides hold, the merged sums
+ *    differ from those of one map fed all the points by that one rounding per field.  Refusals, each as a whole with the
+ *    map unchanged: no map, NULL ijk / count / sums4, a leaf that is not bit-equal to the map's, moments9 == NULL on a
+ *    map with moments (one without ignores moments9), any count < 1 (NDT_ERR_INVALID_ARG, the message names how many);
+ *    any |ijk| >= 2^20 (NDT_ERR_GRID_OVERFLOW); a table that cannot grow to 2 x (n_voxels + n) slots (NDT_ERR_ALLOC).
+ *    n = 0 is a no-op.  On success n_points grows by the sum of the counts, min_ijk / max_ijk widen, n_adds grows by 1.
+ *    The sums are NOT checked for finiteness, and keeping a voxel's int32 count in range is the caller's business, as
+ *    it is for ndt_map_add.  The caller's arrays are free when the call returns.
+ * The target (also one made from this map before), source, align state, iteration history, evaluation counters and
+ * the keyframe archive are left untouched by all five calls. */
+int ndt_map_crop(ndt_handle* h, const float box_min[3], const float box_max[3], int remove_inside, int64_t* n_removed);
+int ndt_map_export_state(ndt_handle* h, const float box_min[3], const float box_max[3], int32_t* ijk, int32_t* count,
+                         float* sums4, double* moments9, size_t cap, size_t* n_out);
+int ndt_map_export_state_device(ndt_handle* h, const float box_min[3], const float box_max[3], int32_t* ijk,
+                                int32_t* count, float* sums4, double* moments9, size_t cap, size_t* n_out);
+int ndt_map_import_state(ndt_handle* h, float leaf, const int32_t* ijk, const int32_t* count, const float* sums4,
+                         const double* moments9, size_t n);
+int ndt_map_import_state_device(ndt_handle* h, float leaf, const int32_t* ijk, const int32_t* count, const float* sums4,
+                                const double* moments9, size_t n);
+
 /* setRegularizationPose (ref: run/pipeline_ligo_tc.cpp:531) */
 int ndt_set_regularization_pose(ndt_handle* h, const float pose_colmajor[16]);
 int ndt_clear_regularization_pose(ndt_handle* h);

@@ -344,6 +344,19 @@ struct PointXYZ { float x, y, z, pad; };                        // 16 bytes like
 struct PointXYZI { float x, y, z, pad; float intensity, p1, p2, p3; };  // 32 bytes like pcl::PointXYZI
 #endif
 
+// The complete state of a map's occupied voxels, ascending (k, j, i): what a caller saves at shutdown, loads at the
+// next start (mapReset with the same leaf, mapEnableMoments if `moments` is filled, mapImportState) or merges into
+// another map.  The sums are the map's own, not divided by the count.  File formats are the caller's business.
+struct MapState {
+  float leaf = 0.0f;
+  bool with_intensity = false;
+  std::vector<int32_t> ijk;      // 3 per voxel
+  std::vector<int32_t> counts;   // 1 per voxel
+  std::vector<float> sums;       // 4 per voxel: sum x, y, z, intensity
+  std::vector<double> moments;   // 9 per voxel (x y z xx xy xz yy yz zz); empty for a map without moments
+  size_t size() const { return counts.size(); }
+};
+
 template <typename PointSource, typename PointTarget>
 class NormalDistributionsTransform
 #if NDT_HIP_WITH_PCL
@@ -730,6 +743,42 @@ class NormalDistributionsTransform
   // box_min / box_max: three floats each, or both null for the whole map
   void setInputTargetFromMapMoments(const float* box_min = nullptr, const float* box_max = nullptr) {
     status_ = h_ ? ndt_set_target_from_map_moments(h_, box_min, box_max) : NDT_ERR_NO_DEVICE;
+  }
+
+  // ---- the map bounded, kept and combined (ndt_map_crop, ndt_map_export_state, ndt_map_import_state) ----
+  // keeps the voxels inside the box (remove_inside: drops them and keeps the rest); returns the number of voxels dropped
+  int64_t mapCrop(const float box_min[3], const float box_max[3], bool remove_inside = false) {
+    int64_t removed = 0;
+    status_ = h_ ? ndt_map_crop(h_, box_min, box_max, remove_inside ? 1 : 0, &removed) : NDT_ERR_NO_DEVICE;
+    return status_ == NDT_OK ? removed : 0;
+  }
+  // box_min / box_max: three floats each, or both null for the whole map
+  void mapExportState(MapState& out, const float* box_min = nullptr, const float* box_max = nullptr) {
+    out = MapState{};
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return; }
+    ndt_map_info mi{};
+    status_ = ndt_map_get_info(h_, &mi);
+    if (status_ != NDT_OK) return;
+    out.leaf = mi.leaf;
+    out.with_intensity = mi.with_intensity != 0;
+    const bool mom = mapHasMoments();
+    const size_t cap = (size_t)mi.n_voxels;   // (no selection holds more)
+    out.ijk.resize(3 * cap); out.counts.resize(cap); out.sums.resize(4 * cap); out.moments.resize(mom ? 9 * cap : 0);
+    size_t m = 0;
+    status_ = ndt_map_export_state(h_, box_min, box_max, out.ijk.data(), out.counts.data(), out.sums.data(),
+                                   mom ? out.moments.data() : nullptr, cap, &m);
+    if (status_ != NDT_OK) m = 0;
+    out.ijk.resize(3 * m); out.counts.resize(m); out.sums.resize(4 * m); out.moments.resize(mom ? 9 * m : 0);
+  }
+  void mapImportState(const MapState& s) {
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return; }
+    const size_t n = s.counts.size();
+    if (s.ijk.size() != 3 * n || s.sums.size() != 4 * n || (!s.moments.empty() && s.moments.size() != 9 * n)) {
+      status_ = NDT_ERR_INVALID_ARG;
+      return;
+    }
+    status_ = ndt_map_import_state(h_, s.leaf, s.ijk.data(), s.counts.data(), s.sums.data(),
+                                   s.moments.empty() ? nullptr : s.moments.data(), n);
   }
 
   // ---- device-resident keyframe archive (ref: run/pipeline_ligo_tc.cpp:519-529, run/pipeline.cpp:554-557,784) ----

@@ -233,6 +233,7 @@ ABI_SYMBOLS = [
     "ndt_map_reset", "ndt_map_clear", "ndt_map_add", "ndt_map_add_device", "ndt_map_add_keyframe", "ndt_map_get_info",
     "ndt_map_export_device", "ndt_map_export", "ndt_set_target_from_map",
     "ndt_map_enable_moments", "ndt_map_has_moments", "ndt_map_export_moments", "ndt_set_target_from_map_moments",
+    "ndt_map_crop", "ndt_map_export_state", "ndt_map_export_state_device", "ndt_map_import_state", "ndt_map_import_state_device",
 ]
 
 _lib = None
@@ -353,6 +354,11 @@ def lib():
         L.ndt_map_has_moments.argtypes = [vp]
         L.ndt_map_export_moments.argtypes = [vp, C.c_int, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ndt_set_target_from_map_moments.argtypes = [vp, fp, fp]
+        L.ndt_map_crop.argtypes = [vp, fp, fp, C.c_int, C.POINTER(C.c_int64)]
+        L.ndt_map_export_state.argtypes = [vp, fp, fp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ndt_map_export_state_device.argtypes = [vp, fp, fp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ndt_map_import_state.argtypes = [vp, C.c_float, vp, vp, vp, vp, C.c_size_t]
+        L.ndt_map_import_state_device.argtypes = [vp, C.c_float, vp, vp, vp, vp, C.c_size_t]
         L.ndt_set_handoff_mode.argtypes = [vp, C.c_int]
         L.ndt_get_handoff_mode.argtypes = [vp]
         L.ndt_wait.argtypes = [vp]
@@ -821,6 +827,79 @@ class NormalDistributionsTransform:
             return
         lo, hi = self._box_corner(box_min, "box_min"), self._box_corner(box_max, "box_max")
         self._check(lib().ndt_set_target_from_map_moments(self._h, _fp(lo), _fp(hi)))
+
+    # --- the map bounded, kept and combined: crop to a box, the full per-voxel state out and back in ---
+    def _box_or_none(self, box_min, box_max):
+        """(lo, hi) float32 corners, or (None, None) for the whole map; ValueError on half a box or a non-finite one."""
+        if (box_min is None) != (box_max is None):
+            raise ValueError("box_min and box_max go together (both None: the whole map)")
+        if box_min is None:
+            return None, None
+        return self._box_corner(box_min, "box_min"), self._box_corner(box_max, "box_max")
+
+    def mapCrop(self, box_min, box_max, remove_inside=False):
+        """Keep the voxels inside the box and drop the rest (remove_inside: the other way round); returns the number of
+        voxels dropped.  box_min > box_max on an axis is an empty box."""
+        if box_min is None or box_max is None:
+            raise ValueError("a crop needs both corners of its box")
+        lo, hi = self._box_or_none(box_min, box_max)
+        removed = C.c_int64(0)
+        self._check(lib().ndt_map_crop(self._h, _fp(lo), _fp(hi), int(bool(remove_inside)), C.byref(removed)))
+        return int(removed.value)
+
+    def mapExportState(self, box_min=None, box_max=None):
+        """The complete state of the occupied voxels (of the box, if one is given) in ascending (k, j, i) order:
+        dict(leaf, with_intensity, ijk [m, 3] int32, count [m] int32, sums [m, 4] float32 -- the sums as the map holds
+        them, not divided -- and moments [m, 9] float64, None for a map without moments).  mapImportState takes it."""
+        lo, hi = self._box_or_none(box_min, box_max)
+        info = self.mapInfo()
+        cap = info["n_voxels"]                        # (no selection holds more)
+        with_mom = self.mapHasMoments()
+        ijk = np.zeros((cap, 3), dtype=np.int32)
+        cnt = np.zeros(cap, dtype=np.int32)
+        sums = np.zeros((cap, 4), dtype=np.float32)
+        mom = np.zeros((cap, 9), dtype=np.float64) if with_mom else None
+        m = C.c_size_t(0)
+        self._check(lib().ndt_map_export_state(self._h, None if lo is None else _fp(lo), None if hi is None else _fp(hi),
+                                               ijk.ctypes.data if cap else None, cnt.ctypes.data if cap else None,
+                                               sums.ctypes.data if cap else None,
+                                               mom.ctypes.data if with_mom and cap else None, cap, C.byref(m)))
+        k = m.value
+        return dict(leaf=info["leaf"], with_intensity=info["with_intensity"], ijk=ijk[:k], count=cnt[:k], sums=sums[:k],
+                    moments=None if mom is None else mom[:k])
+
+    def mapExportStateDevice(self, d_ijk, d_count, d_sums, d_moments, cap, box_min=None, box_max=None):
+        """Into device arrays of `cap` records (integer addresses, any may be None); returns the number of voxels."""
+        lo, hi = self._box_or_none(box_min, box_max)
+        m = C.c_size_t(0)
+        self._check(lib().ndt_map_export_state_device(self._h, None if lo is None else _fp(lo), None if hi is None else _fp(hi),
+                                                      d_ijk, d_count, d_sums, d_moments, int(cap), C.byref(m)))
+        return int(m.value)
+
+    def mapImportState(self, state=None, leaf=None, ijk=None, count=None, sums=None, moments=None):
+        """Merge voxel records into the map: a dict as mapExportState returns it, or leaf and the arrays themselves
+        (ijk [n, 3], count [n], sums [n, 4], moments [n, 9] or None)."""
+        if state is not None:
+            leaf, ijk, count, sums, moments = state["leaf"], state["ijk"], state["count"], state["sums"], state.get("moments")
+        if leaf is None or ijk is None or count is None or sums is None:
+            raise ValueError("a state needs leaf, ijk, count and sums")
+        ijk = np.ascontiguousarray(ijk, dtype=np.int32)
+        count = np.ascontiguousarray(count, dtype=np.int32)
+        sums = np.ascontiguousarray(sums, dtype=np.float32)
+        n = len(count)
+        if count.ndim != 1 or ijk.shape != (n, 3) or sums.shape != (n, 4):
+            raise ValueError("ijk must be n x 3 and sums n x 4 for the n counts")
+        if moments is not None:
+            moments = np.ascontiguousarray(moments, dtype=np.float64)
+            if moments.shape != (n, 9):
+                raise ValueError("moments must be n x 9")
+        self._check(lib().ndt_map_import_state(self._h, float(leaf), ijk.ctypes.data if n else None, count.ctypes.data if n else None,
+                                               sums.ctypes.data if n else None,
+                                               moments.ctypes.data if moments is not None and n else None, n))
+
+    def mapImportStateDevice(self, leaf, d_ijk, d_count, d_sums, d_moments, n):
+        """As mapImportState, from device arrays (integer addresses; d_moments None for a map without moments)."""
+        self._check(lib().ndt_map_import_state_device(self._h, float(leaf), d_ijk, d_count, d_sums, d_moments, int(n)))
 
     def setGlobalSourceSize(self, n):
         self._check(lib().ndt_set_global_source_size(self._h, int(n)))

@@ -6,6 +6,7 @@
 //   ndt_keyframes.hip  multi-grid targets, the device-resident keyframe archive, voxel downsample
 //   ndt_point_scores.hip  per-point scores and the score-based source filter (its compaction kernels included)
 //   ndt_map.hip        the sparse voxel map accumulated scan by scan (ndt_map_*), its kernels included
+//   ndt_map_state.hip  the map's crop, full-state export / import and merge (k_mapstate_* kernels)
 // One handle = one engine instance = one HIP stream on one gfx950 device; it owns every device allocation.  There is no
 // CPU path: without a device every compute call fails with NDT_ERR_NO_DEVICE.
 #pragma once
@@ -42,6 +43,9 @@
 using namespace ndt;
 
 namespace ndt {
+
+struct MapSel;   // ndt_map_device.h
+
 namespace engine {
 
 template <typename T>
@@ -190,6 +194,7 @@ struct VoxelMap {
   double* mom = nullptr;               // capacity x 9 doubles; allocated only with moments on
   bool moments = false;
   int64_t capacity = 0;
+  int64_t reset_capacity = 0;          // the capacity ndt_map_reset gave it: a crop never shrinks the table below it
   int64_t n_voxels = 0, n_points = 0, n_dropped = 0, n_adds = 0, n_grows = 0;
   int mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
   bool nvox_stale = false;             // the device's voxel counter is ahead of n_voxels
@@ -481,6 +486,21 @@ int settle(ndt_handle* h);
 void settle_discard_keep_grid(ndt_handle* h);
 void settle_discard(ndt_handle* h);
 void map_release(ndt_handle* h);   // ndt_map.hip: frees the voxel map, if any (ndt_destroy)
+// ndt_map.hip's host side as ndt_map_state.hip uses it (the kernels stay where they are)
+constexpr int64_t MAP_MAX_CAPACITY = 1ll << 30;   // slots are 32-bit sort keys with one sentinel above them
+int no_map(ndt_handle* h);
+int map_bits_for(long long v);
+int64_t map_pow2_at_least(int64_t v);
+int map_box_floor(float v, float inv_leaf);
+void map_free_table(unsigned long long* k, float* s, int* c, double* q);
+int map_alloc_table(ndt_handle* h, int64_t cap, bool with_moments, unsigned long long** k, float** s, int** c, double** q);
+int map_grow_table(ndt_handle* h, int64_t new_cap);
+int map_sort_scratch(ndt_handle* h, size_t n);
+int map_refresh_voxel_count(ndt_handle* h);
+int map_group_batch(ndt_handle* h, size_t n, const uint32_t** keys_sorted, const uint32_t** vals_sorted);
+int map_export_count(ndt_handle* h, const MapSel& sel, bool box, size_t* total);
+int map_export_order(ndt_handle* h, const MapSel& sel, bool box_sel, size_t total, const int mn[3], const int mx[3],
+                     const uint32_t** order_out, const uint32_t** slots_out);
 void fill_pose_consts(const double p[6], const float T[16], PoseConsts* pc);
 unsigned long long process_item_salt();
 EvalConsts make_eval_consts(const ndt_handle* h, bool need_h);

@@ -13,50 +13,17 @@
 //            voxel's points to; ndt_set_target_from_map_moments selects the voxels of a box with the export's count / scan /
 //            compaction / key sort under a predicate (ONE host wait: selection count, ijk box and point total decide the
 //            refusals and size the grid) and hands each to the ordinary build's finalize_leaf (launch_map_finalize).
+// Crop, state export and state import are in ndt_map_state.hip; the constants and device helpers both files use are in
+// ndt_map_device.h, and the host functions of this file that the other one calls are declared in ndt_engine.h.
 #include "ndt_engine.h"
+#include "ndt_map_device.h"
 
 namespace ndt {
 
 namespace {
 
-constexpr int MAP_THREADS = 256, MAP_WAVES = MAP_THREADS / 64;
-constexpr int MAP_SCAN_THREADS = 1024, MAP_SCAN_WAVES = MAP_SCAN_THREADS / 64;
-constexpr int MAP_XROUNDS = 4;                         // slots per thread of the export's compaction
-constexpr int MAP_XTILE = MAP_THREADS * MAP_XROUNDS;
-constexpr unsigned long long MAP_EMPTY = ~0ull;
-constexpr int MAP_BIAS = 1 << 20;                      // |ijk| < 2^20 per axis: 21 bits each once biased
-constexpr float MAP_LIMIT = 1048576.0f;
-// words of VoxelMap::stats
-enum { MS_FINITE = 0, MS_OOR = 1, MS_MIN = 2, MS_MAX = 5, MS_PROBE_FAIL = 8, MS_WORDS = 16 };
-// words of VoxelMap::tsel: ijk box, number and point total (64 bits) of the occupied voxels a selection's box holds,
-// and the leaves its finalize launch accepted
-enum { TS_MIN = 0, TS_MAX = 3, TS_VOXELS = 6, TS_POINTS = 8, TS_VALID = 10, TS_WORDS = 16 };
-
 __device__ __forceinline__ bool map_finite3(float a, float b, float c) {
   return isfinite(a) && isfinite(b) && isfinite(c);
-}
-
-__device__ __forceinline__ unsigned long long map_hash(unsigned long long k) {  // splitmix64's finaliser
-  k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
-  k ^= k >> 27; k *= 0x94d049bb133111ebull;
-  k ^= k >> 31;
-  return k;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off));
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
-  return v;
 }
 
 // Voxel key per point: floor(p * inv_leaf) per axis in f32 (the downsample's arithmetic), (k, j, i) biased into 21 bits
@@ -107,26 +74,6 @@ __global__ void __launch_bounds__(MAP_THREADS) k_map_keys(const float* __restric
     else if (t < 5) { if (v != INT_MAX) atomicMin(stats + t, v); }
     else if (v != INT_MIN) atomicMax(stats + t, v);
   }
-}
-
-// The slot of `key` in the table (linear probing from its hash): the position whose key word holds it, claimed with
-// atomicCAS if no position does yet.  *claimed: this call put the key there.  -1 if all `mask + 1` positions hold other
-// keys (cannot happen at a load of 1/2).  A plain load may show a stale EMPTY, never a wrong key (key words are written
-// once): the CAS then tells the truth.
-__device__ __forceinline__ long long map_slot_of(unsigned long long* __restrict__ tkeys, unsigned long long mask,
-                                                 unsigned long long key, bool* claimed) {
-  unsigned long long s = map_hash(key) & mask;
-  *claimed = false;
-  for (unsigned long long probe = 0; probe <= mask; ++probe) {
-    unsigned long long cur = tkeys[s];
-    if (cur == MAP_EMPTY) {
-      cur = atomicCAS(tkeys + s, MAP_EMPTY, key);
-      if (cur == MAP_EMPTY) { *claimed = true; return (long long)s; }
-    }
-    if (cur == key) return (long long)s;
-    s = (s + 1) & mask;
-  }
-  return -1;
 }
 
 // slot per point (the sort key of the grouping; `mask + 1`, the sentinel, for a skipped point) + the number of
@@ -227,19 +174,6 @@ __global__ void __launch_bounds__(MAP_THREADS) k_map_rehash(const unsigned long 
 }
 
 // ---- export ----
-// What a selection takes: the occupied slots with count >= min_points and, in the BOX instantiations, a voxel inside
-// lo <= ijk <= hi (absolute voxel coordinates, both ends included).
-struct MapSel {
-  int min_points;
-  int lo[3], hi[3];
-};
-
-__device__ __forceinline__ bool map_in_box(unsigned long long key, const MapSel& sel) {
-  const int vi = (int)(key & 0x1fffffull) - MAP_BIAS, vj = (int)((key >> 21) & 0x1fffffull) - MAP_BIAS,
-            vk = (int)(key >> 42) - MAP_BIAS;
-  return vi >= sel.lo[0] && vi <= sel.hi[0] && vj >= sel.lo[1] && vj <= sel.hi[1] && vk >= sel.lo[2] && vk <= sel.hi[2];
-}
-
 template <bool BOX>
 __device__ __forceinline__ bool map_pass(const unsigned long long* __restrict__ tkeys, const int* __restrict__ cnt,
                                          long long slot, long long cap, const MapSel& sel) {
@@ -433,21 +367,24 @@ __global__ void __launch_bounds__(MAP_THREADS) k_map_xcentroids(const uint32_t* 
   if (ocount) ocount[r] = c;
 }
 
-int bits_for(long long v) {  // bits that hold 0 .. v
-  int b = 0;
-  while (b < 62 && (1ll << b) <= v) ++b;
-  return b;
-}
-
 }  // namespace
 
 namespace engine {
 namespace {
 
 constexpr int64_t MAP_DEFAULT_CAPACITY = 1ll << 18;
-constexpr int64_t MAP_MAX_CAPACITY = 1ll << 30;   // slots are 32-bit sort keys with one sentinel above them
 
-void free_table(unsigned long long* k, float* s, int* c, double* q) {
+}  // namespace
+
+// ---- the host side ndt_map_state.hip shares (declared in ndt_engine.h) ----
+
+int map_bits_for(long long v) {  // bits that hold 0 .. v
+  int b = 0;
+  while (b < 62 && (1ll << b) <= v) ++b;
+  return b;
+}
+
+void map_free_table(unsigned long long* k, float* s, int* c, double* q) {
   if (k) (void)hipFree(k);
   if (s) (void)hipFree(s);
   if (c) (void)hipFree(c);
@@ -455,7 +392,7 @@ void free_table(unsigned long long* k, float* s, int* c, double* q) {
 }
 
 // an empty table of `cap` slots (keys ~0, sums, counts and -- with_moments -- moments zero), written on the engine's stream
-int alloc_table(ndt_handle* h, int64_t cap, bool with_moments, unsigned long long** k, float** s, int** c, double** q) {
+int map_alloc_table(ndt_handle* h, int64_t cap, bool with_moments, unsigned long long** k, float** s, int** c, double** q) {
   *k = nullptr; *s = nullptr; *c = nullptr; *q = nullptr;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(k), (size_t)cap * sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(s), (size_t)cap * 4 * sizeof(float));
@@ -467,21 +404,21 @@ int alloc_table(ndt_handle* h, int64_t cap, bool with_moments, unsigned long lon
   if (e == hipSuccess && with_moments) e = hipMemsetAsync(*q, 0, (size_t)cap * 9 * sizeof(double), h->stream);
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    free_table(*k, *s, *c, *q);
+    map_free_table(*k, *s, *c, *q);
     *k = nullptr; *s = nullptr; *c = nullptr; *q = nullptr;
     return fail(h, e == hipErrorOutOfMemory ? NDT_ERR_ALLOC : NDT_ERR_HIP, std::string("voxel map table: ") + hipGetErrorString(e));
   }
   return NDT_OK;
 }
 
-int64_t pow2_at_least(int64_t v) {
+int64_t map_pow2_at_least(int64_t v) {
   int64_t c = 64;
   while (c < v) c <<= 1;
   return c;
 }
 
 // the scratch of the build that the sort and the run search work in, for n pairs
-int ensure_sort_scratch(ndt_handle* h, size_t n) {
+int map_sort_scratch(ndt_handle* h, size_t n) {
   HIP_TRY(h, h->gd.ensure(1));
   HIP_TRY(h, h->gdh.ensure(1));
   if (!h->tickets.p) {
@@ -502,7 +439,7 @@ int ensure_sort_scratch(ndt_handle* h, size_t n) {
 }
 
 // a sort plan for keys of `bits` bits in pinned slot `which`, copied to the build's device-side BuildGeom on the stream
-int put_plan(ndt_handle* h, int which, int bits, int ncells, int* passes) {
+int map_put_plan(ndt_handle* h, int which, int bits, int ncells, int* passes) {
   VoxelMap& m = *h->map;
   BuildGeom& b = m.plan_h.h[which];
   b = BuildGeom{};
@@ -515,7 +452,7 @@ int put_plan(ndt_handle* h, int which, int bits, int ncells, int* passes) {
 }
 
 // n_voxels as the device counts it (the insert launches before this point have run when the call returns)
-int refresh_voxel_count(ndt_handle* h) {
+int map_refresh_voxel_count(ndt_handle* h) {
   VoxelMap& m = *h->map;
   if (!m.nvox_stale) return NDT_OK;
   HIP_TRY(h, hipMemcpyAsync(m.nvox_h.h, m.nvox.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
@@ -525,10 +462,10 @@ int refresh_voxel_count(ndt_handle* h) {
   return NDT_OK;
 }
 
-int grow_table(ndt_handle* h, int64_t new_cap) {
+int map_grow_table(ndt_handle* h, int64_t new_cap) {
   VoxelMap& m = *h->map;
   unsigned long long* nk; float* ns; int* nc; double* nq;
-  int rc = alloc_table(h, new_cap, m.moments, &nk, &ns, &nc, &nq);
+  int rc = map_alloc_table(h, new_cap, m.moments, &nk, &ns, &nc, &nq);
   if (rc) return rc;   // the map is as it was
   hipLaunchKernelGGL(k_map_rehash, dim3((unsigned)((m.capacity + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0, h->stream,
                      m.keys, reinterpret_cast<const float4*>(m.sums), m.cnt, (long long)m.capacity, nk,
@@ -536,15 +473,39 @@ int grow_table(ndt_handle* h, int64_t new_cap) {
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // (growth is rare: the old table is freed behind its last reader)
   if (e != hipSuccess) {
-    free_table(nk, ns, nc, nq);
+    map_free_table(nk, ns, nc, nq);
     return fail(h, NDT_ERR_HIP, std::string("voxel map growth: ") + hipGetErrorString(e));
   }
-  free_table(m.keys, m.sums, m.cnt, m.mom);
+  map_free_table(m.keys, m.sums, m.cnt, m.mom);
   m.keys = nk; m.sums = ns; m.cnt = nc; m.mom = nq;
   m.capacity = new_cap;
   ++m.n_grows;
   return NDT_OK;
 }
+
+// The batch's n keys (m.pkey; MAP_EMPTY: skipped) get their slots (k_map_insert: the device's voxel counter goes up by
+// the voxels created), then the stable sort of (slot, index) and the run search: run r of *keys_sorted / *vals_sorted is one
+// voxel's entries in input order (h->nleaf, h->leaf_start, h->leaf_cnt).  After map_sort_scratch(n); enqueued, not awaited.
+int map_group_batch(ndt_handle* h, size_t n, const uint32_t** keys_sorted, const uint32_t** vals_sorted) {
+  VoxelMap& m = *h->map;
+  hipStream_t s = h->stream;
+  const unsigned blocks = (unsigned)((n + MAP_THREADS - 1) / MAP_THREADS);
+  hipLaunchKernelGGL(k_map_insert, dim3(blocks), dim3(MAP_THREADS), 0, s, m.pkey.p, (int)n, m.keys,
+                     (unsigned long long)(m.capacity - 1), h->keys.p, m.nvox.p, m.stats.p);
+  int passes = 0;
+  int rc = map_put_plan(h, 0, map_bits_for(m.capacity), (int)m.capacity, &passes);   // (the sentinel `capacity` sorts behind every slot)
+  if (rc) return rc;
+  launch_sort_first_count(h->keys.p, n, h->gd.p, h->sort_tmp.p, s);
+  bool in_b = false;
+  HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, n, passes, h->gd.p, s, &in_b));
+  *keys_sorted = in_b ? h->keys2.p : h->keys.p;
+  *vals_sorted = in_b ? h->vals2.p : h->vals.p;
+  HIP_TRY(h, launch_find_runs(*keys_sorted, n, h->gd.p, h->gdh.d, /*min_pts=*/1, h->nleaf.p, h->run_counts.p, h->run_offsets.p,
+                              h->tickets.p + 1, nullptr, 0, &h->run_seq, h->leaf_start.p, h->leaf_cnt.p, s));
+  return NDT_OK;
+}
+
+namespace {
 
 // One batch in device memory (di may be null in a map without intensity) under an optional pose.
 int map_add_device(ndt_handle* h, const float* dx, const float* dy, const float* dz, const float* di, size_t n,
@@ -561,7 +522,7 @@ int map_add_device(ndt_handle* h, const float* dx, const float* dy, const float*
     HIP_TRY(h, m.py.ensure(n));
     HIP_TRY(h, m.pz.ensure(n));
   }
-  int rc = ensure_sort_scratch(h, n);
+  int rc = map_sort_scratch(h, n);
   if (rc) return rc;
   const float *qx = dx, *qy = dy, *qz = dz;
   if (pose16) {
@@ -581,10 +542,10 @@ int map_add_device(ndt_handle* h, const float* dx, const float* dy, const float*
   if (st[MS_OOR] > 0)
     return fail(h, NDT_ERR_GRID_OVERFLOW, std::to_string(st[MS_OOR]) + " point(s) beyond the map's coordinate range (|voxel index| < 2^20 per axis); nothing was added");
   const int64_t n_finite = st[MS_FINITE];
-  const int64_t want = pow2_at_least(2 * (m.n_voxels + (int64_t)n));
+  const int64_t want = map_pow2_at_least(2 * (m.n_voxels + (int64_t)n));
   if (want > m.capacity) {
     if (want > MAP_MAX_CAPACITY) return fail(h, NDT_ERR_ALLOC, "voxel map: more than 2^30 table slots needed");
-    rc = grow_table(h, want);
+    rc = map_grow_table(h, want);
     if (rc) return rc;
   }
   // from here on the map changes
@@ -597,18 +558,9 @@ int map_add_device(ndt_handle* h, const float* dx, const float* dy, const float*
   }
   m.n_points += n_finite;
   m.nvox_stale = true;
-  hipLaunchKernelGGL(k_map_insert, dim3(blocks), dim3(MAP_THREADS), 0, s, m.pkey.p, (int)n, m.keys,
-                     (unsigned long long)(m.capacity - 1), h->keys.p, m.nvox.p, m.stats.p);
-  int passes = 0;
-  rc = put_plan(h, 0, bits_for(m.capacity), (int)m.capacity, &passes);   // (the sentinel `capacity` sorts behind every slot)
+  const uint32_t *keys_sorted = nullptr, *vals_sorted = nullptr;
+  rc = map_group_batch(h, n, &keys_sorted, &vals_sorted);
   if (rc) return rc;
-  launch_sort_first_count(h->keys.p, n, h->gd.p, h->sort_tmp.p, s);
-  bool in_b = false;
-  HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, n, passes, h->gd.p, s, &in_b));
-  const uint32_t* keys_sorted = in_b ? h->keys2.p : h->keys.p;
-  const uint32_t* vals_sorted = in_b ? h->vals2.p : h->vals.p;
-  HIP_TRY(h, launch_find_runs(keys_sorted, n, h->gd.p, h->gdh.d, /*min_pts=*/1, h->nleaf.p, h->run_counts.p, h->run_offsets.p,
-                              h->tickets.p + 1, nullptr, 0, &h->run_seq, h->leaf_start.p, h->leaf_cnt.p, s));
   if (m.moments)
     hipLaunchKernelGGL(k_map_accumulate<true>, dim3(blocks), dim3(MAP_THREADS), 0, s, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p,
                        keys_sorted, vals_sorted, qx, qy, qz, m.with_intensity ? di : nullptr,
@@ -629,12 +581,14 @@ MapSel sel_all(int min_points) {
   return sel;
 }
 
+}  // namespace
+
 // the voxels a selection takes (count + scan, awaited); the block offsets stay in xcounts.  box: the selection is
 // limited to sel.lo .. sel.hi, and tsel_h receives the TS_* words of the occupied voxels inside (same wait)
 int map_export_count(ndt_handle* h, const MapSel& sel, bool box, size_t* total) {
   VoxelMap& m = *h->map;
   *total = 0;
-  int rc = refresh_voxel_count(h);
+  int rc = map_refresh_voxel_count(h);
   if (rc) return rc;
   if (m.n_voxels == 0) return NDT_OK;
   hipStream_t s = h->stream;
@@ -664,13 +618,13 @@ int map_export_order(ndt_handle* h, const MapSel& sel, bool box_sel, size_t tota
                      const uint32_t** order_out, const uint32_t** slots_out) {
   VoxelMap& m = *h->map;
   hipStream_t s = h->stream;
-  int rc = ensure_sort_scratch(h, total);
+  int rc = map_sort_scratch(h, total);
   if (rc) return rc;
   MapKeyBox box;
   for (int a = 0; a < 3; ++a) box.mn[a] = mn[a];
-  box.bx = bits_for((long long)mx[0] - mn[0]);
-  box.by = bits_for((long long)mx[1] - mn[1]);
-  const int bits = box.bx + box.by + bits_for((long long)mx[2] - mn[2]);
+  box.bx = map_bits_for((long long)mx[0] - mn[0]);
+  box.by = map_bits_for((long long)mx[1] - mn[1]);
+  const int bits = box.bx + box.by + map_bits_for((long long)mx[2] - mn[2]);
   const bool two_words = bits > 32;
   HIP_TRY(h, m.xslot.ensure(total));
   if (two_words) {
@@ -686,7 +640,7 @@ int map_export_order(ndt_handle* h, const MapSel& sel, bool box_sel, size_t tota
                        m.xcounts.p, box, m.xslot.p, h->keys.p, two_words ? m.xhi.p : nullptr);
   HIP_TRY(h, hipGetLastError());
   int passes = 0;
-  rc = put_plan(h, 1, std::min(bits, 32), 0, &passes);
+  rc = map_put_plan(h, 1, std::min(bits, 32), 0, &passes);
   if (rc) return rc;
   launch_sort_first_count(h->keys.p, total, h->gd.p, h->sort_tmp.p, s);
   bool in_b = false;
@@ -697,7 +651,7 @@ int map_export_order(ndt_handle* h, const MapSel& sel, bool box_sel, size_t tota
     const unsigned tb = (unsigned)((total + MAP_THREADS - 1) / MAP_THREADS);
     hipLaunchKernelGGL(k_map_xgather, dim3(tb), dim3(MAP_THREADS), 0, s, order, m.xhi.p, m.xslot.p, (int)total, h->keys.p, m.xslot2.p);
     HIP_TRY(h, hipGetLastError());
-    rc = put_plan(h, 2, bits - 32, 0, &passes);
+    rc = map_put_plan(h, 2, bits - 32, 0, &passes);
     if (rc) return rc;
     launch_sort_first_count(h->keys.p, total, h->gd.p, h->sort_tmp.p, s);
     HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, total, passes, h->gd.p, s, &in_b));
@@ -708,6 +662,8 @@ int map_export_order(ndt_handle* h, const MapSel& sel, bool box_sel, size_t tota
   *slots_out = slots;
   return NDT_OK;
 }
+
+namespace {
 
 // after map_export_count(min_points) = total > 0: the first min(total, cap) voxels in ascending (k, j, i) order
 int map_export_write(ndt_handle* h, int min_points, size_t total, float* ox, float* oy, float* oz, float* oi, int32_t* oc,
@@ -727,7 +683,17 @@ int map_export_write(ndt_handle* h, int min_points, size_t total, float* ox, flo
   return NDT_OK;
 }
 
+}  // namespace
+
 int no_map(ndt_handle* h) { return fail(h, NDT_ERR_INVALID_ARG, "no map (ndt_map_reset creates one)"); }
+
+// floor(v * inv_leaf) in f32 as a point's voxel coordinate is, held to the map's coordinate range
+int map_box_floor(float v, float inv_leaf) {
+  const float f = floorf(v * inv_leaf);
+  return f <= -MAP_LIMIT ? -MAP_BIAS : f >= MAP_LIMIT ? MAP_BIAS : (int)f;
+}
+
+namespace {
 
 bool pose_finite(const double* p) {
   for (int i = 0; i < 16; ++i)
@@ -737,12 +703,6 @@ bool pose_finite(const double* p) {
 
 int no_moments(ndt_handle* h) { return fail(h, NDT_ERR_INVALID_ARG, "the map keeps no moments (ndt_map_enable_moments right after ndt_map_reset)"); }
 
-// floor(v * inv_leaf) in f32 as a point's voxel coordinate is, held to the map's coordinate range
-int box_floor(float v, float inv_leaf) {
-  const float f = floorf(v * inv_leaf);
-  return f <= -MAP_LIMIT ? -MAP_BIAS : f >= MAP_LIMIT ? MAP_BIAS : (int)f;
-}
-
 // ndt_set_target_from_map_moments behind its argument checks.  Up to the one host wait nothing of the target is touched.
 int target_from_moments(ndt_handle* h, const float* box_min, const float* box_max) {
   VoxelMap& m = *h->map;
@@ -751,8 +711,8 @@ int target_from_moments(ndt_handle* h, const float* box_min, const float* box_ma
   MapSel sel{};
   sel.min_points = std::max(3, h->prm.min_points_per_voxel);  // the ordinary build's rule (build_begin)
   for (int a = 0; a < 3; ++a) {
-    sel.lo[a] = box_min ? box_floor(box_min[a], m.inv_leaf) : -MAP_BIAS;
-    sel.hi[a] = box_max ? box_floor(box_max[a], m.inv_leaf) : MAP_BIAS;
+    sel.lo[a] = box_min ? map_box_floor(box_min[a], m.inv_leaf) : -MAP_BIAS;
+    sel.hi[a] = box_max ? map_box_floor(box_max[a], m.inv_leaf) : MAP_BIAS;
   }
   size_t total = 0;
   int rc = map_export_count(h, sel, true, &total);
@@ -887,11 +847,11 @@ int ndt_map_reset(ndt_handle* h, float leaf, int with_intensity, int64_t initial
   m.leaf = leaf;
   m.inv_leaf = 1.0f / leaf;
   m.with_intensity = with_intensity ? 1 : 0;
-  const int64_t cap = pow2_at_least(initial_capacity > 0 ? initial_capacity : MAP_DEFAULT_CAPACITY);
+  const int64_t cap = map_pow2_at_least(initial_capacity > 0 ? initial_capacity : MAP_DEFAULT_CAPACITY);
   auto undo = [&](int code) { map_release(h); return code; };
-  rc = alloc_table(h, cap, false, &m.keys, &m.sums, &m.cnt, &m.mom);
+  rc = map_alloc_table(h, cap, false, &m.keys, &m.sums, &m.cnt, &m.mom);
   if (rc) return undo(rc);
-  m.capacity = cap;
+  m.capacity = m.reset_capacity = cap;
   hipError_t e = m.stats.ensure(MS_WORDS);
   if (e == hipSuccess) e = m.nvox.ensure(1);
   if (e == hipSuccess) e = m.stats_h.ensure(2 * MS_WORDS);

@@ -1,6 +1,7 @@
 """Two library builds against each other on ONE box, for the voxel map's calls (tuning aid, not collected by pytest): what
 tools/lib_ab.py does for the align step -- child processes that alternate between the libraries (A B A B ...), so
-box-to-box differences and drift cancel -- for ndt_map_add_device, ndt_map_export_device and ndt_set_target_from_map.
+box-to-box differences and drift cancel -- for ndt_map_add_device, ndt_map_export_device, ndt_set_target_from_map and, on
+a second handle whose resolution is the map's leaf, ndt_set_target_from_map_moments (100 m box around the last pose).
 
     python tools/map_add_ab.py <libA.so> <libB.so> [rounds]     (names relative to slam-sam_amd/)
 
@@ -34,6 +35,8 @@ def child(path, tag):
     L.ndt_map_export_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.ndt_set_target_from_map.argtypes = [vp, C.c_int]
     L.ndt_wait.argtypes = [vp]
+    L.ndt_map_enable_moments.argtypes = [vp]
+    L.ndt_set_target_from_map_moments.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     prm = pkg.Params()
     L.ndt_default_params(C.byref(prm))
     prm.resolution, prm.device_id = 1.0, 0
@@ -85,8 +88,25 @@ def child(path, tag):
     t2 = med(export)
     target()
     t3 = med(target)
+    # the target from the moments of the same 16 scans
+    prm.resolution = LEAF
+    h2 = vp()
+    assert L.ndt_create(C.byref(prm), C.byref(h2)) == 0
+    ok(L.ndt_map_reset(h2, LEAF, 0, 0))
+    ok(L.ndt_map_enable_moments(h2))
+    for k in range(16):
+        ok(L.ndt_map_add_device(h2, d[k][0], d[k][1], d[k][2], None, n, None))
+    c = stream[15][1][:3, 3]
+    lo, hi = (C.c_float * 3)(*(c - 50.0)), (C.c_float * 3)(*(c + 50.0))
+
+    def moments_target():
+        ok(L.ndt_set_target_from_map_moments(h2, lo, hi))
+
+    moments_target()
+    t4 = med(moments_target)
     print("%-34s add into an empty map %7.3f ms | into the 16-scan map %7.3f ms | export %7.3f ms | setInputTargetFromMap %7.3f ms"
-          % (tag, t0, t1, t2, t3), flush=True)
+          " | setInputTargetFromMapMoments %7.3f ms" % (tag, t0, t1, t2, t3, t4), flush=True)
+    L.ndt_destroy(h2)
     L.ndt_destroy(h)
 
 
