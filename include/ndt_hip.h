@@ -373,6 +373,81 @@ int ndt_set_target_from_keyframes(ndt_handle* h, const int64_t* ids, const doubl
  * unsets the source (NDT_ERR_NO_SOURCE until one is set again). */
 int ndt_set_source_from_keyframe(ndt_handle* h, int64_t id);
 
+/* Deskew (motion compensation) of a scan on the device, from per-point times and a pose trajectory.  The reference
+ * computes a per-point interpolation factor pointsAlpha and keeps pointsTimestamp (ref: include/dataframe.hpp:406-433),
+ * its sync thread cuts the INS frames of the scan interval into FrameData::ins (ref: run/pipeline.cpp:224-246) and
+ * CompFrame::linearInterpolate says how a pose between two frames is meant (position linearly, attitude by slerp, the
+ * factor clamped to [0, 1]; ref: include/dataframe.hpp:184-251) -- but no driver reads pointsAlpha: the scan is
+ * registered as if taken at one instant.  These calls undo the motion.
+ *
+ * The model.  A trajectory is n_knots poses, 1 <= n_knots <= NDT_DESKEW_MAX_KNOTS: knot_poses16 holds n_knots 4 x 4
+ * doubles, column-major, body -> map at that knot (as ndt_set_target_from_keyframes takes poses); knot_t[n_knots] their
+ * times, strictly increasing.  ref_pose16 is the pose the scan is to be expressed in, NULL = the last knot (the drivers
+ * take ins.back() and timestamp = end_interval as the frame's pose and time).  Per knot the host forms
+ * D_k = ref^-1 T_k in f64 and reduces it to a unit quaternion q_k (sign: q_k . q_{k-1} >= 0) and a translation d_k; a
+ * knot whose pose equals the reference bit for bit reduces to the exact identity.  Per segment it computes the
+ * half-angle theta_k = atan2(|vec(conj(q_k) q_{k+1})|, scalar part) and 1 / sin(theta_k).  A point with time t:
+ *   t is clamped to [knot_t[0], knot_t[n_knots - 1]]; its segment k has knot_t[k] <= t <= knot_t[k + 1];
+ *   u = (t - t_k) / (t_{k+1} - t_k) in f64;
+ *   q(u) = (sin((1 - u) theta) / sin(theta)) q_k + (sin(u theta) / sin(theta)) q_{k+1}; for theta < 1e-8 the normalised
+ *   linear blend; d(u) = d_k + u (d_{k+1} - d_k);
+ *   p' = R(q(u)) p + d(u), everything in f64, rounded to f32 once.
+ * A segment whose two knots reduce to bit-equal (q, d) is RIGID: the pose is (q_k, d_k) itself and no interpolation
+ * arithmetic is applied (n_knots == 1 included).  "No motion" is therefore exact: with every knot equal to the
+ * reference every finite point comes back bit for bit.
+ * ndt_trajectory_pose (host only: no handle, no device) returns D(t) as the deskew uses it.  NDT_ERR_INVALID_ARG when a
+ * pointer is NULL (the reference pose excepted), n_knots is outside 1 .. 64, knot_t is not strictly increasing, or a
+ * knot time, a pose entry or t is not finite. */
+#define NDT_DESKEW_MAX_KNOTS 64
+int ndt_trajectory_pose(const double* knot_t, const double* knot_poses16, int n_knots, const double* ref_pose16_or_null,
+                        double t, double out_pose16[16]);
+/* The acquisition filter of the drivers' lidar callback, applied to the RAW coordinates in the same pass (sensor frame,
+ * as at capture; ref: src/lidarcallback.cpp:533-538):
+ *   keep = finite(x, y, z, t)
+ *       && !(use_box && box_min[a] <= p[a] <= box_max[a] on all three axes)
+ *       && (!use_z_or_intensity || (z_min <= z && z <= z_max)
+ *           || (intensity != NULL && intensity[i] >= intensity_keep_min))
+ * A zeroed struct keeps every finite point (a compaction of the NaN returns). */
+typedef struct ndt_scan_filter {
+  int use_box;              float box_min[3], box_max[3];           /* vehicleFilterBox: centre -/+ dimensions / 2 */
+  int use_z_or_intensity;   float z_min, z_max, intensity_keep_min; /* zAxisFilter, reflectivity threshold */
+} ndt_scan_filter;
+/* ndt_deskew_device: SoA float arrays in device memory in and out; d_t is one float per point in the units of knot_t
+ * (pointsAlpha with knots at normalised times, or LidarFrame::relative_timestamp with knots at
+ * ins[k].timestamp_20 - frame.timestamp).  d_intensity, o_intensity and d_index_out may be NULL (an intensity output
+ * needs an intensity input); d_intensity == NULL with use_z_or_intensity set is valid, the second alternative is then
+ * false for every point.  n <= INT32_MAX; n = 0 is a no-op with *n_out = 0.
+ *  - filter_or_null == NULL (aligned): one launch, out[i] is the deskewed in[i], a point whose t or coordinates are not
+ *    finite gives NaN in x, y and z; *n_out = n; cap >= n (NDT_ERR_INVALID_ARG otherwise, nothing written).  An output
+ *    may BE an input array (the same address: in place); any other overlap of an output with an input is refused.
+ *  - filter_or_null != NULL (compacting): the kept points, deskewed, densely and in input order (the three launches of
+ *    ndt_filter_source's compaction: ballots, one block scanning the block counts, emit; integer offsets, no atomics).
+ *    At most cap points are written, *n_out is the number selected, NDT_ERR_INVALID_ARG naming it if it exceeds cap
+ *    (cap = n always suffices).  d_index_out receives each kept point's position in the input.  No output may
+ *    overlap an input (NDT_ERR_INVALID_ARG).
+ * Everything runs on the engine's stream and is complete when the call returns.  The handle's target, source, align
+ * state, iteration history, evaluation counters, map and archive are left alone.  An argument error refuses the call as
+ * a whole: nothing is written. */
+int ndt_deskew_device(ndt_handle* h, const float* dx, const float* dy, const float* dz, const float* d_intensity,
+                      const float* d_t, size_t n, const double* knot_t, const double* knot_poses16, int n_knots,
+                      const double* ref_pose16_or_null, const ndt_scan_filter* filter_or_null, float* ox, float* oy, float* oz,
+                      float* o_intensity, int32_t* d_index_out, size_t cap, size_t* n_out);
+/* host form: a strided cloud in (stride_bytes apart; intensity at intensity_offset_bytes, < 0: none -- pcl::PointXYZI:
+ * stride 32, intensity at 16), t contiguous (n floats); out: a cloud of the same layout, of which x, y, z and the
+ * intensity of the first *n_out points are written (nothing if *n_out exceeds cap); index_out (nullable): n_out ints */
+int ndt_deskew(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, long intensity_offset_bytes, const float* t,
+               const double* knot_t, const double* knot_poses16, int n_knots, const double* ref_pose16_or_null,
+               const ndt_scan_filter* filter_or_null, float* out, int32_t* index_out, size_t cap, size_t* n_out);
+/* ndt_keyframe_put of the deskewed (and, with a filter, compacted) scan: the archive holds under `id` exactly what
+ * ndt_keyframe_put would hold for the output of ndt_deskew -- replaced-keyframe and viewed-source rules and the buffer
+ * pool included -- so ndt_set_source_from_keyframe(id) and ndt_map_add_keyframe work on it: one upload serves the source
+ * and the archive (ref: run/pipeline.cpp:558,784).  *n_kept (nullable) receives the number of points archived.  An
+ * argument error leaves the archive untouched. */
+int ndt_keyframe_put_deskewed(ndt_handle* h, int64_t id, const float* xyz, size_t n, size_t stride_bytes,
+                              long intensity_offset_bytes, const float* t, const double* knot_t, const double* knot_poses16,
+                              int n_knots, const double* ref_pose16_or_null, const ndt_scan_filter* filter_or_null,
+                              size_t* n_kept);
+
 /* pcl::VoxelGrid downsample on the device (ref: run/pipeline_ins_map_distribution.cpp:324-340: the accumulated map
  * is filtered at `mapvoxelsize` before the NDT export).  PCL's published algorithm: the grid of
  * getMinMax3D over the finite points, voxel index floor(p * inv_leaf) - min_b, every field averaged (in float) over

@@ -149,6 +149,13 @@ inline void to_colmajor(const M& in, int rows, int cols, S* a) {
   for (int c = 0; c < cols; ++c)
     for (int r = 0; r < rows; ++r) a[rows * c + r] = (S)in(r, c);
 }
+// n 4 x 4 matrices of any indexable container -> n x 16 column-major doubles
+template <class Poses>
+inline std::vector<double> pack_poses(const Poses& poses) {
+  std::vector<double> p(16 * poses.size() + 16);
+  for (size_t k = 0; k < poses.size(); ++k) to_colmajor(poses[k], 4, 4, &p[16 * k]);
+  return p;
+}
 }  // namespace detail
 
 inline Matrix4f identity4f() {
@@ -799,6 +806,90 @@ class NormalDistributionsTransform
   void setInputSourceFromKeyframe(int64_t id) {
     status_ = h_ ? ndt_set_source_from_keyframe(h_, id) : NDT_ERR_NO_DEVICE;
     if (status_ == NDT_OK) n_src_ = 0;  // align()'s output cloud is not filled on this path
+  }
+
+  // ---- deskew: a scan expressed in one pose, from per-point times and a pose trajectory (ndt_deskew* in ndt_hip.h:
+  // position blended linearly, attitude by slerp, times clamped to the knots; ref_pose null = the last knot), with the
+  // acquisition filter of the lidar callback in the same pass (filter null: every point comes back, a non-finite one
+  // as NaN).  Not part of pclomp -- the reference computes pointsAlpha and never reads it.  Each returns the number of
+  // points written / archived (0 on error, lastStatus() says why). ----
+  size_t deskew(const float* xyz, size_t n, size_t stride_bytes, long intensity_offset_bytes, const float* t,
+                const double* knot_t, const double* knot_poses16, int n_knots, const double* ref_pose16_or_null,
+                const ndt_scan_filter* filter_or_null, float* out, int32_t* index_out, size_t cap) {
+    size_t m = 0;
+    status_ = h_ ? ndt_deskew(h_, xyz, n, stride_bytes, intensity_offset_bytes, t, knot_t, knot_poses16, n_knots,
+                              ref_pose16_or_null, filter_or_null, out, index_out, cap, &m)
+                 : NDT_ERR_NO_DEVICE;
+    return status_ == NDT_OK ? m : 0;
+  }
+  size_t deskewDevice(const float* dx, const float* dy, const float* dz, const float* d_intensity, const float* d_t, size_t n,
+                      const double* knot_t, const double* knot_poses16, int n_knots, const double* ref_pose16_or_null,
+                      const ndt_scan_filter* filter_or_null, float* ox, float* oy, float* oz, float* o_intensity,
+                      int32_t* d_index_out, size_t cap) {
+    size_t m = 0;
+    status_ = h_ ? ndt_deskew_device(h_, dx, dy, dz, d_intensity, d_t, n, knot_t, knot_poses16, n_knots, ref_pose16_or_null,
+                                     filter_or_null, ox, oy, oz, o_intensity, d_index_out, cap, &m)
+                 : NDT_ERR_NO_DEVICE;
+    return status_ == NDT_OK ? m : 0;
+  }
+  // archives the deskewed scan under `id` (one upload serves the archive and, through setInputSourceFromKeyframe, the
+  // source); the frame's pose is then the reference pose
+  size_t putKeyframeDeskewed(int64_t id, const float* xyz, size_t n, size_t stride_bytes, long intensity_offset_bytes,
+                             const float* t, const double* knot_t, const double* knot_poses16, int n_knots,
+                             const double* ref_pose16_or_null, const ndt_scan_filter* filter_or_null) {
+    size_t m = 0;
+    status_ = h_ ? ndt_keyframe_put_deskewed(h_, id, xyz, n, stride_bytes, intensity_offset_bytes, t, knot_t, knot_poses16,
+                                             n_knots, ref_pose16_or_null, filter_or_null, &m)
+                 : NDT_ERR_NO_DEVICE;
+    return status_ == NDT_OK ? m : 0;
+  }
+  // the typed face: a cloud (pcl::PointCloud<pcl::PointXYZI>: the intensity travels and feeds the filter), one time per
+  // point, the knots' times and poses (std::vector<Eigen::Matrix4d>, or any indexable container of 4 x 4 matrices)
+  template <class Cloud, class Poses>
+  Cloud deskew(const Cloud& scan, const std::vector<float>& t, const std::vector<double>& knot_t, const Poses& knot_poses,
+               const Matrix4d* ref_pose = nullptr, const ndt_scan_filter* filter = nullptr, std::vector<int32_t>* index = nullptr) {
+    Cloud out;
+    if (index) index->clear();
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return out; }
+    if (t.size() != scan.points.size() || knot_t.size() != knot_poses.size()) { status_ = NDT_ERR_INVALID_ARG; return out; }
+    using P = typename std::decay<decltype(scan.points[0])>::type;
+    const size_t n = scan.points.size();
+    const std::vector<double> poses = detail::pack_poses(knot_poses);
+    double ref[16];
+    if (ref_pose) detail::to_colmajor(*ref_pose, 4, 4, ref);
+    out.points.resize(n);   // value-initialised points: the fields the engine does not write keep their defaults
+    std::vector<int32_t> idx(index ? n + 1 : 0);
+    const size_t m = deskew(n ? &scan.points[0].x : nullptr, n, sizeof(P), intensity_offset_of<P>(0), t.data(), knot_t.data(),
+                            poses.data(), (int)knot_t.size(), ref_pose ? ref : nullptr, filter, n ? &out.points[0].x : nullptr,
+                            index ? idx.data() : nullptr, n);
+    out.points.resize(m);
+    if (index && status_ == NDT_OK) index->assign(idx.begin(), idx.begin() + (std::ptrdiff_t)m);
+    return out;
+  }
+  template <class Cloud, class Poses>
+  size_t putKeyframeDeskewed(int64_t id, const Cloud& scan, const std::vector<float>& t, const std::vector<double>& knot_t,
+                             const Poses& knot_poses, const Matrix4d* ref_pose = nullptr, const ndt_scan_filter* filter = nullptr) {
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return 0; }
+    if (t.size() != scan.points.size() || knot_t.size() != knot_poses.size()) { status_ = NDT_ERR_INVALID_ARG; return 0; }
+    using P = typename std::decay<decltype(scan.points[0])>::type;
+    const size_t n = scan.points.size();
+    const std::vector<double> poses = detail::pack_poses(knot_poses);
+    double ref[16];
+    if (ref_pose) detail::to_colmajor(*ref_pose, 4, 4, ref);
+    return putKeyframeDeskewed(id, n ? &scan.points[0].x : nullptr, n, sizeof(P), intensity_offset_of<P>(0), t.data(),
+                               knot_t.data(), poses.data(), (int)knot_t.size(), ref_pose ? ref : nullptr, filter);
+  }
+  // D(t) of that model as a matrix (host only)
+  template <class Poses>
+  static bool trajectoryPose(const std::vector<double>& knot_t, const Poses& knot_poses, double t, Matrix4d& out,
+                             const Matrix4d* ref_pose = nullptr) {
+    if (knot_t.size() != knot_poses.size()) return false;
+    const std::vector<double> poses = detail::pack_poses(knot_poses);
+    double ref[16], o[16];
+    if (ref_pose) detail::to_colmajor(*ref_pose, 4, 4, ref);
+    if (ndt_trajectory_pose(knot_t.data(), poses.data(), (int)knot_t.size(), ref_pose ? ref : nullptr, t, o) != NDT_OK) return false;
+    out = detail::from_colmajor<Matrix4d>(o, 4, 4);
+    return true;
   }
 
   // ---- clouds that are already in HBM (SoA float arrays on this engine's device) ----

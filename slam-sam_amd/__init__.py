@@ -108,6 +108,37 @@ class MapInfo(C.Structure):
                 ("max_ijk", C.c_int * 3), ("n_adds", C.c_int64), ("n_grows", C.c_int64)]
 
 
+DESKEW_MAX_KNOTS = 64
+
+
+class ScanFilter(C.Structure):
+    """ndt_scan_filter: the acquisition filter of the deskew calls, on the raw coordinates.  A zeroed filter keeps every
+    finite point."""
+    _fields_ = [("use_box", C.c_int), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3),
+                ("use_z_or_intensity", C.c_int), ("z_min", C.c_float), ("z_max", C.c_float),
+                ("intensity_keep_min", C.c_float)]
+
+    @classmethod
+    def from_vehicle_box(cls, center, dimensions, z_band=None, intensity_keep_min=None):
+        """vehicleFilterBox as the drivers configure it (centre and dimensions: the box is centre -/+ dimensions / 2,
+        None for no box), zAxisFilter as z_band = (z_min, z_max) and the reflectivity threshold; with a z band and no
+        threshold the second alternative of the predicate never holds."""
+        f = cls()
+        if center is not None:
+            c, d = np.asarray(center, np.float32), np.asarray(dimensions, np.float32)
+            if c.shape != (3,) or d.shape != (3,):
+                raise ValueError("center and dimensions must have 3 components")
+            f.use_box = 1
+            f.box_min[:] = [float(v) for v in c - d / np.float32(2)]
+            f.box_max[:] = [float(v) for v in c + d / np.float32(2)]
+        if z_band is not None or intensity_keep_min is not None:
+            f.use_z_or_intensity = 1
+            # (an empty band when only the threshold is given: z_min > z_max holds for no z)
+            f.z_min, f.z_max = (float(z_band[0]), float(z_band[1])) if z_band is not None else (1.0, 0.0)
+            f.intensity_keep_min = float("inf") if intensity_keep_min is None else float(intensity_keep_min)
+        return f
+
+
 class Timing(C.Structure):
     _fields_ = [
         ("ms_last_eval_kernel", C.c_double), ("ms_last_reduce_kernel", C.c_double),
@@ -233,6 +264,7 @@ ABI_SYMBOLS = [
     "ndt_map_reset", "ndt_map_clear", "ndt_map_add", "ndt_map_add_device", "ndt_map_add_keyframe", "ndt_map_get_info",
     "ndt_map_export_device", "ndt_map_export", "ndt_set_target_from_map",
     "ndt_map_enable_moments", "ndt_map_has_moments", "ndt_map_export_moments", "ndt_set_target_from_map_moments",
+    "ndt_trajectory_pose", "ndt_deskew_device", "ndt_deskew", "ndt_keyframe_put_deskewed",
     "ndt_map_crop", "ndt_map_export_state", "ndt_map_export_state_device", "ndt_map_import_state", "ndt_map_import_state_device",
 ]
 
@@ -359,6 +391,14 @@ def lib():
         L.ndt_map_export_state_device.argtypes = [vp, fp, fp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ndt_map_import_state.argtypes = [vp, C.c_float, vp, vp, vp, vp, C.c_size_t]
         L.ndt_map_import_state_device.argtypes = [vp, C.c_float, vp, vp, vp, vp, C.c_size_t]
+        L.ndt_trajectory_pose.argtypes = [dp, dp, C.c_int, dp, C.c_double, dp]
+        traj = [dp, dp, C.c_int, dp, C.POINTER(ScanFilter)]
+        L.ndt_deskew_device.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t] + traj + [vp, vp, vp, vp, vp, C.c_size_t,
+                                                                                      C.POINTER(C.c_size_t)]
+        L.ndt_deskew.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_long, vp] + traj + [vp, vp, C.c_size_t,
+                                                                                         C.POINTER(C.c_size_t)]
+        L.ndt_keyframe_put_deskewed.argtypes = [vp, C.c_int64, vp, C.c_size_t, C.c_size_t, C.c_long, vp] + traj + [
+            C.POINTER(C.c_size_t)]
         L.ndt_set_handoff_mode.argtypes = [vp, C.c_int]
         L.ndt_get_handoff_mode.argtypes = [vp]
         L.ndt_wait.argtypes = [vp]
@@ -456,6 +496,35 @@ def backend_info():
     buf = C.create_string_buffer(256)
     n = lib().ndt_backend_info(buf, 256)
     return n, buf.value.decode()
+
+
+def _trajectory_args(knot_t, knot_poses, ref_pose):
+    """(knot_t [n] f64, poses [n * 16] f64 column-major, n, ref [16] f64 or None) as the C-ABI takes a trajectory"""
+    kt = np.ascontiguousarray(knot_t, dtype=np.float64).ravel()
+    kp = np.asarray(knot_poses, dtype=np.float64)
+    if kp.ndim == 2 and kp.shape == (4, 4):
+        kp = kp[None]
+    if kp.ndim != 3 or kp.shape[1:] != (4, 4) or len(kp) != len(kt):
+        raise ValueError("knot_poses must be n_knots x 4 x 4, one pose per knot time")
+    poses = np.ascontiguousarray(np.transpose(kp, (0, 2, 1))).ravel()
+    ref = None
+    if ref_pose is not None:
+        r = np.asarray(ref_pose, dtype=np.float64)
+        if r.shape != (4, 4):
+            raise ValueError("ref_pose must be 4 x 4")
+        ref = np.ascontiguousarray(r.T).ravel()
+    return kt, poses, len(kt), ref
+
+
+def trajectory_pose(knot_t, knot_poses, t, ref_pose=None):
+    """D(t) = ref^-1 T(t) of the deskew model as a 4 x 4 float64 matrix (host only, no device): knot poses body -> map,
+    position blended linearly, attitude by slerp, t clamped to the knots; ref_pose None = the last knot."""
+    kt, poses, n, ref = _trajectory_args(knot_t, knot_poses, ref_pose)
+    out = np.zeros(16, np.float64)
+    rc = lib().ndt_trajectory_pose(_dp(kt), _dp(poses), n, None if ref is None else _dp(ref), float(t), _dp(out))
+    if rc != 0:
+        raise NdtError(rc, "ndt_trajectory_pose")
+    return out.reshape(4, 4).T.copy()
 
 
 def shard_range(n, rank, nranks):
@@ -671,6 +740,69 @@ class NormalDistributionsTransform:
         # (NumPy reports strides of 0 for an empty array; ndt_keyframe_put accepts n = 0 but checks the stride)
         stride = a.strides[0] if len(a) else a.itemsize * a.shape[1]
         self._check(lib().ndt_keyframe_put(self._h, int(kf_id), a.ctypes.data, len(a), stride))
+
+    # --- deskew: per-point times + a pose trajectory, the acquisition filter in the same pass ---
+    @staticmethod
+    def _filter_ref(filter):
+        if filter is None:
+            return None
+        if not isinstance(filter, ScanFilter):
+            raise TypeError("filter must be a ScanFilter")
+        return C.byref(filter)
+
+    @staticmethod
+    def _scan(cloud, t, intensity_column):
+        a = np.ascontiguousarray(cloud, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] < 3:
+            raise ValueError("cloud must be N x >=3 float32")
+        tt = np.ascontiguousarray(t, dtype=np.float32).ravel()
+        if len(tt) != len(a):
+            raise ValueError("t must hold one time per point")
+        if intensity_column is not None and not 3 <= int(intensity_column) < a.shape[1]:
+            raise ValueError("intensity_column outside the cloud's columns")
+        off = -1 if intensity_column is None else 4 * int(intensity_column)
+        stride = a.strides[0] if len(a) else a.itemsize * a.shape[1]
+        return a, tt, stride, off
+
+    def deskew(self, cloud, t, knot_t, knot_poses, ref_pose=None, filter=None, intensity_column=None, with_index=False):
+        """The scan (N x >= 3 float32, one time per point in the units of knot_t) expressed in ref_pose (None: the last
+        knot) -- see trajectory_pose for the model.  filter None: N points out, a non-finite point as NaN; a ScanFilter:
+        the kept points in input order.  Returns a cloud of the same layout (x, y, z and the intensity column written,
+        other columns zero), with_index: (cloud, index [m] int32)."""
+        a, tt, stride, off = self._scan(cloud, t, intensity_column)
+        kt, poses, n, ref = _trajectory_args(knot_t, knot_poses, ref_pose)
+        out = np.zeros_like(a)
+        idx = np.zeros(len(a), np.int32) if with_index else None
+        m = C.c_size_t(0)
+        self._check(lib().ndt_deskew(self._h, a.ctypes.data, len(a), stride, off, tt.ctypes.data, _dp(kt), _dp(poses), n,
+                                     None if ref is None else _dp(ref), self._filter_ref(filter), out.ctypes.data,
+                                     None if idx is None else idx.ctypes.data, len(a), C.byref(m)))
+        out = out[:m.value].copy()
+        return (out, idx[:m.value].copy()) if with_index else out
+
+    def deskewDevice(self, dx, dy, dz, d_t, n, knot_t, knot_poses, ox, oy, oz, cap, ref_pose=None, filter=None,
+                     d_intensity=None, o_intensity=None, d_index=None):
+        """deskew on device SoA arrays (integer device addresses as setInputTargetDevice takes them; the intensity and
+        index arrays may be None); returns the number of points written.  Without a filter the outputs may be the inputs."""
+        kt, poses, nk, ref = _trajectory_args(knot_t, knot_poses, ref_pose)
+        m = C.c_size_t(0)
+        rc = lib().ndt_deskew_device(self._h, dx, dy, dz, d_intensity, d_t, int(n), _dp(kt), _dp(poses), nk,
+                                     None if ref is None else _dp(ref), self._filter_ref(filter), ox, oy, oz, o_intensity,
+                                     d_index, int(cap), C.byref(m))
+        self.last_deskew_count = int(m.value)
+        self._check(rc)
+        return int(m.value)
+
+    def putKeyframeDeskewed(self, kf_id, cloud, t, knot_t, knot_poses, ref_pose=None, filter=None, intensity_column=None):
+        """putKeyframe(kf_id, deskew(cloud, ...)) with one upload: the archived scan is expressed in ref_pose (None: the
+        last knot), which is then the frame's pose.  Returns the number of points archived."""
+        a, tt, stride, off = self._scan(cloud, t, intensity_column)
+        kt, poses, n, ref = _trajectory_args(knot_t, knot_poses, ref_pose)
+        m = C.c_size_t(0)
+        self._check(lib().ndt_keyframe_put_deskewed(self._h, int(kf_id), a.ctypes.data, len(a), stride, off, tt.ctypes.data,
+                                                    _dp(kt), _dp(poses), n, None if ref is None else _dp(ref),
+                                                    self._filter_ref(filter), C.byref(m)))
+        return int(m.value)
 
     def setInputSourceFromKeyframe(self, kf_id):
         self._check(lib().ndt_set_source_from_keyframe(self._h, int(kf_id)))

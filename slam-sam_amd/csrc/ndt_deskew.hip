@@ -1,0 +1,333 @@
+// ndt_deskew.hip -- motion compensation of a scan from per-point times and a pose trajectory, with the acquisition
+// filter of the drivers in the same pass (see ndt_trajectory.h for the model, include/ndt_hip.h for the contract).
+//   aligned    (no filter)  ONE launch of k_deskew_aligned: out[i] = deskewed in[i], a non-finite point -> NaN
+//   compacting (filter)     the three launches of ndt_filter_source's compaction: k_deskew_count (wave ballots of the
+//                           predicate -> per-block counts), the shared one-block scan (launch_filter_scan), k_deskew_emit
+//                           (the ballots again, the per-block LDS scan, the deskewed point behind its offset)
+// One thread per point, coalesced SoA loads; the knot table (<= 64 rows of 12 doubles) is copied into LDS by every block
+// and the segment is a binary search in it.  Integer offsets only, no atomics.  Everything on the engine's stream;
+// the target, the source, the align state, the history and the counters of the handle are not touched.
+#include "ndt_engine.h"
+#include "ndt_trajectory.h"
+
+namespace ndt {
+
+namespace {
+
+constexpr int DSK_THREADS = 256, DSK_WAVES = DSK_THREADS / 64;
+
+// the acquisition filter on the RAW point (sensor frame), every comparison inclusive as the header states it
+__device__ __forceinline__ bool dsk_keep(const ndt_scan_filter& f, float x, float y, float z, float t, const float* intensity,
+                                         size_t i) {
+  if (!(isfinite(x) && isfinite(y) && isfinite(z) && isfinite(t))) return false;
+  if (f.use_box && f.box_min[0] <= x && x <= f.box_max[0] && f.box_min[1] <= y && y <= f.box_max[1] && f.box_min[2] <= z &&
+      z <= f.box_max[2])
+    return false;
+  if (!f.use_z_or_intensity) return true;
+  if (f.z_min <= z && z <= f.z_max) return true;
+  return intensity != nullptr && intensity[i] >= f.intensity_keep_min;
+}
+
+// the block's copy of the knot table
+__device__ __forceinline__ void dsk_load_table(const double* __restrict__ table, int n_knots, double* s_tab) {
+  for (int w = (int)threadIdx.x; w < n_knots * traj::ROW_WORDS; w += DSK_THREADS) s_tab[w] = table[w];
+  __syncthreads();
+}
+
+// p' = R(q(u)) p + d(u) in f64, rounded to f32 once; the exact identity hands the point back as it is
+__device__ __forceinline__ void dsk_move(const traj::KnotRow* rows, int n_knots, float x, float y, float z, float t, float* ox,
+                                         float* oy, float* oz) {
+  double q[4], d[3], R[9];
+  if (traj::pose_at(rows, n_knots, (double)t, q, d)) {
+    *ox = x; *oy = y; *oz = z;
+    return;
+  }
+  traj::quat_to_rot(q, R);
+  const double px = (double)x, py = (double)y, pz = (double)z;
+  *ox = (float)(R[0] * px + R[1] * py + R[2] * pz + d[0]);
+  *oy = (float)(R[3] * px + R[4] * py + R[5] * pz + d[1]);
+  *oz = (float)(R[6] * px + R[7] * py + R[8] * pz + d[2]);
+}
+
+// (no __restrict__ on the clouds: the outputs may be the inputs -- every thread reads its point before it writes it)
+__global__ void __launch_bounds__(DSK_THREADS) k_deskew_aligned(const float* sx, const float* sy, const float* sz, const float* st,
+                                                               const float* si, unsigned int n, const double* __restrict__ table,
+                                                               int n_knots, float* ox, float* oy, float* oz, float* oi,
+                                                               int* o_index) {
+  __shared__ double s_tab[traj::MAX_KNOTS * traj::ROW_WORDS];
+  dsk_load_table(table, n_knots, s_tab);
+  const unsigned int i = blockIdx.x * DSK_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const float x = sx[i], y = sy[i], z = sz[i], t = st[i];
+  float rx, ry, rz;
+  if (isfinite(x) && isfinite(y) && isfinite(z) && isfinite(t)) {
+    dsk_move(reinterpret_cast<const traj::KnotRow*>(s_tab), n_knots, x, y, z, t, &rx, &ry, &rz);
+  } else {
+    rx = ry = rz = __builtin_nanf("");
+  }
+  const float inten = oi ? si[i] : 0.0f;
+  ox[i] = rx;
+  oy[i] = ry;
+  oz[i] = rz;
+  if (oi) oi[i] = inten;
+  if (o_index) o_index[i] = (int)i;
+}
+
+__global__ void __launch_bounds__(DSK_THREADS) k_deskew_count(const float* __restrict__ sx, const float* __restrict__ sy,
+                                                             const float* __restrict__ sz, const float* __restrict__ st,
+                                                             const float* __restrict__ si, unsigned int n, ndt_scan_filter f,
+                                                             unsigned int* __restrict__ counts) {
+  __shared__ unsigned int s_w[DSK_WAVES];
+  const unsigned int i = blockIdx.x * DSK_THREADS + threadIdx.x;
+  const bool keep = i < n && dsk_keep(f, sx[i], sy[i], sz[i], st[i], si, i);
+  const unsigned long long bal = __ballot(keep);
+  if ((threadIdx.x & 63u) == 0) s_w[threadIdx.x >> 6] = (unsigned int)__popcll(bal);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned int c = 0;
+#pragma unroll
+    for (int w = 0; w < DSK_WAVES; ++w) c += s_w[w];
+    counts[blockIdx.x] = c;
+  }
+}
+
+__global__ void __launch_bounds__(DSK_THREADS) k_deskew_emit(const float* __restrict__ sx, const float* __restrict__ sy,
+                                                            const float* __restrict__ sz, const float* __restrict__ st,
+                                                            const float* __restrict__ si, unsigned int n, ndt_scan_filter f,
+                                                            const double* __restrict__ table, int n_knots,
+                                                            const unsigned int* __restrict__ offsets, float* __restrict__ ox,
+                                                            float* __restrict__ oy, float* __restrict__ oz, float* __restrict__ oi,
+                                                            int* __restrict__ o_index, unsigned int cap) {
+  __shared__ double s_tab[traj::MAX_KNOTS * traj::ROW_WORDS];
+  __shared__ unsigned int s_w[DSK_WAVES];
+  const unsigned int i = blockIdx.x * DSK_THREADS + threadIdx.x;
+  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+  float x = 0.0f, y = 0.0f, z = 0.0f, t = 0.0f;
+  bool keep = false;
+  if (i < n) {
+    x = sx[i]; y = sy[i]; z = sz[i]; t = st[i];
+    keep = dsk_keep(f, x, y, z, t, si, i);
+  }
+  const unsigned long long bal = __ballot(keep);
+  if (lane == 0) s_w[wave] = (unsigned int)__popcll(bal);
+  dsk_load_table(table, n_knots, s_tab);   // (its barrier also publishes s_w)
+  unsigned int wave_off = 0;
+#pragma unroll
+  for (int w = 0; w < DSK_WAVES; ++w) wave_off += w < wave ? s_w[w] : 0u;
+  const unsigned int rank = (unsigned int)__popcll(bal & ((1ull << lane) - 1ull));
+  const unsigned int pos = offsets[blockIdx.x] + wave_off + rank;
+  if (keep && pos < cap) {   // (the output holds cap points: a selection beyond it is counted, not written)
+    float rx, ry, rz;
+    dsk_move(reinterpret_cast<const traj::KnotRow*>(s_tab), n_knots, x, y, z, t, &rx, &ry, &rz);
+    ox[pos] = rx;
+    oy[pos] = ry;
+    oz[pos] = rz;
+    if (oi) oi[pos] = si[i];
+    if (o_index) o_index[pos] = (int)i;
+  }
+}
+
+}  // namespace
+
+namespace engine {
+namespace {
+
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  if (!a || !b || na == 0 || nb == 0) return false;
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb + nb && pb < pa + na;
+}
+
+// The trajectory's table to the device (pinned staging -> the handle's table, on the engine's stream), then the
+// launches; awaited.  dx .. dt (and di, ox .. o_index) are device arrays.  Arguments have been checked.
+int deskew_device(ndt_handle* h, const float* dx, const float* dy, const float* dz, const float* di, const float* dt, size_t n,
+                  const traj::KnotRow* rows, int n_knots, const ndt_scan_filter* filter, float* ox, float* oy, float* oz, float* oi,
+                  int32_t* o_index, size_t cap, size_t* n_out) {
+  *n_out = 0;
+  if (n == 0) return NDT_OK;
+  DeskewBufs& b = h->dsk;
+  hipStream_t s = h->stream;
+  HIP_TRY(h, b.tab.ensure((size_t)traj::MAX_KNOTS * traj::ROW_WORDS));
+  HIP_TRY(h, b.tab_h.ensure((size_t)traj::MAX_KNOTS * traj::ROW_WORDS));
+  HIP_TRY(h, b.total_h.ensure(4));
+  const size_t tab_bytes = (size_t)n_knots * sizeof(traj::KnotRow);
+  std::memcpy(b.tab_h.h, rows, tab_bytes);   // (the previous call's copy out of the staging has been awaited)
+  HIP_TRY(h, hipMemcpyAsync(b.tab.p, b.tab_h.h, tab_bytes, hipMemcpyHostToDevice, s));
+  const int nb = (int)((n + DSK_THREADS - 1) / DSK_THREADS);
+  static_assert(sizeof(int) == sizeof(int32_t), "index type");
+  if (!filter) {
+    hipLaunchKernelGGL(k_deskew_aligned, dim3((unsigned)nb), dim3(DSK_THREADS), 0, s, dx, dy, dz, dt, di, (unsigned int)n, b.tab.p,
+                       n_knots, ox, oy, oz, di ? oi : nullptr, o_index);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(s));
+    *n_out = n;
+    return NDT_OK;
+  }
+  HIP_TRY(h, b.counts.ensure((size_t)nb + 2));
+  unsigned int* d_total = b.counts.p + nb + 1;
+  const unsigned int ucap = (unsigned int)std::min<size_t>(cap, n);
+  hipLaunchKernelGGL(k_deskew_count, dim3((unsigned)nb), dim3(DSK_THREADS), 0, s, dx, dy, dz, dt, di, (unsigned int)n, *filter,
+                     b.counts.p);
+  launch_filter_scan(b.counts.p, nb, d_total, s);
+  hipLaunchKernelGGL(k_deskew_emit, dim3((unsigned)nb), dim3(DSK_THREADS), 0, s, dx, dy, dz, dt, di, (unsigned int)n, *filter,
+                     b.tab.p, n_knots, b.counts.p, ox, oy, oz, di ? oi : nullptr, o_index, ucap);
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipMemcpyAsync(b.total_h.h, d_total, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  *n_out = (size_t)b.total_h.h[0];
+  if (*n_out > cap) return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(*n_out) + " points selected");
+  return NDT_OK;
+}
+
+// what every form checks before anything is written: the trajectory (into rows) and the sizes
+int deskew_check(ndt_handle* h, size_t n, const double* knot_t, const double* knot_poses16, int n_knots, const double* ref16,
+                 traj::KnotRow* rows) {
+  if (n > (size_t)std::numeric_limits<int32_t>::max()) return fail(h, NDT_ERR_INVALID_ARG, "deskew: more than INT32_MAX points");
+  const char* why = "";
+  const int rc = traj::build_rows(knot_t, knot_poses16, n_knots, ref16, rows, &why);
+  return rc ? fail(h, rc, why) : NDT_OK;
+}
+
+bool layout_valid(size_t stride_bytes, long intensity_offset_bytes) {
+  if (stride_bytes < 12 || stride_bytes % 4) return false;
+  return intensity_offset_bytes < 0 || (intensity_offset_bytes % 4 == 0 && intensity_offset_bytes >= 12 &&
+                                        (size_t)intensity_offset_bytes + 4 <= stride_bytes);
+}
+
+// a strided host cloud and its times -> the handle's device scratch [x | y | z | t | intensity] of n floats each, through
+// the pinned staging (one transfer, enqueued on the engine's stream)
+int deskew_upload(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, long intensity_offset_bytes, const float* t) {
+  DeskewBufs& b = h->dsk;
+  const bool has_i = intensity_offset_bytes >= 0;
+  const size_t words = (has_i ? 5 : 4) * n;
+  if (words > b.stage.cap) HIP_TRY(h, b.stage.ensure(5 * n + (5 * n) / 8 + 4096));
+  HIP_TRY(h, b.in.ensure(5 * n));
+  float* sx = b.stage.h, *sy = sx + n, *sz = sy + n, *st = sz + n, *si = st + n;
+  const char* base = reinterpret_cast<const char*>(xyz);
+  for (size_t i = 0; i < n; ++i) {
+    const float* p = reinterpret_cast<const float*>(base + i * stride_bytes);
+    sx[i] = p[0]; sy[i] = p[1]; sz[i] = p[2];
+    if (has_i) si[i] = *reinterpret_cast<const float*>(base + i * stride_bytes + intensity_offset_bytes);
+  }
+  std::memcpy(st, t, n * sizeof(float));
+  HIP_TRY(h, hipMemcpyAsync(b.in.p, b.stage.h, words * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  return NDT_OK;
+}
+
+}  // namespace
+}  // namespace engine
+}  // namespace ndt
+
+extern "C" {
+
+int ndt_deskew_device(ndt_handle* h, const float* dx, const float* dy, const float* dz, const float* d_intensity, const float* d_t,
+                      size_t n, const double* knot_t, const double* knot_poses16, int n_knots, const double* ref_pose16_or_null,
+                      const ndt_scan_filter* filter_or_null, float* ox, float* oy, float* oz, float* o_intensity,
+                      int32_t* d_index_out, size_t cap, size_t* n_out) {
+  if (!h || !n_out || ((!dx || !dy || !dz || !d_t) && n) || ((!ox || !oy || !oz) && cap && n)) return NDT_ERR_INVALID_ARG;
+  traj::KnotRow rows[traj::MAX_KNOTS];
+  int rc = deskew_check(h, n, knot_t, knot_poses16, n_knots, ref_pose16_or_null, rows);
+  if (rc) return rc;
+  if (o_intensity && !d_intensity) return fail(h, NDT_ERR_INVALID_ARG, "deskew: an intensity output without an intensity input");
+  if (!filter_or_null && cap < n) {
+    *n_out = n;
+    return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(n) + " points selected");
+  }
+  {
+    // compacting: the emit writes where other threads still read -- no output may overlap an input.  Aligned: a thread
+    // reads element i of every input before it writes element i of every output, so an output may BE an input array
+    // (same address), but must not overlap one in any other way.
+    const size_t m = std::min(cap, n) * sizeof(float), nb = n * sizeof(float);
+    const void* ins[5] = {dx, dy, dz, d_t, d_intensity};
+    const void* outs[5] = {ox, oy, oz, o_intensity, d_index_out};
+    for (const void* o : outs)
+      for (const void* i : ins)
+        if (ranges_overlap(o, m, i, nb) && (filter_or_null || o != i))
+          return fail(h, NDT_ERR_INVALID_ARG, filter_or_null ? "deskew: a compacted output overlaps an input"
+                                                             : "deskew: an output overlaps an input without being that array");
+  }
+  rc = bind_device(h);
+  if (rc) return rc;
+  return deskew_device(h, dx, dy, dz, d_intensity, d_t, n, rows, n_knots, filter_or_null, ox, oy, oz, o_intensity, d_index_out, cap,
+                       n_out);
+}
+
+int ndt_deskew(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, long intensity_offset_bytes, const float* t,
+               const double* knot_t, const double* knot_poses16, int n_knots, const double* ref_pose16_or_null,
+               const ndt_scan_filter* filter_or_null, float* out, int32_t* index_out, size_t cap, size_t* n_out) {
+  if (!h || !n_out || ((!xyz || !t) && n) || (!out && cap && n) || !layout_valid(stride_bytes, intensity_offset_bytes))
+    return NDT_ERR_INVALID_ARG;
+  traj::KnotRow rows[traj::MAX_KNOTS];
+  int rc = deskew_check(h, n, knot_t, knot_poses16, n_knots, ref_pose16_or_null, rows);
+  if (rc) return rc;
+  if (!filter_or_null && cap < n) {
+    *n_out = n;
+    return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(n) + " points selected");
+  }
+  *n_out = 0;
+  rc = bind_device(h);
+  if (rc) return rc;
+  if (n == 0) return NDT_OK;
+  rc = deskew_upload(h, xyz, n, stride_bytes, intensity_offset_bytes, t);
+  if (rc) return rc;
+  DeskewBufs& b = h->dsk;
+  const bool has_i = intensity_offset_bytes >= 0;
+  HIP_TRY(h, b.out.ensure(4 * n));
+  HIP_TRY(h, b.index.ensure(n));
+  const float* in = b.in.p;
+  float* o = b.out.p;
+  rc = deskew_device(h, in, in + n, in + 2 * n, has_i ? in + 4 * n : nullptr, in + 3 * n, n, rows, n_knots, filter_or_null, o, o + n,
+                     o + 2 * n, has_i ? o + 3 * n : nullptr, index_out ? b.index.p : nullptr, n, n_out);
+  if (rc) return rc;
+  const size_t m = *n_out;
+  if (m > cap) return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(m) + " points selected");
+  if (m == 0) return NDT_OK;
+  // (the staging is free again: the upload out of it has been awaited)
+  float* back = b.stage.h;
+  const int cols = has_i ? 4 : 3;
+  for (int a = 0; a < cols; ++a)
+    HIP_TRY(h, hipMemcpyAsync(back + (size_t)a * m, o + (size_t)a * n, m * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (index_out) HIP_TRY(h, hipMemcpyAsync(index_out, b.index.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  char* ob = reinterpret_cast<char*>(out);
+  for (size_t i = 0; i < m; ++i) {
+    float* p = reinterpret_cast<float*>(ob + i * stride_bytes);
+    p[0] = back[i]; p[1] = back[m + i]; p[2] = back[2 * m + i];
+    if (has_i) *reinterpret_cast<float*>(ob + i * stride_bytes + intensity_offset_bytes) = back[3 * m + i];
+  }
+  return NDT_OK;
+}
+
+int ndt_keyframe_put_deskewed(ndt_handle* h, int64_t id, const float* xyz, size_t n, size_t stride_bytes,
+                              long intensity_offset_bytes, const float* t, const double* knot_t, const double* knot_poses16,
+                              int n_knots, const double* ref_pose16_or_null, const ndt_scan_filter* filter_or_null,
+                              size_t* n_kept) {
+  if (!h || ((!xyz || !t) && n) || !layout_valid(stride_bytes, intensity_offset_bytes)) return NDT_ERR_INVALID_ARG;
+  traj::KnotRow rows[traj::MAX_KNOTS];
+  int rc = deskew_check(h, n, knot_t, knot_poses16, n_knots, ref_pose16_or_null, rows);
+  if (rc) return rc;
+  rc = bind_device(h);
+  if (rc) return rc;
+  if (n) {
+    rc = deskew_upload(h, xyz, n, stride_bytes, intensity_offset_bytes, t);
+    if (rc) return rc;
+  }
+  // every argument error has been reported by now.  From here on only a HIP error (allocation, launch) can end the call
+  // early, and it leaves keyframe `id` in the archive with no point (n = 0) -- never with the previous scan's count over
+  // buffers that may have been re-allocated, never with a half-written scan that counts
+  ndt_handle::Keyframe& kf = keyframe_claim(h, id, n);
+  kf.n = 0;
+  HIP_TRY(h, kf.x.ensure(n));
+  HIP_TRY(h, kf.y.ensure(n));
+  HIP_TRY(h, kf.z.ensure(n));
+  const float* in = h->dsk.in.p;
+  size_t m = 0;
+  rc = deskew_device(h, in, in + n, in + 2 * n, intensity_offset_bytes >= 0 ? in + 4 * n : nullptr, in + 3 * n, n, rows, n_knots,
+                     filter_or_null, kf.x.p, kf.y.p, kf.z.p, nullptr, nullptr, n, &m);
+  if (rc) return rc;
+  kf.n = m;
+  if (n_kept) *n_kept = m;
+  return NDT_OK;
+}
+
+}  // extern "C"

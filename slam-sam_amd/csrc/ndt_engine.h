@@ -7,6 +7,7 @@
 //   ndt_point_scores.hip  per-point scores and the score-based source filter (its compaction kernels included)
 //   ndt_map.hip        the sparse voxel map accumulated scan by scan (ndt_map_*), its kernels included
 //   ndt_map_state.hip  the map's crop, full-state export / import and merge (k_mapstate_* kernels)
+//   ndt_deskew.hip     motion compensation of a scan along a pose trajectory + the acquisition filter (its kernels included)
 // One handle = one engine instance = one HIP stream on one gfx950 device; it owns every device allocation.  There is no
 // CPU path: without a device every compute call fails with NDT_ERR_NO_DEVICE.
 #pragma once
@@ -176,6 +177,23 @@ struct PointScoreBufs {
   DevBuf<float> out;                 // [x | y | z] of the selected points
   void release() {
     score.release(); best.release(); npairs.release(); index.release(); cell.release(); counts.release(); out.release();
+  }
+};
+
+// Scratch of the deskew calls (ndt_deskew.hip), kept between calls: the knot table and its pinned staging, the
+// compaction's block counts, and for the host forms the raw scan and the result on the device and a pinned staging.
+struct DeskewBufs {
+  DevBuf<double> tab;                // <= 64 rows of 12 doubles (traj::KnotRow)
+  PinBuf<double> tab_h;
+  DevBuf<unsigned int> counts;       // per-block counts / offsets, then the total
+  PinBuf<unsigned int> total_h;
+  DevBuf<float> in;                  // [x | y | z | t | intensity] of a host scan
+  DevBuf<float> out;                 // [x | y | z | intensity] of the result
+  DevBuf<int> index;
+  PinBuf<float> stage;               // the host scan on its way up, the result on its way down
+  void release() {
+    tab.release(); tab_h.release(); counts.release(); total_h.release(); in.release(); out.release(); index.release();
+    stage.release();
   }
 };
 
@@ -354,6 +372,7 @@ struct ndt_handle {
   PinBuf<unsigned long long> flag;   // 32 result slots {seq, value} the single-pose kernel writes for the host
   DevBuf<double> partials, dres;
   PointScoreBufs ps;                 // scratch of ndt_score_points / ndt_filter_source (ndt_point_scores.hip)
+  DeskewBufs dsk;                    // scratch of ndt_deskew* / ndt_keyframe_put_deskewed (ndt_deskew.hip)
   DevBuf<unsigned int> counters;     // per-pose tickets of the in-kernel final reduction
   size_t counters_zeroed = 0;
   DevBuf<PoseConsts> dposes;
@@ -485,6 +504,9 @@ int report_deferred(ndt_handle* h);
 int settle(ndt_handle* h);
 void settle_discard_keep_grid(ndt_handle* h);
 void settle_discard(ndt_handle* h);
+// ndt_keyframes.hip: the archive entry `id` for a scan of n points -- a new entry takes pooled buffers that are large
+// enough, a replaced one that is the viewed source unsets the source; the caller fills x / y / z and sets n
+ndt_handle::Keyframe& keyframe_claim(ndt_handle* h, int64_t id, size_t n);
 void map_release(ndt_handle* h);   // ndt_map.hip: frees the voxel map, if any (ndt_destroy)
 // ndt_map.hip's host side as ndt_map_state.hip uses it (the kernels stay where they are)
 constexpr int64_t MAP_MAX_CAPACITY = 1ll << 30;   // slots are 32-bit sort keys with one sentinel above them

@@ -239,6 +239,9 @@ void launch_point_scores(const float* sx, const float* sy, const float* sz, size
 // an exclusive scan of the counts by one block (*d_total receives the number selected), then the emit -- every block
 // recomputes its ballots and writes behind its offset; at most `cap` points are written.  Integer counters only.
 int filter_blocks(size_t n);
+// the scan on its own (shared with the deskew's compaction, ndt_deskew.hip): d_counts[0 .. nb) -> their exclusive prefix
+// sums in place, d_counts[nb] and *d_total receive the sum; one block of 1024 threads, 1024 counts per pass
+void launch_filter_scan(unsigned int* d_counts, int nb, unsigned int* d_total, hipStream_t s);
 void launch_filter_compact(const double* d_value, const float* sx, const float* sy, const float* sz, size_t n, double thr,
                            int keep_below, unsigned int* d_block_counts /* filter_blocks(n) + 1 */, unsigned int* d_total,
                            float* ox, float* oy, float* oz, int* o_index, size_t cap, hipStream_t s);

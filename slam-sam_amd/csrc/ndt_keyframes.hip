@@ -1,6 +1,30 @@
 // ndt_keyframes.hip -- multi-grid targets, device-resident keyframe archive, voxel downsample (see ndt_engine.h).
 #include "ndt_engine.h"
 
+namespace ndt {
+namespace engine {
+
+ndt_handle::Keyframe& keyframe_claim(ndt_handle* h, int64_t id, size_t n) {
+  const bool fresh = h->keyframes.find(id) == h->keyframes.end();
+  ndt_handle::Keyframe& kf = h->keyframes[id];
+  if (fresh) {   // the buffers of an erased keyframe that are large enough, if any (the stream orders their reuse)
+    for (size_t i = 0; i < h->keyframe_pool.size(); ++i)
+      if (h->keyframe_pool[i].x.cap >= n && h->keyframe_pool[i].y.cap >= n && h->keyframe_pool[i].z.cap >= n) {
+        kf = h->keyframe_pool[i];
+        h->keyframe_pool.erase(h->keyframe_pool.begin() + (long)i);
+        break;
+      }
+  }
+  if (kf.x.p && h->vx == kf.x.p) {   // the keyframe being replaced is the viewed source: it has to be set again
+    h->vx = h->vy = h->vz = nullptr;
+    h->n_src = 0;
+  }
+  return kf;
+}
+
+}  // namespace engine
+}  // namespace ndt
+
 extern "C" {
 
 // ---- multi-grid target [RECALLED: tier4 ndt_omp multigrid_ndt_omp.h / multi_voxel_grid_covariance_omp.h,
@@ -169,20 +193,7 @@ int ndt_keyframe_put(ndt_handle* h, int64_t id, const float* xyz, size_t n, size
   if (!h || (!xyz && n) || stride_bytes < 12 || stride_bytes % 4) return NDT_ERR_INVALID_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  const bool fresh = h->keyframes.find(id) == h->keyframes.end();
-  ndt_handle::Keyframe& kf = h->keyframes[id];
-  if (fresh) {   // the buffers of an erased keyframe that are large enough, if any (the stream orders their reuse)
-    for (size_t i = 0; i < h->keyframe_pool.size(); ++i)
-      if (h->keyframe_pool[i].x.cap >= n && h->keyframe_pool[i].y.cap >= n && h->keyframe_pool[i].z.cap >= n) {
-        kf = h->keyframe_pool[i];
-        h->keyframe_pool.erase(h->keyframe_pool.begin() + (long)i);
-        break;
-      }
-  }
-  if (kf.x.p && h->vx == kf.x.p) {   // the keyframe being replaced is the viewed source: it has to be set again
-    h->vx = h->vy = h->vz = nullptr;
-    h->n_src = 0;
-  }
+  ndt_handle::Keyframe& kf = keyframe_claim(h, id, n);
   // like a host hand-off: the caller's cloud is consumed when the call returns, the transfer runs behind it on the
   // engine's stream, where everything that reads the archive is enqueued too
   rc = upload_soa(h, h->lane_t, h->stream, xyz, nullptr, nullptr, nullptr, n, stride_bytes, kf.x, kf.y, kf.z,

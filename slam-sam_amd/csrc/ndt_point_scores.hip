@@ -93,6 +93,10 @@ __global__ void __launch_bounds__(FILT_THREADS) k_filter_emit(const double* __re
 
 }  // namespace
 
+void launch_filter_scan(unsigned int* d_counts, int nb, unsigned int* d_total, hipStream_t s) {
+  hipLaunchKernelGGL(k_filter_scan, dim3(1), dim3(SCAN_THREADS), 0, s, d_counts, nb, d_total);
+}
+
 int filter_blocks(size_t n) { return (int)((n + FILT_THREADS - 1) / FILT_THREADS); }
 
 void launch_filter_compact(const double* d_value, const float* sx, const float* sy, const float* sz, size_t n, double thr,
@@ -102,7 +106,7 @@ void launch_filter_compact(const double* d_value, const float* sx, const float* 
   const int nb = filter_blocks(n);
   const unsigned int ucap = (unsigned int)std::min<size_t>(cap, n);
   hipLaunchKernelGGL(k_filter_count, dim3((unsigned)nb), dim3(FILT_THREADS), 0, s, d_value, (int)n, thr, keep_below, d_block_counts);
-  hipLaunchKernelGGL(k_filter_scan, dim3(1), dim3(SCAN_THREADS), 0, s, d_block_counts, nb, d_total);
+  launch_filter_scan(d_block_counts, nb, d_total, s);
   hipLaunchKernelGGL(k_filter_emit, dim3((unsigned)nb), dim3(FILT_THREADS), 0, s, d_value, sx, sy, sz, (int)n, thr, keep_below,
                      d_block_counts, ox, oy, oz, o_index, ucap);
 }
