@@ -448,6 +448,87 @@ int ndt_keyframe_put_deskewed(ndt_handle* h, int64_t id, const float* xyz, size_
                               int n_knots, const double* ref_pose16_or_null, const ndt_scan_filter* filter_or_null,
                               size_t* n_kept);
 
+/* Unprojection of a lidar range image on the device, fused with the acquisition filter and the deskew.  The drivers'
+ * lidar callback turns every pixel of the range image into a point with one multiply-add per coordinate against a
+ * lookup table (ref: src/lidarcallback.cpp:191-327 builds it, :455-545 and :570-610 use it), applies the range filter
+ * and the acquisition filter and pushes the point; these calls take the range image as received -- a 20-bit range in
+ * millimetres and one reflectivity byte per pixel, one time per column, column by column -- and return the filtered,
+ * deskewed, compacted scan (or, without a filter, the organised cloud).  Packet parsing stays with the driver.
+ *
+ * The scan model: the unprojection tables of the lidar callback (ref: src/lidarcallback.cpp:286-327):
+ *   p = range_m * (x1,y1,z1)[col * n_rows + row] + (x2,y2,z2)[col]
+ * x1,y1,z1: n_cols*n_rows floats each; x2,y2,z2: n_cols floats each; host pointers, copied to the device and kept
+ * until replaced, cleared or the handle is destroyed.  1 <= n_rows, 1 <= n_cols, n_cols*n_rows <= INT32_MAX.
+ * ndt_scan_model_get_info returns 0, 0 when none is set. */
+int ndt_scan_model_set(ndt_handle* h, int n_cols, int n_rows, const float* x1, const float* y1, const float* z1,
+                       const float* x2, const float* y2, const float* z2);
+int ndt_scan_model_clear(ndt_handle* h);
+int ndt_scan_model_get_info(const ndt_handle* h, int* n_cols, int* n_rows);
+/* host only, no handle, no device: the tables as the callback's Initialize() computes them, in its arithmetic (float
+ * angles, float sin/cos, the 4x4 lidar->body transform in double, one rounding to float):
+ *   azimuth of column m = 2 pi (1 - m / n_cols) + beam azimuth of the row; direction = lidar_to_body's rotation applied
+ *   to (cos alt cos az, cos alt sin az, sin alt); offset = lidar_to_body applied to (r0 cos az_m, r0 sin az_m, 0, 1) with
+ *   r0 = lidar_origin_to_beam_origin_mm / 1000.
+ * n_rows beam angles each, in degrees.  NDT_ERR_INVALID_ARG when a pointer is NULL, a size is below 1, n_cols*n_rows
+ * exceeds INT32_MAX or an angle, the beam origin or a transform entry is not finite; nothing is written then. */
+int ndt_scan_model_from_beams(int n_cols, int n_rows, const float* beam_azimuth_deg, const float* beam_altitude_deg,
+                              double lidar_origin_to_beam_origin_mm, const double lidar_to_body16_colmajor[16],
+                              float* x1, float* y1, float* z1, float* x2, float* y2, float* z2);
+typedef struct ndt_range_gate {
+  int use_range;  float range_min, range_max;   /* rangeFilter, metres, inclusive (ref: :531, :575) */
+  int row_step;                                 /* channel stride: only rows with row % row_step == 0; 0 or 1 = all */
+} ndt_range_gate;
+/* Per pixel i = col * n_rows + row of the range image (gate_or_null == NULL: no range filter, every row):
+ *   valid = range_mm[i] != 0 && row % row_step == 0 && finite(col_t[col])
+ *           && (!use_range || (range_min <= range_m && range_m <= range_max))
+ *           (a non-finite column time marks a column that never arrived);
+ *   range_m = (float)range_mm[i] * 0.001f, one f32 multiply;
+ *   x = fmaf(range_m, x1[i], x2[col]), y and z likewise: a fused multiply-add with a single rounding, as the
+ *           reference's AVX path computes it (ref: :512-514), whatever the compiler's contraction setting;
+ *   intensity = (float)reflectivity[i], t = col_t[col];
+ *   n_knots > 0: the point is moved exactly as ndt_deskew moves (x, y, z, t) -- the same trajectory model, the same
+ *           ref_pose16_or_null, the same rigid-segment and exact-identity rules; n_knots == 0 with knot_t, knot_poses16
+ *           and ref_pose16_or_null NULL: no motion, the raw point comes out;
+ *   filter_or_null != NULL: ndt_scan_filter on the RAW (x, y, z) with (float)reflectivity as the intensity (none
+ *           without a reflectivity array) -- exactly the predicate of ndt_deskew.
+ * ndt_unproject_device: d_range_mm (n_cols*n_rows uint32), d_reflectivity (n_cols*n_rows bytes, nullable), d_col_t
+ * (n_cols floats) and every output in device memory; o_intensity, o_t and d_index_out are nullable (o_intensity needs
+ * d_reflectivity); d_index_out receives the pixel index i.
+ *  - filter_or_null == NULL (organised): one launch, out[i] is pixel i, an invalid pixel gives NaN in x, y and z,
+ *    intensity and t are written as they are; *n_out = n_cols*n_rows; cap >= that (NDT_ERR_INVALID_ARG otherwise).
+ *  - filter_or_null != NULL (compacting): the valid, kept points densely and in pixel order, the order in which the
+ *    reference's decode pushes them (the three launches of ndt_deskew's compaction: ballots, one block scanning the
+ *    block counts, emit; integer offsets, no atomics).  A zeroed filter drops only the invalid pixels.  At most cap
+ *    points are written, *n_out is the number selected, NDT_ERR_INVALID_ARG naming it if it exceeds cap.
+ * Any overlap of an output with an input, or of two outputs with each other, is refused (the outputs are distinct
+ * arrays).  NDT_ERR_INVALID_ARG also when no model is set, a required
+ * pointer is NULL, row_step is negative, use_range is set with range_min > range_max (or a NaN bound), or the
+ * trajectory is refused by the rules of ndt_deskew.  Everything runs on the engine's stream and is complete when the
+ * call returns.  The handle's target, source, align state, iteration history, evaluation counters, map and archive are
+ * left alone.  An argument error refuses the call as a whole: nothing is written. */
+int ndt_unproject_device(ndt_handle* h, const uint32_t* d_range_mm, const uint8_t* d_reflectivity, const float* d_col_t,
+                         const ndt_range_gate* gate_or_null, const double* knot_t, const double* knot_poses16, int n_knots,
+                         const double* ref_pose16_or_null, const ndt_scan_filter* filter_or_null, float* ox, float* oy,
+                         float* oz, float* o_intensity, float* o_t, int32_t* d_index_out, size_t cap, size_t* n_out);
+/* host form: range_mm (n_cols*n_rows uint32), reflectivity (n_cols*n_rows bytes, nullable) and col_t (n_cols floats)
+ * are contiguous host arrays and go up through pinned staging in ONE transfer; out: a strided cloud laid out as
+ * ndt_deskew's (x, y, z and, with intensity_offset_bytes >= 0 -- which needs reflectivity --, the intensity of the
+ * first *n_out points are written; nothing if *n_out exceeds cap); t_out (nullable): n_out floats; index_out
+ * (nullable): n_out ints. */
+int ndt_unproject(ndt_handle* h, const uint32_t* range_mm, const uint8_t* reflectivity, const float* col_t,
+                  const ndt_range_gate* gate_or_null, const double* knot_t, const double* knot_poses16, int n_knots,
+                  const double* ref_pose16_or_null, const ndt_scan_filter* filter_or_null, float* out, size_t stride_bytes,
+                  long intensity_offset_bytes, float* t_out, int32_t* index_out, size_t cap, size_t* n_out);
+/* ndt_keyframe_put of the compacting output: the archive holds under `id` exactly what ndt_keyframe_put would hold for
+ * it -- replaced-keyframe and viewed-source rules and the buffer pool as in ndt_keyframe_put_deskewed -- so
+ * ndt_set_source_from_keyframe(id) and ndt_map_add_keyframe work on it: one upload of 5 bytes per pixel serves the
+ * source, the archive and the map.  filter_or_null == NULL means the zeroed filter here (an archive holds no NaN
+ * points).  *n_kept (nullable) receives the number of points archived.  An argument error leaves the archive untouched. */
+int ndt_keyframe_put_from_ranges(ndt_handle* h, int64_t id, const uint32_t* range_mm, const uint8_t* reflectivity,
+                                 const float* col_t, const ndt_range_gate* gate_or_null, const double* knot_t,
+                                 const double* knot_poses16, int n_knots, const double* ref_pose16_or_null,
+                                 const ndt_scan_filter* filter_or_null, size_t* n_kept);
+
 /* pcl::VoxelGrid downsample on the device (ref: run/pipeline_ins_map_distribution.cpp:324-340: the accumulated map
  * is filtered at `mapvoxelsize` before the NDT export).  PCL's published algorithm: the grid of
  * getMinMax3D over the finite points, voxel index floor(p * inv_leaf) - min_b, every field averaged (in float) over

@@ -879,6 +879,143 @@ class NormalDistributionsTransform
     return putKeyframeDeskewed(id, n ? &scan.points[0].x : nullptr, n, sizeof(P), intensity_offset_of<P>(0), t.data(),
                                knot_t.data(), poses.data(), (int)knot_t.size(), ref_pose ? ref : nullptr, filter);
   }
+  // ---- unprojection: the lidar callback's range image (a 20-bit range in millimetres and a reflectivity byte per pixel,
+  // one time per column, column by column) through the scan model's tables to points, with the range gate, the
+  // acquisition filter and the deskew in the same pass (ndt_unproject* in ndt_hip.h).  Replaces the point-forming part
+  // of LidarCallback::DecodePacket*; packet parsing stays with the driver. ----
+  // the tables as the callback's Initialize() computes them (host only); x1 .. z1: n_cols * n_rows, x2 .. z2: n_cols
+  struct ScanModel {
+    int n_cols = 0, n_rows = 0;
+    std::vector<float> x1, y1, z1, x2, y2, z2;
+  };
+  static bool scanModelFromBeams(int n_cols, const std::vector<float>& beam_azimuth_deg, const std::vector<float>& beam_altitude_deg,
+                                 double lidar_origin_to_beam_origin_mm, const Matrix4d* lidar_to_body, ScanModel& out) {
+    if (n_cols < 1 || beam_azimuth_deg.empty() || beam_azimuth_deg.size() != beam_altitude_deg.size()) return false;
+    const int n_rows = (int)beam_azimuth_deg.size();
+    const size_t n = (size_t)n_cols * (size_t)n_rows;
+    double T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    if (lidar_to_body) detail::to_colmajor(*lidar_to_body, 4, 4, T);
+    ScanModel m;
+    m.n_cols = n_cols; m.n_rows = n_rows;
+    m.x1.resize(n); m.y1.resize(n); m.z1.resize(n);
+    m.x2.resize((size_t)n_cols); m.y2.resize((size_t)n_cols); m.z2.resize((size_t)n_cols);
+    if (ndt_scan_model_from_beams(n_cols, n_rows, beam_azimuth_deg.data(), beam_altitude_deg.data(), lidar_origin_to_beam_origin_mm, T,
+                                  m.x1.data(), m.y1.data(), m.z1.data(), m.x2.data(), m.y2.data(), m.z2.data()) != NDT_OK)
+      return false;
+    out = std::move(m);
+    return true;
+  }
+  void setScanModel(int n_cols, int n_rows, const float* x1, const float* y1, const float* z1, const float* x2, const float* y2,
+                    const float* z2) {
+    status_ = h_ ? ndt_scan_model_set(h_, n_cols, n_rows, x1, y1, z1, x2, y2, z2) : NDT_ERR_NO_DEVICE;
+  }
+  void setScanModel(const ScanModel& m) {
+    const size_t n = (size_t)m.n_cols * (size_t)m.n_rows, nc = (size_t)m.n_cols;
+    if (m.n_cols < 1 || m.n_rows < 1 || m.x1.size() != n || m.y1.size() != n || m.z1.size() != n || m.x2.size() != nc ||
+        m.y2.size() != nc || m.z2.size() != nc) {
+      status_ = NDT_ERR_INVALID_ARG;
+      return;
+    }
+    setScanModel(m.n_cols, m.n_rows, m.x1.data(), m.y1.data(), m.z1.data(), m.x2.data(), m.y2.data(), m.z2.data());
+  }
+  void clearScanModel() { status_ = h_ ? ndt_scan_model_clear(h_) : NDT_ERR_NO_DEVICE; }
+  // pixels of the scan model that is set (0: none)
+  size_t scanModelPixels(int* n_cols = nullptr, int* n_rows = nullptr) const {
+    int c = 0, r = 0;
+    if (h_) (void)ndt_scan_model_get_info(h_, &c, &r);
+    if (n_cols) *n_cols = c;
+    if (n_rows) *n_rows = r;
+    return (size_t)c * (size_t)r;
+  }
+  // each returns the number of points written / archived (0 on error, lastStatus() says why); n_knots == 0 with the three
+  // trajectory pointers null: no motion
+  size_t unproject(const uint32_t* range_mm, const uint8_t* reflectivity, const float* col_t, const ndt_range_gate* gate_or_null,
+                   const double* knot_t, const double* knot_poses16, int n_knots, const double* ref_pose16_or_null,
+                   const ndt_scan_filter* filter_or_null, float* out, size_t stride_bytes, long intensity_offset_bytes, float* t_out,
+                   int32_t* index_out, size_t cap) {
+    size_t m = 0;
+    status_ = h_ ? ndt_unproject(h_, range_mm, reflectivity, col_t, gate_or_null, knot_t, knot_poses16, n_knots, ref_pose16_or_null,
+                                 filter_or_null, out, stride_bytes, intensity_offset_bytes, t_out, index_out, cap, &m)
+                 : NDT_ERR_NO_DEVICE;
+    return status_ == NDT_OK ? m : 0;
+  }
+  size_t unprojectDevice(const uint32_t* d_range_mm, const uint8_t* d_reflectivity, const float* d_col_t,
+                         const ndt_range_gate* gate_or_null, const double* knot_t, const double* knot_poses16, int n_knots,
+                         const double* ref_pose16_or_null, const ndt_scan_filter* filter_or_null, float* ox, float* oy, float* oz,
+                         float* o_intensity, float* o_t, int32_t* d_index_out, size_t cap) {
+    size_t m = 0;
+    status_ = h_ ? ndt_unproject_device(h_, d_range_mm, d_reflectivity, d_col_t, gate_or_null, knot_t, knot_poses16, n_knots,
+                                        ref_pose16_or_null, filter_or_null, ox, oy, oz, o_intensity, o_t, d_index_out, cap, &m)
+                 : NDT_ERR_NO_DEVICE;
+    return status_ == NDT_OK ? m : 0;
+  }
+  size_t putKeyframeFromRanges(int64_t id, const uint32_t* range_mm, const uint8_t* reflectivity, const float* col_t,
+                               const ndt_range_gate* gate_or_null, const double* knot_t, const double* knot_poses16, int n_knots,
+                               const double* ref_pose16_or_null, const ndt_scan_filter* filter_or_null) {
+    size_t m = 0;
+    status_ = h_ ? ndt_keyframe_put_from_ranges(h_, id, range_mm, reflectivity, col_t, gate_or_null, knot_t, knot_poses16, n_knots,
+                                                ref_pose16_or_null, filter_or_null, &m)
+                 : NDT_ERR_NO_DEVICE;
+    return status_ == NDT_OK ? m : 0;
+  }
+  // the typed face: the range image as vectors (n_cols * n_rows ranges and reflectivities -- the latter may be empty --,
+  // n_cols times), the knots' times and poses (both empty: no motion); returns the cloud (filter null: organised, every
+  // pixel, an invalid one as NaN) and, if asked for, each point's time and pixel index
+  template <class Cloud, class Poses>
+  Cloud unproject(const std::vector<uint32_t>& range_mm, const std::vector<uint8_t>& reflectivity, const std::vector<float>& col_t,
+                  const std::vector<double>& knot_t, const Poses& knot_poses, const Matrix4d* ref_pose = nullptr,
+                  const ndt_range_gate* gate = nullptr, const ndt_scan_filter* filter = nullptr, std::vector<float>* times = nullptr,
+                  std::vector<int32_t>* index = nullptr) {
+    Cloud out;
+    if (times) times->clear();
+    if (index) index->clear();
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return out; }
+    int n_cols = 0;
+    const size_t n = scanModelPixels(&n_cols);
+    if (range_mm.size() != n || col_t.size() != (size_t)n_cols || (!reflectivity.empty() && reflectivity.size() != n) ||
+        knot_t.size() != knot_poses.size()) {
+      status_ = NDT_ERR_INVALID_ARG;
+      return out;
+    }
+    using P = typename std::decay<decltype(out.points[0])>::type;
+    const bool moving = !knot_t.empty();
+    const std::vector<double> poses = detail::pack_poses(knot_poses);
+    double ref[16];
+    if (ref_pose) detail::to_colmajor(*ref_pose, 4, 4, ref);
+    out.points.resize(n);   // value-initialised points: the fields the engine does not write keep their defaults
+    std::vector<float> tt(times ? n + 1 : 0);
+    std::vector<int32_t> idx(index ? n + 1 : 0);
+    const size_t m = unproject(range_mm.data(), reflectivity.empty() ? nullptr : reflectivity.data(), col_t.data(), gate,
+                               moving ? knot_t.data() : nullptr, moving ? poses.data() : nullptr, (int)knot_t.size(),
+                               ref_pose ? ref : nullptr, filter, n ? &out.points[0].x : nullptr, sizeof(P),
+                               reflectivity.empty() ? -1 : intensity_offset_of<P>(0), times ? tt.data() : nullptr,
+                               index ? idx.data() : nullptr, n);
+    out.points.resize(m);
+    if (times && status_ == NDT_OK) times->assign(tt.begin(), tt.begin() + (std::ptrdiff_t)m);
+    if (index && status_ == NDT_OK) index->assign(idx.begin(), idx.begin() + (std::ptrdiff_t)m);
+    return out;
+  }
+  template <class Poses>
+  size_t putKeyframeFromRanges(int64_t id, const std::vector<uint32_t>& range_mm, const std::vector<uint8_t>& reflectivity,
+                               const std::vector<float>& col_t, const std::vector<double>& knot_t, const Poses& knot_poses,
+                               const Matrix4d* ref_pose = nullptr, const ndt_range_gate* gate = nullptr,
+                               const ndt_scan_filter* filter = nullptr) {
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return 0; }
+    int n_cols = 0;
+    const size_t n = scanModelPixels(&n_cols);
+    if (range_mm.size() != n || col_t.size() != (size_t)n_cols || (!reflectivity.empty() && reflectivity.size() != n) ||
+        knot_t.size() != knot_poses.size()) {
+      status_ = NDT_ERR_INVALID_ARG;
+      return 0;
+    }
+    const bool moving = !knot_t.empty();
+    const std::vector<double> poses = detail::pack_poses(knot_poses);
+    double ref[16];
+    if (ref_pose) detail::to_colmajor(*ref_pose, 4, 4, ref);
+    return putKeyframeFromRanges(id, range_mm.data(), reflectivity.empty() ? nullptr : reflectivity.data(), col_t.data(), gate,
+                                 moving ? knot_t.data() : nullptr, moving ? poses.data() : nullptr, (int)knot_t.size(),
+                                 ref_pose ? ref : nullptr, filter);
+  }
   // D(t) of that model as a matrix (host only)
   template <class Poses>
   static bool trajectoryPose(const std::vector<double>& knot_t, const Poses& knot_poses, double t, Matrix4d& out,

@@ -139,6 +139,20 @@ class ScanFilter(C.Structure):
         return f
 
 
+class RangeGate(C.Structure):
+    """ndt_range_gate: the range filter (metres, inclusive) and the channel stride of the unprojection calls.  A zeroed
+    gate passes every pixel that has a return."""
+    _fields_ = [("use_range", C.c_int), ("range_min", C.c_float), ("range_max", C.c_float), ("row_step", C.c_int)]
+
+    def __init__(self, range_min=None, range_max=None, row_step=0):
+        super().__init__()
+        if range_min is not None or range_max is not None:
+            self.use_range = 1
+            self.range_min = 0.0 if range_min is None else float(range_min)
+            self.range_max = np.inf if range_max is None else float(range_max)
+        self.row_step = int(row_step)
+
+
 class Timing(C.Structure):
     _fields_ = [
         ("ms_last_eval_kernel", C.c_double), ("ms_last_reduce_kernel", C.c_double),
@@ -265,6 +279,8 @@ ABI_SYMBOLS = [
     "ndt_map_export_device", "ndt_map_export", "ndt_set_target_from_map",
     "ndt_map_enable_moments", "ndt_map_has_moments", "ndt_map_export_moments", "ndt_set_target_from_map_moments",
     "ndt_trajectory_pose", "ndt_deskew_device", "ndt_deskew", "ndt_keyframe_put_deskewed",
+    "ndt_scan_model_set", "ndt_scan_model_clear", "ndt_scan_model_get_info", "ndt_scan_model_from_beams",
+    "ndt_unproject_device", "ndt_unproject", "ndt_keyframe_put_from_ranges",
     "ndt_map_crop", "ndt_map_export_state", "ndt_map_export_state_device", "ndt_map_import_state", "ndt_map_import_state_device",
 ]
 
@@ -399,6 +415,14 @@ def lib():
                                                                                          C.POINTER(C.c_size_t)]
         L.ndt_keyframe_put_deskewed.argtypes = [vp, C.c_int64, vp, C.c_size_t, C.c_size_t, C.c_long, vp] + traj + [
             C.POINTER(C.c_size_t)]
+        L.ndt_scan_model_set.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, fp, fp, fp]
+        L.ndt_scan_model_clear.argtypes = [vp]
+        L.ndt_scan_model_get_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.ndt_scan_model_from_beams.argtypes = [C.c_int, C.c_int, fp, fp, C.c_double, dp, fp, fp, fp, fp, fp, fp]
+        ranges = [vp, vp, vp, C.POINTER(RangeGate)] + traj
+        L.ndt_unproject_device.argtypes = [vp] + ranges + [vp, vp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ndt_unproject.argtypes = [vp] + ranges + [vp, C.c_size_t, C.c_long, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ndt_keyframe_put_from_ranges.argtypes = [vp, C.c_int64] + ranges + [C.POINTER(C.c_size_t)]
         L.ndt_set_handoff_mode.argtypes = [vp, C.c_int]
         L.ndt_get_handoff_mode.argtypes = [vp]
         L.ndt_wait.argtypes = [vp]
@@ -527,6 +551,30 @@ def trajectory_pose(knot_t, knot_poses, t, ref_pose=None):
     return out.reshape(4, 4).T.copy()
 
 
+def scan_model_from_beams(n_cols, beam_azimuth_deg, beam_altitude_deg, lidar_origin_to_beam_origin_mm, lidar_to_body=None):
+    """The unprojection tables of a spinning lidar as the drivers' lidar callback computes them (host only, no device):
+    p = range_m * (x1, y1, z1)[col, row] + (x2, y2, z2)[col].  One azimuth and one altitude angle per row, in degrees;
+    lidar_to_body: 4 x 4 (None: the identity).  Returns (x1, y1, z1 [n_cols, n_rows], x2, y2, z2 [n_cols]) float32, what
+    setScanModel takes."""
+    az = np.ascontiguousarray(beam_azimuth_deg, dtype=np.float32).ravel()
+    alt = np.ascontiguousarray(beam_altitude_deg, dtype=np.float32).ravel()
+    if len(az) != len(alt):
+        raise ValueError("one azimuth and one altitude angle per row")
+    n_cols, n_rows = int(n_cols), len(az)
+    T = np.eye(4) if lidar_to_body is None else np.asarray(lidar_to_body, dtype=np.float64)
+    if T.shape != (4, 4):
+        raise ValueError("lidar_to_body must be 4 x 4")
+    T16 = np.ascontiguousarray(T.T).ravel()
+    shape = (max(n_cols, 0), n_rows)
+    x1, y1, z1 = (np.zeros(shape, np.float32) for _ in range(3))
+    x2, y2, z2 = (np.zeros(shape[0], np.float32) for _ in range(3))
+    rc = lib().ndt_scan_model_from_beams(n_cols, n_rows, _fp(az), _fp(alt), float(lidar_origin_to_beam_origin_mm), _dp(T16),
+                                         _fp(x1), _fp(y1), _fp(z1), _fp(x2), _fp(y2), _fp(z2))
+    if rc != 0:
+        raise NdtError(rc, "ndt_scan_model_from_beams")
+    return x1, y1, z1, x2, y2, z2
+
+
 def shard_range(n, rank, nranks):
     b, c = C.c_size_t(), C.c_size_t()
     lib().ndt_shard_range(n, rank, nranks, C.byref(b), C.byref(c))
@@ -587,6 +635,7 @@ class NormalDistributionsTransform:
             raise NdtError(rc, "ndt_create failed (a gfx950 device is required; no CPU fallback)")
         self._raw, self._cooked = None, None
         self._keep = []
+        self.last_unproject_count = 0      # *n_out of the last unprojectDevice call, also when it was refused
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -802,6 +851,100 @@ class NormalDistributionsTransform:
         self._check(lib().ndt_keyframe_put_deskewed(self._h, int(kf_id), a.ctypes.data, len(a), stride, off, tt.ctypes.data,
                                                     _dp(kt), _dp(poses), n, None if ref is None else _dp(ref),
                                                     self._filter_ref(filter), C.byref(m)))
+        return int(m.value)
+
+    # --- unprojection: a range image through the scan model's tables, gate + filter + deskew in the same pass ---
+    def setScanModel(self, x1, y1, z1, x2, y2, z2):
+        """The unprojection tables (scan_model_from_beams returns them): x1, y1, z1 [n_cols, n_rows], x2, y2, z2 [n_cols];
+        copied to the device and kept until replaced or cleared."""
+        d = [np.ascontiguousarray(a, dtype=np.float32) for a in (x1, y1, z1)]
+        o = [np.ascontiguousarray(a, dtype=np.float32).ravel() for a in (x2, y2, z2)]
+        if d[0].ndim != 2 or any(a.shape != d[0].shape for a in d) or any(len(a) != d[0].shape[0] for a in o):
+            raise ValueError("x1, y1, z1 must be n_cols x n_rows and x2, y2, z2 n_cols long")
+        self._check(lib().ndt_scan_model_set(self._h, d[0].shape[0], d[0].shape[1], _fp(d[0]), _fp(d[1]), _fp(d[2]), _fp(o[0]),
+                                             _fp(o[1]), _fp(o[2])))
+
+    def clearScanModel(self):
+        self._check(lib().ndt_scan_model_clear(self._h))
+
+    def scanModelInfo(self):
+        """(n_cols, n_rows) of the scan model, (0, 0) when none is set"""
+        c, r = C.c_int(0), C.c_int(0)
+        self._check(lib().ndt_scan_model_get_info(self._h, C.byref(c), C.byref(r)))
+        return c.value, r.value
+
+    @staticmethod
+    def _gate_ref(gate):
+        if gate is None:
+            return None
+        if not isinstance(gate, RangeGate):
+            raise TypeError("gate must be a RangeGate")
+        return C.byref(gate)
+
+    @staticmethod
+    def _trajectory_or_none(knot_t, knot_poses, ref_pose):
+        """the C-ABI's trajectory arguments; no knots at all = no motion"""
+        if knot_t is None and knot_poses is None and ref_pose is None:
+            return None, None, 0, None
+        kt, poses, n, ref = _trajectory_args(knot_t, knot_poses, ref_pose)
+        return _dp(kt), _dp(poses), n, None if ref is None else _dp(ref)
+
+    def _range_image(self, range_mm, reflectivity, col_t):
+        n_cols, n_rows = self.scanModelInfo()
+        r = np.ascontiguousarray(range_mm, dtype=np.uint32).ravel()
+        t = np.ascontiguousarray(col_t, dtype=np.float32).ravel()
+        refl = None if reflectivity is None else np.ascontiguousarray(reflectivity, dtype=np.uint8).ravel()
+        if n_cols and (len(r) != n_cols * n_rows or len(t) != n_cols or (refl is not None and len(refl) != len(r))):
+            raise ValueError("the range image must hold n_cols x n_rows pixels and one time per column of the scan model")
+        return r, refl, t, n_cols * n_rows
+
+    def unproject(self, range_mm, reflectivity, col_t, knot_t=None, knot_poses=None, ref_pose=None, gate=None, filter=None,
+                  with_t=False, with_index=False):
+        """The range image (uint32 millimetres [n_cols, n_rows], uint8 reflectivity or None, one float32 time per column)
+        as points through the scan model: filter None: the organised cloud, every pixel, an invalid one as NaN; a
+        ScanFilter: the valid, kept points in pixel order.  With knots the points are deskewed as deskew() does it.
+        Returns a cloud [m, 4] (x, y, z, intensity) -- [m, 3] without reflectivity --, then the times and the pixel
+        indices if asked for."""
+        r, refl, t, n = self._range_image(range_mm, reflectivity, col_t)
+        kt, poses, nk, ref = self._trajectory_or_none(knot_t, knot_poses, ref_pose)
+        cols = 3 if refl is None else 4
+        out = np.zeros((n, cols), np.float32)
+        tt = np.zeros(n, np.float32) if with_t else None
+        idx = np.zeros(n, np.int32) if with_index else None
+        m = C.c_size_t(0)
+        self._check(lib().ndt_unproject(self._h, r.ctypes.data, None if refl is None else refl.ctypes.data, t.ctypes.data,
+                                        self._gate_ref(gate), kt, poses, nk, ref, self._filter_ref(filter), out.ctypes.data,
+                                        4 * cols, -1 if refl is None else 12, None if tt is None else tt.ctypes.data,
+                                        None if idx is None else idx.ctypes.data, n, C.byref(m)))
+        res = [out[:m.value].copy()]
+        if with_t:
+            res.append(tt[:m.value].copy())
+        if with_index:
+            res.append(idx[:m.value].copy())
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def unprojectDevice(self, d_range_mm, d_reflectivity, d_col_t, ox, oy, oz, cap, knot_t=None, knot_poses=None, ref_pose=None,
+                        gate=None, filter=None, o_intensity=None, o_t=None, d_index=None):
+        """unproject on device arrays (integer device addresses; the reflectivity and the intensity, time and index outputs
+        may be None); returns the number of points written."""
+        kt, poses, nk, ref = self._trajectory_or_none(knot_t, knot_poses, ref_pose)
+        m = C.c_size_t(0)
+        rc = lib().ndt_unproject_device(self._h, d_range_mm, d_reflectivity, d_col_t, self._gate_ref(gate), kt, poses, nk, ref,
+                                        self._filter_ref(filter), ox, oy, oz, o_intensity, o_t, d_index, int(cap), C.byref(m))
+        self.last_unproject_count = int(m.value)
+        self._check(rc)
+        return int(m.value)
+
+    def putKeyframeFromRanges(self, kf_id, range_mm, reflectivity, col_t, knot_t=None, knot_poses=None, ref_pose=None, gate=None,
+                              filter=None):
+        """putKeyframe(kf_id, unproject(...)) with one upload of the range image (filter None: the zeroed filter -- an
+        archive holds no NaN points).  Returns the number of points archived."""
+        r, refl, t, _ = self._range_image(range_mm, reflectivity, col_t)
+        kt, poses, nk, ref = self._trajectory_or_none(knot_t, knot_poses, ref_pose)
+        m = C.c_size_t(0)
+        self._check(lib().ndt_keyframe_put_from_ranges(self._h, int(kf_id), r.ctypes.data, None if refl is None else refl.ctypes.data,
+                                                       t.ctypes.data, self._gate_ref(gate), kt, poses, nk, ref,
+                                                       self._filter_ref(filter), C.byref(m)))
         return int(m.value)
 
     def setInputSourceFromKeyframe(self, kf_id):

@@ -7,47 +7,15 @@
 // One thread per point, coalesced SoA loads; the knot table (<= 64 rows of 12 doubles) is copied into LDS by every block
 // and the segment is a binary search in it.  Integer offsets only, no atomics.  Everything on the engine's stream;
 // the target, the source, the align state, the history and the counters of the handle are not touched.
+// The predicate (dsk_keep), the knot table's LDS copy and the motion (dsk_move) live in ndt_deskew_device.h, shared with
+// ndt_unproject.hip.
 #include "ndt_engine.h"
+#include "ndt_deskew_device.h"
 #include "ndt_trajectory.h"
 
 namespace ndt {
 
 namespace {
-
-constexpr int DSK_THREADS = 256, DSK_WAVES = DSK_THREADS / 64;
-
-// the acquisition filter on the RAW point (sensor frame), every comparison inclusive as the header states it
-__device__ __forceinline__ bool dsk_keep(const ndt_scan_filter& f, float x, float y, float z, float t, const float* intensity,
-                                         size_t i) {
-  if (!(isfinite(x) && isfinite(y) && isfinite(z) && isfinite(t))) return false;
-  if (f.use_box && f.box_min[0] <= x && x <= f.box_max[0] && f.box_min[1] <= y && y <= f.box_max[1] && f.box_min[2] <= z &&
-      z <= f.box_max[2])
-    return false;
-  if (!f.use_z_or_intensity) return true;
-  if (f.z_min <= z && z <= f.z_max) return true;
-  return intensity != nullptr && intensity[i] >= f.intensity_keep_min;
-}
-
-// the block's copy of the knot table
-__device__ __forceinline__ void dsk_load_table(const double* __restrict__ table, int n_knots, double* s_tab) {
-  for (int w = (int)threadIdx.x; w < n_knots * traj::ROW_WORDS; w += DSK_THREADS) s_tab[w] = table[w];
-  __syncthreads();
-}
-
-// p' = R(q(u)) p + d(u) in f64, rounded to f32 once; the exact identity hands the point back as it is
-__device__ __forceinline__ void dsk_move(const traj::KnotRow* rows, int n_knots, float x, float y, float z, float t, float* ox,
-                                         float* oy, float* oz) {
-  double q[4], d[3], R[9];
-  if (traj::pose_at(rows, n_knots, (double)t, q, d)) {
-    *ox = x; *oy = y; *oz = z;
-    return;
-  }
-  traj::quat_to_rot(q, R);
-  const double px = (double)x, py = (double)y, pz = (double)z;
-  *ox = (float)(R[0] * px + R[1] * py + R[2] * pz + d[0]);
-  *oy = (float)(R[3] * px + R[4] * py + R[5] * pz + d[1]);
-  *oz = (float)(R[6] * px + R[7] * py + R[8] * pz + d[2]);
-}
 
 // (no __restrict__ on the clouds: the outputs may be the inputs -- every thread reads its point before it writes it)
 __global__ void __launch_bounds__(DSK_THREADS) k_deskew_aligned(const float* sx, const float* sy, const float* sz, const float* st,
@@ -132,12 +100,6 @@ __global__ void __launch_bounds__(DSK_THREADS) k_deskew_emit(const float* __rest
 namespace engine {
 namespace {
 
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  if (!a || !b || na == 0 || nb == 0) return false;
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb + nb && pb < pa + na;
-}
-
 // The trajectory's table to the device (pinned staging -> the handle's table, on the engine's stream), then the
 // launches; awaited.  dx .. dt (and di, ox .. o_index) are device arrays.  Arguments have been checked.
 int deskew_device(ndt_handle* h, const float* dx, const float* dy, const float* dz, const float* di, const float* dt, size_t n,
@@ -186,12 +148,6 @@ int deskew_check(ndt_handle* h, size_t n, const double* knot_t, const double* kn
   const char* why = "";
   const int rc = traj::build_rows(knot_t, knot_poses16, n_knots, ref16, rows, &why);
   return rc ? fail(h, rc, why) : NDT_OK;
-}
-
-bool layout_valid(size_t stride_bytes, long intensity_offset_bytes) {
-  if (stride_bytes < 12 || stride_bytes % 4) return false;
-  return intensity_offset_bytes < 0 || (intensity_offset_bytes % 4 == 0 && intensity_offset_bytes >= 12 &&
-                                        (size_t)intensity_offset_bytes + 4 <= stride_bytes);
 }
 
 // a strided host cloud and its times -> the handle's device scratch [x | y | z | t | intensity] of n floats each, through

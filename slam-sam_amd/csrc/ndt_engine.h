@@ -8,6 +8,7 @@
 //   ndt_map.hip        the sparse voxel map accumulated scan by scan (ndt_map_*), its kernels included
 //   ndt_map_state.hip  the map's crop, full-state export / import and merge (k_mapstate_* kernels)
 //   ndt_deskew.hip     motion compensation of a scan along a pose trajectory + the acquisition filter (its kernels included)
+//   ndt_unproject.hip  a lidar range image -> points through the scan model's tables, fused with that filter and deskew
 // One handle = one engine instance = one HIP stream on one gfx950 device; it owns every device allocation.  There is no
 // CPU path: without a device every compute call fails with NDT_ERR_NO_DEVICE.
 #pragma once
@@ -197,6 +198,28 @@ struct DeskewBufs {
   }
 };
 
+// The scan model of ndt_scan_model_set and the scratch of the unprojection calls (ndt_unproject.hip), kept between
+// calls: the model's tables, the knot table and its pinned staging, the compaction's block counts, and for the host and
+// keyframe forms the raw range image and the result on the device and a pinned staging.
+struct ScanModelBufs {
+  int n_cols = 0, n_rows = 0;        // 0, 0: no model set
+  DevBuf<float> dir;                 // [x1 | y1 | z1], n_cols * n_rows floats each, pixel col * n_rows + row
+  DevBuf<float> off;                 // [x2 | y2 | z2], n_cols floats each
+  DevBuf<double> tab;                // <= 64 rows of 12 doubles (traj::KnotRow)
+  PinBuf<double> tab_h;
+  DevBuf<unsigned int> counts;       // per-block counts / offsets, then the total
+  PinBuf<unsigned int> total_h;
+  DevBuf<uint32_t> in;               // a host range image: [range_mm (n words) | col_t (n_cols words) | reflectivity (n bytes)]
+  DevBuf<float> out;                 // [x | y | z | intensity | t] of the result
+  DevBuf<int> index;
+  PinBuf<uint32_t> stage;            // the range image on its way up, the result on its way down
+  void release() {
+    n_cols = n_rows = 0;
+    dir.release(); off.release(); tab.release(); tab_h.release(); counts.release(); total_h.release(); in.release();
+    out.release(); index.release(); stage.release();
+  }
+};
+
 // The sparse voxel map of ndt_map_* (ndt_map.hip): an open-addressing table in HBM keyed by the 63-bit voxel key
 // (k, j, i), the table position being the voxel's slot -- float sums {x, y, z, intensity} and an int32 count per slot,
 // and with moments on (ndt_map_enable_moments) the nine f64 sums of the target build {x, y, z, xx, xy, xz, yy, yz, zz}:
@@ -373,6 +396,7 @@ struct ndt_handle {
   DevBuf<double> partials, dres;
   PointScoreBufs ps;                 // scratch of ndt_score_points / ndt_filter_source (ndt_point_scores.hip)
   DeskewBufs dsk;                    // scratch of ndt_deskew* / ndt_keyframe_put_deskewed (ndt_deskew.hip)
+  ScanModelBufs scan;                // the scan model and the scratch of ndt_unproject* / ndt_keyframe_put_from_ranges (ndt_unproject.hip)
   DevBuf<unsigned int> counters;     // per-pose tickets of the in-kernel final reduction
   size_t counters_zeroed = 0;
   DevBuf<PoseConsts> dposes;

@@ -319,3 +319,96 @@ def _config_c3_wide(n_map, n_src, seed):
     guess = Ts @ pose_matrix(0.22, -0.12, 0.05, 0.0, 0.0, np.deg2rad(1.5))
     return dict(name="C3-wide %dk scan into %dk-pt open-terrain map, 0.5 m" % (n_src // 1000, n_map // 1000),
                 source=s, target=m, gt=Ts, guess=guess, resolution=0.5)
+
+
+# --------------------------------------------------------------------------- range images
+# The analytic scene of range_image(): a ground plane and two walls, each {x : normal . x = offset} in the world frame.
+RANGE_SCENE_PLANES = (((0.0, 0.0, 1.0), 0.0), ((1.0, 0.0, 0.0), 30.0), ((0.0, 1.0, 0.0), -20.0))
+
+
+def _rodrigues_many(w, u):
+    """Exp(u_i w) for a rotation vector w and factors u [m] -> [m, 3, 3]"""
+    th = np.linalg.norm(w)
+    if th == 0.0:
+        return np.broadcast_to(np.eye(3), (len(u), 3, 3)).copy()
+    k = w / th
+    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    a = np.asarray(u, np.float64) * th
+    return np.eye(3) + np.sin(a)[:, None, None] * K + (2.0 * np.sin(0.5 * a) ** 2)[:, None, None] * (K @ K)
+
+
+def trajectory_poses(knot_t, knot_poses, t):
+    """The pose body -> world of the deskew model at the times t [m] (clamped to the knots): the attitude along the
+    geodesic between the two knots, the position blended linearly -> (R [m, 3, 3], p [m, 3])."""
+    kt, kp = np.asarray(knot_t, np.float64), np.asarray(knot_poses, np.float64)
+    t = np.clip(np.asarray(t, np.float64), kt[0], kt[-1])
+    R = np.broadcast_to(kp[0][:3, :3], (len(t), 3, 3)).copy()
+    p = np.broadcast_to(kp[0][:3, 3], (len(t), 3)).copy()
+    if len(kt) == 1:
+        return R, p
+    seg = np.clip(np.searchsorted(kt, t, side="right") - 1, 0, len(kt) - 2)
+    for k in range(len(kt) - 1):
+        m = seg == k
+        if not m.any():
+            continue
+        u = (t[m] - kt[k]) / (kt[k + 1] - kt[k])
+        R[m] = kp[k][:3, :3] @ _rodrigues_many(so3_log(kp[k][:3, :3].T @ kp[k + 1][:3, :3]), u)
+        p[m] = kp[k][:3, 3] + u[:, None] * (kp[k + 1][:3, 3] - kp[k][:3, 3])
+    return R, p
+
+
+def range_image(model, knot_t, knot_poses, col_t, seed=0, no_return=0.05, drop_columns=0, range_max=200.0, range_min=0.3):
+    """A seeded lidar range image of RANGE_SCENE_PLANES seen from a sensor that moves along the trajectory (knot_t,
+    knot_poses: body -> world, the deskew model) while it scans: column c is taken at col_t[c] (rounded to float32, as
+    the image carries it) through the scan model `model` = (x1, y1, z1 [n_cols, n_rows], x2, y2, z2 [n_cols]) -- the ray
+    of pixel (c, r) leaves (x2, y2, z2)[c] along (x1, y1, z1)[c, r] in the body frame, the range is the factor of that
+    direction as the unprojection applies it.  Ranges are quantised to whole millimetres (0: no surface within
+    [range_min, range_max] m), reflectivities are drawn, a share `no_return` of the pixels is zeroed and `drop_columns`
+    columns get a NaN time (their ranges stay: the time alone marks them).  Returns a dict: range_mm uint32 and
+    reflectivity uint8 [n_cols, n_rows], col_t float32 [n_cols], surface int8 [n_cols, n_rows] (the plane a pixel was
+    cast at, -1: none), dropped (the column indices), planes."""
+    x1, y1, z1, x2, y2, z2 = (np.asarray(a, np.float32).astype(np.float64) for a in model)
+    n_cols, n_rows = x1.shape
+    rng = np.random.default_rng(seed)
+    t32 = np.asarray(col_t, np.float32).ravel()
+    assert len(t32) == n_cols and np.isfinite(t32).all()
+    R, p = trajectory_poses(knot_t, knot_poses, t32.astype(np.float64))
+    origin = np.einsum("cij,cj->ci", R, np.stack([x2, y2, z2], 1)) + p                 # [n_cols, 3], world
+    direction = np.einsum("cij,crj->cri", R, np.stack([x1, y1, z1], 2))                # [n_cols, n_rows, 3]
+    best = np.full((n_cols, n_rows), np.inf)
+    surface = np.full((n_cols, n_rows), -1, np.int8)
+    for s, (normal, offset) in enumerate(RANGE_SCENE_PLANES):
+        normal = np.asarray(normal, np.float64)
+        den = direction @ normal
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = (offset - origin @ normal)[:, None] / den
+        hit = np.isfinite(r) & (r >= range_min) & (r <= range_max) & (r < best)
+        best[hit] = r[hit]
+        surface[hit] = s
+    range_mm = np.where(surface >= 0, np.rint(np.where(surface >= 0, best, 0.0) * 1000.0), 0.0).astype(np.uint32)
+    lost = rng.uniform(size=(n_cols, n_rows)) < no_return
+    range_mm[lost] = 0
+    surface[lost | (range_mm == 0)] = -1
+    reflectivity = rng.integers(0, 256, (n_cols, n_rows)).astype(np.uint8)
+    dropped = np.sort(rng.choice(n_cols, size=int(drop_columns), replace=False)) if drop_columns else np.zeros(0, np.int64)
+    t_out = t32.copy()
+    t_out[dropped] = np.nan
+    return dict(range_mm=range_mm, reflectivity=reflectivity, col_t=t_out, surface=surface, dropped=dropped,
+                planes=RANGE_SCENE_PLANES)
+
+
+def unproject_numpy(model, range_mm, col_t, knot_t=None, knot_poses=None, ref_pose=None):
+    """The unprojection (and, with knots, the deskew into ref_pose, None: the last knot) in float64 on the host, a
+    reference for tests: [n_cols, n_rows, 3], NaN where a pixel has no return or its column no time."""
+    x1, y1, z1, x2, y2, z2 = (np.asarray(a, np.float32).astype(np.float64) for a in model)
+    rm = (np.asarray(range_mm, np.uint32).astype(np.float32) * np.float32(0.001)).astype(np.float64)
+    pts = np.stack([rm * x1 + x2[:, None], rm * y1 + y2[:, None], rm * z1 + z2[:, None]], 2)
+    t = np.asarray(col_t, np.float32).astype(np.float64)
+    bad = (np.asarray(range_mm) == 0) | ~np.isfinite(t)[:, None]
+    if knot_t is not None:
+        ref = np.asarray(knot_poses, np.float64)[-1] if ref_pose is None else np.asarray(ref_pose, np.float64)
+        R, p = trajectory_poses(knot_t, knot_poses, np.where(np.isfinite(t), t, 0.0))
+        world = np.einsum("cij,crj->cri", R, pts) + p[:, None, :]
+        pts = (world - ref[:3, 3]) @ ref[:3, :3]
+    pts[bad] = np.nan
+    return pts
