@@ -1,15 +1,15 @@
 // ndt_deskew.hip -- motion compensation of a scan from per-point times and a pose trajectory, with the acquisition
 // filter of the drivers in the same pass (see ndt_trajectory.h for the model, include/ndt_hip.h for the contract).
 //   aligned    (no filter)  ONE launch of k_deskew_aligned: out[i] = deskewed in[i], a non-finite point -> NaN
-//   compacting (filter)     the three launches of ndt_filter_source's compaction: k_deskew_count (wave ballots of the
-//                           predicate -> per-block counts), the shared one-block scan (launch_filter_scan), k_deskew_emit
-//                           (the ballots again, the per-block LDS scan, the deskewed point behind its offset)
+//   compacting (filter)     the stable compaction of ndt_compact_device.h in three launches: k_deskew_count, the
+//                           one-block scan (launch_filter_scan), k_deskew_emit (the deskewed point behind its offset)
 // One thread per point, coalesced SoA loads; the knot table (<= 64 rows of 12 doubles) is copied into LDS by every block
 // and the segment is a binary search in it.  Integer offsets only, no atomics.  Everything on the engine's stream;
 // the target, the source, the align state, the history and the counters of the handle are not touched.
 // The predicate (dsk_keep), the knot table's LDS copy and the motion (dsk_move) live in ndt_deskew_device.h, shared with
-// ndt_unproject.hip.
+// ndt_unproject.hip; so do the host's upload of the knot table and the strided download of a result (this file).
 #include "ndt_engine.h"
+#include "ndt_compact_device.h"
 #include "ndt_deskew_device.h"
 #include "ndt_trajectory.h"
 
@@ -47,16 +47,9 @@ __global__ void __launch_bounds__(DSK_THREADS) k_deskew_count(const float* __res
                                                              unsigned int* __restrict__ counts) {
   __shared__ unsigned int s_w[DSK_WAVES];
   const unsigned int i = blockIdx.x * DSK_THREADS + threadIdx.x;
-  const bool keep = i < n && dsk_keep(f, sx[i], sy[i], sz[i], st[i], si, i);
-  const unsigned long long bal = __ballot(keep);
-  if ((threadIdx.x & 63u) == 0) s_w[threadIdx.x >> 6] = (unsigned int)__popcll(bal);
+  compact_ballot(i < n && dsk_keep(f, sx[i], sy[i], sz[i], st[i], si, i), s_w);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned int c = 0;
-#pragma unroll
-    for (int w = 0; w < DSK_WAVES; ++w) c += s_w[w];
-    counts[blockIdx.x] = c;
-  }
+  compact_block_count(s_w, counts);
 }
 
 __global__ void __launch_bounds__(DSK_THREADS) k_deskew_emit(const float* __restrict__ sx, const float* __restrict__ sy,
@@ -69,21 +62,15 @@ __global__ void __launch_bounds__(DSK_THREADS) k_deskew_emit(const float* __rest
   __shared__ double s_tab[traj::MAX_KNOTS * traj::ROW_WORDS];
   __shared__ unsigned int s_w[DSK_WAVES];
   const unsigned int i = blockIdx.x * DSK_THREADS + threadIdx.x;
-  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
   float x = 0.0f, y = 0.0f, z = 0.0f, t = 0.0f;
   bool keep = false;
   if (i < n) {
     x = sx[i]; y = sy[i]; z = sz[i]; t = st[i];
     keep = dsk_keep(f, x, y, z, t, si, i);
   }
-  const unsigned long long bal = __ballot(keep);
-  if (lane == 0) s_w[wave] = (unsigned int)__popcll(bal);
+  const unsigned long long bal = compact_ballot(keep, s_w);
   dsk_load_table(table, n_knots, s_tab);   // (its barrier also publishes s_w)
-  unsigned int wave_off = 0;
-#pragma unroll
-  for (int w = 0; w < DSK_WAVES; ++w) wave_off += w < wave ? s_w[w] : 0u;
-  const unsigned int rank = (unsigned int)__popcll(bal & ((1ull << lane) - 1ull));
-  const unsigned int pos = offsets[blockIdx.x] + wave_off + rank;
+  const unsigned int pos = compact_position(bal, s_w, offsets);
   if (keep && pos < cap) {   // (the output holds cap points: a selection beyond it is counted, not written)
     float rx, ry, rz;
     dsk_move(reinterpret_cast<const traj::KnotRow*>(s_tab), n_knots, x, y, z, t, &rx, &ry, &rz);
@@ -98,47 +85,74 @@ __global__ void __launch_bounds__(DSK_THREADS) k_deskew_emit(const float* __rest
 }  // namespace
 
 namespace engine {
+
+int knots_upload(ndt_handle* h, const traj::KnotRow* rows, int n_knots) {
+  KnotTable& k = h->knots;
+  HIP_TRY(h, k.tab.ensure((size_t)traj::MAX_KNOTS * traj::ROW_WORDS));
+  HIP_TRY(h, k.tab_h.ensure((size_t)traj::MAX_KNOTS * traj::ROW_WORDS));
+  if (n_knots > 0) {
+    const size_t tab_bytes = (size_t)n_knots * sizeof(traj::KnotRow);
+    std::memcpy(k.tab_h.h, rows, tab_bytes);   // (the previous call's copy out of the staging has been awaited)
+    HIP_TRY(h, hipMemcpyAsync(k.tab.p, k.tab_h.h, tab_bytes, hipMemcpyHostToDevice, h->stream));
+  }
+  return NDT_OK;
+}
+
+int download_strided(ndt_handle* h, const float* d_cols, size_t col_stride, const float* d_t, const int32_t* d_index, size_t m,
+                     size_t cap, float* back, float* out, size_t stride_bytes, long intensity_offset_bytes, float* t_out,
+                     int32_t* index_out) {
+  if (m > cap) return over_capacity(h, m);
+  if (m == 0) return NDT_OK;
+  const bool has_i = intensity_offset_bytes >= 0;
+  const int cols = has_i ? 4 : 3;
+  for (int a = 0; a < cols; ++a)
+    HIP_TRY(h, hipMemcpyAsync(back + (size_t)a * m, d_cols + (size_t)a * col_stride, m * sizeof(float), hipMemcpyDeviceToHost,
+                              h->stream));
+  if (t_out) HIP_TRY(h, hipMemcpyAsync(t_out, d_t, m * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (index_out) HIP_TRY(h, hipMemcpyAsync(index_out, d_index, m * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  char* ob = reinterpret_cast<char*>(out);
+  for (size_t i = 0; i < m; ++i) {
+    float* p = reinterpret_cast<float*>(ob + i * stride_bytes);
+    p[0] = back[i]; p[1] = back[m + i]; p[2] = back[2 * m + i];
+    if (has_i) *reinterpret_cast<float*>(ob + i * stride_bytes + intensity_offset_bytes) = back[3 * m + i];
+  }
+  return NDT_OK;
+}
+
 namespace {
 
-// The trajectory's table to the device (pinned staging -> the handle's table, on the engine's stream), then the
-// launches; awaited.  dx .. dt (and di, ox .. o_index) are device arrays.  Arguments have been checked.
+// The trajectory's table to the device (knots_upload), then the launches; awaited.  dx .. dt (and di, ox .. o_index) are
+// device arrays.  Arguments have been checked.
 int deskew_device(ndt_handle* h, const float* dx, const float* dy, const float* dz, const float* di, const float* dt, size_t n,
                   const traj::KnotRow* rows, int n_knots, const ndt_scan_filter* filter, float* ox, float* oy, float* oz, float* oi,
                   int32_t* o_index, size_t cap, size_t* n_out) {
   *n_out = 0;
   if (n == 0) return NDT_OK;
-  DeskewBufs& b = h->dsk;
   hipStream_t s = h->stream;
-  HIP_TRY(h, b.tab.ensure((size_t)traj::MAX_KNOTS * traj::ROW_WORDS));
-  HIP_TRY(h, b.tab_h.ensure((size_t)traj::MAX_KNOTS * traj::ROW_WORDS));
-  HIP_TRY(h, b.total_h.ensure(4));
-  const size_t tab_bytes = (size_t)n_knots * sizeof(traj::KnotRow);
-  std::memcpy(b.tab_h.h, rows, tab_bytes);   // (the previous call's copy out of the staging has been awaited)
-  HIP_TRY(h, hipMemcpyAsync(b.tab.p, b.tab_h.h, tab_bytes, hipMemcpyHostToDevice, s));
+  int rc = knots_upload(h, rows, n_knots);
+  if (rc) return rc;
+  const double* tab = h->knots.tab.p;
   const int nb = (int)((n + DSK_THREADS - 1) / DSK_THREADS);
   static_assert(sizeof(int) == sizeof(int32_t), "index type");
   if (!filter) {
-    hipLaunchKernelGGL(k_deskew_aligned, dim3((unsigned)nb), dim3(DSK_THREADS), 0, s, dx, dy, dz, dt, di, (unsigned int)n, b.tab.p,
+    hipLaunchKernelGGL(k_deskew_aligned, dim3((unsigned)nb), dim3(DSK_THREADS), 0, s, dx, dy, dz, dt, di, (unsigned int)n, tab,
                        n_knots, ox, oy, oz, di ? oi : nullptr, o_index);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(s));
     *n_out = n;
     return NDT_OK;
   }
-  HIP_TRY(h, b.counts.ensure((size_t)nb + 2));
-  unsigned int* d_total = b.counts.p + nb + 1;
+  rc = compact_scratch(h, nb);
+  if (rc) return rc;
+  unsigned int* counts = h->compact.counts.p;
   const unsigned int ucap = (unsigned int)std::min<size_t>(cap, n);
   hipLaunchKernelGGL(k_deskew_count, dim3((unsigned)nb), dim3(DSK_THREADS), 0, s, dx, dy, dz, dt, di, (unsigned int)n, *filter,
-                     b.counts.p);
-  launch_filter_scan(b.counts.p, nb, d_total, s);
-  hipLaunchKernelGGL(k_deskew_emit, dim3((unsigned)nb), dim3(DSK_THREADS), 0, s, dx, dy, dz, dt, di, (unsigned int)n, *filter,
-                     b.tab.p, n_knots, b.counts.p, ox, oy, oz, di ? oi : nullptr, o_index, ucap);
-  HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipMemcpyAsync(b.total_h.h, d_total, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(h, hipStreamSynchronize(s));
-  *n_out = (size_t)b.total_h.h[0];
-  if (*n_out > cap) return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(*n_out) + " points selected");
-  return NDT_OK;
+                     counts);
+  launch_filter_scan(counts, nb, h->compact.d_total(nb), s);
+  hipLaunchKernelGGL(k_deskew_emit, dim3((unsigned)nb), dim3(DSK_THREADS), 0, s, dx, dy, dz, dt, di, (unsigned int)n, *filter, tab,
+                     n_knots, counts, ox, oy, oz, di ? oi : nullptr, o_index, ucap);
+  return compact_total(h, nb, cap, n_out);
 }
 
 // what every form checks before anything is written: the trajectory (into rows) and the sizes
@@ -187,7 +201,7 @@ int ndt_deskew_device(ndt_handle* h, const float* dx, const float* dy, const flo
   if (o_intensity && !d_intensity) return fail(h, NDT_ERR_INVALID_ARG, "deskew: an intensity output without an intensity input");
   if (!filter_or_null && cap < n) {
     *n_out = n;
-    return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(n) + " points selected");
+    return over_capacity(h, n);
   }
   {
     // compacting: the emit writes where other threads still read -- no output may overlap an input.  Aligned: a thread
@@ -218,7 +232,7 @@ int ndt_deskew(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, l
   if (rc) return rc;
   if (!filter_or_null && cap < n) {
     *n_out = n;
-    return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(n) + " points selected");
+    return over_capacity(h, n);
   }
   *n_out = 0;
   rc = bind_device(h);
@@ -235,23 +249,9 @@ int ndt_deskew(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, l
   rc = deskew_device(h, in, in + n, in + 2 * n, has_i ? in + 4 * n : nullptr, in + 3 * n, n, rows, n_knots, filter_or_null, o, o + n,
                      o + 2 * n, has_i ? o + 3 * n : nullptr, index_out ? b.index.p : nullptr, n, n_out);
   if (rc) return rc;
-  const size_t m = *n_out;
-  if (m > cap) return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(m) + " points selected");
-  if (m == 0) return NDT_OK;
   // (the staging is free again: the upload out of it has been awaited)
-  float* back = b.stage.h;
-  const int cols = has_i ? 4 : 3;
-  for (int a = 0; a < cols; ++a)
-    HIP_TRY(h, hipMemcpyAsync(back + (size_t)a * m, o + (size_t)a * n, m * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (index_out) HIP_TRY(h, hipMemcpyAsync(index_out, b.index.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  char* ob = reinterpret_cast<char*>(out);
-  for (size_t i = 0; i < m; ++i) {
-    float* p = reinterpret_cast<float*>(ob + i * stride_bytes);
-    p[0] = back[i]; p[1] = back[m + i]; p[2] = back[2 * m + i];
-    if (has_i) *reinterpret_cast<float*>(ob + i * stride_bytes + intensity_offset_bytes) = back[3 * m + i];
-  }
-  return NDT_OK;
+  return download_strided(h, o, n, nullptr, b.index.p, *n_out, cap, b.stage.h, out, stride_bytes, intensity_offset_bytes, nullptr,
+                          index_out);
 }
 
 int ndt_keyframe_put_deskewed(ndt_handle* h, int64_t id, const float* xyz, size_t n, size_t stride_bytes,

@@ -4,7 +4,8 @@
 //   ndt_handoff.hip    host hand-off (repack + pull kernels), the target voxel-grid build's orchestration, grid accessors
 //   ndt_evaluate.hip   derivative evaluations (ordinary, pre-launched, batched), align, scoring
 //   ndt_keyframes.hip  multi-grid targets, the device-resident keyframe archive, voxel downsample
-//   ndt_point_scores.hip  per-point scores and the score-based source filter (its compaction kernels included)
+//   ndt_point_scores.hip  per-point scores and the score-based source filter; the engine's one scan of block counts and
+//                      the host side of every compaction (the device side: ndt_compact_device.h)
 //   ndt_map.hip        the sparse voxel map accumulated scan by scan (ndt_map_*), its kernels included
 //   ndt_map_state.hip  the map's crop, full-state export / import and merge (k_mapstate_* kernels)
 //   ndt_deskew.hip     motion compensation of a scan along a pose trajectory + the acquisition filter (its kernels included)
@@ -47,6 +48,9 @@ using namespace ndt;
 namespace ndt {
 
 struct MapSel;   // ndt_map_device.h
+namespace traj {
+struct KnotRow;  // ndt_trajectory.h
+}
 
 namespace engine {
 
@@ -168,55 +172,56 @@ struct FitIndex {
   }
 };
 
-// Scratch of the per-point scoring calls: the host forms' device-side outputs, the filter's predicate values, block
-// counts and (host form) compacted output.  Kept between calls.
+// Scratch of a stream compaction (ndt_compact_device.h), one per handle: ndt_filter_source*, ndt_deskew* and
+// ndt_unproject* are serial on a handle and awaited before they return.  compact_scratch / compact_total use it.
+struct CompactBufs {
+  DevBuf<unsigned int> counts;       // nb block counts / offsets, their sum, then the total the scan writes: nb + 2 words
+  PinBuf<unsigned int> total_h;      // ... and where the host reads it
+  unsigned int* d_total(int nb) const { return counts.p + nb + 1; }
+  void release() { counts.release(); total_h.release(); }
+};
+
+// The knot table of a trajectory on the device, one per handle (knots_upload; ndt_deskew* and ndt_unproject* read it)
+struct KnotTable {
+  DevBuf<double> tab;                // <= 64 rows of 12 doubles (traj::KnotRow)
+  PinBuf<double> tab_h;              // its pinned staging
+  void release() { tab.release(); tab_h.release(); }
+};
+
+// Scratch of the per-point scoring calls: the host forms' device-side outputs, the filter's predicate values and (host
+// form) compacted output.  Kept between calls.
 struct PointScoreBufs {
   DevBuf<double> score, best;
   DevBuf<int> npairs, index;
   DevBuf<long long> cell;
-  DevBuf<unsigned int> counts;       // filter_blocks(n) block counts / offsets, then the total
   DevBuf<float> out;                 // [x | y | z] of the selected points
-  void release() {
-    score.release(); best.release(); npairs.release(); index.release(); cell.release(); counts.release(); out.release();
-  }
+  void release() { score.release(); best.release(); npairs.release(); index.release(); cell.release(); out.release(); }
 };
 
-// Scratch of the deskew calls (ndt_deskew.hip), kept between calls: the knot table and its pinned staging, the
-// compaction's block counts, and for the host forms the raw scan and the result on the device and a pinned staging.
+// Scratch of the deskew calls' host forms (ndt_deskew.hip), kept between calls: the raw scan and the result on the
+// device and a pinned staging.
 struct DeskewBufs {
-  DevBuf<double> tab;                // <= 64 rows of 12 doubles (traj::KnotRow)
-  PinBuf<double> tab_h;
-  DevBuf<unsigned int> counts;       // per-block counts / offsets, then the total
-  PinBuf<unsigned int> total_h;
   DevBuf<float> in;                  // [x | y | z | t | intensity] of a host scan
   DevBuf<float> out;                 // [x | y | z | intensity] of the result
   DevBuf<int> index;
   PinBuf<float> stage;               // the host scan on its way up, the result on its way down
-  void release() {
-    tab.release(); tab_h.release(); counts.release(); total_h.release(); in.release(); out.release(); index.release();
-    stage.release();
-  }
+  void release() { in.release(); out.release(); index.release(); stage.release(); }
 };
 
 // The scan model of ndt_scan_model_set and the scratch of the unprojection calls (ndt_unproject.hip), kept between
-// calls: the model's tables, the knot table and its pinned staging, the compaction's block counts, and for the host and
-// keyframe forms the raw range image and the result on the device and a pinned staging.
+// calls: the model's tables, and for the host and keyframe forms the raw range image and the result on the device and a
+// pinned staging.
 struct ScanModelBufs {
   int n_cols = 0, n_rows = 0;        // 0, 0: no model set
   DevBuf<float> dir;                 // [x1 | y1 | z1], n_cols * n_rows floats each, pixel col * n_rows + row
   DevBuf<float> off;                 // [x2 | y2 | z2], n_cols floats each
-  DevBuf<double> tab;                // <= 64 rows of 12 doubles (traj::KnotRow)
-  PinBuf<double> tab_h;
-  DevBuf<unsigned int> counts;       // per-block counts / offsets, then the total
-  PinBuf<unsigned int> total_h;
   DevBuf<uint32_t> in;               // a host range image: [range_mm (n words) | col_t (n_cols words) | reflectivity (n bytes)]
   DevBuf<float> out;                 // [x | y | z | intensity | t] of the result
   DevBuf<int> index;
   PinBuf<uint32_t> stage;            // the range image on its way up, the result on its way down
   void release() {
     n_cols = n_rows = 0;
-    dir.release(); off.release(); tab.release(); tab_h.release(); counts.release(); total_h.release(); in.release();
-    out.release(); index.release(); stage.release();
+    dir.release(); off.release(); in.release(); out.release(); index.release(); stage.release();
   }
 };
 
@@ -247,7 +252,7 @@ struct VoxelMap {
   PinBuf<int> stats_h;                 // [0..15] read-back, [16..31] the neutral words
   PinBuf<unsigned long long> nvox_h;
   PinBuf<BuildGeom> plan_h;            // sort plans: [0] add, [1] / [2] export (low / high word)
-  DevBuf<unsigned int> xcounts;        // export: per-block counts / offsets, then the total
+  DevBuf<unsigned int> xcounts;        // export: per-block counts / offsets, their sum, then the scan's total (nb + 2 words)
   DevBuf<uint32_t> xslot, xslot2, xhi; // export: compacted slots (and in low-word order), high key words
   DevBuf<float> xout;                  // host export: [x | y | z | intensity] ...
   DevBuf<int32_t> xcnt;                // ... and counts
@@ -394,6 +399,8 @@ struct ndt_handle {
   PinBuf<int> small;                 // bounds / counters read-back
   PinBuf<unsigned long long> flag;   // 32 result slots {seq, value} the single-pose kernel writes for the host
   DevBuf<double> partials, dres;
+  CompactBufs compact;               // scratch of the filter's, the deskew's and the unprojection's compaction
+  KnotTable knots;                   // the trajectory of the deskew / unprojection call in flight
   PointScoreBufs ps;                 // scratch of ndt_score_points / ndt_filter_source (ndt_point_scores.hip)
   DeskewBufs dsk;                    // scratch of ndt_deskew* / ndt_keyframe_put_deskewed (ndt_deskew.hip)
   ScanModelBufs scan;                // the scan model and the scratch of ndt_unproject* / ndt_keyframe_put_from_ranges (ndt_unproject.hip)
@@ -507,6 +514,10 @@ namespace ndt {
 namespace engine {
 
 int fail(ndt_handle* h, int code, const std::string& msg);
+// a selection of n points that the caller's output does not hold
+inline int over_capacity(ndt_handle* h, size_t n) {
+  return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(n) + " points selected");
+}
 int bind_device(ndt_handle* h);
 bool params_valid(const ndt_params* p, std::string* why);
 int lane_wait(ndt_handle* h, ndt_handle::UploadLane& lane);
@@ -531,6 +542,21 @@ void settle_discard(ndt_handle* h);
 // ndt_keyframes.hip: the archive entry `id` for a scan of n points -- a new entry takes pooled buffers that are large
 // enough, a replaced one that is the viewed source unsets the source; the caller fills x / y / z and sets n
 ndt_handle::Keyframe& keyframe_claim(ndt_handle* h, int64_t id, size_t n);
+// ndt_point_scores.hip: a compaction's host side around its three launches.  compact_scratch makes h->compact hold nb
+// blocks; compact_total, behind the launches, reports a launch error, fetches the scan's total into *n_out (awaited) and
+// refuses one above cap
+int compact_scratch(ndt_handle* h, int nb);
+int compact_total(ndt_handle* h, int nb, size_t cap, size_t* n_out);
+// ndt_deskew.hip: rows[0 .. n_knots) -> h->knots through its pinned staging, enqueued on the engine's stream (n_knots = 0:
+// the table is only allocated)
+int knots_upload(ndt_handle* h, const traj::KnotRow* rows, int n_knots);
+// ndt_deskew.hip, for the host forms of filter, deskew and unprojection: the first m points of a device result -- columns
+// [x | y | z | intensity] col_stride floats apart at d_cols, d_t and d_index beside them -- to a strided host cloud
+// (layout_valid) through the host staging `back` (m floats per column), t_out and index_out (null: not wanted) directly;
+// awaited.  m > cap is refused, m = 0 copies nothing.
+int download_strided(ndt_handle* h, const float* d_cols, size_t col_stride, const float* d_t, const int32_t* d_index, size_t m,
+                     size_t cap, float* back, float* out, size_t stride_bytes, long intensity_offset_bytes, float* t_out,
+                     int32_t* index_out);
 void map_release(ndt_handle* h);   // ndt_map.hip: frees the voxel map, if any (ndt_destroy)
 // ndt_map.hip's host side as ndt_map_state.hip uses it (the kernels stay where they are)
 constexpr int64_t MAP_MAX_CAPACITY = 1ll << 30;   // slots are 32-bit sort keys with one sentinel above them

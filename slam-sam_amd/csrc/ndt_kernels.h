@@ -234,16 +234,13 @@ void launch_point_scores(const float* sx, const float* sy, const float* sz, size
                          const VoxelRecord* rec, const PoseConsts& pose, const EvalConsts& ec, double* d_score,
                          double* d_best, int* d_npairs, long long* d_cell, hipStream_t s);
 
-// ---- score-based source filter (ndt_point_scores.hip) -----------------------
-// Stable compaction of the points whose value passes  v >= thr  (keep_below: v < thr), in input order: per-block counts,
-// an exclusive scan of the counts by one block (*d_total receives the number selected), then the emit -- every block
-// recomputes its ballots and writes behind its offset; at most `cap` points are written.  Integer counters only.
-int filter_blocks(size_t n);
-// the scan on its own (shared with the deskew's compaction, ndt_deskew.hip): d_counts[0 .. nb) -> their exclusive prefix
-// sums in place, d_counts[nb] and *d_total receive the sum; one block of 1024 threads, 1024 counts per pass
+// ---- stream compaction (ndt_compact_device.h, ndt_point_scores.hip) ---------
+// "Keep what passes a predicate, in input order" is one mechanism in three launches: per-block counts (a count kernel
+// built on ndt_compact_device.h), an exclusive scan of the counts by one block, then the emit -- every block recomputes
+// its ballots and writes behind its offset; at most `cap` elements are written.  Integer counters only.
+// The scan, the one every compaction uses (filter, deskew, unprojection, the map's export): d_counts[0 .. nb) -> their
+// exclusive prefix sums in place, d_counts[nb] and *d_total receive the sum (two distinct words: the kernel's pointers
+// are __restrict__, callers pass d_counts + nb + 1); one block of 1024 threads, 1024 counts per pass
 void launch_filter_scan(unsigned int* d_counts, int nb, unsigned int* d_total, hipStream_t s);
-void launch_filter_compact(const double* d_value, const float* sx, const float* sy, const float* sz, size_t n, double thr,
-                           int keep_below, unsigned int* d_block_counts /* filter_blocks(n) + 1 */, unsigned int* d_total,
-                           float* ox, float* oy, float* oz, int* o_index, size_t cap, hipStream_t s);
 
 }  // namespace ndt

@@ -4,8 +4,9 @@
 //   add      [transform] -> keys + range check (ONE host wait: refusal / growth are decided before anything is written)
 //            -> insert (atomicCAS on the key word; the table position is the slot) -> the build's stable radix sort of
 //            (slot, point index) and its run search -> one thread per run continues the voxel's float sums in input order
-//   export   compaction of the slots that pass min_points (ballots, integer block offsets) -> sort by the voxel key
-//            relative to the map's bounding box (one 32-bit sort, or two: low word then high word) -> centroids
+//   export   compaction of the slots that pass min_points (k_map_xcount / k_map_xemit: four-round tiles of ballots; the
+//            block offsets by the engine's one scan, launch_filter_scan) -> sort by the voxel key relative to the map's
+//            bounding box (one 32-bit sort, or two: low word then high word) -> centroids
 // Integer atomics only (the CAS, the block totals of the statistics); no kernel waits for another block, every probe loop
 // is bounded by the capacity.  Which slot a voxel gets depends on the race, on the hash and on the capacity -- what the
 // slot holds does not: a voxel's sums are ((old + p1) + p2) ... over its points in input order, and the export orders by key.
@@ -257,36 +258,6 @@ __global__ void __launch_bounds__(MAP_THREADS) k_map_xcount(const unsigned long 
       if (v) atomicAdd(reinterpret_cast<unsigned long long*>(tsel + TS_POINTS), v);
     }
   }
-}
-
-// counts[0 .. nb) -> their exclusive prefix sums, in place; counts[nb] receives the sum.  One block.
-__global__ void __launch_bounds__(MAP_SCAN_THREADS) k_map_xscan(unsigned int* __restrict__ counts, int nb) {
-  __shared__ unsigned int s_w[MAP_SCAN_WAVES];
-  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
-  unsigned int carry = 0;   // block-uniform
-  for (int base = 0; base < nb; base += MAP_SCAN_THREADS) {
-    const int idx = base + (int)threadIdx.x;
-    const unsigned int c = idx < nb ? counts[idx] : 0u;
-    unsigned int incl = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const unsigned int v = __shfl_up(incl, off);
-      if (lane >= off) incl += v;
-    }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    unsigned int wave_off = 0, chunk = 0;
-#pragma unroll
-    for (int w = 0; w < MAP_SCAN_WAVES; ++w) {
-      const unsigned int t = s_w[w];
-      wave_off += w < wave ? t : 0u;
-      chunk += t;
-    }
-    if (idx < nb) counts[idx] = carry + wave_off + incl - c;
-    carry += chunk;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) counts[nb] = carry;
 }
 
 // the key relative to the map's bounding box: (k - min_k, j - min_j, i - min_i) packed into bz + by + bx bits
@@ -593,7 +564,7 @@ int map_export_count(ndt_handle* h, const MapSel& sel, bool box, size_t* total) 
   if (m.n_voxels == 0) return NDT_OK;
   hipStream_t s = h->stream;
   const int nb = (int)((m.capacity + MAP_XTILE - 1) / MAP_XTILE);
-  HIP_TRY(h, m.xcounts.ensure((size_t)nb + 1));
+  HIP_TRY(h, m.xcounts.ensure((size_t)nb + 2));
   if (box) {
     HIP_TRY(h, hipMemcpyAsync(m.tsel.p, m.tsel_h.h + TS_WORDS, TS_WORDS * sizeof(int), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_map_xcount<true>, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.keys, m.cnt, (long long)m.capacity, sel,
@@ -602,7 +573,7 @@ int map_export_count(ndt_handle* h, const MapSel& sel, bool box, size_t* total) 
     hipLaunchKernelGGL(k_map_xcount<false>, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.keys, m.cnt, (long long)m.capacity, sel,
                        m.xcounts.p, static_cast<int*>(nullptr));
   }
-  hipLaunchKernelGGL(k_map_xscan, dim3(1), dim3(MAP_SCAN_THREADS), 0, s, m.xcounts.p, nb);
+  launch_filter_scan(m.xcounts.p, nb, m.xcounts.p + nb + 1, s);   // (xcounts[nb] receives the sum as well: read below)
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(m.nvox_h.h + 1, m.xcounts.p + nb, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
   if (box) HIP_TRY(h, hipMemcpyAsync(m.tsel_h.h, m.tsel.p, TS_WORDS * sizeof(int), hipMemcpyDeviceToHost, s));

@@ -6,7 +6,6 @@
 namespace ndt {
 
 constexpr int MAP_THREADS = 256, MAP_WAVES = MAP_THREADS / 64;
-constexpr int MAP_SCAN_THREADS = 1024, MAP_SCAN_WAVES = MAP_SCAN_THREADS / 64;
 constexpr int MAP_XROUNDS = 4;                         // slots per thread of the export's compaction
 constexpr int MAP_XTILE = MAP_THREADS * MAP_XROUNDS;
 constexpr unsigned long long MAP_EMPTY = ~0ull;

@@ -1,11 +1,13 @@
 // ndt_point_scores.hip -- per-point NDT scores and the score-based source filter (see ndt_engine.h).
 //   ndt_score_points*        one launch of k_point_scores (ndt_derivs.hip) on the engine's stream
-//   ndt_filter_source*       k_point_scores for the predicate values, then a stable compaction in three small launches:
-//                            per-block counts (wave ballots + popcounts), an exclusive scan of the counts by ONE block,
-//                            and the emit (the ballots again, a per-block exclusive scan of the wave counts in LDS).
+//   ndt_filter_source*       k_point_scores for the predicate values, then the stable compaction of
+//                            ndt_compact_device.h in three small launches: k_filter_count, k_filter_scan, k_filter_emit.
 // Integer counters only, no atomics: where a point lands depends on the points in front of it and on nothing else.
 // Neither call touches the align state, the iteration history or the evaluation counters of the handle.
+// This file also holds what every compaction of the engine shares beyond the device helpers: the one-block exclusive
+// scan of the block counts (k_filter_scan, launch_filter_scan) and the host side (compact_scratch, compact_total).
 #include "ndt_engine.h"
+#include "ndt_compact_device.h"
 
 namespace ndt {
 
@@ -21,16 +23,9 @@ __global__ void __launch_bounds__(FILT_THREADS) k_filter_count(const double* __r
                                                               unsigned int* __restrict__ counts) {
   __shared__ unsigned int s_w[FILT_WAVES];
   const int i = (int)(blockIdx.x * FILT_THREADS + threadIdx.x);
-  const bool keep = i < n && filt_keep(value[i], thr, keep_below);
-  const unsigned long long bal = __ballot(keep);
-  if ((threadIdx.x & 63u) == 0) s_w[threadIdx.x >> 6] = (unsigned int)__popcll(bal);
+  compact_ballot(i < n && filt_keep(value[i], thr, keep_below), s_w);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned int c = 0;
-#pragma unroll
-    for (int w = 0; w < FILT_WAVES; ++w) c += s_w[w];
-    counts[blockIdx.x] = c;
-  }
+  compact_block_count(s_w, counts);
 }
 
 // counts[0 .. nb) -> their exclusive prefix sums, in place; counts[nb] and *total receive the sum.  One block.
@@ -73,16 +68,10 @@ __global__ void __launch_bounds__(FILT_THREADS) k_filter_emit(const double* __re
                                                              int* __restrict__ o_index, unsigned int cap) {
   __shared__ unsigned int s_w[FILT_WAVES];
   const int i = (int)(blockIdx.x * FILT_THREADS + threadIdx.x);
-  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
   const bool keep = i < n && filt_keep(value[i], thr, keep_below);
-  const unsigned long long bal = __ballot(keep);
-  if (lane == 0) s_w[wave] = (unsigned int)__popcll(bal);
+  const unsigned long long bal = compact_ballot(keep, s_w);
   __syncthreads();
-  unsigned int wave_off = 0;
-#pragma unroll
-  for (int w = 0; w < FILT_WAVES; ++w) wave_off += w < wave ? s_w[w] : 0u;
-  const unsigned int rank = (unsigned int)__popcll(bal & ((1ull << lane) - 1ull));
-  const unsigned int pos = offsets[blockIdx.x] + wave_off + rank;
+  const unsigned int pos = compact_position(bal, s_w, offsets);
   if (keep && pos < cap) {   // (the output holds cap points: a selection beyond it is counted, not written)
     ox[pos] = sx[i];
     oy[pos] = sy[i];
@@ -97,21 +86,23 @@ void launch_filter_scan(unsigned int* d_counts, int nb, unsigned int* d_total, h
   hipLaunchKernelGGL(k_filter_scan, dim3(1), dim3(SCAN_THREADS), 0, s, d_counts, nb, d_total);
 }
 
-int filter_blocks(size_t n) { return (int)((n + FILT_THREADS - 1) / FILT_THREADS); }
+namespace engine {
 
-void launch_filter_compact(const double* d_value, const float* sx, const float* sy, const float* sz, size_t n, double thr,
-                           int keep_below, unsigned int* d_block_counts, unsigned int* d_total, float* ox, float* oy, float* oz,
-                           int* o_index, size_t cap, hipStream_t s) {
-  if (n == 0) return;
-  const int nb = filter_blocks(n);
-  const unsigned int ucap = (unsigned int)std::min<size_t>(cap, n);
-  hipLaunchKernelGGL(k_filter_count, dim3((unsigned)nb), dim3(FILT_THREADS), 0, s, d_value, (int)n, thr, keep_below, d_block_counts);
-  launch_filter_scan(d_block_counts, nb, d_total, s);
-  hipLaunchKernelGGL(k_filter_emit, dim3((unsigned)nb), dim3(FILT_THREADS), 0, s, d_value, sx, sy, sz, (int)n, thr, keep_below,
-                     d_block_counts, ox, oy, oz, o_index, ucap);
+int compact_scratch(ndt_handle* h, int nb) {
+  HIP_TRY(h, h->compact.counts.ensure((size_t)nb + 2));
+  HIP_TRY(h, h->compact.total_h.ensure(4));
+  return NDT_OK;
 }
 
-namespace engine {
+int compact_total(ndt_handle* h, int nb, size_t cap, size_t* n_out) {
+  CompactBufs& c = h->compact;
+  HIP_TRY(h, hipGetLastError());   // (of the three launches)
+  HIP_TRY(h, hipMemcpyAsync(c.total_h.h, c.d_total(nb), sizeof(unsigned int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  *n_out = (size_t)c.total_h.h[0];
+  return *n_out > cap ? over_capacity(h, *n_out) : NDT_OK;
+}
+
 namespace {
 
 // as ndt_score_transform: a pending deferred build is settled, then target and source are asked for
@@ -147,21 +138,21 @@ int filter_device(ndt_handle* h, const float T[16], double min_score, int keep_b
                   int32_t* d_index, size_t cap, size_t* n_out) {
   const size_t n = h->n_src;
   if (n == 0) return NDT_OK;   // (an empty shard of a sharded source)
-  PointScoreBufs& ps = h->ps;
-  HIP_TRY(h, ps.best.ensure(n));
-  HIP_TRY(h, ps.counts.ensure((size_t)filter_blocks(n) + 2));
-  int rc = enqueue_point_scores(h, T, nullptr, ps.best.p, nullptr, nullptr);
+  const int nb = (int)((n + FILT_THREADS - 1) / FILT_THREADS), below = keep_below ? 1 : 0;
+  HIP_TRY(h, h->ps.best.ensure(n));
+  int rc = compact_scratch(h, nb);
   if (rc) return rc;
-  unsigned int* d_total = ps.counts.p + filter_blocks(n) + 1;
-  launch_filter_compact(ps.best.p, h->vx, h->vy, h->vz, n, min_score, keep_below ? 1 : 0, ps.counts.p, d_total, ox, oy, oz,
-                        d_index, cap, h->stream);
-  HIP_TRY(h, hipGetLastError());
-  unsigned int total = 0;
-  HIP_TRY(h, hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  *n_out = (size_t)total;
-  if (*n_out > cap) return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(*n_out) + " points selected");
-  return NDT_OK;
+  rc = enqueue_point_scores(h, T, nullptr, h->ps.best.p, nullptr, nullptr);
+  if (rc) return rc;
+  hipStream_t s = h->stream;
+  const double* value = h->ps.best.p;
+  unsigned int* counts = h->compact.counts.p;
+  const unsigned int ucap = (unsigned int)std::min<size_t>(cap, n);
+  hipLaunchKernelGGL(k_filter_count, dim3((unsigned)nb), dim3(FILT_THREADS), 0, s, value, (int)n, min_score, below, counts);
+  launch_filter_scan(counts, nb, h->compact.d_total(nb), s);
+  hipLaunchKernelGGL(k_filter_emit, dim3((unsigned)nb), dim3(FILT_THREADS), 0, s, value, h->vx, h->vy, h->vz, (int)n, min_score,
+                     below, counts, ox, oy, oz, d_index, ucap);
+  return compact_total(h, nb, cap, n_out);
 }
 
 }  // namespace
@@ -233,20 +224,9 @@ int ndt_filter_source(ndt_handle* h, const float T[16], double min_score, int ke
   HIP_TRY(h, ps.index.ensure(n));
   rc = filter_device(h, T, min_score, keep_below, ps.out.p, ps.out.p + n, ps.out.p + 2 * n, ps.index.p, n, n_out);
   if (rc) return rc;
-  const size_t m = *n_out;
-  if (m > cap_points) return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(m) + " points selected");
-  if (m == 0) return NDT_OK;
-  std::vector<float> back(3 * m);
-  for (int a = 0; a < 3; ++a)
-    HIP_TRY(h, hipMemcpyAsync(back.data() + (size_t)a * m, ps.out.p + (size_t)a * n, m * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (index_out) HIP_TRY(h, hipMemcpyAsync(index_out, ps.index.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  for (size_t i = 0; i < m; ++i) {
-    out_xyz[3 * i + 0] = back[i];
-    out_xyz[3 * i + 1] = back[m + i];
-    out_xyz[3 * i + 2] = back[2 * m + i];
-  }
-  return NDT_OK;
+  std::vector<float> back(3 * *n_out);   // the staging; a tight cloud is a stride of 12 bytes without intensity
+  return download_strided(h, ps.out.p, n, nullptr, ps.index.p, *n_out, cap_points, back.data(), out_xyz, 3 * sizeof(float), -1,
+                          nullptr, index_out);
 }
 
 }  // extern "C"

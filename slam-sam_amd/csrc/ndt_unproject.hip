@@ -1,9 +1,9 @@
 // ndt_unproject.hip -- a lidar range image to points through the scan model's tables, with the range gate, the
 // acquisition filter and the deskew in the same pass (include/ndt_hip.h has the contract, DESIGN 7h the figures).
 //   organised  (no filter)  ONE launch of k_unproject_aligned: out[i] = pixel i, an invalid pixel -> NaN
-//   compacting (filter)     the three launches of the deskew's compaction: k_unproject_count (wave ballots of
-//                           valid && kept -> per-block counts), the shared one-block scan (launch_filter_scan),
-//                           k_unproject_emit (the ballots again, the per-block LDS scan, the moved point behind its offset)
+//   compacting (filter)     the stable compaction of ndt_compact_device.h in three launches: k_unproject_count
+//                           (valid && kept), the one-block scan (launch_filter_scan), k_unproject_emit (the moved point
+//                           behind its offset)
 // One thread per pixel, pixel i = col * n_rows + row: the u32 range, the u8 reflectivity and the three direction tables
 // are read at i by consecutive lanes (coalesced; a wave's 64 reflectivity bytes are one 64-byte line).  A block's 256
 // pixels lie in at most 256 columns: the block reads the time and the three offsets of each of ITS columns once into LDS
@@ -11,6 +11,7 @@
 // predicate and the motion ARE that file's (ndt_deskew_device.h).  Integer offsets only, no atomics.  Everything on the
 // engine's stream; the target, the source, the align state, the history and the counters of the handle are not touched.
 #include "ndt_engine.h"
+#include "ndt_compact_device.h"
 #include "ndt_deskew_device.h"
 #include "ndt_trajectory.h"
 
@@ -113,15 +114,9 @@ __global__ void __launch_bounds__(DSK_THREADS) k_unproject_count(UnpArgs a, ndt_
     float x, y, z, t, inten;
     keep = unp_pixel(a, s_cols, c0, i, &x, &y, &z, &t, &inten) && unp_keep(a, f, x, y, z, t, inten);
   }
-  const unsigned long long bal = __ballot(keep);
-  if ((threadIdx.x & 63u) == 0) s_w[threadIdx.x >> 6] = (unsigned int)__popcll(bal);
+  compact_ballot(keep, s_w);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned int c = 0;
-#pragma unroll
-    for (int w = 0; w < DSK_WAVES; ++w) c += s_w[w];
-    counts[blockIdx.x] = c;
-  }
+  compact_block_count(s_w, counts);
 }
 
 __global__ void __launch_bounds__(DSK_THREADS) k_unproject_emit(UnpArgs a, ndt_scan_filter f, const double* __restrict__ table,
@@ -136,18 +131,12 @@ __global__ void __launch_bounds__(DSK_THREADS) k_unproject_emit(UnpArgs a, ndt_s
   const unsigned int c0 = unp_load_cols(a, s_cols);
   dsk_load_table(table, n_knots, s_tab);   // (its barrier also publishes s_cols)
   const unsigned int i = blockIdx.x * DSK_THREADS + threadIdx.x;
-  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
   float x = 0.0f, y = 0.0f, z = 0.0f, t = 0.0f, inten = 0.0f;
   bool keep = false;
   if (i < a.n) keep = unp_pixel(a, s_cols, c0, i, &x, &y, &z, &t, &inten) && unp_keep(a, f, x, y, z, t, inten);
-  const unsigned long long bal = __ballot(keep);
-  if (lane == 0) s_w[wave] = (unsigned int)__popcll(bal);
+  const unsigned long long bal = compact_ballot(keep, s_w);
   __syncthreads();
-  unsigned int wave_off = 0;
-#pragma unroll
-  for (int w = 0; w < DSK_WAVES; ++w) wave_off += w < wave ? s_w[w] : 0u;
-  const unsigned int rank = (unsigned int)__popcll(bal & ((1ull << lane) - 1ull));
-  const unsigned int pos = offsets[blockIdx.x] + wave_off + rank;
+  const unsigned int pos = compact_position(bal, s_w, offsets);
   if (keep && pos < cap) {   // (the output holds cap points: a selection beyond it is counted, not written)
     if (n_knots > 0) dsk_move(reinterpret_cast<const traj::KnotRow*>(s_tab), n_knots, x, y, z, t, &x, &y, &z);
     ox[pos] = x;
@@ -166,8 +155,8 @@ namespace {
 
 size_t unp_pixels(const ndt_handle* h) { return (size_t)h->scan.n_cols * (size_t)h->scan.n_rows; }
 
-// The trajectory's table to the device (pinned staging -> the handle's table, on the engine's stream), then the
-// launches; awaited.  Every pointer but `rows` is device memory.  Arguments have been checked.
+// The trajectory's table to the device (knots_upload), then the launches; awaited.  Every pointer but `rows` is device
+// memory.  Arguments have been checked.
 int unproject_device(ndt_handle* h, const uint32_t* d_range, const uint8_t* d_refl, const float* d_col_t, const ndt_range_gate* gate,
                      const traj::KnotRow* rows, int n_knots, const ndt_scan_filter* filter, float* ox, float* oy, float* oz, float* oi,
                      float* ot, int32_t* o_index, size_t cap, size_t* n_out) {
@@ -175,14 +164,9 @@ int unproject_device(ndt_handle* h, const uint32_t* d_range, const uint8_t* d_re
   ScanModelBufs& b = h->scan;
   hipStream_t s = h->stream;
   const size_t n = unp_pixels(h);
-  HIP_TRY(h, b.tab.ensure((size_t)traj::MAX_KNOTS * traj::ROW_WORDS));
-  HIP_TRY(h, b.tab_h.ensure((size_t)traj::MAX_KNOTS * traj::ROW_WORDS));
-  HIP_TRY(h, b.total_h.ensure(4));
-  if (n_knots > 0) {
-    const size_t tab_bytes = (size_t)n_knots * sizeof(traj::KnotRow);
-    std::memcpy(b.tab_h.h, rows, tab_bytes);   // (the previous call's copy out of the staging has been awaited)
-    HIP_TRY(h, hipMemcpyAsync(b.tab.p, b.tab_h.h, tab_bytes, hipMemcpyHostToDevice, s));
-  }
+  int rc = knots_upload(h, rows, n_knots);
+  if (rc) return rc;
+  const double* tab = h->knots.tab.p;
   UnpArgs a;
   a.range = d_range; a.refl = d_refl; a.col_t = d_col_t;
   a.x1 = b.dir.p; a.y1 = b.dir.p + n; a.z1 = b.dir.p + 2 * n;
@@ -195,26 +179,22 @@ int unproject_device(ndt_handle* h, const uint32_t* d_range, const uint8_t* d_re
   const int nb = (int)((n + DSK_THREADS - 1) / DSK_THREADS);
   static_assert(sizeof(int) == sizeof(int32_t), "index type");
   if (!filter) {
-    hipLaunchKernelGGL(k_unproject_aligned, dim3((unsigned)nb), dim3(DSK_THREADS), 0, s, a, b.tab.p, n_knots, ox, oy, oz, oi, ot,
+    hipLaunchKernelGGL(k_unproject_aligned, dim3((unsigned)nb), dim3(DSK_THREADS), 0, s, a, tab, n_knots, ox, oy, oz, oi, ot,
                        o_index);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(s));
     *n_out = n;
     return NDT_OK;
   }
-  HIP_TRY(h, b.counts.ensure((size_t)nb + 2));
-  unsigned int* d_total = b.counts.p + nb + 1;
+  rc = compact_scratch(h, nb);
+  if (rc) return rc;
+  unsigned int* counts = h->compact.counts.p;
   const unsigned int ucap = (unsigned int)std::min<size_t>(cap, n);
-  hipLaunchKernelGGL(k_unproject_count, dim3((unsigned)nb), dim3(DSK_THREADS), 0, s, a, *filter, b.counts.p);
-  launch_filter_scan(b.counts.p, nb, d_total, s);
-  hipLaunchKernelGGL(k_unproject_emit, dim3((unsigned)nb), dim3(DSK_THREADS), 0, s, a, *filter, b.tab.p, n_knots, b.counts.p, ox, oy,
-                     oz, oi, ot, o_index, ucap);
-  HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipMemcpyAsync(b.total_h.h, d_total, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(h, hipStreamSynchronize(s));
-  *n_out = (size_t)b.total_h.h[0];
-  if (*n_out > cap) return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(*n_out) + " points selected");
-  return NDT_OK;
+  hipLaunchKernelGGL(k_unproject_count, dim3((unsigned)nb), dim3(DSK_THREADS), 0, s, a, *filter, counts);
+  launch_filter_scan(counts, nb, h->compact.d_total(nb), s);
+  hipLaunchKernelGGL(k_unproject_emit, dim3((unsigned)nb), dim3(DSK_THREADS), 0, s, a, *filter, tab, n_knots, counts, ox, oy, oz, oi,
+                     ot, o_index, ucap);
+  return compact_total(h, nb, cap, n_out);
 }
 
 // what every form checks before anything is written: the model, the gate and the trajectory (into rows; n_knots = 0
@@ -310,7 +290,7 @@ int ndt_unproject_device(ndt_handle* h, const uint32_t* d_range_mm, const uint8_
   const size_t n = unp_pixels(h);
   if (!filter_or_null && cap < n) {
     *n_out = n;
-    return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(n) + " points selected");
+    return over_capacity(h, n);
   }
   {
     // inputs and outputs differ in type and layout: no output may overlap an input in either form
@@ -349,7 +329,7 @@ int ndt_unproject(ndt_handle* h, const uint32_t* range_mm, const uint8_t* reflec
   const size_t n = unp_pixels(h), nc = (size_t)h->scan.n_cols;
   if (!filter_or_null && cap < n) {
     *n_out = n;
-    return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(n) + " points selected");
+    return over_capacity(h, n);
   }
   *n_out = 0;
   rc = bind_device(h);
@@ -364,24 +344,9 @@ int ndt_unproject(ndt_handle* h, const uint32_t* range_mm, const uint8_t* reflec
                         reinterpret_cast<const float*>(b.in.p + n), gate_or_null, rows, n_knots, filter_or_null, o, o + n, o + 2 * n,
                         has_i ? o + 3 * n : nullptr, t_out ? o + 4 * n : nullptr, index_out ? b.index.p : nullptr, n, n_out);
   if (rc) return rc;
-  const size_t m = *n_out;
-  if (m > cap) return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(m) + " points selected");
-  if (m == 0) return NDT_OK;
   // (the staging is free again: the upload out of it has been awaited)
-  float* back = reinterpret_cast<float*>(b.stage.h);
-  const int cols = has_i ? 4 : 3;
-  for (int a = 0; a < cols; ++a)
-    HIP_TRY(h, hipMemcpyAsync(back + (size_t)a * m, o + (size_t)a * n, m * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (t_out) HIP_TRY(h, hipMemcpyAsync(t_out, o + 4 * n, m * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (index_out) HIP_TRY(h, hipMemcpyAsync(index_out, b.index.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  char* ob = reinterpret_cast<char*>(out);
-  for (size_t i = 0; i < m; ++i) {
-    float* p = reinterpret_cast<float*>(ob + i * stride_bytes);
-    p[0] = back[i]; p[1] = back[m + i]; p[2] = back[2 * m + i];
-    if (has_i) *reinterpret_cast<float*>(ob + i * stride_bytes + intensity_offset_bytes) = back[3 * m + i];
-  }
-  return NDT_OK;
+  return download_strided(h, o, n, o + 4 * n, b.index.p, *n_out, cap, reinterpret_cast<float*>(b.stage.h), out, stride_bytes,
+                          intensity_offset_bytes, t_out, index_out);
 }
 
 int ndt_keyframe_put_from_ranges(ndt_handle* h, int64_t id, const uint32_t* range_mm, const uint8_t* reflectivity, const float* col_t,

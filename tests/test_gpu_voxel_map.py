@@ -299,6 +299,26 @@ def test_min_points(pkg):
     assert_equals_b(ndt, cloud, leaf)                                        # the map is as it was
 
 
+@pytest.mark.parametrize("capacity", [1 << 20, 1 << 21])
+def test_export_at_the_scan_pass_boundary(pkg, capacity):
+    """The export's block offsets come from the engine's one-block scan, 1024 block counts per pass: a table of 2^20
+    slots is 1024 export blocks (exactly one pass), one of 2^21 is 2048 (two passes, the second behind the first's
+    carry).  The hash spreads a few thousand voxels over the whole table."""
+    leaf = 0.5
+    rng = np.random.default_rng(23)
+    cloud = rng.uniform([-8, -8, -1], [8, 8, 1], (3000, 3)).astype(np.float32)
+    counts = voxelmap_numpy(cloud, leaf)[2]
+    assert (counts == 1).sum() > 100 and (counts >= 2).sum() > 100
+    ndt = engine(pkg)
+    ndt.mapReset(leaf, initial_capacity=capacity)
+    assert ndt.mapInfo()["capacity"] == capacity
+    ndt.mapAdd(cloud[:1700])
+    ndt.mapAdd(cloud[1700:])
+    assert ndt.mapInfo()["capacity"] == capacity and ndt.mapInfo()["n_grows"] == 0
+    assert_equals_b(ndt, cloud, leaf, min_points=1)
+    assert_equals_b(ndt, cloud, leaf, min_points=2)
+
+
 def test_keyframes_and_the_target(pkg, stream6, hipmem):
     leaf = 0.5
     kw = dict(resolution=1.0, step_size=0.1, trans_epsilon=1e-4, max_iterations=35)

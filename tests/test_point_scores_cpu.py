@@ -108,3 +108,23 @@ def test_compaction_kernels_do_not_spill(tmp_path):
     assert kernels == {"k_filter_count", "k_filter_scan", "k_filter_emit"}, kernels
     for k, u in usage.items():
         assert u["ScratchSize"] == 0, (k, u)
+
+
+def test_the_compaction_has_one_definition():
+    """The ballot, the block count and the emit position are defined in ndt_compact_device.h and nowhere else, the
+    filter's, the deskew's and the unprojection's kernels call them, and the block counts have ONE scan kernel."""
+    csrc = os.path.join(ROOT, "slam-sam_amd", "csrc")
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".h", ".hip", ".cpp"))}
+    for fn in ("compact_ballot", "compact_block_count", "compact_position"):
+        defs = [f for f, text in sources.items() if re.search(r"\b(unsigned long long|void|unsigned int) %s\(" % fn, text)]
+        assert defs == ["ndt_compact_device.h"], (fn, defs)
+        for f in ("ndt_point_scores.hip", "ndt_deskew.hip", "ndt_unproject.hip"):
+            assert re.search(r"\b%s\(" % fn, sources[f]), (fn, f)
+    # nobody else writes the arithmetic out: a ballot's popcount into a per-wave word, the lanes below in a ballot
+    for f, text in sources.items():
+        if f != "ndt_compact_device.h" and f.startswith(("ndt_point_scores", "ndt_deskew", "ndt_unproject")):
+            assert "__ballot" not in text and "__popcll" not in text, f
+    scans = [(f, m.group(1)) for f, text in sources.items()
+             for m in re.finditer(r"__global__[^{;]*?\b(k_\w*scan)\(([^)]*)\)", text)
+             if re.search(r"\bcounts\b.*\bnb\b.*\btotal\b", m.group(2), re.S)]
+    assert scans == [("ndt_point_scores.hip", "k_filter_scan")], scans
