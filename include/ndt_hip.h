@@ -680,6 +680,62 @@ int ndt_map_import_state(ndt_handle* h, float leaf, const int32_t* ijk, const in
 int ndt_map_import_state_device(ndt_handle* h, float leaf, const int32_t* ijk, const int32_t* count, const float* sums4,
                                 const double* moments9, size_t n);
 
+/* Free-space carving: drop the map voxels that a later scan looks straight through (NDT-OM).  ndt_map_add only gains
+ * evidence and ndt_map_crop removes by position; a map kept for hours otherwise fills with the trails of everything
+ * that moved, and ndt_set_target_from_map* turns the trails into leaves.  A measured ray from the sensor to a return
+ * says that every voxel it crosses before the return is empty now.  One call takes one scan -- a strided host cloud,
+ * SoA arrays in device memory or an archived keyframe -- and `origin`, the sensor position in the cloud's own frame;
+ * the pose (NULL: none) moves the origin together with the points.
+ *  1. Frame.  Points and origin are moved by the pose exactly as ndt_map_add moves a point: f64 products summed left to
+ *     right, rounded to f32 once; with a NULL pose they are taken as they are.  Per axis g = (double)(p_f32 *
+ *     inv_leaf_f32): the f32 product the add floors, widened to f64.  The start voxel is vs = floor(gs) of the origin,
+ *     the end voxel ve = floor(ge) of the point: a ray ends in exactly the voxel ndt_map_add would put its point in.
+ *  2. Skipped rays, counted in n_rays_skipped: a point that is not finite, before or after the pose; |vs| or |ve|
+ *     reaching 2^20 on an axis.  An origin that is not finite (also: behind the pose) is NDT_ERR_INVALID_ARG.
+ *  3. Traversal: Amanatides-Woo in f64 in voxel units, every operation rounded as written, IEEE division.  d = ge - gs.
+ *     Per axis with ve[a] != vs[a]: step = +-1, tDelta = 1.0 / fabs(d), tMax = ((double)(vs + (step > 0 ? 1 : 0)) - gs)
+ *     / d.  An axis with v[a] == ve[a], initially or once reached, has tMax = +inf.  Each step advances the axis with the
+ *     smallest tMax, the lowest axis index on equal values: v[a] += step; tMax[a] += tDelta[a].  The path v_0 = vs ..
+ *     v_L = ve therefore has exactly L = |ve - vs|_1 steps.
+ *  4. Marks.  A miss goes to v_i for 1 <= i <= min(L - 1 - keep_last, max_steps) (none when that bound is below 1), a
+ *     hit goes to v_L whatever L is.  Only voxels the map holds take marks.  n_steps is the sum of those bounds over
+ *     the rays that are not skipped, clamped at 0 per ray.  Marks are integers per table slot and do not depend on the
+ *     order of the rays: results are deterministic.  They live for one call only, in engine scratch sized by the
+ *     capacity; nothing is added to the table's persistent state or to ndt_map_export_state's record.
+ *  5. Removal.  A voxel is removed when misses >= min_misses, it took no hit in this call, and protect_min_count == 0
+ *     or its count < protect_min_count.  n_voxels_crossed: occupied voxels with at least one miss; n_voxels_hit:
+ *     occupied voxels with a hit; n_removed / n_points_removed: the voxels that go and the points they held.
+ *     Everything else is ndt_map_crop's contract: when nothing is removed the table is untouched; otherwise the
+ *     survivors move bit for bit, moments included, into a fresh table of crop's capacity; ndt_map_get_info reports
+ *     the kept voxels and points and their tight ijk box; n_points_dropped, n_adds and n_grows are unchanged; an
+ *     emptied map still exists; an allocation failure is NDT_ERR_ALLOC and leaves the map as it was.  With dry_run the
+ *     counts are reported and the map is untouched in every case.
+ *  6. n == 0 is a no-op with a zeroed result.  No map, a NULL origin or params, a field outside its range or a non-zero
+ *     reserved word is NDT_ERR_INVALID_ARG; so are a non-finite pose, an unknown keyframe id and a keyframe form
+ *     without a pose.  Nothing changes in any of those cases.  The result pointer may be NULL.  Target, source, align
+ *     state, iteration history, evaluation counters and the keyframe archive are left alone, as with ndt_map_crop.
+ *     The call is complete when it returns, and the caller's arrays are free. */
+typedef struct ndt_map_carve_params {
+  int min_misses;        /* >= 1: a voxel goes when at least this many rays of THIS call crossed it */
+  int keep_last;         /* >= 0: the last keep_last voxels before a ray's end voxel are never counted (grazing rays) */
+  int max_steps;         /* 1 .. 65536: a ray is followed for at most this many voxel steps */
+  int protect_min_count; /* 0: off; > 0: a voxel whose count is >= this is never removed */
+  int dry_run;           /* != 0: count everything, change nothing */
+  int reserved[3];       /* zero */
+} ndt_map_carve_params;
+typedef struct ndt_map_carve_result {
+  int64_t n_rays, n_rays_skipped, n_steps, n_voxels_crossed, n_voxels_hit, n_removed, n_points_removed;
+} ndt_map_carve_result;
+void ndt_map_carve_default_params(ndt_map_carve_params* p);   /* 2, 1, 4096, 0, 0 */
+int ndt_map_carve_device(ndt_handle* h, const float* dx, const float* dy, const float* dz, size_t n,
+                         const float origin[3], const double* pose16_colmajor_or_null,
+                         const ndt_map_carve_params* params, ndt_map_carve_result* out_or_null);
+int ndt_map_carve(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, const float origin[3],
+                  const double* pose16_colmajor_or_null, const ndt_map_carve_params* params,
+                  ndt_map_carve_result* out_or_null);
+int ndt_map_carve_keyframe(ndt_handle* h, int64_t id, const float origin[3], const double pose16_colmajor[16],
+                           const ndt_map_carve_params* params, ndt_map_carve_result* out_or_null);
+
 /* setRegularizationPose (ref: run/pipeline_ligo_tc.cpp:531) */
 int ndt_set_regularization_pose(ndt_handle* h, const float pose_colmajor[16]);
 int ndt_clear_regularization_pose(ndt_handle* h);

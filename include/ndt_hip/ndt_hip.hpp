@@ -759,6 +759,40 @@ class NormalDistributionsTransform
     status_ = h_ ? ndt_map_crop(h_, box_min, box_max, remove_inside ? 1 : 0, &removed) : NDT_ERR_NO_DEVICE;
     return status_ == NDT_OK ? removed : 0;
   }
+  // ---- free-space carving (ndt_map_carve*): the voxels that the rays of a scan pass through, and none ends in, go.
+  // origin: the sensor position in the cloud's own frame (the pose moves it with the points; null pose: as it is);
+  // params null: ndt_map_carve_default_params.  Returns the call's counts (all zero on error, lastStatus() says why). ----
+  template <class Cloud>
+  ndt_map_carve_result mapCarve(const Cloud& cloud, const float origin[3], const double* pose_colmajor = nullptr,
+                                const ndt_map_carve_params* params = nullptr) {
+    ndt_map_carve_result r{};
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return r; }
+    ndt_map_carve_params def;
+    ndt_map_carve_default_params(&def);
+    if (cloud.points.empty()) status_ = ndt_map_carve(h_, nullptr, 0, 12, origin, pose_colmajor, params ? params : &def, &r);
+    else status_ = ndt_map_carve(h_, &cloud.points[0].x, cloud.points.size(), sizeof(cloud.points[0]), origin, pose_colmajor,
+                                 params ? params : &def, &r);
+    return status_ == NDT_OK ? r : ndt_map_carve_result{};
+  }
+  ndt_map_carve_result mapCarveDevice(const float* dx, const float* dy, const float* dz, size_t n, const float origin[3],
+                                      const double* pose_colmajor = nullptr, const ndt_map_carve_params* params = nullptr) {
+    ndt_map_carve_result r{};
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return r; }
+    ndt_map_carve_params def;
+    ndt_map_carve_default_params(&def);
+    status_ = ndt_map_carve_device(h_, dx, dy, dz, n, origin, pose_colmajor, params ? params : &def, &r);
+    return status_ == NDT_OK ? r : ndt_map_carve_result{};
+  }
+  ndt_map_carve_result mapCarveKeyframe(int64_t id, const float origin[3], const double* pose_colmajor,
+                                        const ndt_map_carve_params* params = nullptr) {
+    ndt_map_carve_result r{};
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return r; }
+    ndt_map_carve_params def;
+    ndt_map_carve_default_params(&def);
+    status_ = ndt_map_carve_keyframe(h_, id, origin, pose_colmajor, params ? params : &def, &r);
+    return status_ == NDT_OK ? r : ndt_map_carve_result{};
+  }
+
   // box_min / box_max: three floats each, or both null for the whole map
   void mapExportState(MapState& out, const float* box_min = nullptr, const float* box_max = nullptr) {
     out = MapState{};

@@ -108,6 +108,17 @@ class MapInfo(C.Structure):
                 ("max_ijk", C.c_int * 3), ("n_adds", C.c_int64), ("n_grows", C.c_int64)]
 
 
+class MapCarveParams(C.Structure):
+    """ndt_map_carve_params (ndt_map_carve_default_params: 2, 1, 4096, 0, 0)"""
+    _fields_ = [("min_misses", C.c_int), ("keep_last", C.c_int), ("max_steps", C.c_int), ("protect_min_count", C.c_int),
+                ("dry_run", C.c_int), ("reserved", C.c_int * 3)]
+
+
+class MapCarveResult(C.Structure):
+    _fields_ = [("n_rays", C.c_int64), ("n_rays_skipped", C.c_int64), ("n_steps", C.c_int64), ("n_voxels_crossed", C.c_int64),
+                ("n_voxels_hit", C.c_int64), ("n_removed", C.c_int64), ("n_points_removed", C.c_int64)]
+
+
 DESKEW_MAX_KNOTS = 64
 
 
@@ -282,6 +293,7 @@ ABI_SYMBOLS = [
     "ndt_scan_model_set", "ndt_scan_model_clear", "ndt_scan_model_get_info", "ndt_scan_model_from_beams",
     "ndt_unproject_device", "ndt_unproject", "ndt_keyframe_put_from_ranges",
     "ndt_map_crop", "ndt_map_export_state", "ndt_map_export_state_device", "ndt_map_import_state", "ndt_map_import_state_device",
+    "ndt_map_carve_default_params", "ndt_map_carve_device", "ndt_map_carve", "ndt_map_carve_keyframe",
 ]
 
 _lib = None
@@ -407,6 +419,13 @@ def lib():
         L.ndt_map_export_state_device.argtypes = [vp, fp, fp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ndt_map_import_state.argtypes = [vp, C.c_float, vp, vp, vp, vp, C.c_size_t]
         L.ndt_map_import_state_device.argtypes = [vp, C.c_float, vp, vp, vp, vp, C.c_size_t]
+        L.ndt_map_carve_default_params.restype = None
+        L.ndt_map_carve_default_params.argtypes = [C.POINTER(MapCarveParams)]
+        L.ndt_map_carve_device.argtypes = [vp, vp, vp, vp, C.c_size_t, fp, dp, C.POINTER(MapCarveParams),
+                                           C.POINTER(MapCarveResult)]
+        L.ndt_map_carve.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, dp, C.POINTER(MapCarveParams),
+                                    C.POINTER(MapCarveResult)]
+        L.ndt_map_carve_keyframe.argtypes = [vp, C.c_int64, fp, dp, C.POINTER(MapCarveParams), C.POINTER(MapCarveResult)]
         L.ndt_trajectory_pose.argtypes = [dp, dp, C.c_int, dp, C.c_double, dp]
         traj = [dp, dp, C.c_int, dp, C.POINTER(ScanFilter)]
         L.ndt_deskew_device.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t] + traj + [vp, vp, vp, vp, vp, C.c_size_t,
@@ -1175,6 +1194,67 @@ class NormalDistributionsTransform:
     def mapImportStateDevice(self, leaf, d_ijk, d_count, d_sums, d_moments, n):
         """As mapImportState, from device arrays (integer addresses; d_moments None for a map without moments)."""
         self._check(lib().ndt_map_import_state_device(self._h, float(leaf), d_ijk, d_count, d_sums, d_moments, int(n)))
+
+    # --- free-space carving: the voxels that the rays of a scan pass through, and none ends in, leave the map ---
+    @staticmethod
+    def _carve_args(origin, min_misses, keep_last, max_steps, protect_min_count, dry_run):
+        """(origin float32[3], MapCarveParams); ValueError on what the library would refuse"""
+        o = np.ascontiguousarray(origin, dtype=np.float32)
+        if o.shape != (3,) or not np.isfinite(o).all():
+            raise ValueError("origin must be three finite numbers")
+        prm = MapCarveParams()
+        lib().ndt_map_carve_default_params(C.byref(prm))
+        for name, v in (("min_misses", min_misses), ("keep_last", keep_last), ("max_steps", max_steps),
+                        ("protect_min_count", protect_min_count)):
+            if v is not None:
+                setattr(prm, name, int(v))
+        prm.dry_run = int(bool(dry_run))
+        if prm.min_misses < 1 or prm.keep_last < 0 or not 1 <= prm.max_steps <= 65536 or prm.protect_min_count < 0:
+            raise ValueError("min_misses >= 1, keep_last >= 0, 1 <= max_steps <= 65536, protect_min_count >= 0")
+        return o, prm
+
+    @staticmethod
+    def _carve_result(r):
+        return {name: int(getattr(r, name)) for name, _ in MapCarveResult._fields_}
+
+    def mapCarve(self, cloud, origin, pose=None, min_misses=None, keep_last=None, max_steps=None, protect_min_count=None,
+                 dry_run=False):
+        """One scan as a host cloud (N x >= 3 float32) seen from `origin` (the sensor position in the cloud's own frame;
+        `pose`, 4x4 double, moves both): every voxel at least min_misses rays pass through and none ends in is removed.
+        keep_last voxels before a ray's end are never counted, a ray is followed for max_steps voxels, a voxel with
+        protect_min_count points or more stays (0: off), dry_run only counts.  None: the library's default.  Returns
+        dict(n_rays, n_rays_skipped, n_steps, n_voxels_crossed, n_voxels_hit, n_removed, n_points_removed)."""
+        o, prm = self._carve_args(origin, min_misses, keep_last, max_steps, protect_min_count, dry_run)
+        a = np.ascontiguousarray(cloud, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] < 3:
+            raise ValueError("cloud must be N x >=3 float32")
+        p = self._pose16_or_none(pose)
+        stride = a.strides[0] if len(a) else a.itemsize * a.shape[1]
+        r = MapCarveResult()
+        self._check(lib().ndt_map_carve(self._h, a.ctypes.data if len(a) else None, len(a), stride, _fp(o),
+                                        None if p is None else _dp(p), C.byref(prm), C.byref(r)))
+        return self._carve_result(r)
+
+    def mapCarveDevice(self, dx, dy, dz, n, origin, pose=None, min_misses=None, keep_last=None, max_steps=None,
+                       protect_min_count=None, dry_run=False):
+        """SoA float32 arrays in device memory (integer addresses), as mapCarve."""
+        o, prm = self._carve_args(origin, min_misses, keep_last, max_steps, protect_min_count, dry_run)
+        p = self._pose16_or_none(pose)
+        r = MapCarveResult()
+        self._check(lib().ndt_map_carve_device(self._h, dx, dy, dz, int(n), _fp(o), None if p is None else _dp(p),
+                                               C.byref(prm), C.byref(r)))
+        return self._carve_result(r)
+
+    def mapCarveKeyframe(self, kf_id, origin, pose, min_misses=None, keep_last=None, max_steps=None, protect_min_count=None,
+                         dry_run=False):
+        """An archived keyframe (putKeyframe) under its 4x4 double pose, as mapCarve."""
+        o, prm = self._carve_args(origin, min_misses, keep_last, max_steps, protect_min_count, dry_run)
+        p = self._pose16_or_none(pose)
+        if p is None:
+            raise ValueError("a keyframe is carved under a pose")
+        r = MapCarveResult()
+        self._check(lib().ndt_map_carve_keyframe(self._h, int(kf_id), _fp(o), _dp(p), C.byref(prm), C.byref(r)))
+        return self._carve_result(r)
 
     def setGlobalSourceSize(self, n):
         self._check(lib().ndt_set_global_source_size(self._h, int(n)))

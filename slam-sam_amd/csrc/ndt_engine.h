@@ -8,6 +8,7 @@
 //                      the host side of every compaction (the device side: ndt_compact_device.h)
 //   ndt_map.hip        the sparse voxel map accumulated scan by scan (ndt_map_*), its kernels included
 //   ndt_map_state.hip  the map's crop, full-state export / import and merge (k_mapstate_* kernels)
+//   ndt_map_carve.hip  free-space carving of the map: voxels that a scan's rays pass through go (k_mapcarve_* kernels)
 //   ndt_deskew.hip     motion compensation of a scan along a pose trajectory + the acquisition filter (its kernels included)
 //   ndt_unproject.hip  a lidar range image -> points through the scan model's tables, fused with that filter and deskew
 // One handle = one engine instance = one HIP stream on one gfx950 device; it owns every device allocation.  There is no
@@ -260,6 +261,9 @@ struct VoxelMap {
   DevBuf<double> xmom;                 // ... and its 9 sums
   DevBuf<int> tsel;                    // target from moments: what the selection pass reduces (TS_* words, ndt_map.hip)
   PinBuf<int> tsel_h;                  // [0..15] read-back, [16..31] the neutral words
+  DevBuf<unsigned int> cmarks;         // carve (ndt_map_carve.hip): one call's mark word per slot, `capacity` of them
+  DevBuf<unsigned long long> cstat;    // ... and its counters
+  PinBuf<unsigned long long> cstat_h;
   void release() {
     if (keys) (void)hipFree(keys);
     if (sums) (void)hipFree(sums);
@@ -269,7 +273,7 @@ struct VoxelMap {
     pkey.release(); px.release(); py.release(); pz.release(); ux.release(); uy.release(); uz.release(); ui.release();
     stats.release(); nvox.release(); stats_h.release(); nvox_h.release(); plan_h.release(); xcounts.release();
     xslot.release(); xslot2.release(); xhi.release(); xout.release(); xcnt.release(); xijk.release(); xmom.release();
-    tsel.release(); tsel_h.release();
+    tsel.release(); tsel_h.release(); cmarks.release(); cstat.release(); cstat_h.release();
   }
 };
 

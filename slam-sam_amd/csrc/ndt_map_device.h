@@ -1,6 +1,7 @@
-// ndt_map_device.h -- what the voxel map's kernels share across translation units (ndt_map.hip, ndt_map_state.hip):
-// the table's constants, the words of VoxelMap::stats / tsel, the hash and the probe that claims a slot, the box
-// predicate of a selection and the wave reductions.  Device code only; include it after hip_runtime.
+// ndt_map_device.h -- what the voxel map's kernels share across translation units (ndt_map.hip, ndt_map_state.hip,
+// ndt_map_carve.hip): the table's constants, the words of VoxelMap::stats / tsel, the hash, the probe that claims a slot
+// and the one that only looks, the box predicate of a selection and the wave reductions.  Device code only; include it
+// after hip_runtime.
 #pragma once
 
 namespace ndt {
@@ -55,6 +56,21 @@ __device__ __forceinline__ long long map_slot_of(unsigned long long* __restrict_
       if (cur == MAP_EMPTY) { *claimed = true; return (long long)s; }
     }
     if (cur == key) return (long long)s;
+    s = (s + 1) & mask;
+  }
+  return -1;
+}
+
+// The slot that holds `key`, or -1 if the table does not hold it: the same probe sequence, read only, ended by the first
+// empty position (nothing is ever deleted in place) or after all `mask + 1` positions.  For a table no launch in flight
+// inserts into.
+__device__ __forceinline__ long long map_find(const unsigned long long* __restrict__ tkeys, unsigned long long mask,
+                                              unsigned long long key) {
+  unsigned long long s = map_hash(key) & mask;
+  for (unsigned long long probe = 0; probe <= mask; ++probe) {
+    const unsigned long long cur = tkeys[s];
+    if (cur == key) return (long long)s;
+    if (cur == MAP_EMPTY) return -1;
     s = (s + 1) & mask;
   }
   return -1;
