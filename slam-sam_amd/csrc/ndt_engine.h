@@ -226,6 +226,16 @@ struct ScanModelBufs {
   }
 };
 
+// The voxel map's table, as its kernels take it (by value) and as growth, crop and carve replace it (map_replace_table).
+struct MapTable {
+  unsigned long long* keys = nullptr;  // capacity words, ~0 = empty
+  float4* sums = nullptr;              // capacity
+  int* cnt = nullptr;                  // capacity
+  double* mom = nullptr;               // capacity x 9 doubles; allocated only with moments on
+  int64_t capacity = 0;
+};
+void map_free_table(MapTable& t);      // ndt_map.hip: frees what t holds and leaves it empty
+
 // The sparse voxel map of ndt_map_* (ndt_map.hip): an open-addressing table in HBM keyed by the 63-bit voxel key
 // (k, j, i), the table position being the voxel's slot -- float sums {x, y, z, intensity} and an int32 count per slot,
 // and with moments on (ndt_map_enable_moments) the nine f64 sums of the target build {x, y, z, xx, xy, xz, yy, yz, zz}:
@@ -235,12 +245,8 @@ struct ScanModelBufs {
 struct VoxelMap {
   float leaf = 0.0f, inv_leaf = 0.0f;
   int with_intensity = 0;
-  unsigned long long* keys = nullptr;  // capacity words, ~0 = empty
-  float* sums = nullptr;               // capacity x float4
-  int* cnt = nullptr;                  // capacity
-  double* mom = nullptr;               // capacity x 9 doubles; allocated only with moments on
+  MapTable tab;
   bool moments = false;
-  int64_t capacity = 0;
   int64_t reset_capacity = 0;          // the capacity ndt_map_reset gave it: a crop never shrinks the table below it
   int64_t n_voxels = 0, n_points = 0, n_dropped = 0, n_adds = 0, n_grows = 0;
   int mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
@@ -265,11 +271,8 @@ struct VoxelMap {
   DevBuf<unsigned long long> cstat;    // ... and its counters
   PinBuf<unsigned long long> cstat_h;
   void release() {
-    if (keys) (void)hipFree(keys);
-    if (sums) (void)hipFree(sums);
-    if (cnt) (void)hipFree(cnt);
-    if (mom) (void)hipFree(mom);
-    keys = nullptr; sums = nullptr; cnt = nullptr; mom = nullptr; moments = false; capacity = 0;
+    map_free_table(tab);
+    moments = false;
     pkey.release(); px.release(); py.release(); pz.release(); ux.release(); uy.release(); uz.release(); ui.release();
     stats.release(); nvox.release(); stats_h.release(); nvox_h.release(); plan_h.release(); xcounts.release();
     xslot.release(); xslot2.release(); xhi.release(); xout.release(); xcnt.release(); xijk.release(); xmom.release();
@@ -568,8 +571,15 @@ int no_map(ndt_handle* h);
 int map_bits_for(long long v);
 int64_t map_pow2_at_least(int64_t v);
 int map_box_floor(float v, float inv_leaf);
-void map_free_table(unsigned long long* k, float* s, int* c, double* q);
-int map_alloc_table(ndt_handle* h, int64_t cap, bool with_moments, unsigned long long** k, float** s, int** c, double** q);
+bool pose_finite(const double p[16]);
+bool finite3(const float v[3]);
+int map_alloc_table(ndt_handle* h, int64_t cap, bool with_moments, MapTable* t);
+// The map's table is replaced by a fresh one of new_cap slots that `launch` fills from the old one (the caller's one
+// kernel launch on the engine's stream; awaited here).  kept < 0: growth, every voxel moves.  kept >= 0: a selective move
+// that keeps `kept` voxels -- tsel is reset in front of the launch and read back behind it, the device's voxel counter,
+// n_voxels and (kept > 0) the ijk box follow.  On any error the map is as it was and `what` heads the text.
+int map_replace_table(ndt_handle* h, int64_t new_cap, const char* what, const std::function<void(const MapTable&)>& launch,
+                      int64_t kept);
 int map_grow_table(ndt_handle* h, int64_t new_cap);
 int map_sort_scratch(ndt_handle* h, size_t n);
 int map_refresh_voxel_count(ndt_handle* h);

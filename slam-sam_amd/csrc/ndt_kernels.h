@@ -115,18 +115,18 @@ void launch_finalize_leaves(const ndt_tuning& tn, const float* xyz4, const uint3
                             int done_tag, hipStream_t s);
 
 // Target from the voxel map's moments (ndt_set_target_from_map_moments, ndt_map.hip): leaf slot r < m is the map voxel
-// in table position slots[order[r]] -- its 63-bit key (k, j, i), 21 bits each, biased; key_min: the grid's min_b per axis
-// with the same bias -- its count and its nine f64 sums (9 doubles per table position), through the ordinary build's
+// in table position slots[order[r]] -- its 63-bit key (map_key, ndt_map_device.h); min_b: the grid's min_b per axis -- its
+// count and its nine f64 sums (9 doubles per table position), through the ordinary build's
 // finalize_leaf: statistics, record, centroid, dense index entry.  *d_nvalid (zero before the launch) receives the
 // number of accepted leaves, one integer add per block.
 void launch_map_finalize(const uint32_t* order, const uint32_t* slots, size_t m, const unsigned long long* table_keys,
-                         const int* table_cnt, const double* table_mom, const int key_min[3], int mul1, int mul2,
+                         const int* table_cnt, const double* table_mom, const int min_b[3], int mul1, int mul2,
                          FinalizeParams fp, VoxelRecord* rec, float* cent4, LeafStats* stats, int* cell2leaf, int* d_nvalid,
                          hipStream_t s);
 
-// ... and the same voxels as they are (ndt_map_export_moments): absolute ijk (key fields minus key_bias), count, nine sums
+// ... and the same voxels as they are (ndt_map_export_moments): absolute ijk, count, nine sums
 void launch_map_gather_moments(const uint32_t* order, const uint32_t* slots, size_t m, const unsigned long long* table_keys,
-                               const int* table_cnt, const double* table_mom, int key_bias, int32_t* oijk, int32_t* ocount,
+                               const int* table_cnt, const double* table_mom, int32_t* oijk, int32_t* ocount,
                                double* osums, hipStream_t s);
 // the cells the previous build published (old_stats[0 .. dirty_slots)) back to -1: what the ordinary build's bounds
 // launch does on its way

@@ -14,8 +14,10 @@
 //            voxel's points to; ndt_set_target_from_map_moments selects the voxels of a box with the export's count / scan /
 //            compaction / key sort under a predicate (ONE host wait: selection count, ijk box and point total decide the
 //            refusals and size the grid) and hands each to the ordinary build's finalize_leaf (launch_map_finalize).
-// Crop, state export and state import are in ndt_map_state.hip; the constants and device helpers both files use are in
-// ndt_map_device.h, and the host functions of this file that the other one calls are declared in ndt_engine.h.
+// Crop, state export and state import are in ndt_map_state.hip, the carve in ndt_map_carve.hip; the constants and device
+// helpers the three files use (key, probes, box reduction, a slot's move) are in ndt_map_device.h, and the host functions
+// of this file that the others call -- map_replace_table, the one way a table is replaced, among them -- are declared in
+// ndt_engine.h.
 #include "ndt_engine.h"
 #include "ndt_map_device.h"
 
@@ -34,9 +36,8 @@ __device__ __forceinline__ bool map_finite3(float a, float b, float c) {
 __global__ void __launch_bounds__(MAP_THREADS) k_map_keys(const float* __restrict__ x, const float* __restrict__ y,
                                                          const float* __restrict__ z, int n, float inv_leaf,
                                                          unsigned long long* __restrict__ pkey, int* __restrict__ stats) {
-  __shared__ int red[MAP_WAVES][8];
+  __shared__ int red[MAP_WAVES][2], box[MAP_WAVES][6];
   const int i = (int)(blockIdx.x * MAP_THREADS + threadIdx.x);
-  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
   int fin = 0, oor = 0;
   int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
   if (i < n) {
@@ -48,8 +49,7 @@ __global__ void __launch_bounds__(MAP_THREADS) k_map_keys(const float* __restric
       if (fabsf(fi) < MAP_LIMIT && fabsf(fj) < MAP_LIMIT && fabsf(fk) < MAP_LIMIT) {
         const int vi = (int)fi, vj = (int)fj, vk = (int)fk;
         mn[0] = mx[0] = vi; mn[1] = mx[1] = vj; mn[2] = mx[2] = vk;
-        key = ((unsigned long long)(vk + MAP_BIAS) << 42) | ((unsigned long long)(vj + MAP_BIAS) << 21) |
-              (unsigned long long)(vi + MAP_BIAS);
+        key = map_key(vi, vj, vk);
       } else {
         oor = 1;
       }
@@ -58,22 +58,16 @@ __global__ void __launch_bounds__(MAP_THREADS) k_map_keys(const float* __restric
   }
   fin = wave_sum(fin);
   oor = wave_sum(oor);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { mn[a] = wave_min(mn[a]); mx[a] = wave_max(mx[a]); }
-  if (lane == 0) {
-    red[wave][0] = fin; red[wave][1] = oor;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { red[wave][2 + a] = mn[a]; red[wave][5 + a] = mx[a]; }
-  }
+  if ((threadIdx.x & 63u) == 0) { red[threadIdx.x >> 6][0] = fin; red[threadIdx.x >> 6][1] = oor; }
+  map_box_waves(mn, mx, box);
   __syncthreads();
-  if (threadIdx.x < 8) {
-    const int t = (int)threadIdx.x;
-    int v = red[0][t];
+  map_box_commit(box, stats + MS_MIN, stats + MS_MAX);
+  if (threadIdx.x == 6 || threadIdx.x == 7) {   // (the two counters: the threads of that wave the box leaves idle)
+    const int t = (int)threadIdx.x - 6;          // MS_FINITE, MS_OOR
+    int v = 0;
 #pragma unroll
-    for (int w = 1; w < MAP_WAVES; ++w) v = t < 2 ? v + red[w][t] : t < 5 ? min(v, red[w][t]) : max(v, red[w][t]);
-    if (t < 2) { if (v) atomicAdd(stats + t, v); }
-    else if (t < 5) { if (v != INT_MAX) atomicMin(stats + t, v); }
-    else if (v != INT_MIN) atomicMax(stats + t, v);
+    for (int w = 0; w < MAP_WAVES; ++w) v += red[w][t];
+    if (v) atomicAdd(stats + t, v);
   }
 }
 
@@ -153,25 +147,11 @@ __global__ void __launch_bounds__(MAP_THREADS) k_map_accumulate(const int* __res
 }
 
 // growth: every occupied slot of the old table moves to the new one with its sums and its count as they are
-__global__ void __launch_bounds__(MAP_THREADS) k_map_rehash(const unsigned long long* __restrict__ okeys,
-                                                           const float4* __restrict__ osums, const int* __restrict__ ocnt,
-                                                           long long ocap, unsigned long long* __restrict__ tkeys,
-                                                           unsigned long long mask, float4* __restrict__ sums,
-                                                           int* __restrict__ cnt, int* __restrict__ stats,
-                                                           const double* __restrict__ omom, double* __restrict__ mom) {
+__global__ void __launch_bounds__(MAP_THREADS) k_map_rehash(MapTable o, MapTable t, int* __restrict__ stats) {
   const long long i = (long long)blockIdx.x * MAP_THREADS + threadIdx.x;
-  if (i >= ocap) return;
-  const unsigned long long key = okeys[i];
-  if (key == MAP_EMPTY) return;
-  bool claimed;
-  const long long s = map_slot_of(tkeys, mask, key, &claimed);
-  if (s < 0) { atomicAdd(stats + MS_PROBE_FAIL, 1); return; }
-  sums[s] = osums[i];
-  cnt[s] = ocnt[i];
-  if (mom) {
-#pragma unroll
-    for (int a = 0; a < 9; ++a) mom[(size_t)s * 9 + a] = omom[(size_t)i * 9 + a];
-  }
+  if (i >= o.capacity) return;
+  const unsigned long long key = o.keys[i];
+  if (key != MAP_EMPTY) map_move_slot(o, i, key, t, stats);
 }
 
 // ---- export ----
@@ -192,7 +172,7 @@ __global__ void __launch_bounds__(MAP_THREADS) k_map_xcount(const unsigned long 
                                                            const int* __restrict__ cnt, long long cap, MapSel sel,
                                                            unsigned int* __restrict__ counts, int* __restrict__ tsel) {
   __shared__ unsigned int s_w[MAP_WAVES];
-  __shared__ int red[MAP_WAVES][8];
+  __shared__ int box[MAP_WAVES][6], red_vox[MAP_WAVES];
   __shared__ unsigned long long red_pts[MAP_WAVES];
   unsigned int c = 0;
   int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN}, nvox = 0;
@@ -206,8 +186,8 @@ __global__ void __launch_bounds__(MAP_THREADS) k_map_xcount(const unsigned long 
         const unsigned long long key = tkeys[slot];
         if (key != MAP_EMPTY && map_in_box(key, sel)) {
           const int n = cnt[slot];
-          const int v[3] = {(int)(key & 0x1fffffull) - MAP_BIAS, (int)((key >> 21) & 0x1fffffull) - MAP_BIAS,
-                            (int)(key >> 42) - MAP_BIAS};
+          int v[3];
+          map_ijk(key, v);
 #pragma unroll
           for (int a = 0; a < 3; ++a) { mn[a] = min(mn[a], v[a]); mx[a] = max(mx[a], v[a]); }
           ++nvox;
@@ -223,16 +203,9 @@ __global__ void __launch_bounds__(MAP_THREADS) k_map_xcount(const unsigned long 
   const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
   if (BOX) {
     nvox = wave_sum(nvox);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { mn[a] = wave_min(mn[a]); mx[a] = wave_max(mx[a]); }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) pts += __shfl_xor(pts, off);
-    if (lane == 0) {
-#pragma unroll
-      for (int a = 0; a < 3; ++a) { red[wave][TS_MIN + a] = mn[a]; red[wave][TS_MAX + a] = mx[a]; }
-      red[wave][TS_VOXELS] = nvox;
-      red_pts[wave] = pts;
-    }
+    pts = wave_sum_u64(pts);
+    if (lane == 0) { red_vox[wave] = nvox; red_pts[wave] = pts; }
+    map_box_waves(mn, mx, box);
   }
   if (lane == 0) s_w[wave] = c;
   __syncthreads();
@@ -242,16 +215,14 @@ __global__ void __launch_bounds__(MAP_THREADS) k_map_xcount(const unsigned long 
     for (int w = 0; w < MAP_WAVES; ++w) t += s_w[w];
     counts[blockIdx.x] = t;
   }
-  if (BOX && threadIdx.x < 8) {
-    const int t = (int)threadIdx.x;
-    if (t < 7) {
-      int v = red[0][t];
+  if (BOX) {
+    map_box_commit(box, tsel + TS_MIN, tsel + TS_MAX);
+    if (threadIdx.x == 6) {
+      int v = 0;
 #pragma unroll
-      for (int w = 1; w < MAP_WAVES; ++w) v = t < TS_MAX ? min(v, red[w][t]) : t < TS_VOXELS ? max(v, red[w][t]) : v + red[w][t];
-      if (t < TS_MAX) { if (v != INT_MAX) atomicMin(tsel + t, v); }
-      else if (t < TS_VOXELS) { if (v != INT_MIN) atomicMax(tsel + t, v); }
-      else if (v) atomicAdd(tsel + t, v);
-    } else {
+      for (int w = 0; w < MAP_WAVES; ++w) v += red_vox[w];
+      if (v) atomicAdd(tsel + TS_VOXELS, v);
+    } else if (threadIdx.x == 7) {
       unsigned long long v = 0;
 #pragma unroll
       for (int w = 0; w < MAP_WAVES; ++w) v += red_pts[w];
@@ -298,10 +269,10 @@ __global__ void __launch_bounds__(MAP_THREADS) k_map_xemit(const unsigned long l
     if (keep[r]) {
       const long long slot = (long long)blockIdx.x * MAP_XTILE + r * MAP_THREADS + threadIdx.x;
       const unsigned int pos = before + wave_off + (unsigned int)__popcll(bal[r] & ((1ull << lane) - 1ull));
-      const unsigned long long key = tkeys[slot];
-      const unsigned long long vi = (key & 0x1fffffull) - (unsigned long long)(box.mn[0] + MAP_BIAS);
-      const unsigned long long vj = ((key >> 21) & 0x1fffffull) - (unsigned long long)(box.mn[1] + MAP_BIAS);
-      const unsigned long long vk = (key >> 42) - (unsigned long long)(box.mn[2] + MAP_BIAS);
+      int v[3];
+      map_ijk(tkeys[slot], v);   // (inside the box: no difference is negative)
+      const unsigned long long vi = (unsigned long long)(v[0] - box.mn[0]), vj = (unsigned long long)(v[1] - box.mn[1]),
+                               vk = (unsigned long long)(v[2] - box.mn[2]);
       const unsigned long long rk = (vk << (box.bx + box.by)) | (vj << box.bx) | vi;
       xslot[pos] = (uint32_t)slot;
       klo[pos] = (uint32_t)rk;
@@ -355,30 +326,32 @@ int map_bits_for(long long v) {  // bits that hold 0 .. v
   return b;
 }
 
-void map_free_table(unsigned long long* k, float* s, int* c, double* q) {
-  if (k) (void)hipFree(k);
-  if (s) (void)hipFree(s);
-  if (c) (void)hipFree(c);
-  if (q) (void)hipFree(q);
+void map_free_table(MapTable& t) {
+  if (t.keys) (void)hipFree(t.keys);
+  if (t.sums) (void)hipFree(t.sums);
+  if (t.cnt) (void)hipFree(t.cnt);
+  if (t.mom) (void)hipFree(t.mom);
+  t = MapTable{};
 }
 
 // an empty table of `cap` slots (keys ~0, sums, counts and -- with_moments -- moments zero), written on the engine's stream
-int map_alloc_table(ndt_handle* h, int64_t cap, bool with_moments, unsigned long long** k, float** s, int** c, double** q) {
-  *k = nullptr; *s = nullptr; *c = nullptr; *q = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(k), (size_t)cap * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(s), (size_t)cap * 4 * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(c), (size_t)cap * sizeof(int));
-  if (e == hipSuccess && with_moments) e = hipMalloc(reinterpret_cast<void**>(q), (size_t)cap * 9 * sizeof(double));
-  if (e == hipSuccess) e = hipMemsetAsync(*k, 0xFF, (size_t)cap * sizeof(unsigned long long), h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(*s, 0, (size_t)cap * 4 * sizeof(float), h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(*c, 0, (size_t)cap * sizeof(int), h->stream);
-  if (e == hipSuccess && with_moments) e = hipMemsetAsync(*q, 0, (size_t)cap * 9 * sizeof(double), h->stream);
+int map_alloc_table(ndt_handle* h, int64_t cap, bool with_moments, MapTable* t) {
+  *t = MapTable{};
+  const size_t n = (size_t)cap;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&t->keys), n * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->sums), n * sizeof(float4));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->cnt), n * sizeof(int));
+  if (e == hipSuccess && with_moments) e = hipMalloc(reinterpret_cast<void**>(&t->mom), n * 9 * sizeof(double));
+  if (e == hipSuccess) e = hipMemsetAsync(t->keys, 0xFF, n * sizeof(unsigned long long), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t->sums, 0, n * sizeof(float4), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t->cnt, 0, n * sizeof(int), h->stream);
+  if (e == hipSuccess && with_moments) e = hipMemsetAsync(t->mom, 0, n * 9 * sizeof(double), h->stream);
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    map_free_table(*k, *s, *c, *q);
-    *k = nullptr; *s = nullptr; *c = nullptr; *q = nullptr;
+    map_free_table(*t);
     return fail(h, e == hipErrorOutOfMemory ? NDT_ERR_ALLOC : NDT_ERR_HIP, std::string("voxel map table: ") + hipGetErrorString(e));
   }
+  t->capacity = cap;
   return NDT_OK;
 }
 
@@ -433,25 +406,50 @@ int map_refresh_voxel_count(ndt_handle* h) {
   return NDT_OK;
 }
 
+int map_replace_table(ndt_handle* h, int64_t new_cap, const char* what, const std::function<void(const MapTable&)>& launch,
+                      int64_t kept) {
+  VoxelMap& m = *h->map;
+  hipStream_t s = h->stream;
+  const bool selective = kept >= 0;
+  MapTable fresh;
+  int rc = map_alloc_table(h, new_cap, m.moments, &fresh);
+  if (rc) return rc;   // the map is as it was
+  hipError_t e = hipSuccess;
+  if (selective) e = hipMemcpyAsync(m.tsel.p, m.tsel_h.h + TS_WORDS, TS_WORDS * sizeof(int), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) {
+    launch(fresh);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && selective) e = hipMemcpyAsync(m.tsel_h.h, m.tsel.p, TS_WORDS * sizeof(int), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);   // (a replacement is rare: the old table is freed behind its last reader)
+  if (e == hipSuccess && selective) {   // the next add reads the device's counter
+    m.nvox_h.h[0] = (unsigned long long)kept;
+    e = hipMemcpy(m.nvox.p, m.nvox_h.h, sizeof(unsigned long long), hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    map_free_table(fresh);
+    return fail(h, NDT_ERR_HIP, std::string(what) + hipGetErrorString(e));
+  }
+  map_free_table(m.tab);
+  m.tab = fresh;
+  if (selective) {
+    m.n_voxels = kept;
+    m.nvox_stale = false;
+    if (kept > 0)
+      for (int a = 0; a < 3; ++a) { m.mn[a] = m.tsel_h.h[TS_MIN + a]; m.mx[a] = m.tsel_h.h[TS_MAX + a]; }
+  }
+  return NDT_OK;
+}
+
 int map_grow_table(ndt_handle* h, int64_t new_cap) {
   VoxelMap& m = *h->map;
-  unsigned long long* nk; float* ns; int* nc; double* nq;
-  int rc = map_alloc_table(h, new_cap, m.moments, &nk, &ns, &nc, &nq);
-  if (rc) return rc;   // the map is as it was
-  hipLaunchKernelGGL(k_map_rehash, dim3((unsigned)((m.capacity + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0, h->stream,
-                     m.keys, reinterpret_cast<const float4*>(m.sums), m.cnt, (long long)m.capacity, nk,
-                     (unsigned long long)(new_cap - 1), reinterpret_cast<float4*>(ns), nc, m.stats.p, m.mom, nq);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // (growth is rare: the old table is freed behind its last reader)
-  if (e != hipSuccess) {
-    map_free_table(nk, ns, nc, nq);
-    return fail(h, NDT_ERR_HIP, std::string("voxel map growth: ") + hipGetErrorString(e));
-  }
-  map_free_table(m.keys, m.sums, m.cnt, m.mom);
-  m.keys = nk; m.sums = ns; m.cnt = nc; m.mom = nq;
-  m.capacity = new_cap;
-  ++m.n_grows;
-  return NDT_OK;
+  const int rc = map_replace_table(h, new_cap, "voxel map growth: ", [&](const MapTable& fresh) {
+    hipLaunchKernelGGL(k_map_rehash, dim3((unsigned)((m.tab.capacity + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0,
+                       h->stream, m.tab, fresh, m.stats.p);
+  }, -1);
+  if (rc == NDT_OK) ++m.n_grows;
+  return rc;
 }
 
 // The batch's n keys (m.pkey; MAP_EMPTY: skipped) get their slots (k_map_insert: the device's voxel counter goes up by
@@ -461,10 +459,10 @@ int map_group_batch(ndt_handle* h, size_t n, const uint32_t** keys_sorted, const
   VoxelMap& m = *h->map;
   hipStream_t s = h->stream;
   const unsigned blocks = (unsigned)((n + MAP_THREADS - 1) / MAP_THREADS);
-  hipLaunchKernelGGL(k_map_insert, dim3(blocks), dim3(MAP_THREADS), 0, s, m.pkey.p, (int)n, m.keys,
-                     (unsigned long long)(m.capacity - 1), h->keys.p, m.nvox.p, m.stats.p);
+  hipLaunchKernelGGL(k_map_insert, dim3(blocks), dim3(MAP_THREADS), 0, s, m.pkey.p, (int)n, m.tab.keys,
+                     (unsigned long long)(m.tab.capacity - 1), h->keys.p, m.nvox.p, m.stats.p);
   int passes = 0;
-  int rc = map_put_plan(h, 0, map_bits_for(m.capacity), (int)m.capacity, &passes);   // (the sentinel `capacity` sorts behind every slot)
+  int rc = map_put_plan(h, 0, map_bits_for(m.tab.capacity), (int)m.tab.capacity, &passes);   // (the sentinel `capacity` sorts behind every slot)
   if (rc) return rc;
   launch_sort_first_count(h->keys.p, n, h->gd.p, h->sort_tmp.p, s);
   bool in_b = false;
@@ -514,7 +512,7 @@ int map_add_device(ndt_handle* h, const float* dx, const float* dy, const float*
     return fail(h, NDT_ERR_GRID_OVERFLOW, std::to_string(st[MS_OOR]) + " point(s) beyond the map's coordinate range (|voxel index| < 2^20 per axis); nothing was added");
   const int64_t n_finite = st[MS_FINITE];
   const int64_t want = map_pow2_at_least(2 * (m.n_voxels + (int64_t)n));
-  if (want > m.capacity) {
+  if (want > m.tab.capacity) {
     if (want > MAP_MAX_CAPACITY) return fail(h, NDT_ERR_ALLOC, "voxel map: more than 2^30 table slots needed");
     rc = map_grow_table(h, want);
     if (rc) return rc;
@@ -535,11 +533,11 @@ int map_add_device(ndt_handle* h, const float* dx, const float* dy, const float*
   if (m.moments)
     hipLaunchKernelGGL(k_map_accumulate<true>, dim3(blocks), dim3(MAP_THREADS), 0, s, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p,
                        keys_sorted, vals_sorted, qx, qy, qz, m.with_intensity ? di : nullptr,
-                       reinterpret_cast<float4*>(m.sums), m.cnt, m.mom);
+                       m.tab.sums, m.tab.cnt, m.tab.mom);
   else
     hipLaunchKernelGGL(k_map_accumulate<false>, dim3(blocks), dim3(MAP_THREADS), 0, s, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p,
                        keys_sorted, vals_sorted, qx, qy, qz, m.with_intensity ? di : nullptr,
-                       reinterpret_cast<float4*>(m.sums), m.cnt, static_cast<double*>(nullptr));
+                       m.tab.sums, m.tab.cnt, static_cast<double*>(nullptr));
   HIP_TRY(h, hipGetLastError());
   // the caller's arrays (and the engine's scratch) are free again when the call returns
   HIP_TRY(h, hipStreamSynchronize(s));
@@ -563,14 +561,14 @@ int map_export_count(ndt_handle* h, const MapSel& sel, bool box, size_t* total) 
   if (rc) return rc;
   if (m.n_voxels == 0) return NDT_OK;
   hipStream_t s = h->stream;
-  const int nb = (int)((m.capacity + MAP_XTILE - 1) / MAP_XTILE);
+  const int nb = (int)((m.tab.capacity + MAP_XTILE - 1) / MAP_XTILE);
   HIP_TRY(h, m.xcounts.ensure((size_t)nb + 2));
   if (box) {
     HIP_TRY(h, hipMemcpyAsync(m.tsel.p, m.tsel_h.h + TS_WORDS, TS_WORDS * sizeof(int), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_map_xcount<true>, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.keys, m.cnt, (long long)m.capacity, sel,
+    hipLaunchKernelGGL(k_map_xcount<true>, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.tab.keys, m.tab.cnt, (long long)m.tab.capacity, sel,
                        m.xcounts.p, m.tsel.p);
   } else {
-    hipLaunchKernelGGL(k_map_xcount<false>, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.keys, m.cnt, (long long)m.capacity, sel,
+    hipLaunchKernelGGL(k_map_xcount<false>, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.tab.keys, m.tab.cnt, (long long)m.tab.capacity, sel,
                        m.xcounts.p, static_cast<int*>(nullptr));
   }
   launch_filter_scan(m.xcounts.p, nb, m.xcounts.p + nb + 1, s);   // (xcounts[nb] receives the sum as well: read below)
@@ -602,12 +600,12 @@ int map_export_order(ndt_handle* h, const MapSel& sel, bool box_sel, size_t tota
     HIP_TRY(h, m.xhi.ensure(total));
     HIP_TRY(h, m.xslot2.ensure(total));
   }
-  const int nb = (int)((m.capacity + MAP_XTILE - 1) / MAP_XTILE);
+  const int nb = (int)((m.tab.capacity + MAP_XTILE - 1) / MAP_XTILE);
   if (box_sel)
-    hipLaunchKernelGGL(k_map_xemit<true>, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.keys, m.cnt, (long long)m.capacity, sel,
+    hipLaunchKernelGGL(k_map_xemit<true>, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.tab.keys, m.tab.cnt, (long long)m.tab.capacity, sel,
                        m.xcounts.p, box, m.xslot.p, h->keys.p, two_words ? m.xhi.p : nullptr);
   else
-    hipLaunchKernelGGL(k_map_xemit<false>, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.keys, m.cnt, (long long)m.capacity, sel,
+    hipLaunchKernelGGL(k_map_xemit<false>, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.tab.keys, m.tab.cnt, (long long)m.tab.capacity, sel,
                        m.xcounts.p, box, m.xslot.p, h->keys.p, two_words ? m.xhi.p : nullptr);
   HIP_TRY(h, hipGetLastError());
   int passes = 0;
@@ -647,7 +645,7 @@ int map_export_write(ndt_handle* h, int min_points, size_t total, float* ox, flo
   int rc = map_export_order(h, sel_all(min_points), false, total, m.mn, m.mx, &order, &slots);
   if (rc) return rc;
   hipLaunchKernelGGL(k_map_xcentroids, dim3((unsigned)((w + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0, s, order, slots,
-                     (int)w, reinterpret_cast<const float4*>(m.sums), m.cnt, ox, oy, oz, m.with_intensity ? oi : nullptr, oc);
+                     (int)w, m.tab.sums, m.tab.cnt, ox, oy, oz, m.with_intensity ? oi : nullptr, oc);
   HIP_TRY(h, hipGetLastError());
   if (oi && !m.with_intensity) HIP_TRY(h, hipMemsetAsync(oi, 0, w * sizeof(float), s));
   HIP_TRY(h, hipStreamSynchronize(s));
@@ -664,13 +662,15 @@ int map_box_floor(float v, float inv_leaf) {
   return f <= -MAP_LIMIT ? -MAP_BIAS : f >= MAP_LIMIT ? MAP_BIAS : (int)f;
 }
 
-namespace {
-
-bool pose_finite(const double* p) {
+bool pose_finite(const double p[16]) {
   for (int i = 0; i < 16; ++i)
     if (!std::isfinite(p[i])) return false;
   return true;
 }
+
+bool finite3(const float v[3]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+
+namespace {
 
 int no_moments(ndt_handle* h) { return fail(h, NDT_ERR_INVALID_ARG, "the map keeps no moments (ndt_map_enable_moments right after ndt_map_reset)"); }
 
@@ -760,9 +760,8 @@ int target_from_moments(ndt_handle* h, const float* box_min, const float* box_ma
     const uint32_t *order = nullptr, *slots = nullptr;
     rc = map_export_order(h, sel, true, total, mn, mx, &order, &slots);
     if (rc) return rc;
-    const int key_min[3] = {mn[0] + MAP_BIAS, mn[1] + MAP_BIAS, mn[2] + MAP_BIAS};
     FinalizeParams fp{h->prm.eig_inflation_ratio, h->prm.cov_mode};
-    launch_map_finalize(order, slots, total, m.keys, m.cnt, m.mom, key_min, g.mul1, g.mul2, fp, h->rec.p, h->cent.p, h->stats.p,
+    launch_map_finalize(order, slots, total, m.tab.keys, m.tab.cnt, m.tab.mom, mn, g.mul1, g.mul2, fp, h->rec.p, h->cent.p, h->stats.p,
                         h->cell2leaf.p, m.tsel.p + TS_VALID, s);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemcpyAsync(m.tsel_h.h + TS_VALID, m.tsel.p + TS_VALID, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -820,9 +819,9 @@ int ndt_map_reset(ndt_handle* h, float leaf, int with_intensity, int64_t initial
   m.with_intensity = with_intensity ? 1 : 0;
   const int64_t cap = map_pow2_at_least(initial_capacity > 0 ? initial_capacity : MAP_DEFAULT_CAPACITY);
   auto undo = [&](int code) { map_release(h); return code; };
-  rc = map_alloc_table(h, cap, false, &m.keys, &m.sums, &m.cnt, &m.mom);
+  rc = map_alloc_table(h, cap, false, &m.tab);
   if (rc) return undo(rc);
-  m.capacity = m.reset_capacity = cap;
+  m.reset_capacity = cap;
   hipError_t e = m.stats.ensure(MS_WORDS);
   if (e == hipSuccess) e = m.nvox.ensure(1);
   if (e == hipSuccess) e = m.stats_h.ensure(2 * MS_WORDS);
@@ -916,7 +915,7 @@ int ndt_map_get_info(const ndt_handle* h, ndt_map_info* out) {
   out->n_voxels = m.n_voxels;
   out->n_points = m.n_points;
   out->n_points_dropped = m.n_dropped;
-  out->capacity = m.capacity;
+  out->capacity = m.tab.capacity;
   for (int a = 0; a < 3; ++a) { out->min_ijk[a] = m.mn[a]; out->max_ijk[a] = m.mx[a]; }
   out->n_adds = m.n_adds;
   out->n_grows = m.n_grows;
@@ -1007,13 +1006,13 @@ int ndt_map_enable_moments(ndt_handle* h) {
   if (m.moments) return fail(h, NDT_ERR_INVALID_ARG, "the map keeps moments already");
   if (m.n_points > 0 || m.n_voxels > 0 || m.nvox_stale)
     return fail(h, NDT_ERR_INVALID_ARG, "the map holds points already: moments are enabled right after ndt_map_reset");
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&m.mom), (size_t)m.capacity * 9 * sizeof(double));
-  if (e == hipSuccess) e = hipMemsetAsync(m.mom, 0, (size_t)m.capacity * 9 * sizeof(double), h->stream);
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&m.tab.mom), (size_t)m.tab.capacity * 9 * sizeof(double));
+  if (e == hipSuccess) e = hipMemsetAsync(m.tab.mom, 0, (size_t)m.tab.capacity * 9 * sizeof(double), h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    if (m.mom) (void)hipFree(m.mom);
-    m.mom = nullptr;
+    if (m.tab.mom) (void)hipFree(m.tab.mom);
+    m.tab.mom = nullptr;
     return fail(h, e == hipErrorOutOfMemory ? NDT_ERR_ALLOC : NDT_ERR_HIP, std::string("voxel map moments: ") + hipGetErrorString(e));
   }
   m.moments = true;
@@ -1046,7 +1045,7 @@ int ndt_map_export_moments(ndt_handle* h, int min_points, int32_t* ijk, int32_t*
     const uint32_t *order = nullptr, *slots = nullptr;
     rc = map_export_order(h, sel_all(min_points), false, total, m.mn, m.mx, &order, &slots);
     if (rc) return rc;
-    launch_map_gather_moments(order, slots, w, m.keys, m.cnt, m.mom, MAP_BIAS, m.xijk.p, m.xcnt.p, m.xmom.p, h->stream);
+    launch_map_gather_moments(order, slots, w, m.tab.keys, m.tab.cnt, m.tab.mom, m.xijk.p, m.xcnt.p, m.xmom.p, h->stream);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (ijk) HIP_TRY(h, hipMemcpy(ijk, m.xijk.p, 3 * w * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -1066,9 +1065,7 @@ int ndt_set_target_from_map_moments(ndt_handle* h, const float box_min[3], const
   if (!m.moments) return no_moments(h);
   if (std::memcmp(&m.leaf, &h->prm.resolution, sizeof(float)) != 0)
     return fail(h, NDT_ERR_INVALID_ARG, "the map's leaf size is not ndt_params::resolution: a voxel of the map is not a voxel of the grid");
-  if (box_min)
-    for (int a = 0; a < 3; ++a)
-      if (!std::isfinite(box_min[a]) || !std::isfinite(box_max[a])) return fail(h, NDT_ERR_INVALID_ARG, "non-finite box");
+  if (box_min && !(finite3(box_min) && finite3(box_max))) return fail(h, NDT_ERR_INVALID_ARG, "non-finite box");
   return target_from_moments(h, box_min, box_max);
 }
 

@@ -36,17 +36,6 @@ struct CarveRays {
   int keep_last, max_steps;
 };
 
-__device__ __forceinline__ unsigned long long carve_key(int vi, int vj, int vk) {
-  return ((unsigned long long)(vk + MAP_BIAS) << 42) | ((unsigned long long)(vj + MAP_BIAS) << 21) |
-         (unsigned long long)(vi + MAP_BIAS);
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // Ray i runs from the origin to point i.  Path v_0 = vs .. v_L = ve, L = |ve - vs|_1: every step advances the axis with
 // the smallest tMax (the lowest axis on equal values), an axis that has reached ve[a] has tMax = +inf.  v_i takes a miss
 // for 1 <= i <= min(L - 1 - keep_last, max_steps), v_L the hit; only voxels the table holds take marks.  The three axes
@@ -93,10 +82,10 @@ __global__ void __launch_bounds__(MAP_THREADS) k_mapcarve_rays(const float* __re
         if (tx <= ty && tx <= tz) { vx += sx; tx = vx == ex ? inf : tx + tdx; }
         else if (ty <= tz) { vy += sy; ty = vy == ey ? inf : ty + tdy; }
         else { vz += sz; tz = vz == ez ? inf : tz + tdz; }
-        const long long s = map_find(tkeys, mask, carve_key(vx, vy, vz));
+        const long long s = map_find(tkeys, mask, map_key(vx, vy, vz));
         if (s >= 0) atomicAdd(marks + s, 1u);
       }
-      const long long s = map_find(tkeys, mask, carve_key(ex, ey, ez));
+      const long long s = map_find(tkeys, mask, map_key(ex, ey, ez));
       if (s >= 0) atomicOr(marks + s, CARVE_HIT);
     }
   }
@@ -152,58 +141,25 @@ __global__ void __launch_bounds__(MAP_THREADS) k_mapcarve_count(const unsigned l
   }
 }
 
-// Every occupied slot of the old table that stays moves to the new table with its sums, its count and its moments as
-// they are; the survivors' ijk box goes to tsel (TS_MIN / TS_MAX).  k_mapstate_crop under the mark predicate.
-__global__ void __launch_bounds__(MAP_THREADS) k_mapcarve_move(const unsigned long long* __restrict__ okeys,
-                                                              const float4* __restrict__ osums, const int* __restrict__ ocnt,
-                                                              const unsigned int* __restrict__ marks, long long ocap,
-                                                              int min_misses, int protect_min_count,
-                                                              unsigned long long* __restrict__ tkeys, unsigned long long mask,
-                                                              float4* __restrict__ sums, int* __restrict__ cnt,
-                                                              int* __restrict__ stats, const double* __restrict__ omom,
-                                                              double* __restrict__ mom, int* __restrict__ tsel) {
-  __shared__ int red[MAP_WAVES][6];
+// Every occupied slot of the old table that stays moves to the new table (map_move_slot); the survivors' ijk box goes to
+// tsel (TS_MIN / TS_MAX).  k_mapstate_crop under the mark predicate.
+__global__ void __launch_bounds__(MAP_THREADS) k_mapcarve_move(MapTable o, const unsigned int* __restrict__ marks, int min_misses,
+                                                              int protect_min_count, MapTable t, int* __restrict__ stats,
+                                                              int* __restrict__ tsel) {
+  __shared__ int box[MAP_WAVES][6];
   const long long i = (long long)blockIdx.x * MAP_THREADS + threadIdx.x;
-  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
   int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
-  if (i < ocap) {
-    const unsigned long long key = okeys[i];
-    if (key != MAP_EMPTY) {
-      const int count = ocnt[i];
-      if (!carve_removes(marks[i], count, min_misses, protect_min_count)) {
-        bool claimed;
-        const long long s = map_slot_of(tkeys, mask, key, &claimed);
-        if (s < 0) {
-          atomicAdd(stats + MS_PROBE_FAIL, 1);
-        } else {
-          sums[s] = osums[i];
-          cnt[s] = count;
-          if (mom) {
-#pragma unroll
-            for (int a = 0; a < 9; ++a) mom[(size_t)s * 9 + a] = omom[(size_t)i * 9 + a];
-          }
-          mn[0] = mx[0] = (int)(key & 0x1fffffull) - MAP_BIAS;
-          mn[1] = mx[1] = (int)((key >> 21) & 0x1fffffull) - MAP_BIAS;
-          mn[2] = mx[2] = (int)(key >> 42) - MAP_BIAS;
-        }
-      }
+  if (i < o.capacity) {
+    const unsigned long long key = o.keys[i];
+    if (key != MAP_EMPTY && !carve_removes(marks[i], o.cnt[i], min_misses, protect_min_count) &&
+        map_move_slot(o, i, key, t, stats)) {
+      map_ijk(key, mn);
+      map_ijk(key, mx);
     }
   }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { mn[a] = wave_min(mn[a]); mx[a] = wave_max(mx[a]); }
-  if (lane == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { red[wave][a] = mn[a]; red[wave][3 + a] = mx[a]; }
-  }
+  map_box_waves(mn, mx, box);
   __syncthreads();
-  if (threadIdx.x < 6) {
-    const int t = (int)threadIdx.x;
-    int v = red[0][t];
-#pragma unroll
-    for (int w = 1; w < MAP_WAVES; ++w) v = t < 3 ? min(v, red[w][t]) : max(v, red[w][t]);
-    if (t < 3) { if (v != INT_MAX) atomicMin(tsel + TS_MIN + t, v); }
-    else if (v != INT_MIN) atomicMax(tsel + TS_MAX + (t - 3), v);
-  }
+  map_box_commit(box, tsel + TS_MIN, tsel + TS_MAX);
 }
 
 }  // namespace
@@ -216,17 +172,9 @@ bool carve_params_valid(const ndt_map_carve_params* p) {
          p->reserved[0] == 0 && p->reserved[1] == 0 && p->reserved[2] == 0;
 }
 
-bool carve_finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
-
-bool carve_pose_finite(const double* p) {
-  for (int i = 0; i < 16; ++i)
-    if (!std::isfinite(p[i])) return false;
-  return true;
-}
-
 // what every form refuses before the handle is looked at
 bool carve_args_ok(const float* origin, const ndt_map_carve_params* prm) {
-  return origin && prm && carve_params_valid(prm) && carve_finite3(origin);
+  return origin && prm && carve_params_valid(prm) && finite3(origin);
 }
 
 // One scan in device memory under an optional pose, behind the argument checks.
@@ -251,7 +199,7 @@ int map_carve_device(ndt_handle* h, const float* dx, const float* dy, const floa
     }
     const double a = (double)origin[0], b = (double)origin[1], d = (double)origin[2];
     for (int i = 0; i < 3; ++i) o[i] = (float)(c.R[3 * i] * a + c.R[3 * i + 1] * b + c.R[3 * i + 2] * d + c.t[i]);
-    if (!carve_finite3(o)) return fail(h, NDT_ERR_INVALID_ARG, "the origin is not finite behind the pose");
+    if (!finite3(o)) return fail(h, NDT_ERR_INVALID_ARG, "the origin is not finite behind the pose");
   }
   c.origin_in_range = 1;
   for (int a = 0; a < 3; ++a) {
@@ -264,17 +212,17 @@ int map_carve_device(ndt_handle* h, const float* dx, const float* dy, const floa
   hipStream_t s = h->stream;
   int rc = map_refresh_voxel_count(h);
   if (rc) return rc;
-  HIP_TRY(h, m.cmarks.ensure((size_t)m.capacity));
+  HIP_TRY(h, m.cmarks.ensure((size_t)m.tab.capacity));
   HIP_TRY(h, m.cstat.ensure(CS_WORDS));
   HIP_TRY(h, m.cstat_h.ensure(CS_WORDS));
-  HIP_TRY(h, hipMemsetAsync(m.cmarks.p, 0, (size_t)m.capacity * sizeof(unsigned int), s));
+  HIP_TRY(h, hipMemsetAsync(m.cmarks.p, 0, (size_t)m.tab.capacity * sizeof(unsigned int), s));
   HIP_TRY(h, hipMemsetAsync(m.cstat.p, 0, CS_WORDS * sizeof(unsigned long long), s));
   const unsigned ray_blocks = (unsigned)((n + MAP_THREADS - 1) / MAP_THREADS);
-  const unsigned slot_blocks = (unsigned)((m.capacity + MAP_THREADS - 1) / MAP_THREADS);
-  hipLaunchKernelGGL(k_mapcarve_rays, dim3(ray_blocks), dim3(MAP_THREADS), 0, s, dx, dy, dz, (int)n, c, m.keys,
-                     (unsigned long long)(m.capacity - 1), m.cmarks.p, m.cstat.p);
+  const unsigned slot_blocks = (unsigned)((m.tab.capacity + MAP_THREADS - 1) / MAP_THREADS);
+  hipLaunchKernelGGL(k_mapcarve_rays, dim3(ray_blocks), dim3(MAP_THREADS), 0, s, dx, dy, dz, (int)n, c, m.tab.keys,
+                     (unsigned long long)(m.tab.capacity - 1), m.cmarks.p, m.cstat.p);
   HIP_TRY(h, hipGetLastError());
-  hipLaunchKernelGGL(k_mapcarve_count, dim3(slot_blocks), dim3(MAP_THREADS), 0, s, m.keys, m.cnt, m.cmarks.p, (long long)m.capacity,
+  hipLaunchKernelGGL(k_mapcarve_count, dim3(slot_blocks), dim3(MAP_THREADS), 0, s, m.tab.keys, m.tab.cnt, m.cmarks.p, (long long)m.tab.capacity,
                      prm.min_misses, prm.protect_min_count, m.cstat.p);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(m.cstat_h.h, m.cstat.p, CS_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
@@ -295,35 +243,12 @@ int map_carve_device(ndt_handle* h, const float* dx, const float* dy, const floa
 
   const int64_t kept = m.n_voxels - removed;
   const int64_t new_cap = std::max(map_pow2_at_least(2 * kept), m.reset_capacity);
-  unsigned long long* nk; float* ns; int* nc; double* nq;
-  rc = map_alloc_table(h, new_cap, m.moments, &nk, &ns, &nc, &nq);
-  if (rc) return rc;   // the map is as it was
-  hipError_t e = hipMemcpyAsync(m.tsel.p, m.tsel_h.h + TS_WORDS, TS_WORDS * sizeof(int), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_mapcarve_move, dim3(slot_blocks), dim3(MAP_THREADS), 0, s, m.keys, reinterpret_cast<const float4*>(m.sums),
-                       m.cnt, m.cmarks.p, (long long)m.capacity, prm.min_misses, prm.protect_min_count, nk,
-                       (unsigned long long)(new_cap - 1), reinterpret_cast<float4*>(ns), nc, m.stats.p, m.mom, nq, m.tsel.p);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(m.tsel_h.h, m.tsel.p, TS_WORDS * sizeof(int), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);   // (the old table is freed behind its last reader)
-  if (e == hipSuccess) {   // the next add reads the device's counter
-    m.nvox_h.h[0] = (unsigned long long)kept;
-    e = hipMemcpy(m.nvox.p, m.nvox_h.h, sizeof(unsigned long long), hipMemcpyHostToDevice);
-  }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    map_free_table(nk, ns, nc, nq);
-    return fail(h, NDT_ERR_HIP, std::string("voxel map carve: ") + hipGetErrorString(e));
-  }
-  map_free_table(m.keys, m.sums, m.cnt, m.mom);
-  m.keys = nk; m.sums = ns; m.cnt = nc; m.mom = nq;
-  m.capacity = new_cap;
-  m.n_voxels = kept;
-  m.nvox_stale = false;
+  rc = map_replace_table(h, new_cap, "voxel map carve: ", [&](const MapTable& fresh) {
+    hipLaunchKernelGGL(k_mapcarve_move, dim3(slot_blocks), dim3(MAP_THREADS), 0, s, m.tab, m.cmarks.p, prm.min_misses,
+                       prm.protect_min_count, fresh, m.stats.p, m.tsel.p);
+  }, kept);
+  if (rc) return rc;
   m.n_points -= pts_removed;
-  if (kept > 0)
-    for (int a = 0; a < 3; ++a) { m.mn[a] = m.tsel_h.h[TS_MIN + a]; m.mx[a] = m.tsel_h.h[TS_MAX + a]; }
   return NDT_OK;
 }
 
@@ -347,7 +272,7 @@ int ndt_map_carve_device(ndt_handle* h, const float* dx, const float* dy, const 
   int rc = bind_device(h);
   if (rc) return rc;
   if (!h->map) return no_map(h);
-  if (pose16 && !carve_pose_finite(pose16)) return fail(h, NDT_ERR_INVALID_ARG, "non-finite pose");
+  if (pose16 && !pose_finite(pose16)) return fail(h, NDT_ERR_INVALID_ARG, "non-finite pose");
   return map_carve_device(h, dx, dy, dz, n, origin, pose16, *prm, out);
 }
 
@@ -357,7 +282,7 @@ int ndt_map_carve(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes
   int rc = bind_device(h);
   if (rc) return rc;
   if (!h->map) return no_map(h);
-  if (pose16 && !carve_pose_finite(pose16)) return fail(h, NDT_ERR_INVALID_ARG, "non-finite pose");
+  if (pose16 && !pose_finite(pose16)) return fail(h, NDT_ERR_INVALID_ARG, "non-finite pose");
   VoxelMap& m = *h->map;
   if (n == 0) return map_carve_device(h, nullptr, nullptr, nullptr, 0, origin, pose16, *prm, out);
   settle_discard_keep_grid(h);
@@ -372,7 +297,7 @@ int ndt_map_carve_keyframe(ndt_handle* h, int64_t id, const float origin[3], con
   int rc = bind_device(h);
   if (rc) return rc;
   if (!h->map) return no_map(h);
-  if (!carve_pose_finite(pose16)) return fail(h, NDT_ERR_INVALID_ARG, "non-finite pose");
+  if (!pose_finite(pose16)) return fail(h, NDT_ERR_INVALID_ARG, "non-finite pose");
   auto it = h->keyframes.find(id);
   if (it == h->keyframes.end()) return fail(h, NDT_ERR_INVALID_ARG, "unknown keyframe id");
   const ndt_handle::Keyframe& kf = it->second;

@@ -1,8 +1,12 @@
 // ndt_map_device.h -- what the voxel map's kernels share across translation units (ndt_map.hip, ndt_map_state.hip,
-// ndt_map_carve.hip): the table's constants, the words of VoxelMap::stats / tsel, the hash, the probe that claims a slot
-// and the one that only looks, the box predicate of a selection and the wave reductions.  Device code only; include it
-// after hip_runtime.
+// ndt_map_carve.hip; ndt_target.hip for the key alone): the table's constants, the words of VoxelMap::stats / tsel, the
+// 63-bit key and its inverse (map_key / map_ijk: the only place that knows the layout), the hash, the probe that claims
+// a slot and the one that only looks, the box predicate of a selection, the wave reductions, the block's reduction of an
+// ijk box (map_box_waves / map_box_commit around the kernel's barrier) and one slot's move into a fresh table
+// (map_move_slot: what growth, crop and carve do with a voxel that stays).  Device code only.
 #pragma once
+
+#include "ndt_engine.h"   // MapTable
 
 namespace ndt {
 
@@ -18,6 +22,17 @@ enum { MS_FINITE = 0, MS_OOR = 1, MS_MIN = 2, MS_MAX = 5, MS_PROBE_FAIL = 8, MS_
 // and the leaves its finalize launch accepted
 enum { TS_MIN = 0, TS_MAX = 3, TS_VOXELS = 6, TS_POINTS = 8, TS_VALID = 10, TS_WORDS = 16 };
 
+// The voxel key: (k, j, i) biased into 21 bits each -- 63 bits that order as PCL's dense index does; |ijk| < 2^20.
+__device__ __forceinline__ unsigned long long map_key(int i, int j, int k) {
+  return ((unsigned long long)(k + MAP_BIAS) << 42) | ((unsigned long long)(j + MAP_BIAS) << 21) |
+         (unsigned long long)(i + MAP_BIAS);
+}
+__device__ __forceinline__ void map_ijk(unsigned long long key, int (&v)[3]) {
+  v[0] = (int)(key & 0x1fffffull) - MAP_BIAS;
+  v[1] = (int)((key >> 21) & 0x1fffffull) - MAP_BIAS;
+  v[2] = (int)(key >> 42) - MAP_BIAS;
+}
+
 __device__ __forceinline__ unsigned long long map_hash(unsigned long long k) {  // splitmix64's finaliser
   k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
   k ^= k >> 27; k *= 0x94d049bb133111ebull;
@@ -26,6 +41,11 @@ __device__ __forceinline__ unsigned long long map_hash(unsigned long long k) {  
 }
 
 __device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
   return v;
@@ -84,9 +104,59 @@ struct MapSel {
 };
 
 __device__ __forceinline__ bool map_in_box(unsigned long long key, const MapSel& sel) {
-  const int vi = (int)(key & 0x1fffffull) - MAP_BIAS, vj = (int)((key >> 21) & 0x1fffffull) - MAP_BIAS,
-            vk = (int)(key >> 42) - MAP_BIAS;
-  return vi >= sel.lo[0] && vi <= sel.hi[0] && vj >= sel.lo[1] && vj <= sel.hi[1] && vk >= sel.lo[2] && vk <= sel.hi[2];
+  int v[3];
+  map_ijk(key, v);
+  return v[0] >= sel.lo[0] && v[0] <= sel.hi[0] && v[1] >= sel.lo[1] && v[1] <= sel.hi[1] && v[2] >= sel.lo[2] && v[2] <= sel.hi[2];
+}
+
+// The ijk box of what a block's threads hold (mn / mx; a thread without a voxel brings INT_MAX / INT_MIN), reduced into
+// the words bmin[0..2] / bmax[0..2] with at most one integer atomic per word and block.  Split around the barrier, which
+// the kernel owns (it may reduce its counters across the same one), as ndt_compact_device.h's helpers are; `box` is the
+// kernel's own __shared__ array.
+// in front of the barrier: the wave's box to box[wave]
+__device__ __forceinline__ void map_box_waves(const int (&mn)[3], const int (&mx)[3], int (&box)[MAP_WAVES][6]) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int lo = wave_min(mn[a]), hi = wave_max(mx[a]);
+    if ((threadIdx.x & 63u) == 0) { box[threadIdx.x >> 6][a] = lo; box[threadIdx.x >> 6][3 + a] = hi; }
+  }
+}
+// behind it: threads 0..5 fold the waves, one word each; a block without a voxel writes nothing
+__device__ __forceinline__ void map_box_commit(const int (&box)[MAP_WAVES][6], int* __restrict__ bmin, int* __restrict__ bmax) {
+  if (threadIdx.x < 6) {
+    const int t = (int)threadIdx.x;
+    int v = box[0][t];
+#pragma unroll
+    for (int w = 1; w < MAP_WAVES; ++w) v = t < 3 ? min(v, box[w][t]) : max(v, box[w][t]);
+    if (t < 3) { if (v != INT_MAX) atomicMin(bmin + t, v); }
+    else if (v != INT_MIN) atomicMax(bmax + (t - 3), v);
+  }
+}
+
+// The occupied slot i of table `o` (its key: `key`) moves to the fresh table `t` with its sums, its count and -- where
+// the tables have them -- its nine moments as they are.  false: the probe found no position (counted in stats; cannot
+// happen at a load of 1/2), nothing was written.
+__device__ __forceinline__ bool map_move_slot(const engine::MapTable& o, long long i, unsigned long long key,
+                                              const engine::MapTable& t, int* __restrict__ stats) {
+  bool claimed;
+  const long long s = map_slot_of(t.keys, (unsigned long long)(t.capacity - 1), key, &claimed);
+  if (s < 0) { atomicAdd(stats + MS_PROBE_FAIL, 1); return false; }
+  // (every load in front of the first store: the pointers of a struct carry no __restrict__, and a store in between
+  // would make the loads behind it wait for it)
+  const float4 sm = o.sums[i];
+  const int c = o.cnt[i];
+  double q[9];
+  if (t.mom) {
+#pragma unroll
+    for (int a = 0; a < 9; ++a) q[a] = o.mom[(size_t)i * 9 + a];
+  }
+  t.sums[s] = sm;
+  t.cnt[s] = c;
+  if (t.mom) {
+#pragma unroll
+    for (int a = 0; a < 9; ++a) t.mom[(size_t)s * 9 + a] = q[a];
+  }
+  return true;
 }
 
 }  // namespace ndt

@@ -24,54 +24,22 @@ namespace {
 enum { MS_BAD_COUNT = 9, MS_POINTS = 10 /* 64 bits */ };
 
 // Crop: every occupied slot of the old table whose voxel is inside the box (remove_inside == 0) or outside it
-// (remove_inside != 0) moves to the new table with its sums, its count and its moments as they are; the survivors' ijk
-// box goes to tsel (TS_MIN / TS_MAX).
-__global__ void __launch_bounds__(MAP_THREADS) k_mapstate_crop(const unsigned long long* __restrict__ okeys,
-                                                              const float4* __restrict__ osums, const int* __restrict__ ocnt,
-                                                              long long ocap, MapSel sel, int remove_inside,
-                                                              unsigned long long* __restrict__ tkeys, unsigned long long mask,
-                                                              float4* __restrict__ sums, int* __restrict__ cnt,
-                                                              int* __restrict__ stats, const double* __restrict__ omom,
-                                                              double* __restrict__ mom, int* __restrict__ tsel) {
-  __shared__ int red[MAP_WAVES][6];
+// (remove_inside != 0) moves to the new table (map_move_slot); the survivors' ijk box goes to tsel (TS_MIN / TS_MAX).
+__global__ void __launch_bounds__(MAP_THREADS) k_mapstate_crop(MapTable o, MapSel sel, int remove_inside, MapTable t,
+                                                              int* __restrict__ stats, int* __restrict__ tsel) {
+  __shared__ int box[MAP_WAVES][6];
   const long long i = (long long)blockIdx.x * MAP_THREADS + threadIdx.x;
-  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
   int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
-  if (i < ocap) {
-    const unsigned long long key = okeys[i];
-    if (key != MAP_EMPTY && map_in_box(key, sel) == (remove_inside == 0)) {
-      bool claimed;
-      const long long s = map_slot_of(tkeys, mask, key, &claimed);
-      if (s < 0) {
-        atomicAdd(stats + MS_PROBE_FAIL, 1);
-      } else {
-        sums[s] = osums[i];
-        cnt[s] = ocnt[i];
-        if (mom) {
-#pragma unroll
-          for (int a = 0; a < 9; ++a) mom[(size_t)s * 9 + a] = omom[(size_t)i * 9 + a];
-        }
-        mn[0] = mx[0] = (int)(key & 0x1fffffull) - MAP_BIAS;
-        mn[1] = mx[1] = (int)((key >> 21) & 0x1fffffull) - MAP_BIAS;
-        mn[2] = mx[2] = (int)(key >> 42) - MAP_BIAS;
-      }
+  if (i < o.capacity) {
+    const unsigned long long key = o.keys[i];
+    if (key != MAP_EMPTY && map_in_box(key, sel) == (remove_inside == 0) && map_move_slot(o, i, key, t, stats)) {
+      map_ijk(key, mn);
+      map_ijk(key, mx);
     }
   }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { mn[a] = wave_min(mn[a]); mx[a] = wave_max(mx[a]); }
-  if (lane == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { red[wave][a] = mn[a]; red[wave][3 + a] = mx[a]; }
-  }
+  map_box_waves(mn, mx, box);
   __syncthreads();
-  if (threadIdx.x < 6) {
-    const int t = (int)threadIdx.x;
-    int v = red[0][t];
-#pragma unroll
-    for (int w = 1; w < MAP_WAVES; ++w) v = t < 3 ? min(v, red[w][t]) : max(v, red[w][t]);
-    if (t < 3) { if (v != INT_MAX) atomicMin(tsel + TS_MIN + t, v); }
-    else if (v != INT_MIN) atomicMax(tsel + TS_MAX + (t - 3), v);
-  }
+  map_box_commit(box, tsel + TS_MIN, tsel + TS_MAX);
 }
 
 // output record r = the voxel slots[order[r]] as the table holds it: absolute ijk, count, the four float sums (NOT
@@ -86,10 +54,9 @@ __global__ void __launch_bounds__(MAP_THREADS) k_mapstate_gather(const uint32_t*
   if (r >= m) return;
   const uint32_t slot = slots[order[r]];
   if (oijk) {
-    const unsigned long long key = tkeys[slot];
-    oijk[(size_t)r * 3 + 0] = (int)(key & 0x1fffffull) - MAP_BIAS;
-    oijk[(size_t)r * 3 + 1] = (int)((key >> 21) & 0x1fffffull) - MAP_BIAS;
-    oijk[(size_t)r * 3 + 2] = (int)(key >> 42) - MAP_BIAS;
+    int v[3];
+    map_ijk(tkeys[slot], v);
+    oijk[(size_t)r * 3 + 0] = v[0]; oijk[(size_t)r * 3 + 1] = v[1]; oijk[(size_t)r * 3 + 2] = v[2];
   }
   if (ocount) ocount[r] = cnt[slot];
   if (osums) {   // (the caller's array need not be 16-byte aligned)
@@ -108,7 +75,7 @@ __global__ void __launch_bounds__(MAP_THREADS) k_mapstate_gather(const uint32_t*
 __global__ void __launch_bounds__(MAP_THREADS) k_mapstate_keys(const int32_t* __restrict__ ijk, const int32_t* __restrict__ count,
                                                               int n, unsigned long long* __restrict__ pkey,
                                                               int* __restrict__ stats) {
-  __shared__ int red[MAP_WAVES][8];
+  __shared__ int red[MAP_WAVES][2], box[MAP_WAVES][6];
   __shared__ unsigned long long red_pts[MAP_WAVES];
   const int i = (int)(blockIdx.x * MAP_THREADS + threadIdx.x);
   const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
@@ -125,33 +92,23 @@ __global__ void __launch_bounds__(MAP_THREADS) k_mapstate_keys(const int32_t* __
     if (in_range && c >= 1) {
       mn[0] = mx[0] = vi; mn[1] = mx[1] = vj; mn[2] = mx[2] = vk;
       pts = (unsigned long long)c;
-      key = ((unsigned long long)(vk + MAP_BIAS) << 42) | ((unsigned long long)(vj + MAP_BIAS) << 21) |
-            (unsigned long long)(vi + MAP_BIAS);
+      key = map_key(vi, vj, vk);
     }
     pkey[i] = key;
   }
   oor = wave_sum(oor);
   bad = wave_sum(bad);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { mn[a] = wave_min(mn[a]); mx[a] = wave_max(mx[a]); }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) pts += __shfl_xor(pts, off);
-  if (lane == 0) {
-    red[wave][0] = oor; red[wave][1] = bad;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { red[wave][2 + a] = mn[a]; red[wave][5 + a] = mx[a]; }
-    red_pts[wave] = pts;
-  }
+  pts = wave_sum_u64(pts);
+  if (lane == 0) { red[wave][0] = oor; red[wave][1] = bad; red_pts[wave] = pts; }
+  map_box_waves(mn, mx, box);
   __syncthreads();
-  if (threadIdx.x < 8) {
-    const int t = (int)threadIdx.x;
-    int v = red[0][t];
+  map_box_commit(box, stats + MS_MIN, stats + MS_MAX);
+  if (threadIdx.x == 6 || threadIdx.x == 7) {
+    const int t = (int)threadIdx.x - 6;
+    int v = 0;
 #pragma unroll
-    for (int w = 1; w < MAP_WAVES; ++w) v = t < 2 ? v + red[w][t] : t < 5 ? min(v, red[w][t]) : max(v, red[w][t]);
-    if (t == 0) { if (v) atomicAdd(stats + MS_OOR, v); }
-    else if (t == 1) { if (v) atomicAdd(stats + MS_BAD_COUNT, v); }
-    else if (t < 5) { if (v != INT_MAX) atomicMin(stats + MS_MIN + (t - 2), v); }
-    else if (v != INT_MIN) atomicMax(stats + MS_MAX + (t - 5), v);
+    for (int w = 0; w < MAP_WAVES; ++w) v += red[w][t];
+    if (v) atomicAdd(stats + (t == 0 ? MS_OOR : MS_BAD_COUNT), v);
   } else if (threadIdx.x == 8) {
     unsigned long long v = 0;
 #pragma unroll
@@ -206,12 +163,6 @@ __global__ void __launch_bounds__(MAP_THREADS) k_mapstate_accumulate(const int* 
 namespace engine {
 namespace {
 
-bool box_finite(const float* lo, const float* hi) {
-  for (int a = 0; a < 3; ++a)
-    if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return false;
-  return true;
-}
-
 // the selection of a box (both corners null: the whole coordinate range), whatever the voxels' counts
 MapSel sel_box(const VoxelMap& m, const float* box_min, const float* box_max) {
   MapSel sel{};
@@ -225,7 +176,6 @@ MapSel sel_box(const VoxelMap& m, const float* box_min, const float* box_max) {
 
 int map_crop(ndt_handle* h, const float* box_min, const float* box_max, int remove_inside, int64_t* n_removed) {
   VoxelMap& m = *h->map;
-  hipStream_t s = h->stream;
   const MapSel sel = sel_box(m, box_min, box_max);
   size_t inside = 0;
   int rc = map_export_count(h, sel, true, &inside);   // (settles nvox_stale first; one host wait)
@@ -239,35 +189,12 @@ int map_crop(ndt_handle* h, const float* box_min, const float* box_max, int remo
   if (removed == 0) return NDT_OK;   // the table is as it was
 
   const int64_t new_cap = std::max(map_pow2_at_least(2 * kept), m.reset_capacity);
-  unsigned long long* nk; float* ns; int* nc; double* nq;
-  rc = map_alloc_table(h, new_cap, m.moments, &nk, &ns, &nc, &nq);
-  if (rc) return rc;   // the map is as it was
-  hipError_t e = hipMemcpyAsync(m.tsel.p, m.tsel_h.h + TS_WORDS, TS_WORDS * sizeof(int), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_mapstate_crop, dim3((unsigned)((m.capacity + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0, s, m.keys,
-                       reinterpret_cast<const float4*>(m.sums), m.cnt, (long long)m.capacity, sel, remove_inside, nk,
-                       (unsigned long long)(new_cap - 1), reinterpret_cast<float4*>(ns), nc, m.stats.p, m.mom, nq, m.tsel.p);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(m.tsel_h.h, m.tsel.p, TS_WORDS * sizeof(int), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);   // (the old table is freed behind its last reader)
-  if (e == hipSuccess) {   // the next add reads the device's counter
-    m.nvox_h.h[0] = (unsigned long long)kept;
-    e = hipMemcpy(m.nvox.p, m.nvox_h.h, sizeof(unsigned long long), hipMemcpyHostToDevice);
-  }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    map_free_table(nk, ns, nc, nq);
-    return fail(h, NDT_ERR_HIP, std::string("voxel map crop: ") + hipGetErrorString(e));
-  }
-  map_free_table(m.keys, m.sums, m.cnt, m.mom);
-  m.keys = nk; m.sums = ns; m.cnt = nc; m.mom = nq;
-  m.capacity = new_cap;
-  m.n_voxels = kept;
-  m.nvox_stale = false;
+  rc = map_replace_table(h, new_cap, "voxel map crop: ", [&](const MapTable& fresh) {
+    hipLaunchKernelGGL(k_mapstate_crop, dim3((unsigned)((m.tab.capacity + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0,
+                       h->stream, m.tab, sel, remove_inside, fresh, m.stats.p, m.tsel.p);
+  }, kept);
+  if (rc) return rc;
   m.n_points = remove_inside ? m.n_points - (int64_t)pts_inside : (int64_t)pts_inside;
-  if (kept > 0)
-    for (int a = 0; a < 3; ++a) { m.mn[a] = m.tsel_h.h[TS_MIN + a]; m.mx[a] = m.tsel_h.h[TS_MAX + a]; }
   return NDT_OK;
 }
 
@@ -289,7 +216,7 @@ int map_export_state(ndt_handle* h, const float* box_min, const float* box_max, 
   rc = map_export_order(h, sel, true, total, mn, mx, &order, &slots);
   if (rc) return rc;
   hipLaunchKernelGGL(k_mapstate_gather, dim3((unsigned)((w + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0, h->stream, order,
-                     slots, (int)w, m.keys, reinterpret_cast<const float4*>(m.sums), m.cnt, m.mom, d_ijk, d_count, d_sums, d_mom);
+                     slots, (int)w, m.tab.keys, m.tab.sums, m.tab.cnt, m.tab.mom, d_ijk, d_count, d_sums, d_mom);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return NDT_OK;
@@ -318,7 +245,7 @@ int map_import_state(ndt_handle* h, const int32_t* d_ijk, const int32_t* d_count
   if (st[MS_OOR] > 0)
     return fail(h, NDT_ERR_GRID_OVERFLOW, std::to_string(st[MS_OOR]) + " record(s) beyond the map's coordinate range (|voxel index| < 2^20 per axis); nothing was imported");
   const int64_t want = map_pow2_at_least(2 * (m.n_voxels + (int64_t)n));
-  if (want > m.capacity) {
+  if (want > m.tab.capacity) {
     if (want > MAP_MAX_CAPACITY) return fail(h, NDT_ERR_ALLOC, "voxel map: more than 2^30 table slots needed");
     rc = map_grow_table(h, want);
     if (rc) return rc;
@@ -338,12 +265,12 @@ int map_import_state(ndt_handle* h, const int32_t* d_ijk, const int32_t* d_count
   if (rc) return rc;
   if (m.moments)
     hipLaunchKernelGGL(k_mapstate_accumulate<true>, dim3(blocks), dim3(MAP_THREADS), 0, s, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p,
-                       keys_sorted, vals_sorted, d_count, d_sums, d_mom, m.with_intensity, reinterpret_cast<float4*>(m.sums), m.cnt,
-                       m.mom);
+                       keys_sorted, vals_sorted, d_count, d_sums, d_mom, m.with_intensity, m.tab.sums, m.tab.cnt,
+                       m.tab.mom);
   else
     hipLaunchKernelGGL(k_mapstate_accumulate<false>, dim3(blocks), dim3(MAP_THREADS), 0, s, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p,
                        keys_sorted, vals_sorted, d_count, d_sums, static_cast<const double*>(nullptr), m.with_intensity,
-                       reinterpret_cast<float4*>(m.sums), m.cnt, static_cast<double*>(nullptr));
+                       m.tab.sums, m.tab.cnt, static_cast<double*>(nullptr));
   HIP_TRY(h, hipGetLastError());
   // the caller's arrays (and the engine's scratch) are free again when the call returns
   HIP_TRY(h, hipStreamSynchronize(s));
@@ -367,7 +294,7 @@ int export_checks(ndt_handle* h, const float* box_min, const float* box_max, con
   if (!h->map) return no_map(h);
   if (moments9 && !h->map->moments)
     return fail(h, NDT_ERR_INVALID_ARG, "the map keeps no moments (ndt_map_enable_moments right after ndt_map_reset)");
-  if (box_min && !box_finite(box_min, box_max)) return fail(h, NDT_ERR_INVALID_ARG, "non-finite box");
+  if (box_min && !(finite3(box_min) && finite3(box_max))) return fail(h, NDT_ERR_INVALID_ARG, "non-finite box");
   return NDT_OK;
 }
 
@@ -382,7 +309,7 @@ int ndt_map_crop(ndt_handle* h, const float box_min[3], const float box_max[3], 
   int rc = bind_device(h);
   if (rc) return rc;
   if (!h->map) return no_map(h);
-  if (!box_finite(box_min, box_max)) return fail(h, NDT_ERR_INVALID_ARG, "non-finite box");
+  if (!(finite3(box_min) && finite3(box_max))) return fail(h, NDT_ERR_INVALID_ARG, "non-finite box");
   return map_crop(h, box_min, box_max, remove_inside, n_removed);
 }
 

@@ -22,6 +22,7 @@
 //                      cell -> leaf index.
 // Compiled with -ffp-contract=off: f32 index arithmetic must round as written.
 #include "ndt_kernels.h"
+#include "ndt_map_device.h"   // the voxel map's key (k_map_finalize, k_map_gather_moments)
 
 #include <climits>
 #include <cstdlib>
@@ -1224,7 +1225,7 @@ __device__ __forceinline__ bool finalize_leaf(int slot, int cell, int cnt, const
 // The leaves of a target made from the voxel map's moments (launch_map_finalize): one thread per selected voxel, in
 // ascending key order, so slot order is cell order.  The sums were accumulated by the map; nothing is added here.
 struct MapCellDecode {
-  int key_min[3];  // min_b + the key's bias, per axis
+  int min_b[3];
   int mul1, mul2;
 };
 __global__ void __launch_bounds__(256) k_map_finalize(const uint32_t* __restrict__ order, const uint32_t* __restrict__ slots,
@@ -1238,11 +1239,9 @@ __global__ void __launch_bounds__(256) k_map_finalize(const uint32_t* __restrict
   bool ok = false;
   if (r < m) {
     const uint32_t t = slots[order[r]];
-    const unsigned long long key = tkeys[t];
-    const int ci = (int)(key & 0x1fffffull) - dc.key_min[0];
-    const int cj = (int)((key >> 21) & 0x1fffffull) - dc.key_min[1];
-    const int ck = (int)(key >> 42) - dc.key_min[2];
-    ok = finalize_leaf(r, ci + cj * dc.mul1 + ck * dc.mul2, tcnt[t], tmom + (size_t)t * 9, fp, rec, cent, stats, cell2leaf);
+    int v[3];
+    map_ijk(tkeys[t], v);
+    ok = finalize_leaf(r, (v[0] - dc.min_b[0]) + (v[1] - dc.min_b[1]) * dc.mul1 + (v[2] - dc.min_b[2]) * dc.mul2, tcnt[t], tmom + (size_t)t * 9, fp, rec, cent, stats, cell2leaf);
   }
   const int wave_ok = __popcll(__ballot(ok));
   if ((threadIdx.x & 63) == 0) s_ok[threadIdx.x >> 6] = wave_ok;
@@ -1257,15 +1256,14 @@ __global__ void __launch_bounds__(256) k_map_finalize(const uint32_t* __restrict
 __global__ void __launch_bounds__(256) k_map_gather_moments(const uint32_t* __restrict__ order, const uint32_t* __restrict__ slots,
                                                            int m, const unsigned long long* __restrict__ tkeys,
                                                            const int* __restrict__ tcnt, const double* __restrict__ tmom,
-                                                           int key_bias, int32_t* __restrict__ oijk,
-                                                           int32_t* __restrict__ ocount, double* __restrict__ osums) {
+                                                           int32_t* __restrict__ oijk, int32_t* __restrict__ ocount,
+                                                           double* __restrict__ osums) {
   const int r = (int)(blockIdx.x * 256 + threadIdx.x);
   if (r >= m) return;
   const uint32_t t = slots[order[r]];
-  const unsigned long long key = tkeys[t];
-  oijk[3 * r + 0] = (int)(key & 0x1fffffull) - key_bias;
-  oijk[3 * r + 1] = (int)((key >> 21) & 0x1fffffull) - key_bias;
-  oijk[3 * r + 2] = (int)(key >> 42) - key_bias;
+  int v[3];
+  map_ijk(tkeys[t], v);
+  oijk[3 * r + 0] = v[0]; oijk[3 * r + 1] = v[1]; oijk[3 * r + 2] = v[2];
   ocount[r] = tcnt[t];
 #pragma unroll
   for (int a = 0; a < 9; ++a) osums[(size_t)r * 9 + a] = tmom[(size_t)t * 9 + a];
@@ -2705,11 +2703,11 @@ void launch_scatter_heads(const int* cells, const int* slots, size_t n, int* cel
 int finalize_blocks(int max_leaves) { return (max_leaves + 63) / 64; }
 
 void launch_map_gather_moments(const uint32_t* order, const uint32_t* slots, size_t m, const unsigned long long* table_keys,
-                               const int* table_cnt, const double* table_mom, int key_bias, int32_t* oijk, int32_t* ocount,
+                               const int* table_cnt, const double* table_mom, int32_t* oijk, int32_t* ocount,
                                double* osums, hipStream_t s) {
   if (m == 0) return;
   hipLaunchKernelGGL(k_map_gather_moments, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, order, slots, (int)m, table_keys,
-                     table_cnt, table_mom, key_bias, oijk, ocount, osums);
+                     table_cnt, table_mom, oijk, ocount, osums);
 }
 
 void launch_reset_cells(const LeafStats* old_stats, int dirty_slots, int* cell2leaf, size_t c2l_cap, hipStream_t s) {
@@ -2719,12 +2717,12 @@ void launch_reset_cells(const LeafStats* old_stats, int dirty_slots, int* cell2l
 }
 
 void launch_map_finalize(const uint32_t* order, const uint32_t* slots, size_t m, const unsigned long long* table_keys,
-                         const int* table_cnt, const double* table_mom, const int key_min[3], int mul1, int mul2,
+                         const int* table_cnt, const double* table_mom, const int min_b[3], int mul1, int mul2,
                          FinalizeParams fp, VoxelRecord* rec, float* cent4, LeafStats* stats, int* cell2leaf, int* d_nvalid,
                          hipStream_t s) {
   if (m == 0) return;
   MapCellDecode dc;
-  for (int a = 0; a < 3; ++a) dc.key_min[a] = key_min[a];
+  for (int a = 0; a < 3; ++a) dc.min_b[a] = min_b[a];
   dc.mul1 = mul1;
   dc.mul2 = mul2;
   hipLaunchKernelGGL(k_map_finalize, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, order, slots, (int)m, table_keys,

@@ -18,6 +18,7 @@ import pytest
 
 from test_gpu_map_target import (assert_grid_matches, assert_leaves_match, code_of, engine, eval_words, in_box, leaf_bytes,
                                  moment_cases, oracle_params)
+from test_map_carve_cpu import DEFAULTS, SCENE_LEAF, carve_numpy, carve_scene, result_of
 from test_map_state_cpu import continue_numpy, filter_state, mapstate_numpy, merge_numpy, state_key, states_equal
 from test_map_target_cpu import host_transform_f64, voxel_ijk
 
@@ -229,6 +230,59 @@ def test_crop_then_continue(pkg, base, leaf, remove_inside):
     info = ndt.mapInfo()
     assert info["n_voxels"] == len(want["count"]) and info["n_points"] == int(want["count"].sum())
     assert info["min_ijk"] == tuple(want["ijk"].min(0)) and info["max_ijk"] == tuple(want["ijk"].max(0))
+
+
+# ---- 3b. growth, crop, carve and growth again: one handle through every replacement of its table ------------------------
+def test_every_table_replacement_in_a_row_on_one_handle(pkg):
+    """The three replacements share one host tail (map_replace_table) and one device move (map_move_slot).  One map with
+    moments and intensity, reset at the smallest capacity (64 slots), takes the carve scene's first two scans (2 x 2 048
+    points, a few hundred voxels; both adds grow the table), then a crop that removes the inside of a box, a carve by the
+    third scan and a third add that grows the shrunken table again.  After every step the exported state is the
+    restatements applied in the same order, bit for bit, and mapInfo's counters and ijk box are the restatement's."""
+    leaf = SCENE_LEAF
+    scene = carve_scene(cols=64, rows=32)
+    rng = np.random.default_rng(11)
+    clouds = [np.concatenate([s, rng.uniform(0, 255, (len(s), 1)).astype(np.float32)], axis=1) for s in scene["scans"]]
+    assert sum(len(c) for c in clouds[:2]) == 4096
+    ndt = engine(pkg, leaf)
+    ndt.mapReset(leaf, with_intensity=True, initial_capacity=1)
+    ndt.mapEnableMoments()
+    assert ndt.mapInfo()["capacity"] == 64
+
+    def check(want, n_grows, capacity):
+        assert states_equal(ndt.mapExportState(), want)
+        info = ndt.mapInfo()
+        assert info["n_voxels"] == len(want["count"]) and info["n_points"] == int(want["count"].sum())
+        assert info["min_ijk"] == tuple(want["ijk"].min(0)) and info["max_ijk"] == tuple(want["ijk"].max(0))
+        assert info["n_grows"] == n_grows and info["capacity"] == capacity
+
+    ndt.mapAdd(clouds[0], intensity_column=3)
+    st = mapstate_numpy(clouds[0][:, :3], leaf, clouds[0][:, 3])
+    check(st, 1, 4096)                                                                         # the first add grew the table
+    v0 = len(st["count"])
+    ndt.mapAdd(clouds[1], intensity_column=3)
+    st = continue_numpy(st, clouds[1][:, :3], leaf, clouds[1][:, 3])
+    assert 200 <= len(st["count"]) <= 999 and st["sums"][:, 3].any()
+    check(st, 2, pow2_at_least(2 * (v0 + 2048)))
+    # 1. crop: the inside of a box that holds a piece of the wall and of the ground in front of it goes
+    box = ([10.0, 1.0, -2.0], [13.0, 9.0, 4.0])
+    inside = box_mask(st["ijk"], leaf, *box)
+    assert 20 <= inside.sum() < len(inside) - 100
+    assert ndt.mapCrop(*box, remove_inside=True) == int(inside.sum())
+    st = filter_state(st, ~inside)
+    check(st, 2, pow2_at_least(2 * len(st["count"])))
+    # 2. carve: the third scan looks through where the car was
+    want = carve_numpy(st["ijk"], st["count"], scene["scans"][2], scene["origin"], leaf, **DEFAULTS)
+    assert 1 <= want["n_removed"] < len(st["count"]) - 100
+    assert ndt.mapCarve(scene["scans"][2], scene["origin"]) == result_of(want)
+    st = filter_state(st, want["keep"])
+    check(st, 2, pow2_at_least(2 * len(st["count"])))
+    # 3. an add that grows the shrunken table: survivors go on, removed voxels seen again start from this scan alone
+    kept = len(st["count"])
+    assert pow2_at_least(2 * (kept + 2048)) > pow2_at_least(2 * kept)
+    ndt.mapAdd(clouds[2], intensity_column=3)
+    st = continue_numpy(st, clouds[2][:, :3], leaf, clouds[2][:, 3])
+    check(st, 3, pow2_at_least(2 * (kept + 2048)))
 
 
 # ---- 4. save, load, continue = never stopped ---------------------------------------------------------------------------

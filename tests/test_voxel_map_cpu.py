@@ -167,3 +167,45 @@ def test_map_kernels_do_not_spill(tmp_path):
     assert len(re.findall(r"__global__ void __launch_bounds__\(", src)) == len(re.findall(r"__global__", src)) == len(kernels)
     # no floating-point atomics, no inline assembly
     assert not re.search(r"atomicAdd\([^;]*float|unsafeAtomicAdd|\basm\b", src)
+
+
+def test_the_table_move_has_one_definition():
+    """The key's layout, a slot's move into a fresh table, the block's reduction of an ijk box and the 64-bit wave sum are
+    defined in ndt_map_device.h and nowhere else; growth, crop and carve call the move and replace the table through ONE
+    host function."""
+    csrc = os.path.join(ROOT, "slam-sam_amd", "csrc")
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".h", ".hip", ".cpp"))}
+    maps = ("ndt_map.hip", "ndt_map_state.hip", "ndt_map_carve.hip")
+    for fn in ("map_key", "map_ijk", "map_move_slot", "map_box_waves", "map_box_commit", "wave_sum_u64"):
+        defs = [f for f, text in sources.items() if re.search(r"\b(unsigned long long|void|bool) %s\(" % fn, text)]
+        assert defs == ["ndt_map_device.h"], (fn, defs)
+    for f in maps:
+        assert re.search(r"\bmap_move_slot\(", sources[f]), f
+    # nobody else writes the key's arithmetic or the box's atomics out
+    for f, text in sources.items():
+        if f != "ndt_map_device.h":
+            assert "0x1fffff" not in text.lower() and "<< 42" not in text, f
+    for f in maps:
+        assert "atomicMin(" not in sources[f] and "atomicMax(" not in sources[f], f
+    assert "atomicMin(" in sources["ndt_map_device.h"] and "atomicMax(" in sources["ndt_map_device.h"]
+
+    def callers(fn):
+        """(file, enclosing function) of every call of fn: the nearest definition line above it that starts in column 0"""
+        out = []
+        for f, text in sources.items():
+            for m in re.finditer(r"\b%s\(" % fn, text):
+                line_start = text.rfind("\n", 0, m.start()) + 1
+                if re.match(r"(int|void) %s\(" % fn, text[line_start:]):        # its own definition / declaration
+                    continue
+                heads = re.findall(r"^(?:int|void|bool) (\w+)\([^;]*?\) \{$", text[:m.start()], flags=re.M | re.S)
+                out.append((f, heads[-1]))
+        return sorted(out)
+
+    assert callers("map_alloc_table") == [("ndt_map.hip", "map_replace_table"), ("ndt_map.hip", "ndt_map_reset")]
+    assert callers("map_replace_table") == [("ndt_map.hip", "map_grow_table"), ("ndt_map_carve.hip", "map_carve_device"),
+                                            ("ndt_map_state.hip", "map_crop")]
+    everything = "\n".join(sources.values())
+    for gone in ("carve_pose_finite", "carve_finite3", "carve_key", "box_finite"):
+        assert not re.search(r"\b%s\b" % gone, everything), gone
+    for fn in ("pose_finite", "finite3"):
+        assert len(re.findall(r"^bool %s\(const" % fn, everything, flags=re.M)) == 2, fn      # declared once, defined once
