@@ -453,7 +453,8 @@ int ndt_keyframe_put_deskewed(ndt_handle* h, int64_t id, const float* xyz, size_
  * lookup table (ref: src/lidarcallback.cpp:191-327 builds it, :455-545 and :570-610 use it), applies the range filter
  * and the acquisition filter and pushes the point; these calls take the range image as received -- a 20-bit range in
  * millimetres and one reflectivity byte per pixel, one time per column, column by column -- and return the filtered,
- * deskewed, compacted scan (or, without a filter, the organised cloud).  Packet parsing stays with the driver.
+ * deskewed, compacted scan (or, without a filter, the organised cloud).  Packet parsing stays with the driver (or goes
+ * to the device as well: ndt_packet_frame_push and ndt_unproject_packet_frame* below take the UDP payloads).
  *
  * The scan model: the unprojection tables of the lidar callback (ref: src/lidarcallback.cpp:286-327):
  *   p = range_m * (x1,y1,z1)[col * n_rows + row] + (x2,y2,z2)[col]
@@ -528,6 +529,107 @@ int ndt_keyframe_put_from_ranges(ndt_handle* h, int64_t id, const uint32_t* rang
                                  const float* col_t, const ndt_range_gate* gate_or_null, const double* knot_t,
                                  const double* knot_poses16, int n_knots, const double* ref_pose16_or_null,
                                  const ndt_scan_filter* filter_or_null, size_t* n_kept);
+
+/* Lidar packets decoded on the device: the UDP payloads as the socket delivered them (the reference's DataBuffer) to the
+ * range image and on to the deskewed scan.  The host reads the packet and column HEADERS only; a kernel gathers the
+ * pixels (ref: src/lidarcallback.cpp:382-891 walks every pixel on the host).  n_cols (columns per frame) and n_rows
+ * (pixels per column) are the scan model's; columns_per_packet (cpp) >= 1 is the caller's.
+ *
+ *                              NDT_LIDAR_PROFILE_RNG19 (RNG19_RFL8_SIG16_NIR16)   NDT_LIDAR_PROFILE_LEGACY
+ *   packet header / footer     32 / 32 bytes                                      0 / 0
+ *   column header              12 bytes                                           16 bytes
+ *   per-column trailer         none                                               4-byte block status
+ *   block (one column)         12 + 12*n_rows                                     16 + 12*n_rows + 4
+ *   packet size                64 + cpp*block                                     cpp*block
+ *   packet accepted when       size matches and LE u16 at byte 0 is 0x0001        size matches
+ *   packet frame id            LE u16 at byte 2                                   LE u16 at byte 10 of its FIRST column
+ *   column timestamp           LE u64 ns at block+0                               LE u64 ns at block+0
+ *   column m_id                LE u16 at block+8                                  LE u16 at block+8
+ *   column valid when          byte[block+10] & 1                                 LE u32 at block+16+12*n_rows is 0xFFFFFFFF
+ *                                                                                 and LE u16 at block+10 is the packet frame id
+ *   first pixel at             block+12                                           block+16
+ *   pixel: 12 bytes, LE dwords d0 d1 d2
+ *     range_mm                 d0 & 0x0007FFFF                                    d0 & 0x000FFFFF
+ *     reflectivity, signal, nir   d1 & 0xFF, d1 >> 16, d2 & 0xFFFF (both)
+ * A column whose m_id is not below n_cols is rejected (checked first; then, LEGACY, the frame id; then the status).
+ * Every offset is a multiple of 4: the packed packet buffer keeps each accepted packet, in arrival order, at a stride of
+ * the packet size rounded up to 16 bytes, and the kernel uses dword loads only.
+ * Column time: ts = fmod((double)timestamp_ns * 1e-9, 86400.0); col_t[m] = (float)max(0.0, ts - t_ref), one rounding; a
+ * column that never arrived or was rejected has col_t = NaN (and the validity rule of ndt_unproject* drops its pixels).
+ * t_ref is the caller's when it is finite, otherwise the ts of the first accepted column in arrival order (the
+ * reference's active_frame_->timestamp whenever that column holds a kept point).
+ * Two deviations from the reference: it pushes points in arrival order and would push a duplicated column twice -- an
+ * image holds one column per m_id; when an m_id arrives more than once the LAST arrival holds (decided on the host).
+ * A frame holds at most 2 * ceil(n_cols / cpp) accepted packets. */
+#define NDT_LIDAR_PROFILE_RNG19 0
+#define NDT_LIDAR_PROFILE_LEGACY 1
+typedef struct ndt_packet_frame_info {
+  int32_t frame_id;                /* of the first accepted packet; -1: none yet */
+  int32_t next_frame_pending;      /* a packet of another frame id stopped the last push */
+  double t_ref;                    /* the reference time in use; NaN: automatic and no column accepted yet */
+  double ts_first, ts_last;        /* ts of the first and the latest accepted column in arrival order; NaN: none */
+  int64_t n_columns;               /* image columns that hold an arrival */
+  int64_t n_packets;               /* packets taken, the rejected ones included */
+  int64_t n_packets_accepted;      /* ... of which accepted = slots of the packed buffer in use */
+  int64_t n_packets_bad_size, n_packets_bad_type;
+  int64_t n_columns_bad_id, n_columns_bad_frame, n_columns_bad_status;
+  int64_t n_columns_overridden;    /* arrivals of an m_id that already held a column */
+} ndt_packet_frame_info;
+/* host only, no handle, no device: the whole host pre-pass.  packets: n_packets payloads stride_bytes apart, packet k
+ * being bytes_each[k] bytes long; taken in order until one carries another frame id than the first accepted one
+ * (info->next_frame_pending, that packet is not taken) or the frame's capacity is used up.  col_src[n_cols]: the DWORD
+ * offset of the column's first pixel inside the packed packet buffer, -1 where no column holds; col_t[n_cols] as above;
+ * t_ref NaN: automatic.  NDT_ERR_INVALID_ARG when an output pointer is NULL, packets or bytes_each is NULL with
+ * n_packets > 0, the profile is unknown, a count is below 1, the packed buffer would exceed 2^31 dwords, t_ref is
+ * infinite or a bytes_each[k] exceeds stride_bytes; nothing is written then. */
+int ndt_packet_columns(int profile, int columns_per_packet, int n_cols, int n_rows, const uint8_t* packets,
+                       const size_t* bytes_each, size_t n_packets, size_t stride_bytes, double t_ref, int32_t* col_src,
+                       float* col_t, ndt_packet_frame_info* info);
+/* The format of the handle's packets; needs a scan model (its n_cols and n_rows).  ndt_scan_model_set and
+ * ndt_scan_model_clear drop the format and any frame in progress.  ndt_packet_format_get: *profile = -1 when none is
+ * set.  ndt_packet_size: the payload size that is accepted, 0 when no format is set. */
+int ndt_packet_format_set(ndt_handle* h, int profile, int columns_per_packet);
+int ndt_packet_format_get(const ndt_handle* h, int* profile, int* columns_per_packet);
+size_t ndt_packet_size(const ndt_handle* h);
+/* A frame, packet by packet.  ndt_packet_frame_begin waits for the engine's stream and forgets the frame in progress.
+ * ndt_packet_frame_push takes n_packets payloads in order (layout as ndt_packet_columns takes them): the first accepted
+ * packet fixes the frame id; a packet with another frame id stops the call -- *n_taken < n_packets, NDT_OK,
+ * next_frame_pending = 1: finish the frame, call begin and push that packet again (the reference's completion rule).
+ * Rejected packets count as taken.  Each accepted packet is copied into its own slot of a pinned staging area and the
+ * call's slots go to the device packet buffer with one asynchronous copy on the engine's stream: a push returns without
+ * waiting, no slot is reused before the next begin.  One accepted packet more than the capacity is
+ * NDT_ERR_INVALID_ARG ("frame overfull") with nothing of that call taken and the frame in progress as it was.
+ * ndt_packet_frame_get_info: the counters of the frame in progress. */
+int ndt_packet_frame_begin(ndt_handle* h);
+int ndt_packet_frame_push(ndt_handle* h, const uint8_t* packets, const size_t* bytes_each, size_t n_packets, size_t stride_bytes,
+                          size_t* n_taken);
+int ndt_packet_frame_get_info(const ndt_handle* h, ndt_packet_frame_info* info);
+/* The range image of the frame in progress into caller-owned DEVICE memory: d_range_mm (n_cols*n_rows uint32),
+ * d_reflectivity (n_cols*n_rows bytes, nullable), d_signal and d_nir (n_cols*n_rows uint16, nullable), d_col_t (n_cols
+ * floats); pixel i = col * n_rows + row, a column that does not hold is zeros with col_t = NaN.  One launch of
+ * k_decode_packets; complete on return.  The frame stays in progress: more packets may follow and be decoded again. */
+int ndt_decode_packet_frame_device(ndt_handle* h, uint32_t* d_range_mm, uint8_t* d_reflectivity, uint16_t* d_signal,
+                                   uint16_t* d_nir, float* d_col_t);
+/* ndt_unproject_device, ndt_unproject and ndt_keyframe_put_from_ranges on the frame in progress: the image is decoded
+ * into the handle's scratch and goes through the same launches, so every output is bit for bit what those calls return
+ * for the decoded image (reflectivity always present).  signal_out / nir_out (nullable, uint16; device memory in the
+ * _device form, host memory otherwise): signal and nir of the points written, in their order -- in the compacting form
+ * gathered through the pixel index by a second small kernel; cap elements (the keyframe form: n_cols*n_rows).
+ * Refused, with nothing written and the cause in ndt_last_error: no scan model, no packet format, no accepted column,
+ * signal_out / nir_out overlapping another output, and every refusal of the call it stands for.  The handle's target,
+ * source, align state, map and archive are left alone, except the archive entry being put.  Complete on return. */
+int ndt_unproject_packet_frame_device(ndt_handle* h, const ndt_range_gate* gate_or_null, const double* knot_t,
+                                      const double* knot_poses16, int n_knots, const double* ref_pose16_or_null,
+                                      const ndt_scan_filter* filter_or_null, float* ox, float* oy, float* oz, float* o_intensity,
+                                      float* o_t, int32_t* d_index_out, uint16_t* d_signal_out, uint16_t* d_nir_out, size_t cap,
+                                      size_t* n_out);
+int ndt_unproject_packet_frame(ndt_handle* h, const ndt_range_gate* gate_or_null, const double* knot_t, const double* knot_poses16,
+                               int n_knots, const double* ref_pose16_or_null, const ndt_scan_filter* filter_or_null, float* out,
+                               size_t stride_bytes, long intensity_offset_bytes, float* t_out, int32_t* index_out,
+                               uint16_t* signal_out, uint16_t* nir_out, size_t cap, size_t* n_out);
+int ndt_keyframe_put_from_packets(ndt_handle* h, int64_t id, const ndt_range_gate* gate_or_null, const double* knot_t,
+                                  const double* knot_poses16, int n_knots, const double* ref_pose16_or_null,
+                                  const ndt_scan_filter* filter_or_null, uint16_t* signal_out, uint16_t* nir_out, size_t* n_kept);
 
 /* pcl::VoxelGrid downsample on the device (ref: run/pipeline_ins_map_distribution.cpp:324-340: the accumulated map
  * is filtered at `mapvoxelsize` before the NDT export).  PCL's published algorithm: the grid of

@@ -916,7 +916,7 @@ class NormalDistributionsTransform
   // ---- unprojection: the lidar callback's range image (a 20-bit range in millimetres and a reflectivity byte per pixel,
   // one time per column, column by column) through the scan model's tables to points, with the range gate, the
   // acquisition filter and the deskew in the same pass (ndt_unproject* in ndt_hip.h).  Replaces the point-forming part
-  // of LidarCallback::DecodePacket*; packet parsing stays with the driver. ----
+  // of LidarCallback::DecodePacket*; packet parsing stays with the driver (or goes to the device too: pushPackets below). ----
   // the tables as the callback's Initialize() computes them (host only); x1 .. z1: n_cols * n_rows, x2 .. z2: n_cols
   struct ScanModel {
     int n_cols = 0, n_rows = 0;
@@ -1049,6 +1049,122 @@ class NormalDistributionsTransform
     return putKeyframeFromRanges(id, range_mm.data(), reflectivity.empty() ? nullptr : reflectivity.data(), col_t.data(), gate,
                                  moving ? knot_t.data() : nullptr, moving ? poses.data() : nullptr, (int)knot_t.size(),
                                  ref_pose ? ref : nullptr, filter);
+  }
+  // ---- lidar packets: the UDP payloads of a frame (the lidar callback's DataBuffer) decoded on the device, then the calls
+  // above on the decoded image (ndt_packet_* / ndt_unproject_packet_frame* in ndt_hip.h).  Replaces the whole of
+  // LidarCallback::DecodePacket*: the host reads the column headers, a kernel gathers the pixels. ----
+  void setPacketFormat(int profile, int columns_per_packet) {
+    status_ = h_ ? ndt_packet_format_set(h_, profile, columns_per_packet) : NDT_ERR_NO_DEVICE;
+  }
+  size_t packetSize() const { return h_ ? ndt_packet_size(h_) : 0; }
+  void beginPacketFrame() { status_ = h_ ? ndt_packet_frame_begin(h_) : NDT_ERR_NO_DEVICE; }
+  // each returns the number of packets taken; fewer than given: a packet of the next frame stopped the call
+  // (packetFrameInfo().next_frame_pending) -- finish the frame, beginPacketFrame(), push the rest
+  size_t pushPackets(const uint8_t* packets, const size_t* bytes_each, size_t n_packets, size_t stride_bytes) {
+    size_t taken = 0;
+    status_ = h_ ? ndt_packet_frame_push(h_, packets, bytes_each, n_packets, stride_bytes, &taken) : NDT_ERR_NO_DEVICE;
+    return status_ == NDT_OK ? taken : 0;
+  }
+  size_t pushPackets(const std::vector<uint8_t>& packet) {
+    const size_t bytes = packet.size();
+    return pushPackets(packet.data(), &bytes, 1, bytes);
+  }
+  size_t pushPackets(const std::vector<std::vector<uint8_t>>& packets) {
+    size_t taken = 0;
+    for (const std::vector<uint8_t>& p : packets) {
+      if (pushPackets(p) != 1) break;
+      ++taken;
+    }
+    return taken;
+  }
+  ndt_packet_frame_info packetFrameInfo() const {
+    ndt_packet_frame_info info;
+    std::memset(&info, 0, sizeof(info));
+    info.frame_id = -1;
+    if (h_) (void)ndt_packet_frame_get_info(h_, &info);
+    return info;
+  }
+  void decodePacketFrameDevice(uint32_t* d_range_mm, uint8_t* d_reflectivity, uint16_t* d_signal, uint16_t* d_nir, float* d_col_t) {
+    status_ = h_ ? ndt_decode_packet_frame_device(h_, d_range_mm, d_reflectivity, d_signal, d_nir, d_col_t) : NDT_ERR_NO_DEVICE;
+  }
+  size_t unprojectPacketFrameDevice(const ndt_range_gate* gate_or_null, const double* knot_t, const double* knot_poses16, int n_knots,
+                                    const double* ref_pose16_or_null, const ndt_scan_filter* filter_or_null, float* ox, float* oy,
+                                    float* oz, float* o_intensity, float* o_t, int32_t* d_index_out, uint16_t* d_signal_out,
+                                    uint16_t* d_nir_out, size_t cap) {
+    size_t m = 0;
+    status_ = h_ ? ndt_unproject_packet_frame_device(h_, gate_or_null, knot_t, knot_poses16, n_knots, ref_pose16_or_null, filter_or_null,
+                                                     ox, oy, oz, o_intensity, o_t, d_index_out, d_signal_out, d_nir_out, cap, &m)
+                 : NDT_ERR_NO_DEVICE;
+    return status_ == NDT_OK ? m : 0;
+  }
+  size_t unprojectPacketFrame(const ndt_range_gate* gate_or_null, const double* knot_t, const double* knot_poses16, int n_knots,
+                              const double* ref_pose16_or_null, const ndt_scan_filter* filter_or_null, float* out, size_t stride_bytes,
+                              long intensity_offset_bytes, float* t_out, int32_t* index_out, uint16_t* signal_out, uint16_t* nir_out,
+                              size_t cap) {
+    size_t m = 0;
+    status_ = h_ ? ndt_unproject_packet_frame(h_, gate_or_null, knot_t, knot_poses16, n_knots, ref_pose16_or_null, filter_or_null, out,
+                                              stride_bytes, intensity_offset_bytes, t_out, index_out, signal_out, nir_out, cap, &m)
+                 : NDT_ERR_NO_DEVICE;
+    return status_ == NDT_OK ? m : 0;
+  }
+  // the typed face, as unproject<Cloud>() above: the cloud of the frame in progress and, if asked for, each point's time,
+  // pixel index, signal and nir
+  template <class Cloud, class Poses>
+  Cloud unprojectPacketFrame(const std::vector<double>& knot_t, const Poses& knot_poses, const Matrix4d* ref_pose = nullptr,
+                             const ndt_range_gate* gate = nullptr, const ndt_scan_filter* filter = nullptr,
+                             std::vector<float>* times = nullptr, std::vector<int32_t>* index = nullptr,
+                             std::vector<uint16_t>* signal = nullptr, std::vector<uint16_t>* nir = nullptr) {
+    Cloud out;
+    if (times) times->clear();
+    if (index) index->clear();
+    if (signal) signal->clear();
+    if (nir) nir->clear();
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return out; }
+    if (knot_t.size() != knot_poses.size()) { status_ = NDT_ERR_INVALID_ARG; return out; }
+    const size_t n = scanModelPixels();
+    using P = typename std::decay<decltype(out.points[0])>::type;
+    const bool moving = !knot_t.empty();
+    const std::vector<double> poses = detail::pack_poses(knot_poses);
+    double ref[16];
+    if (ref_pose) detail::to_colmajor(*ref_pose, 4, 4, ref);
+    out.points.resize(n);
+    std::vector<float> tt(times ? n + 1 : 0);
+    std::vector<int32_t> idx(index ? n + 1 : 0);
+    std::vector<uint16_t> sg(signal ? n + 1 : 0), nr(nir ? n + 1 : 0);
+    const size_t m = unprojectPacketFrame(gate, moving ? knot_t.data() : nullptr, moving ? poses.data() : nullptr, (int)knot_t.size(),
+                                          ref_pose ? ref : nullptr, filter, n ? &out.points[0].x : nullptr, sizeof(P),
+                                          intensity_offset_of<P>(0), times ? tt.data() : nullptr, index ? idx.data() : nullptr,
+                                          signal ? sg.data() : nullptr, nir ? nr.data() : nullptr, n);
+    out.points.resize(m);
+    if (status_ != NDT_OK) return out;
+    if (times) times->assign(tt.begin(), tt.begin() + (std::ptrdiff_t)m);
+    if (index) index->assign(idx.begin(), idx.begin() + (std::ptrdiff_t)m);
+    if (signal) signal->assign(sg.begin(), sg.begin() + (std::ptrdiff_t)m);
+    if (nir) nir->assign(nr.begin(), nr.begin() + (std::ptrdiff_t)m);
+    return out;
+  }
+  template <class Poses>
+  size_t putKeyframeFromPackets(int64_t id, const std::vector<double>& knot_t, const Poses& knot_poses, const Matrix4d* ref_pose = nullptr,
+                                const ndt_range_gate* gate = nullptr, const ndt_scan_filter* filter = nullptr,
+                                std::vector<uint16_t>* signal = nullptr, std::vector<uint16_t>* nir = nullptr) {
+    if (signal) signal->clear();
+    if (nir) nir->clear();
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return 0; }
+    if (knot_t.size() != knot_poses.size()) { status_ = NDT_ERR_INVALID_ARG; return 0; }
+    const size_t n = scanModelPixels();
+    const bool moving = !knot_t.empty();
+    const std::vector<double> poses = detail::pack_poses(knot_poses);
+    double ref[16];
+    if (ref_pose) detail::to_colmajor(*ref_pose, 4, 4, ref);
+    std::vector<uint16_t> sg(signal ? n + 1 : 0), nr(nir ? n + 1 : 0);
+    size_t m = 0;
+    status_ = ndt_keyframe_put_from_packets(h_, id, gate, moving ? knot_t.data() : nullptr, moving ? poses.data() : nullptr,
+                                            (int)knot_t.size(), ref_pose ? ref : nullptr, filter, signal ? sg.data() : nullptr,
+                                            nir ? nr.data() : nullptr, &m);
+    if (status_ != NDT_OK) return 0;
+    if (signal) signal->assign(sg.begin(), sg.begin() + (std::ptrdiff_t)m);
+    if (nir) nir->assign(nr.begin(), nr.begin() + (std::ptrdiff_t)m);
+    return m;
   }
   // D(t) of that model as a matrix (host only)
   template <class Poses>

@@ -164,6 +164,20 @@ class RangeGate(C.Structure):
         self.row_step = int(row_step)
 
 
+LIDAR_PROFILE_RNG19, LIDAR_PROFILE_LEGACY = 0, 1
+
+
+class PacketFrameInfo(C.Structure):
+    """ndt_packet_frame_info: what the host pre-pass over a frame's packets found"""
+    _fields_ = [("frame_id", C.c_int32), ("next_frame_pending", C.c_int32), ("t_ref", C.c_double), ("ts_first", C.c_double),
+                ("ts_last", C.c_double)] + [(k, C.c_int64) for k in (
+                    "n_columns", "n_packets", "n_packets_accepted", "n_packets_bad_size", "n_packets_bad_type", "n_columns_bad_id",
+                    "n_columns_bad_frame", "n_columns_bad_status", "n_columns_overridden")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Timing(C.Structure):
     _fields_ = [
         ("ms_last_eval_kernel", C.c_double), ("ms_last_reduce_kernel", C.c_double),
@@ -292,6 +306,9 @@ ABI_SYMBOLS = [
     "ndt_trajectory_pose", "ndt_deskew_device", "ndt_deskew", "ndt_keyframe_put_deskewed",
     "ndt_scan_model_set", "ndt_scan_model_clear", "ndt_scan_model_get_info", "ndt_scan_model_from_beams",
     "ndt_unproject_device", "ndt_unproject", "ndt_keyframe_put_from_ranges",
+    "ndt_packet_columns", "ndt_packet_format_set", "ndt_packet_format_get", "ndt_packet_size", "ndt_packet_frame_begin",
+    "ndt_packet_frame_push", "ndt_packet_frame_get_info", "ndt_decode_packet_frame_device",
+    "ndt_unproject_packet_frame_device", "ndt_unproject_packet_frame", "ndt_keyframe_put_from_packets",
     "ndt_map_crop", "ndt_map_export_state", "ndt_map_export_state_device", "ndt_map_import_state", "ndt_map_import_state_device",
     "ndt_map_carve_default_params", "ndt_map_carve_device", "ndt_map_carve", "ndt_map_carve_keyframe",
 ]
@@ -442,6 +459,21 @@ def lib():
         L.ndt_unproject_device.argtypes = [vp] + ranges + [vp, vp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ndt_unproject.argtypes = [vp] + ranges + [vp, C.c_size_t, C.c_long, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ndt_keyframe_put_from_ranges.argtypes = [vp, C.c_int64] + ranges + [C.POINTER(C.c_size_t)]
+        L.ndt_packet_columns.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t, C.c_size_t, C.c_double, vp, vp,
+                                         C.POINTER(PacketFrameInfo)]
+        L.ndt_packet_format_set.argtypes = [vp, C.c_int, C.c_int]
+        L.ndt_packet_format_get.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.ndt_packet_size.argtypes = [vp]
+        L.ndt_packet_size.restype = C.c_size_t
+        L.ndt_packet_frame_begin.argtypes = [vp]
+        L.ndt_packet_frame_push.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ndt_packet_frame_get_info.argtypes = [vp, C.POINTER(PacketFrameInfo)]
+        L.ndt_decode_packet_frame_device.argtypes = [vp, vp, vp, vp, vp, vp]
+        gated = [C.POINTER(RangeGate)] + traj
+        L.ndt_unproject_packet_frame_device.argtypes = [vp] + gated + [vp] * 8 + [C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ndt_unproject_packet_frame.argtypes = [vp] + gated + [vp, C.c_size_t, C.c_long, vp, vp, vp, vp, C.c_size_t,
+                                                                 C.POINTER(C.c_size_t)]
+        L.ndt_keyframe_put_from_packets.argtypes = [vp, C.c_int64] + gated + [vp, vp, C.POINTER(C.c_size_t)]
         L.ndt_set_handoff_mode.argtypes = [vp, C.c_int]
         L.ndt_get_handoff_mode.argtypes = [vp]
         L.ndt_wait.argtypes = [vp]
@@ -592,6 +624,36 @@ def scan_model_from_beams(n_cols, beam_azimuth_deg, beam_altitude_deg, lidar_ori
     if rc != 0:
         raise NdtError(rc, "ndt_scan_model_from_beams")
     return x1, y1, z1, x2, y2, z2
+
+
+def _packet_array(packets):
+    """(uint8 array [k, stride], sizes [k] size_t, stride) of a 2-D uint8 array (every packet as long as a row) or of a
+    sequence of bytes-like payloads of any lengths (padded with zeros to the longest)"""
+    if isinstance(packets, np.ndarray) and packets.ndim == 2:
+        a = np.ascontiguousarray(packets, dtype=np.uint8)
+        return a, np.full(len(a), a.shape[1], np.uintp), a.shape[1]
+    rows = [np.frombuffer(bytes(p), np.uint8) for p in packets]
+    stride = max([len(r) for r in rows] + [1])
+    a = np.zeros((len(rows), stride), np.uint8)
+    for k, r in enumerate(rows):
+        a[k, :len(r)] = r
+    return a, np.array([len(r) for r in rows], np.uintp), stride
+
+
+def packet_columns(profile, columns_per_packet, n_cols, n_rows, packets, t_ref=None):
+    """The host pre-pass over a frame's UDP payloads (host only, no device; ndt_packet_columns): packets as a uint8 array
+    [k, bytes] or a sequence of bytes-like payloads, t_ref None: the first accepted column's time.  Returns (col_src int32
+    [n_cols]: dword offset of the column's first pixel in the packed packet buffer, -1: none; col_t float32 [n_cols], NaN:
+    none; info dict)."""
+    a, sizes, stride = _packet_array(packets)
+    src, col_t = np.full(max(int(n_cols), 0), -1, np.int32), np.full(max(int(n_cols), 0), np.nan, np.float32)
+    info = PacketFrameInfo()
+    rc = lib().ndt_packet_columns(int(profile), int(columns_per_packet), int(n_cols), int(n_rows), a.ctypes.data, sizes.ctypes.data,
+                                  len(a), stride, float("nan") if t_ref is None else float(t_ref), src.ctypes.data,
+                                  col_t.ctypes.data, C.byref(info))
+    if rc != 0:
+        raise NdtError(rc, "ndt_packet_columns")
+    return src, col_t, info.as_dict()
 
 
 def shard_range(n, rank, nranks):
@@ -965,6 +1027,85 @@ class NormalDistributionsTransform:
                                                        t.ctypes.data, self._gate_ref(gate), kt, poses, nk, ref,
                                                        self._filter_ref(filter), C.byref(m)))
         return int(m.value)
+
+    # --- lidar packets: the UDP payloads of a frame decoded on the device, then the calls above on the decoded image ---
+    def setPacketFormat(self, profile, columns_per_packet):
+        """LIDAR_PROFILE_RNG19 or LIDAR_PROFILE_LEGACY and the columns a packet carries; needs the scan model (setScanModel
+        and clearScanModel drop the format and the frame in progress)."""
+        self._check(lib().ndt_packet_format_set(self._h, int(profile), int(columns_per_packet)))
+
+    def packetFormat(self):
+        """(profile, columns_per_packet, packet bytes); (-1, 0, 0) when none is set"""
+        p, c = C.c_int(0), C.c_int(0)
+        self._check(lib().ndt_packet_format_get(self._h, C.byref(p), C.byref(c)))
+        return p.value, c.value, int(lib().ndt_packet_size(self._h))
+
+    def beginPacketFrame(self):
+        self._check(lib().ndt_packet_frame_begin(self._h))
+
+    def pushPackets(self, packets):
+        """Packets in arrival order (a uint8 array [k, bytes] or a sequence of bytes-like payloads); returns the number
+        taken -- fewer than given when a packet of the next frame stopped the call (packetFrameInfo()
+        ["next_frame_pending"]): finish the frame, beginPacketFrame(), push the rest."""
+        a, sizes, stride = _packet_array(packets)
+        taken = C.c_size_t(0)
+        self._check(lib().ndt_packet_frame_push(self._h, a.ctypes.data, sizes.ctypes.data, len(a), stride, C.byref(taken)))
+        return int(taken.value)
+
+    def packetFrameInfo(self):
+        info = PacketFrameInfo()
+        self._check(lib().ndt_packet_frame_get_info(self._h, C.byref(info)))
+        return info.as_dict()
+
+    def decodePacketFrameDevice(self, d_range_mm, d_reflectivity, d_signal, d_nir, d_col_t):
+        """The range image of the frame in progress into device arrays (integer device addresses; reflectivity, signal and
+        nir may be None)."""
+        self._check(lib().ndt_decode_packet_frame_device(self._h, d_range_mm, d_reflectivity, d_signal, d_nir, d_col_t))
+
+    def unprojectPacketFrame(self, knot_t=None, knot_poses=None, ref_pose=None, gate=None, filter=None, with_t=False,
+                             with_index=False, with_signal=False, with_nir=False):
+        """unproject() of the frame in progress: a cloud [m, 4] (x, y, z, intensity), then the times, the pixel indices,
+        the signal and the nir values (uint16) of its points if asked for."""
+        n_cols, n_rows = self.scanModelInfo()
+        n = n_cols * n_rows
+        kt, poses, nk, ref = self._trajectory_or_none(knot_t, knot_poses, ref_pose)
+        out = np.zeros((max(n, 1), 4), np.float32)
+        tt = np.zeros(max(n, 1), np.float32) if with_t else None
+        idx = np.zeros(max(n, 1), np.int32) if with_index else None
+        sig = np.zeros(max(n, 1), np.uint16) if with_signal else None
+        nir = np.zeros(max(n, 1), np.uint16) if with_nir else None
+        m = C.c_size_t(0)
+        ptr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
+        self._check(lib().ndt_unproject_packet_frame(self._h, self._gate_ref(gate), kt, poses, nk, ref, self._filter_ref(filter),
+                                                     out.ctypes.data, 16, 12, ptr(tt), ptr(idx), ptr(sig), ptr(nir), n, C.byref(m)))
+        res = [out[:m.value].copy()] + [a[:m.value].copy() for a in (tt, idx, sig, nir) if a is not None]
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def unprojectPacketFrameDevice(self, ox, oy, oz, cap, knot_t=None, knot_poses=None, ref_pose=None, gate=None, filter=None,
+                                   o_intensity=None, o_t=None, d_index=None, d_signal=None, d_nir=None):
+        """unprojectDevice() of the frame in progress (integer device addresses); returns the number of points written."""
+        kt, poses, nk, ref = self._trajectory_or_none(knot_t, knot_poses, ref_pose)
+        m = C.c_size_t(0)
+        rc = lib().ndt_unproject_packet_frame_device(self._h, self._gate_ref(gate), kt, poses, nk, ref, self._filter_ref(filter), ox, oy,
+                                                     oz, o_intensity, o_t, d_index, d_signal, d_nir, int(cap), C.byref(m))
+        self.last_unproject_count = int(m.value)
+        self._check(rc)
+        return int(m.value)
+
+    def putKeyframeFromPackets(self, kf_id, knot_t=None, knot_poses=None, ref_pose=None, gate=None, filter=None, with_signal=False,
+                               with_nir=False):
+        """putKeyframeFromRanges() of the frame in progress; returns the number of points archived, then their signal and
+        nir values if asked for."""
+        n_cols, n_rows = self.scanModelInfo()
+        kt, poses, nk, ref = self._trajectory_or_none(knot_t, knot_poses, ref_pose)
+        sig = np.zeros(max(n_cols * n_rows, 1), np.uint16) if with_signal else None
+        nir = np.zeros(max(n_cols * n_rows, 1), np.uint16) if with_nir else None
+        m = C.c_size_t(0)
+        self._check(lib().ndt_keyframe_put_from_packets(self._h, int(kf_id), self._gate_ref(gate), kt, poses, nk, ref,
+                                                        self._filter_ref(filter), None if sig is None else sig.ctypes.data,
+                                                        None if nir is None else nir.ctypes.data, C.byref(m)))
+        res = [int(m.value)] + [a[:m.value].copy() for a in (sig, nir) if a is not None]
+        return res[0] if len(res) == 1 else tuple(res)
 
     def setInputSourceFromKeyframe(self, kf_id):
         self._check(lib().ndt_set_source_from_keyframe(self._h, int(kf_id)))

@@ -41,6 +41,7 @@
 #include "ndt_keepwarm.h"
 #include "ndt_kernels.h"
 #include "ndt_newton.h"
+#include "ndt_packets.h"
 #include "ndt_repack_pool.h"
 #include "ndt_tuning.h"
 
@@ -223,6 +224,26 @@ struct ScanModelBufs {
   void release() {
     n_cols = n_rows = 0;
     dir.release(); off.release(); in.release(); out.release(); index.release(); stage.release();
+  }
+};
+
+// The packet format of ndt_packet_format_set, the frame in progress and the scratch of the packet calls (ndt_packets.hip):
+// the accepted packets in a pinned staging and in the device packet buffer (slot k of both = the k-th accepted packet),
+// the column table on its way up, and signal / nir of the decoded image for the forms that unproject.
+struct PacketBufs {
+  pkt::Pass pass;                    // pass.f.profile < 0: no format set
+  PinBuf<uint32_t> stage;            // capacity * slot bytes
+  DevBuf<uint32_t> dev;              // the packed packet buffer
+  PinBuf<uint32_t> cols_h;           // [col_src (n_cols int32) | col_t (n_cols floats)]
+  DevBuf<int32_t> col_src;           // n_cols
+  DevBuf<uint16_t> sig, nir;         // n_cols * n_rows each: the decoded image's
+  DevBuf<uint16_t> sig_out, nir_out; // ... and the selected points' (host forms)
+  PinBuf<uint16_t> back;             // ... on their way down
+  void drop() { pass.f = pkt::Format{}; pass.begin(pass.f); }
+  void release() {
+    drop();
+    stage.release(); dev.release(); cols_h.release(); col_src.release(); sig.release(); nir.release(); sig_out.release();
+    nir_out.release(); back.release();
   }
 };
 
@@ -411,6 +432,7 @@ struct ndt_handle {
   PointScoreBufs ps;                 // scratch of ndt_score_points / ndt_filter_source (ndt_point_scores.hip)
   DeskewBufs dsk;                    // scratch of ndt_deskew* / ndt_keyframe_put_deskewed (ndt_deskew.hip)
   ScanModelBufs scan;                // the scan model and the scratch of ndt_unproject* / ndt_keyframe_put_from_ranges (ndt_unproject.hip)
+  PacketBufs pkt;                    // the packet format, the frame in progress and the scratch of the packet calls (ndt_packets.hip)
   DevBuf<unsigned int> counters;     // per-pose tickets of the in-kernel final reduction
   size_t counters_zeroed = 0;
   DevBuf<PoseConsts> dposes;
@@ -564,6 +586,13 @@ int knots_upload(ndt_handle* h, const traj::KnotRow* rows, int n_knots);
 int download_strided(ndt_handle* h, const float* d_cols, size_t col_stride, const float* d_t, const int32_t* d_index, size_t m,
                      size_t cap, float* back, float* out, size_t stride_bytes, long intensity_offset_bytes, float* t_out,
                      int32_t* index_out);
+// ndt_unproject.hip, for the packet forms (ndt_packets.hip): what every unprojection checks before anything is written
+// (the model, the gate, the trajectory into rows), and the launches on device arrays whose arguments have been checked
+int unproject_check(ndt_handle* h, const ndt_range_gate* gate, const double* knot_t, const double* knot_poses16, int n_knots,
+                    const double* ref16, traj::KnotRow* rows);
+int unproject_device(ndt_handle* h, const uint32_t* d_range, const uint8_t* d_refl, const float* d_col_t, const ndt_range_gate* gate,
+                     const traj::KnotRow* rows, int n_knots, const ndt_scan_filter* filter, float* ox, float* oy, float* oz, float* oi,
+                     float* ot, int32_t* o_index, size_t cap, size_t* n_out);
 void map_release(ndt_handle* h);   // ndt_map.hip: frees the voxel map, if any (ndt_destroy)
 // ndt_map.hip's host side as ndt_map_state.hip uses it (the kernels stay where they are)
 constexpr int64_t MAP_MAX_CAPACITY = 1ll << 30;   // slots are 32-bit sort keys with one sentinel above them

@@ -166,6 +166,7 @@ int ndt_destroy(ndt_handle* h) {
   h->ps.release();
   h->dsk.release();
   h->scan.release();
+  h->pkt.release();
   h->keys.release(); h->vals.release(); h->keys2.release(); h->vals2.release();
   h->sort_tmp.release(); h->nleaf.release(); h->leaf_start.release(); h->leaf_cnt.release();
   h->cell2leaf.release(); h->rec.release(); h->prec.release(); h->prec_valid = false; h->cent.release(); h->stats.release();

@@ -155,6 +155,8 @@ namespace {
 
 size_t unp_pixels(const ndt_handle* h) { return (size_t)h->scan.n_cols * (size_t)h->scan.n_rows; }
 
+}  // namespace
+
 // The trajectory's table to the device (knots_upload), then the launches; awaited.  Every pointer but `rows` is device
 // memory.  Arguments have been checked.
 int unproject_device(ndt_handle* h, const uint32_t* d_range, const uint8_t* d_refl, const float* d_col_t, const ndt_range_gate* gate,
@@ -213,6 +215,8 @@ int unproject_check(ndt_handle* h, const ndt_range_gate* gate, const double* kno
   return rc ? fail(h, rc, why) : NDT_OK;
 }
 
+namespace {
+
 size_t unp_stage_words(size_t n, size_t n_cols) { return n + n_cols + (n + 3) / 4; }
 
 // a host range image -> the handle's device scratch [range_mm | col_t | reflectivity] through the pinned staging: ONE
@@ -248,6 +252,7 @@ int ndt_scan_model_set(ndt_handle* h, int n_cols, int n_rows, const float* x1, c
   ScanModelBufs& b = h->scan;
   const size_t n = (size_t)n_cols * (size_t)n_rows, nc = (size_t)n_cols;
   b.n_cols = b.n_rows = 0;   // (a HIP error below leaves no model rather than half of one)
+  h->pkt.drop();             // the packet format is the model's shape: gone with it, and any frame in progress
   HIP_TRY(h, b.dir.ensure(3 * n));
   HIP_TRY(h, b.off.ensure(3 * nc));
   const float* dir[3] = {x1, y1, z1};
@@ -265,6 +270,7 @@ int ndt_scan_model_set(ndt_handle* h, int n_cols, int n_rows, const float* x1, c
 int ndt_scan_model_clear(ndt_handle* h) {
   if (!h) return NDT_ERR_INVALID_ARG;
   h->scan.n_cols = h->scan.n_rows = 0;   // (the buffers stay for the next model)
+  h->pkt.drop();
   return NDT_OK;
 }
 

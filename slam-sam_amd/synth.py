@@ -412,3 +412,88 @@ def unproject_numpy(model, range_mm, col_t, knot_t=None, knot_poses=None, ref_po
         pts = (world - ref[:3, 3]) @ ref[:3, :3]
     pts[bad] = np.nan
     return pts
+
+
+# --------------------------------------------------------------------------- lidar packets (ndt_packet_* in ndt_hip.h)
+PACKET_PROFILE_RNG19, PACKET_PROFILE_LEGACY = 0, 1
+
+
+def packet_layout(profile, cpp, n_rows):
+    """(packet header bytes, block bytes, first pixel offset in a block, packet bytes) of a profile: the table of
+    include/ndt_hip.h"""
+    legacy = int(profile) == PACKET_PROFILE_LEGACY
+    first = 16 if legacy else 12
+    block = first + 12 * int(n_rows) + (4 if legacy else 0)
+    return (0 if legacy else 32), block, first, (0 if legacy else 64) + int(cpp) * block
+
+
+def encode_packets(n_cols, n_rows, profile, cpp, range_mm, reflectivity, signal, nir, ts_ns, frame_id, seed=0, garbage=True,
+                   order=None, duplicate=(), invalid_status=(), bad_m_id=(), other_frame=(), wrong_type=()):
+    """The UDP payloads of one lidar frame from its range image: range_mm (uint32), reflectivity (uint8), signal and nir
+    (uint16) [n_cols, n_rows], ts_ns (uint64 [n_cols], the column timestamps).  Packet k carries columns k * cpp ..
+    k * cpp + cpp - 1; columns beyond n_cols in the last packet carry m_id = n_cols and an invalid status.  Returns a uint8
+    array [n_packets, packet bytes].  Knobs (seeded):
+      garbage         random bits where the format has none to read: the high bits of d0 (19-31 RNG19, 20-31 LEGACY), bytes
+                      5, 10 and 11 of a pixel, the packet header and footer beyond type and frame id, the spare header bytes
+      order           which packets go out and in which order (indices, default all in order): drops and reorders
+      duplicate       packets emitted once more at the END with other pixel contents (the later arrival must win)
+      invalid_status  columns (m_id) sent with an invalid status
+      bad_m_id        columns sent with m_id = n_cols
+      other_frame     LEGACY: columns whose own frame id field is frame_id + 1
+      wrong_type      RNG19: packets (indices before `order`) sent with packet type 2"""
+    n_cols, n_rows, cpp = int(n_cols), int(n_rows), int(cpp)
+    legacy = int(profile) == PACKET_PROFILE_LEGACY
+    header, block, first, size = packet_layout(profile, cpp, n_rows)
+    rng = np.random.default_rng(seed)
+    r = np.asarray(range_mm, np.uint32).reshape(n_cols, n_rows)
+    mask = np.uint32(0x000FFFFF if legacy else 0x0007FFFF)
+    assert np.all(r <= mask)
+    d = np.zeros((n_cols, n_rows, 3), np.uint32)
+    d[:, :, 0] = r
+    d[:, :, 1] = np.asarray(reflectivity, np.uint8).reshape(n_cols, n_rows).astype(np.uint32) | \
+        (np.asarray(signal, np.uint16).reshape(n_cols, n_rows).astype(np.uint32) << np.uint32(16))
+    d[:, :, 2] = np.asarray(nir, np.uint16).reshape(n_cols, n_rows).astype(np.uint32)
+    ts = np.asarray(ts_ns, np.uint64).ravel()
+    assert len(ts) == n_cols
+    n_packets = (n_cols + cpp - 1) // cpp
+
+    def junk(shape, keep_mask):
+        g = rng.integers(0, 2 ** 32, shape, dtype=np.uint64).astype(np.uint32) if garbage else np.zeros(shape, np.uint32)
+        return g & ~np.uint32(keep_mask)
+
+    def build(k, pixels):
+        p = (rng.integers(0, 256, size).astype(np.uint8) if garbage else np.zeros(size, np.uint8))
+        if not legacy:
+            p[0:2] = np.frombuffer(np.uint16(2 if k in wrong_type else 1).tobytes(), np.uint8)
+            p[2:4] = np.frombuffer(np.uint16(frame_id).tobytes(), np.uint8)
+        for c in range(cpp):
+            m = k * cpp + c
+            b = header + c * block
+            live = m < n_cols
+            m_field = m if live and m not in bad_m_id else n_cols
+            p[b:b + 8] = np.frombuffer(np.uint64(ts[m] if live else 0).tobytes(), np.uint8)
+            p[b + 8:b + 10] = np.frombuffer(np.uint16(m_field).tobytes(), np.uint8)
+            ok = live and m not in invalid_status
+            if legacy:
+                p[b + 10:b + 12] = np.frombuffer(np.uint16((frame_id + 1) & 0xFFFF if m in other_frame else frame_id).tobytes(), np.uint8)
+                status = 0xFFFFFFFF if ok else int(rng.integers(0, 0xFFFFFFFF))
+                p[b + 16 + 12 * n_rows:b + 20 + 12 * n_rows] = np.frombuffer(np.uint32(status).tobytes(), np.uint8)
+            else:
+                p[b + 10] = (p[b + 10] & 0xFE) | (1 if ok else 0)
+            if live:
+                px = pixels[m].copy()
+                px[:, 0] |= junk(n_rows, mask)
+                px[:, 1] |= junk(n_rows, 0xFFFF00FF)                 # byte 5
+                px[:, 2] |= junk(n_rows, 0x0000FFFF)                 # bytes 10 and 11
+                p[b + first:b + first + 12 * n_rows] = np.frombuffer(px.astype("<u4").tobytes(), np.uint8)
+        return p
+
+    natural = list(range(n_packets)) if order is None else [int(k) for k in order]
+    out = [build(k, d) for k in natural]
+    for k in duplicate:
+        other = d.copy()
+        other[:, :, 0] = rng.integers(1, int(mask) + 1, (n_cols, n_rows)).astype(np.uint32)
+        other[:, :, 1] = rng.integers(0, 2 ** 32, (n_cols, n_rows), dtype=np.uint64).astype(np.uint32) & np.uint32(0xFFFF00FF)
+        other[:, :, 2] = rng.integers(0, 2 ** 16, (n_cols, n_rows)).astype(np.uint32)
+        out.append(build(int(k), other))
+    return np.stack(out) if out else np.zeros((0, size), np.uint8)
