@@ -43,6 +43,7 @@
 #include "ndt_newton.h"
 #include "ndt_packets.h"
 #include "ndt_repack_pool.h"
+#include "ndt_target_state.h"
 #include "ndt_tuning.h"
 
 using namespace ndt;
@@ -147,7 +148,7 @@ struct FitGeom {
 // The index itself (built lazily by the first fitness call after the target changed; owns every buffer it uses --
 // the grid build's scratch is reused by ndt_voxel_downsample* and by builds).
 struct FitIndex {
-  uint64_t gen = 0;                  // ndt_handle::tgt_gen of the target it indexes
+  uint64_t gen = 0;                  // TargetState::gen() of the target it indexes
   bool valid = false;
   FitGeom g{};
   DevBuf<float> pts;                 // the finite target points as float4, sorted by cell (stable)
@@ -317,11 +318,12 @@ struct ndt_handle {
   std::string err;
 
   // target
-  DevBuf<float> tx, ty, tz;          // owned copy when the target came from the host
-  size_t n_tgt = 0;
-  uint64_t tgt_gen = 0;              // counts target builds (build_begin): what the fitness index was built for
+  // What is published and what became of its cloud: changed only by target_retire / target_publish / target_drop
+  // (ndt_handoff.hip) and, for the cloud, by the producers' claim_cloud in front of their first write to tx/ty/tz.
+  TargetState tgt;
+  DevBuf<float> tx, ty, tz;          // the engine's own cloud: the first tgt.cloud_n() points are what the published grid was
+                                     // built from (host targets, keyframes, map centroids); freed by a retire that keeps none
   FitIndex fit;                      // point-level nearest-neighbour index of getFitnessScore (ndt_fitness.hip)
-  bool have_grid = false;
   GridGeom geom{};
   int max_b[3] = {0, 0, 0};
   DevBuf<uint32_t> keys, vals, keys2, vals2;
@@ -359,11 +361,6 @@ struct ndt_handle {
   int record_format = NDT_RECORDS_F64;
   DevBuf<float> cent;                // 4 floats per leaf slot: f32 centroid (what the radius search tests) + chain link
   DevBuf<LeafStats> stats;
-  int n_slots = 0, n_valid = 0;
-  // The dense index grid is filled with -1 once per allocation; afterwards only the cells the
-  // previous build published are reset (a 33 MB fill per build otherwise).
-  size_t grid_clean_cap = 0;  // capacity that is -1 everywhere except the dirty leaves' cells
-  int grid_dirty_slots = 0;   // slots of `stats` whose cells may hold an index
   double ms_build = 0;
 
   // source
@@ -466,8 +463,8 @@ struct ndt_handle {
     double eig_ratio = 0.0;
   };
   std::map<int64_t, MultiGridEntry> mgrids;
-  bool multi_active = false;          // the device table is the union (neighbourhood: radius search, chained cells)
-  std::vector<LeafStats> multi_stats; // ... and its leaves in table order, for export
+  std::vector<LeafStats> multi_stats; // the union's leaves in table order, for export (tgt.is_union(): the device table is
+                                      // the union -- neighbourhood: radius search, chained cells)
 
   // pre-launched evaluation (ndt_prelaunch): mailbox in BAR-mapped fine-grained device memory
   PoseMailbox* mbox = nullptr;
@@ -509,7 +506,6 @@ struct ndt_handle {
   // known (evaluate()): spec_first is set by ndt_align for its first evaluate() call.
   bool spec_first = false;
   bool spec_enabled = true;            // (ndt_debug_set_speculation: in-process A/B)
-  int prev_n_valid = 0;                // valid voxels of the grid the build in flight replaces
   bool spec_build_failed = false;      // the deferred build's failure surfaced inside that first evaluation
   int64_t n_spec_used = 0, n_spec_discarded = 0;
   int64_t n_p2p_host_finishes = 0;     // peer-write evaluations whose exchange the host finished (a peer was late)
@@ -556,6 +552,33 @@ int upload_soa(ndt_handle* h, ndt_handle::UploadLane& lane, hipStream_t stream, 
 int pack_records(ndt_handle* h, bool wait);
 int records_for_eval(ndt_handle* h, EvalConsts* ec, const VoxelRecord** rec);
 int neutral_bounds(ndt_handle* h);
+// The target's three transitions on a handle (ndt_handoff.hip; the state itself: ndt_target_state.h).
+// target_retire: the published target makes way for the one being produced -- the cached source order and packed records
+// go with it, nothing is pending or deferred any more, and tx/ty/tz are freed unless their first kept_cloud_n points are
+// what the new grid is built from.  Returns the index grid's reuse pair.
+IndexReuse target_retire(ndt_handle* h, size_t kept_cloud_n);
+// target_publish: the produced grid becomes the target (n_slots == n_valid == the leaves of a UNION); behind a SINGLE the
+// packed records are written while that format is selected.
+int target_publish(ndt_handle* h, TargetKind kind, const GridGeom& geom, const int max_b[3], size_t n_points, int n_slots,
+                   int n_valid, double ms);
+void target_drop(ndt_handle* h);
+// the geometry of a grid of edge `leaf` over the lattice box mn .. mx (inclusive; the caller has checked: fewer than 2^31 cells)
+template <typename I>
+GridGeom grid_geom_from_box(float leaf, const I mn[3], const I mx[3]) {
+  GridGeom g{};
+  g.leaf = leaf;
+  g.inv_leaf = 1.0f / leaf;
+  for (int a = 0; a < 3; ++a) {
+    g.min_b[a] = (int)mn[a];
+    g.div_b[a] = (int)(mx[a] - mn[a] + 1);
+    g.lo[a] = (float)g.min_b[a] * g.leaf;
+    g.hi[a] = (float)(mx[a] + 1) * g.leaf;
+  }
+  g.mul1 = g.div_b[0];
+  g.mul2 = g.div_b[0] * g.div_b[1];
+  g.ncells = g.mul2 * g.div_b[2];
+  return g;
+}
 int build_begin(ndt_handle* h, const float* x, const float* y, const float* z, size_t n, ndt_handle::BuildRun& br);
 int build_enqueue(ndt_handle* h, ndt_handle::BuildRun& br);
 int build_collect(ndt_handle* h, ndt_handle::BuildRun& br);

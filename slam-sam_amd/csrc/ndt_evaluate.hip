@@ -12,9 +12,10 @@ namespace engine {
 
 // (re)writes the packed copy of the record table; `wait`: the caller is about to launch on another stream
 int pack_records(ndt_handle* h, bool wait) {
-  if (h->n_slots <= 0) return NDT_OK;
-  HIP_TRY(h, h->prec.ensure((size_t)h->n_slots));
-  launch_pack_records(h->rec.p, h->prec.p, (size_t)h->n_slots, h->stream);
+  const int n_slots = h->tgt.n_slots();
+  if (n_slots <= 0) return NDT_OK;
+  HIP_TRY(h, h->prec.ensure((size_t)n_slots));
+  launch_pack_records(h->rec.p, h->prec.p, (size_t)n_slots, h->stream);
   HIP_TRY(h, hipGetLastError());
   if (wait) HIP_TRY(h, hipStreamSynchronize(h->stream));
   h->prec_valid = true;
@@ -27,7 +28,7 @@ int pack_records(ndt_handle* h, bool wait) {
 int records_for_eval(ndt_handle* h, EvalConsts* ec, const VoxelRecord** rec) {
   ec->packed = 0;
   *rec = h->rec.p;
-  if (h->record_format != NDT_RECORDS_PACKED48 || h->multi_active || h->n_slots <= 0 ||
+  if (h->record_format != NDT_RECORDS_PACKED48 || h->tgt.is_union() || h->tgt.n_slots() <= 0 ||
       (h->prm.search_method != NDT_DIRECT7 && h->prm.search_method != NDT_DIRECT1))
     return NDT_OK;  // (an empty table: slot 0 of the f64 one is what absent neighbours read)
   if (!h->prec_valid) {
@@ -69,7 +70,7 @@ EvalConsts make_eval_consts(const ndt_handle* h, bool need_h) {
   ec.kd_radius2 = (float)((double)h->prm.resolution * (double)h->prm.resolution);
   ec.need_hessian = need_h ? 1 : 0;
   ec.gauss_newton = h->prm.hessian_mode == NDT_HESSIAN_GAUSS_NEWTON ? 1 : 0;
-  ec.multigrid = h->multi_active ? 1 : 0;
+  ec.multigrid = h->tgt.is_union() ? 1 : 0;
   ec.mbox_tagged = h->mbox_tagged ? 1 : 0;
   ec.mbox_preload = h->mbox_preload ? 1 : 0;
   ec.compute_units = h->n_cus;   // block shapes and the XCD count are those of THIS handle's device (CPX partitions: 32)
@@ -90,7 +91,7 @@ int ensure_counters(ndt_handle* h, size_t k) {
 
 int ready_for_eval(ndt_handle* h) {
   if (int rc = settle(h)) return rc;
-  if (!h->have_grid || h->n_valid <= 0) return fail(h, NDT_ERR_NO_TARGET, "no target voxel grid (setInputTarget first)");
+  if (!h->tgt.have_grid() || h->tgt.n_valid() <= 0) return fail(h, NDT_ERR_NO_TARGET, "no target voxel grid (setInputTarget first)");
   if (h->n_src == 0 && h->red.mode() == NDT_REDUCE_NONE) return fail(h, NDT_ERR_NO_SOURCE, "no source cloud (setInputSource first)");
   return NDT_OK;
 }
@@ -108,7 +109,7 @@ int ensure_flag_slots(ndt_handle* h, size_t K) {
 // (NDT_SOURCE_ORDER_*).  Done once per (source, target): the copy stays a valid permutation of the
 // source whatever the later poses are.
 int maybe_sort_source(ndt_handle* h, const float T[16]) {
-  if (!h->have_grid || !source_sort_wanted(h, h->n_valid)) return NDT_OK;
+  if (!h->tgt.have_grid() || !source_sort_wanted(h, h->tgt.n_valid())) return NDT_OK;
   const size_t n = h->n_src;
   HIP_TRY(h, h->ox.ensure(n));
   HIP_TRY(h, h->oy.ensure(n));
@@ -148,9 +149,9 @@ bool source_sort_wanted(const ndt_handle* h, int n_valid) {
 // for a grid of the size of the previous one (checked again once the verdict is in: a mismatch discards the launch).
 // ndt_tuning::speculate_first = 0: off.
 bool first_eval_behind_build(const ndt_tuning& tn, const ndt_handle* h) {
-  return tn.speculate_first != 0 && h->spec_enabled && h->build_pending && h->prev_n_valid > 0 && h->n_src > 0 && !h->timing &&
+  return tn.speculate_first != 0 && h->spec_enabled && h->build_pending && h->tgt.prev_n_valid() > 0 && h->n_src > 0 && !h->timing &&
          h->prm.wait_mode == NDT_WAIT_SPIN && !h->red.wants_device_buffer() && h->red.mode() != NDT_REDUCE_P2P &&
-         h->record_format != NDT_RECORDS_PACKED48 && !source_sort_wanted(h, h->prev_n_valid);
+         h->record_format != NDT_RECORDS_PACKED48 && !source_sort_wanted(h, h->tgt.prev_n_valid());
 }
 
 // Launch sequence numbers tag every partial / result slot the derivative kernel writes; they
@@ -500,7 +501,7 @@ int evaluate(ndt_handle* h, const double p[6], const float T[16], bool need_h, E
   if (speculate) {
     // the launch is on the stream behind the build; NOW the verdict (the host had nothing else to do meanwhile)
     const int rs = settle(h);
-    const bool keep = rs == NDT_OK && h->have_grid && h->n_valid > 0 && h->brun.attempt == 0 && !source_sort_wanted(h, h->n_valid);
+    const bool keep = rs == NDT_OK && h->tgt.have_grid() && h->tgt.n_valid() > 0 && h->brun.attempt == 0 && !source_sort_wanted(h, h->tgt.n_valid());
     if (!keep) {
       // refused or repeated build (the kernel left at once, or evaluated a grid that has been rebuilt since), no valid
       // voxel, or a grid for which the source is to be re-ordered: the launch is drained and forgotten

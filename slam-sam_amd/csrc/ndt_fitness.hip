@@ -305,10 +305,10 @@ unsigned grid1(size_t n) { return (unsigned)((n + FIT_THREADS - 1) / FIT_THREADS
 // Lazily (re)builds the index over the engine's copy of the target.  Called with the target settled.
 int fit_build(ndt_handle* h) {
   FitIndex& f = h->fit;
-  if (f.valid && f.gen == h->tgt_gen) return NDT_OK;
+  if (f.valid && f.gen == h->tgt.gen()) return NDT_OK;
   f.valid = false;
   hipStream_t s = h->stream;
-  const size_t n = h->n_tgt;
+  const size_t n = h->tgt.cloud_n();
   const float *x = h->tx.p, *y = h->ty.p, *z = h->tz.p;
   // bounds of the finite points: per-block rows, finished on the host (one wait: the geometry sizes everything else)
   const int nb = (int)std::min<size_t>(FIT_BOUNDS_BLOCKS, grid1(n));
@@ -385,7 +385,7 @@ int fit_build(ndt_handle* h) {
   hipLaunchKernelGGL(k_fit_ends, dim3(grid1((size_t)nf)), dim3(FIT_THREADS), 0, s, sk, (int)nf, g.hash_mask, f.tab.p);
   HIP_TRY(h, hipGetLastError());
   f.g = g;
-  f.gen = h->tgt_gen;
+  f.gen = h->tgt.gen();
   f.valid = true;
   return NDT_OK;
 }
@@ -396,12 +396,12 @@ int fit_ready(ndt_handle* h) {
   if (rc) return rc;
   rc = settle(h);   // orders the engine's stream behind the target's upload, the pending build and the source upload
   if (rc) return rc;
-  if (h->multi_active)
+  if (h->tgt.is_union())
     return fail(h, NDT_ERR_UNSUPPORTED, "fitness: a multi-grid target keeps no points (set a single target)");
-  if (h->have_grid && !h->tx.p)
+  if (h->tgt.have_grid() && !h->tgt.has_cloud())
     return fail(h, NDT_ERR_UNSUPPORTED,
                 "fitness: the target came through ndt_set_target_device* and was consumed there (nothing is retained)");
-  if (!h->have_grid || !h->tx.p || h->n_tgt == 0) return fail(h, NDT_ERR_NO_TARGET, "no target (setInputTarget first)");
+  if (!h->tgt.have_grid()) return fail(h, NDT_ERR_NO_TARGET, "no target (setInputTarget first)");
   if (h->n_src == 0 && h->red.mode() == NDT_REDUCE_NONE)
     return fail(h, NDT_ERR_NO_SOURCE, "no source cloud (setInputSource first)");
   return fit_build(h);

@@ -214,11 +214,11 @@ int ndt_set_params(ndt_handle* h, const ndt_params* p) {
     if (rc0) return rc0;
     (void)settle_build(h);  // (a failure stays with the handle for the first call that needs the grid)
   }
-  const bool grid_changed = h->have_grid && (std::fabs(p->resolution - h->prm.resolution) > 1e-6f ||
+  const bool grid_changed = h->tgt.have_grid() && (std::fabs(p->resolution - h->prm.resolution) > 1e-6f ||
                                              p->min_points_per_voxel != h->prm.min_points_per_voxel ||
                                              p->eig_inflation_ratio != h->prm.eig_inflation_ratio ||
                                              p->cov_mode != h->prm.cov_mode);
-  const bool rebuild = grid_changed && h->tx.p && h->n_tgt > 0;
+  const bool rebuild = grid_changed && h->tgt.has_cloud();   // (a union keeps none)
   const int dev = h->prm.device_id;
   if (p->source_order != h->prm.source_order) h->src_sorted = false;
   h->prm = *p;
@@ -230,16 +230,14 @@ int ndt_set_params(ndt_handle* h, const ndt_params* p) {
     // re-voxelised, and the old one must not be evaluated with the new constants.  The next
     // align / eval reports NDT_ERR_NO_TARGET until a target is set again.  (A multi-grid union goes the same way: its
     // tiles were voxelised with the old parameters and ndt_multigrid_create_kdtree keeps no cloud.)
-    h->have_grid = false;
-    h->multi_active = false;
-    h->n_valid = 0;
+    target_drop(h);
     return NDT_OK;
   }
   if (rebuild) {
     // setResolution on a loaded target re-voxelises it (ref: svn_ndt_impl.hpp:162-176)
     int rc = bind_device(h);
     if (rc) return rc;
-    return build_grid(h, h->tx.p, h->ty.p, h->tz.p, h->n_tgt);
+    return build_grid(h, h->tx.p, h->ty.p, h->tz.p, h->tgt.cloud_n());
   }
   return NDT_OK;
 }
@@ -529,7 +527,7 @@ int ndt_debug_sort_pairs(ndt_handle* h, const uint32_t* keys, size_t n, int end_
   HIP_TRY(h, hipMemcpyAsync(keys_out, in_b ? h->keys2.p : h->keys.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(h, hipMemcpyAsync(vals_out, in_b ? h->vals2.p : h->vals.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(h, hipStreamSynchronize(s));
-  h->have_grid = false;  // the build's scratch was overwritten
+  target_drop(h);  // the build's scratch was overwritten
   return NDT_OK;
 }
 

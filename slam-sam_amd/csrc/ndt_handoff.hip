@@ -96,22 +96,46 @@ int neutral_bounds(ndt_handle* h) {
   return NDT_OK;
 }
 
+// ---- the target's transitions on a handle (declared in ndt_engine.h; the only callers of TargetState's) ----------------
+IndexReuse target_retire(ndt_handle* h, size_t kept_cloud_n) {
+  const IndexReuse reuse = h->tgt.retire(kept_cloud_n);
+  h->src_sorted = false;
+  h->prec_valid = false;
+  h->build_pending = false;
+  h->deferred_rc = 0;
+  h->deferred_msg.clear();
+  h->ms_settle_wait = 0;
+  if (kept_cloud_n == 0) { h->tx.release(); h->ty.release(); h->tz.release(); }   // no target points are retained
+  return reuse;
+}
+
+int target_publish(ndt_handle* h, TargetKind kind, const GridGeom& geom, const int max_b[3], size_t n_points, int n_slots,
+                   int n_valid, double ms) {
+  h->geom = geom;
+  for (int a = 0; a < 3; ++a) h->max_b[a] = max_b[a];
+  h->ms_build = ms;
+  h->tm.ms_last_build = ms;
+  h->prec_valid = false;
+  if (kind == TargetKind::UNION) {
+    h->tgt.publish_union(n_points, n_slots);
+    return NDT_OK;
+  }
+  h->tgt.publish_single(n_points, n_slots, n_valid, h->cell2leaf.cap);
+  // behind the build on its stream; the first evaluation of an align is an ordinary launch on the same stream
+  return h->record_format == NDT_RECORDS_PACKED48 ? pack_records(h, false) : NDT_OK;
+}
+
+void target_drop(ndt_handle* h) { h->tgt.drop(); }
+
 // everything of a build that does not depend on the attempt: state reset, allocations, constants
 int build_begin(ndt_handle* h, const float* x, const float* y, const float* z, size_t n, ndt_handle::BuildRun& br) {
-  h->prev_n_valid = h->have_grid && !h->multi_active ? h->n_valid : 0;   // (first_eval_behind_build's size guess)
-  h->have_grid = false;
-  h->multi_active = false;
-  h->src_sorted = false;
-  h->n_tgt = n;
-  ++h->tgt_gen;   // (the fitness index, if any, is rebuilt by the next fitness call)
-  h->n_slots = h->n_valid = 0;
   br = ndt_handle::BuildRun{};
   br.tn = tuning_snapshot();   // the one read of ndt_tuning of this build: everything below and every later step reads br.tn
   br.x = x; br.y = y; br.z = z; br.n = n;
-  br.dirty_slots = h->grid_dirty_slots;
-  br.clean_cap = h->grid_clean_cap;
-  h->grid_clean_cap = 0;  // pessimistic until this build has gone through
-  h->grid_dirty_slots = 0;
+  // a build from the engine's own arrays keeps them as the target's cloud; any other (the caller's device arrays) keeps none
+  const IndexReuse reuse = target_retire(h, x && x == h->tx.p ? n : 0);
+  br.dirty_slots = reuse.dirty_slots;
+  br.clean_cap = reuse.clean_cap;
   if (n == 0) return fail(h, NDT_ERR_NO_TARGET, "empty target cloud");
   if (n > (size_t)std::numeric_limits<int>::max() / 2) return fail(h, NDT_ERR_INVALID_ARG, "target too large");
   hipStream_t s = h->stream;
@@ -338,8 +362,6 @@ int build_collect(ndt_handle* h, ndt_handle::BuildRun& br) {
   if (bg.status != BG_OK)
     return fail(h, NDT_ERR_HIP, "voxel-grid build ended without a verdict (internal, status " + std::to_string(bg.status) +
                                     (br.bucketed ? ", two-launch build)" : ", sort-based build)"));
-  h->geom = bg.g;
-  for (int a = 0; a < 3; ++a) h->max_b[a] = bg.max_b[a];
   return 0;
 }
 
@@ -356,20 +378,8 @@ int build_complete(ndt_handle* h, ndt_handle::BuildRun& br) {
   float ms = 0;
   if (br.build_events) HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
   else ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - br.t0).count();
-  h->ms_build = ms;
-  h->tm.ms_last_build = ms;
-  h->n_slots = h->small.h[8];
-  h->grid_clean_cap = h->cell2leaf.cap;
-  h->grid_dirty_slots = h->n_slots;
-  h->n_valid = h->small.h[9];
-  h->have_grid = true;
-  h->prec_valid = false;
-  if (h->record_format == NDT_RECORDS_PACKED48) {
-    // behind the build on its stream; the first evaluation of an align is an ordinary launch on the same stream
-    int rc = pack_records(h, false);
-    if (rc) return rc;
-  }
-  return NDT_OK;
+  const BuildGeom& bg = *h->gdh.h;   // (the verdict build_collect accepted)
+  return target_publish(h, TargetKind::SINGLE, bg.g, bg.max_b, br.n, h->small.h[8], h->small.h[9], ms);
 }
 
 // The voxel-grid build proper; x/y/z are device pointers.  `defer`: a steady-state build is only ENQUEUED (the
@@ -377,9 +387,6 @@ int build_complete(ndt_handle* h, ndt_handle::BuildRun& br) {
 // call that needs the grid collects the verdict through settle().  A first build, or one that has to wait for the
 // geometry anyway, completes here either way.
 int build_grid(ndt_handle* h, const float* x, const float* y, const float* z, size_t n, bool defer) {
-  h->build_pending = false;
-  h->deferred_rc = 0;
-  h->ms_settle_wait = 0;
   int rc = build_begin(h, x, y, z, n, h->brun);
   if (rc) return rc;
   rc = build_enqueue(h, h->brun);
@@ -402,9 +409,7 @@ int build_grid(ndt_handle* h, const float* x, const float* y, const float* z, si
 // PCIe idle: 0.84 -> 0.92 ms per scan); on a stream of its own the two event hops around the last chunk's launch (pull ->
 // partition -> leaves, ~20 us each on this runtime) cost more than the 14 us of partition they hide (0.80 -> 0.84 ms).
 int build_grid_handoff(ndt_handle* h, const float* xyz, const float* x, const float* y, const float* z, size_t n, size_t stride) {
-  h->build_pending = false;
-  h->deferred_rc = 0;
-  h->ms_settle_wait = 0;
+  h->tgt.claim_cloud();   // (the arrays may be re-allocated, and the pull kernels write them)
   HIP_TRY(h, h->tx.ensure(n));
   HIP_TRY(h, h->ty.ensure(n));
   HIP_TRY(h, h->tz.ensure(n));
@@ -516,7 +521,7 @@ int report_deferred(ndt_handle* h) {
 int settle(ndt_handle* h) {
   (void)settle_build(h);
   int rs = settle_source(h);
-  if (!h->have_grid && h->deferred_rc) return report_deferred(h);
+  if (!h->tgt.have_grid() && h->deferred_rc) return report_deferred(h);
   return rs;
 }
 
@@ -545,6 +550,7 @@ int ndt_set_target(ndt_handle* h, const float* xyz, size_t n, size_t stride_byte
   settle_discard(h);
   const bool async = h->handoff_mode == NDT_HANDOFF_ASYNC;
   if (async && n > 0) return build_grid_handoff(h, xyz, nullptr, nullptr, nullptr, n, stride_bytes);
+  h->tgt.claim_cloud();
   rc = upload_soa(h, h->lane_t, h->stream, xyz, nullptr, nullptr, nullptr, n, stride_bytes, h->tx, h->ty, h->tz, !async);
   if (rc) return rc;
   return build_grid(h, h->tx.p, h->ty.p, h->tz.p, n, async);
@@ -557,6 +563,7 @@ int ndt_set_target_soa(ndt_handle* h, const float* x, const float* y, const floa
   settle_discard(h);
   const bool async = h->handoff_mode == NDT_HANDOFF_ASYNC;
   if (async && n > 0) return build_grid_handoff(h, nullptr, x, y, z, n, 0);
+  h->tgt.claim_cloud();
   rc = upload_soa(h, h->lane_t, h->stream, nullptr, x, y, z, n, 0, h->tx, h->ty, h->tz, !async);
   if (rc) return rc;
   return build_grid(h, h->tx.p, h->ty.p, h->tz.p, n, async);
@@ -566,10 +573,9 @@ int ndt_set_target_device(ndt_handle* h, const float* dx, const float* dy, const
   if (!h || ((!dx || !dy || !dz) && n)) return NDT_ERR_INVALID_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  // built straight from the caller's arrays; nothing is retained, so a later
-  // resolution change cannot re-voxelise this target
+  // built straight from the caller's arrays; nothing is retained (build_begin's retire frees the engine's own cloud), so
+  // a later resolution change cannot re-voxelise this target
   settle_discard(h);
-  h->tx.release(); h->ty.release(); h->tz.release();
   return build_grid(h, dx, dy, dz, n);
 }
 
@@ -578,7 +584,6 @@ int ndt_set_target_device_deferred(ndt_handle* h, const float* dx, const float* 
   int rc = bind_device(h);
   if (rc) return rc;
   settle_discard(h);
-  h->tx.release(); h->ty.release(); h->tz.release();
   // (a first build, or one that has to wait for the geometry anyway, completes inside the call: build_grid)
   return build_grid(h, dx, dy, dz, n, h->handoff_mode == NDT_HANDOFF_ASYNC);
 }
@@ -685,7 +690,7 @@ int ndt_get_grid_info(const ndt_handle* hc, ndt_grid_info* out) {
     int rc = settle(h);
     if (rc) return rc;
   }
-  if (!h->have_grid) return NDT_ERR_NO_TARGET;
+  if (!h->tgt.have_grid()) return NDT_ERR_NO_TARGET;
   for (int a = 0; a < 3; ++a) {
     out->min_b[a] = h->geom.min_b[a];
     out->max_b[a] = h->max_b[a];
@@ -693,9 +698,9 @@ int ndt_get_grid_info(const ndt_handle* hc, ndt_grid_info* out) {
   }
   out->leaf_size = h->geom.leaf;
   out->inverse_leaf_size = h->geom.inv_leaf;
-  out->n_leaves = h->n_valid;
+  out->n_leaves = h->tgt.n_valid();
   out->n_cells = h->geom.ncells;
-  out->n_target_points = (int64_t)h->n_tgt;
+  out->n_target_points = (int64_t)h->tgt.n_points();
   out->ms_build = h->ms_build;
   return NDT_OK;
 }
@@ -707,11 +712,11 @@ int64_t ndt_export_leaves(ndt_handle* h, ndt_leaf* out, size_t cap) {
     int rc = settle(h);
     if (rc) return rc;
   }
-  if (!h->have_grid) return NDT_ERR_NO_TARGET;
-  std::vector<LeafStats> st((size_t)h->n_slots);
-  if (h->multi_active) {
+  if (!h->tgt.have_grid()) return NDT_ERR_NO_TARGET;
+  std::vector<LeafStats> st((size_t)h->tgt.n_slots());
+  if (h->tgt.is_union()) {
     st = h->multi_stats;  // table order; `cell` is the union grid's index
-  } else if (h->n_slots) {
+  } else if (h->tgt.n_slots()) {
     hipError_t e = hipMemcpy(st.data(), h->stats.p, st.size() * sizeof(LeafStats), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(h, NDT_ERR_HIP, hipGetErrorString(e));
   }
@@ -760,7 +765,7 @@ int ndt_wait(ndt_handle* h) {
   if (rc) return rc;
   rc = lane_wait(h, h->lane_s);
   if (rc) return rc;
-  if (!h->have_grid && h->deferred_rc) return report_deferred(h);
+  if (!h->tgt.have_grid() && h->deferred_rc) return report_deferred(h);
   return NDT_OK;
 }
 

@@ -36,17 +36,20 @@ int ndt_multigrid_add_target(ndt_handle* h, int64_t id, const float* xyz, size_t
   int rc = bind_device(h);
   if (rc) return rc;
   settle_discard(h);
-  rc = upload_soa(h, h->lane_t, h->stream, xyz, nullptr, nullptr, nullptr, n, stride_bytes, h->tx, h->ty, h->tz, true);
+  // the tile is voxelised from scratch arrays of this call, like a caller's device arrays: the build retains no cloud (a
+  // later resolution change cannot silently re-voxelise one tile) ...
+  DevBuf<float> x, y, z;
+  auto done = [&](int code) { x.release(); y.release(); z.release(); return code; };
+  rc = upload_soa(h, h->lane_t, h->stream, xyz, nullptr, nullptr, nullptr, n, stride_bytes, x, y, z, true);
+  if (rc) return done(rc);
+  rc = done(build_grid(h, x.p, y.p, z.p, n));
+  // ... and the handle's single-grid table is scratch here: whatever happens, it is not a target to align to
+  target_drop(h);
   if (rc) return rc;
-  rc = build_grid(h, h->tx.p, h->ty.p, h->tz.p, n);
-  // the handle's single-grid table is scratch here: whatever happens, it is not a target to align to,
-  // and the cloud is not kept (a later resolution change cannot silently re-voxelise one tile)
-  h->have_grid = false;
-  h->tx.release(); h->ty.release(); h->tz.release();
-  if (rc) return rc;
-  std::vector<LeafStats> st((size_t)h->n_slots);
-  std::vector<VoxelRecord> rec((size_t)h->n_slots);
-  if (h->n_slots) {
+  const int n_slots = h->tgt.n_slots();
+  std::vector<LeafStats> st((size_t)n_slots);
+  std::vector<VoxelRecord> rec((size_t)n_slots);
+  if (n_slots) {
     HIP_TRY(h, hipMemcpy(st.data(), h->stats.p, st.size() * sizeof(LeafStats), hipMemcpyDeviceToHost));
     HIP_TRY(h, hipMemcpy(rec.data(), h->rec.p, rec.size() * sizeof(VoxelRecord), hipMemcpyDeviceToHost));
   }
@@ -66,8 +69,7 @@ int ndt_multigrid_add_target(ndt_handle* h, int64_t id, const float* xyz, size_t
   e.min_points = h->prm.min_points_per_voxel;
   e.cov_mode = h->prm.cov_mode;
   e.eig_ratio = h->prm.eig_inflation_ratio;
-  h->mgrids[id] = std::move(e);
-  h->multi_active = false;  // the union has to be re-assembled (createVoxelKdtree)
+  h->mgrids[id] = std::move(e);   // (the union has to be re-assembled: createVoxelKdtree)
   return NDT_OK;
 }
 
@@ -76,7 +78,7 @@ int ndt_multigrid_remove_target(ndt_handle* h, int64_t id) {
   auto it = h->mgrids.find(id);
   if (it == h->mgrids.end()) return fail(h, NDT_ERR_INVALID_ARG, "unknown multi-grid target id");
   h->mgrids.erase(it);
-  if (h->multi_active) { h->multi_active = false; h->have_grid = false; }
+  if (h->tgt.is_union()) target_drop(h);
   return NDT_OK;
 }
 
@@ -91,13 +93,10 @@ int ndt_multigrid_create_kdtree(ndt_handle* h) {
   int rc = bind_device(h);
   if (rc) return rc;
   settle_discard(h);
-  h->have_grid = false;
-  h->multi_active = false;
-  h->src_sorted = false;
   // the single target that a ndt_set_target since the last ndt_multigrid_add_target left is not the target any more, and
-  // n_tgt below counts the tiles' points, not that cloud's: kept, ndt_set_params would re-voxelise n_tgt points of it
-  // after a resolution change (a read past its end once the tiles hold more points than it does)
-  h->tx.release(); h->ty.release(); h->tz.release();
+  // its cloud goes with it: a union keeps none (it is dropped, not re-voxelised, by a resolution change).  The index
+  // grid is filled whole below, so the reuse pair is not needed.
+  (void)target_retire(h, 0);
   if (h->mgrids.empty()) return fail(h, NDT_ERR_NO_TARGET, "no multi-grid target (addTarget first)");
   const auto t_begin = std::chrono::steady_clock::now();
   long long mn[3] = {LLONG_MAX, LLONG_MAX, LLONG_MAX}, mx[3] = {LLONG_MIN, LLONG_MIN, LLONG_MIN};
@@ -120,18 +119,7 @@ int ndt_multigrid_create_kdtree(ndt_handle* h) {
   for (int a = 0; a < 3; ++a) { d[a] = mx[a] - mn[a] + 1; ncells *= d[a]; if (ncells >= 2147483647ll) break; }
   if (ncells >= 2147483647ll || total >= (size_t)2147483647)
     return fail(h, NDT_ERR_GRID_OVERFLOW, "the multi-grid targets span too many cells (index overflow)");
-  GridGeom g{};
-  g.leaf = h->prm.resolution;
-  g.inv_leaf = 1.0f / h->prm.resolution;
-  for (int a = 0; a < 3; ++a) {
-    g.min_b[a] = (int)mn[a];
-    g.div_b[a] = (int)d[a];
-    g.lo[a] = (float)g.min_b[a] * g.leaf;
-    g.hi[a] = (float)(mx[a] + 1) * g.leaf;
-  }
-  g.mul1 = g.div_b[0];
-  g.mul2 = g.div_b[0] * g.div_b[1];
-  g.ncells = (int)ncells;
+  const GridGeom g = grid_geom_from_box(h->prm.resolution, mn, mx);
   // (cell, grid, leaf) order: grids in ascending id, leaves in their own ascending cell order
   struct Ref { int cell; const ndt_handle::MultiGridEntry* e; size_t i; };
   std::vector<Ref> refs;
@@ -157,8 +145,6 @@ int ndt_multigrid_create_kdtree(ndt_handle* h) {
   hipStream_t s = h->stream;
   HIP_TRY(h, h->cell2leaf.ensure((size_t)g.ncells));
   HIP_TRY(h, hipMemsetAsync(h->cell2leaf.p, 0xFF, h->cell2leaf.cap * sizeof(int), s));
-  h->grid_clean_cap = 0;   // the next ordinary build starts from a cleared index
-  h->grid_dirty_slots = 0;
   HIP_TRY(h, h->rec.ensure(total));
   HIP_TRY(h, hipMemcpyAsync(h->rec.p, rec.data(), total * sizeof(VoxelRecord), hipMemcpyHostToDevice, s));
   // f32 centroids + the chain link of every leaf (the slot of the next leaf in the same cell, -1: none), as bits
@@ -181,16 +167,9 @@ int ndt_multigrid_create_kdtree(ndt_handle* h) {
   if (e1 == hipSuccess) e1 = hipStreamSynchronize(s);
   dc.release(); ds.release();
   HIP_TRY(h, e1);
-  h->geom = g;
-  for (int a = 0; a < 3; ++a) h->max_b[a] = (int)mx[a];
-  h->n_slots = h->n_valid = (int)total;
-  h->n_tgt = total_points;
-  h->ms_build = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  h->tm.ms_last_build = h->ms_build;
-  h->have_grid = true;
-  h->multi_active = true;
-  h->prec_valid = false;
-  return NDT_OK;
+  const int max_b[3] = {(int)mx[0], (int)mx[1], (int)mx[2]};
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  return target_publish(h, TargetKind::UNION, g, max_b, total_points, (int)total, (int)total, ms);
 }
 
 int ndt_keyframe_put(ndt_handle* h, int64_t id, const float* xyz, size_t n, size_t stride_bytes) {
@@ -251,6 +230,7 @@ int ndt_set_target_from_keyframes(ndt_handle* h, const int64_t* ids, const doubl
     total += it->second.n;
   }
   settle_discard(h);
+  h->tgt.claim_cloud();
   HIP_TRY(h, h->tx.ensure(total));
   HIP_TRY(h, h->ty.ensure(total));
   HIP_TRY(h, h->tz.ensure(total));

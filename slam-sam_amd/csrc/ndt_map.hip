@@ -706,31 +706,17 @@ int target_from_moments(ndt_handle* h, const float* box_min, const float* box_ma
                                               " cells (index overflow): select a box");
   if (total >= (size_t)lim) return fail(h, NDT_ERR_GRID_OVERFLOW, "too many leaves");
 
-  // ---- from here on the target is replaced (what build_begin does for an ordinary build) ----
+  // ---- from here on the target is replaced; no target points are retained ----
   hipStream_t s = h->stream;
-  h->deferred_rc = 0;
-  h->deferred_msg.clear();
-  h->ms_settle_wait = 0;
-  h->prev_n_valid = h->have_grid && !h->multi_active ? h->n_valid : 0;
-  h->have_grid = false;
-  h->multi_active = false;
-  h->src_sorted = false;
-  h->n_tgt = (size_t)n_points;
-  ++h->tgt_gen;
-  h->n_slots = h->n_valid = 0;
-  const int dirty_slots = h->grid_dirty_slots;
-  const size_t clean_cap = h->grid_clean_cap;
-  h->grid_clean_cap = 0;
-  h->grid_dirty_slots = 0;
-  h->tx.release(); h->ty.release(); h->tz.release();   // no target points are retained
+  const IndexReuse reuse = target_retire(h, 0);
 
   // the dense grid: -1 everywhere once per allocation, afterwards only the previous build's cells are reset
   const size_t slots_needed = std::max<size_t>(total, 1);
-  const bool steady = clean_cap != 0 && clean_cap == h->cell2leaf.cap && (size_t)ncells <= h->cell2leaf.cap &&
+  const bool steady = reuse.clean_cap != 0 && reuse.clean_cap == h->cell2leaf.cap && (size_t)ncells <= h->cell2leaf.cap &&
                       slots_needed <= h->stats.cap;
   if (steady) {
-    if (dirty_slots > 0) {
-      launch_reset_cells(h->stats.p, dirty_slots, h->cell2leaf.p, h->cell2leaf.cap, s);
+    if (reuse.dirty_slots > 0) {
+      launch_reset_cells(h->stats.p, reuse.dirty_slots, h->cell2leaf.p, h->cell2leaf.cap, s);
       HIP_TRY(h, hipGetLastError());
     }
   } else {
@@ -742,18 +728,7 @@ int target_from_moments(ndt_handle* h, const float* box_min, const float* box_ma
   HIP_TRY(h, h->rec.ensure(slots_needed));
   HIP_TRY(h, h->cent.ensure(slots_needed * 4));
 
-  GridGeom g{};
-  g.leaf = h->prm.resolution;
-  g.inv_leaf = 1.0f / h->prm.resolution;
-  for (int a = 0; a < 3; ++a) {
-    g.min_b[a] = mn[a];
-    g.div_b[a] = mx[a] - mn[a] + 1;
-    g.lo[a] = (float)mn[a] * g.leaf;
-    g.hi[a] = (float)(mx[a] + 1) * g.leaf;
-  }
-  g.mul1 = g.div_b[0];
-  g.mul2 = g.div_b[0] * g.div_b[1];
-  g.ncells = (int)ncells;
+  const GridGeom g = grid_geom_from_box(h->prm.resolution, mn, mx);
 
   int n_valid = 0;
   if (total > 0) {
@@ -772,23 +747,8 @@ int target_from_moments(ndt_handle* h, const float* box_min, const float* box_ma
     HIP_TRY(h, hipMemsetAsync(h->rec.p, 0, sizeof(VoxelRecord), s));
     HIP_TRY(h, hipStreamSynchronize(s));
   }
-  // ---- publish (what build_collect / build_complete do) ----
-  h->geom = g;
-  for (int a = 0; a < 3; ++a) h->max_b[a] = mx[a];
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->ms_build = ms;
-  h->tm.ms_last_build = ms;
-  h->n_slots = (int)total;
-  h->n_valid = n_valid;
-  h->grid_clean_cap = h->cell2leaf.cap;
-  h->grid_dirty_slots = h->n_slots;
-  h->have_grid = true;
-  h->prec_valid = false;
-  if (h->record_format == NDT_RECORDS_PACKED48) {
-    rc = pack_records(h, false);
-    if (rc) return rc;
-  }
-  return NDT_OK;
+  return target_publish(h, TargetKind::SINGLE, g, mx, (size_t)n_points, (int)total, n_valid, ms);
 }
 
 }  // namespace
@@ -988,6 +948,7 @@ int ndt_set_target_from_map(ndt_handle* h, int min_points) {
   rc = map_export_count(h, sel_all(min_points), false, &total);
   if (rc) return rc;
   if (total == 0) return fail(h, NDT_ERR_NO_TARGET, "the map holds no voxel with that many points");
+  h->tgt.claim_cloud();
   HIP_TRY(h, h->tx.ensure(total));
   HIP_TRY(h, h->ty.ensure(total));
   HIP_TRY(h, h->tz.ensure(total));

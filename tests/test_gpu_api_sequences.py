@@ -23,6 +23,10 @@ identical.  Host arrays handed to a call are overwritten (every byte 0xFF: NaN f
    below (4 000-point two-plane pair, 16 x 256 lidar pair and subsamples).
 3. Random sequences over the full vocabulary, three committed seeds (+ NDT_FUZZ_EXTRA_SEEDS); `sequence(seed)` is a pure
    function that needs no GPU, its coverage condition is checked by tests/test_api_sequences_cpu.py.
+4. The transition table of the target itself, which two engines of the same code cannot see when both are wrong alike:
+   every producer of a target, then every call that invalidates one, against a small Python restatement of the state
+   (kind, cloud kept, reported points) -- after each step the statuses of grid, align, leaves and fitness and what the
+   grid info reports are asserted, on both engines.  (csrc/ndt_target_state.* is that state; DESIGN.md has the table.)
 
 Public methods of NormalDistributionsTransform that take the handle and are NOT in the vocabulary, and why
 (tests/test_api_sequences_cpu.py checks that every public method is either called by the rig or named here):
@@ -816,3 +820,149 @@ def test_random_full_api_sequences_async_equals_sync(rig, seed):
         # not a sequence of refusals (a refusal compares one status code; more than half of the calls must have done their
         # work), and failing builds were left pending on the asynchronous engine
         assert 2 * n_served > len(history) and deferred >= 3
+
+
+# ---- 4. the transition table ------------------------------------------------------------------------------------------
+NO_TARGET, UNSUPPORTED = -4, -9
+# producer (op, k) -> does the engine keep the cloud the grid was built from
+TABLE_PRODUCERS = [("target", 1, True), ("target_xyzi", 2, True), ("target_soa", 3, True), ("target_dev", 0, False),
+                   ("target_dev_deferred", 3, False), ("setInputTargetFromKeyframes", 1, True), ("setInputTargetFromMap", 0, True),
+                   ("setInputTargetFromMapMoments", 1, False), ("addTarget", 2, False), ("createVoxelKdtree", 0, False)]
+TABLE_INVALIDATORS = [("resolution", 0), ("setMinPointPerVoxel", 1), ("removeTarget", 0), ("addTarget", 2), ("target_bad", 0)]
+
+
+class TargetModel:
+    """What the engine's target is after a call, restated: kind NONE | SINGLE | UNION, whether the cloud is kept, the
+    points it reports; the tiles stored for a union and the two grid parameters the invalidators change."""
+
+    def __init__(self, rig, e):
+        self.rig, self.kind, self.cloud, self.points = rig, "NONE", False, 0
+        self.tiles = {11: len(rig.tiles[0]), 12: len(rig.tiles[1])}
+        self.res, self.min_pts = 1.0, 6
+        # what the map-made targets stand for: every voxel's centroid / every point of the map's voxels (the whole map is
+        # selected: what setInputTarget would build from every point ever added)
+        self.map_voxels = e.mapInfo()["n_voxels"]
+        self.map_moment_points = int(e.mapExport(with_counts=True)[1].sum())
+
+    def apply(self, op, k):
+        rig = self.rig
+        single = lambda cloud, points: ("SINGLE", cloud, points)   # noqa: E731
+        if op in ("target", "target_xyzi", "target_soa"):
+            self.kind, self.cloud, self.points = single(True, len(rig.clouds[k % 4]))
+        elif op in ("target_dev", "target_dev_deferred"):
+            self.kind, self.cloud, self.points = single(False, len(rig.clouds[k % 4]))
+        elif op == "setInputTargetFromKeyframes":
+            assert k == 1
+            self.kind, self.cloud, self.points = single(True, len(rig.kf_clouds[0]) + len(rig.kf_clouds[1]))
+        elif op == "setInputTargetFromMap":
+            assert k == 0
+            self.kind, self.cloud, self.points = single(True, self.map_voxels)
+        elif op == "setInputTargetFromMapMoments":
+            assert k == 1
+            self.kind, self.cloud, self.points = single(False, self.map_moment_points)
+        elif op == "addTarget":
+            self.tiles[11 + k % 3] = len(rig.tiles[k % 3])
+            self.kind, self.cloud, self.points = "NONE", False, 0
+        elif op == "createVoxelKdtree":
+            self.kind, self.cloud, self.points = "UNION", False, sum(self.tiles.values())
+        elif op in ("resolution", "setMinPointPerVoxel"):
+            if op == "resolution":
+                self.res = 1.0 if k % 2 else 1.5
+            else:
+                self.min_pts = 4 if k % 2 else 6
+            if not (self.kind == "SINGLE" and self.cloud):       # a kept cloud is re-voxelised, anything else is dropped
+                self.kind, self.points = "NONE", 0
+        elif op == "removeTarget":
+            del self.tiles[11 + k % 3]
+            if self.kind == "UNION":
+                self.kind, self.points = "NONE", 0
+        elif op == "target_bad":
+            self.kind, self.cloud, self.points = "NONE", False, 0
+        else:
+            raise AssertionError(op)
+
+
+def status(r):
+    return r[1] if refused(r) else 0
+
+
+def table_reset(rig, e):
+    """NONE, no cloud, two tiles stored at the parameters in force, every grid parameter where prepare() left it"""
+    e.setParams(resolution=1.0, min_points_per_voxel=6, max_iterations=2)   # (the statuses are what is asserted: a short align)
+    rig.call(e, "removeTarget", 2)
+    assert rig.call(e, "addTarget", 0) == rig.call(e, "addTarget", 1) == 2
+
+
+def table_check(rig, e, m, what):
+    """the public binding against the model; returns (grid, leaves) as observations"""
+    grid, leaves = rig.call(e, "grid", 0), rig.call(e, "leaves", 0)
+    seen = dict(grid=status(grid), leaves=status(leaves), align=status(rig.call(e, "align", 0)), fitness=status(rig.call(e, "fitness", 0)))
+    if m.kind == "NONE":
+        assert seen == dict(grid=NO_TARGET, leaves=NO_TARGET, align=NO_TARGET, fitness=NO_TARGET), (what, e.tag, seen)
+        return grid, leaves
+    g = e.getGridInfo()
+    # (align needs one valid voxel, as the C-ABI documents NDT_ERR_NO_TARGET: the map's centroids, one point a voxel at
+    # its own leaf, make a grid without one)
+    want = dict(grid=0, leaves=0, align=0 if g["n_leaves"] > 0 else NO_TARGET,
+                fitness=0 if m.kind == "SINGLE" and m.cloud else UNSUPPORTED)
+    assert seen == want, (what, e.tag, m.kind, m.cloud, seen, want)
+    assert g["n_target_points"] == m.points and g["leaf_size"] == np.float32(m.res), (what, e.tag, g, m.points, m.res)
+    return grid, leaves
+
+
+def test_target_transition_table(rig):
+    """Every producer, then every invalidator, on both engines: the state each leaves (the tables of the issue that
+    introduced csrc/ndt_target_state.*, derived from the code before it and passing there unchanged).  A resolution or
+    min-points change on a SINGLE with its cloud rebuilds it: grid info and leaves equal, bit for bit, what a third engine
+    that never saw the old parameters builds from the same producer at the new ones."""
+    t0 = time.perf_counter()
+    pkg = rig.pkg
+    ref = rig.engine(pkg.HANDOFF_SYNC)
+    ref.tag = "reference"
+    try:
+        for e in rig.eng + [ref]:
+            rig.prepare(e)
+        fresh = {}
+
+        def reference(p_op, p_k, i_op, i_k):
+            key = (p_op, p_k, i_op, i_k)
+            if key not in fresh:
+                table_reset(rig, ref)
+                assert rig.call(ref, i_op, i_k) is not None           # the new parameter first, on a handle without a target
+                assert rig.call(ref, p_op, p_k) == "ok"
+                fresh[key] = (rig.call(ref, "grid", 0), rig.call(ref, "leaves", 0))
+                assert not refused(fresh[key][0]) and not refused(fresh[key][1])
+            return fresh[key]
+
+        n = 0
+        for e in rig.eng:
+            for p_op, p_k, keeps in TABLE_PRODUCERS:
+                for i_op, i_k in TABLE_INVALIDATORS:
+                    what = "%s(%d) then %s(%d)" % (p_op, p_k, i_op, i_k)
+                    table_reset(rig, e)
+                    m = TargetModel(rig, e)
+                    table_check(rig, e, m, "reset before " + what)
+                    r = rig.call(e, p_op, p_k)
+                    assert not refused(r), (what, e.tag, r)
+                    m.apply(p_op, p_k)
+                    assert m.cloud == keeps
+                    before = table_check(rig, e, m, what + ": after the producer")
+                    was = m.kind
+                    r = rig.call(e, i_op, i_k)
+                    if i_op == "target_bad":
+                        # refused at once, or -- the asynchronous engine in steady state, which a union's whole-index fill
+                        # ends -- left pending and reported by the next consumer
+                        assert r == ("error", NO_TARGET) or (r == "ok" and e is rig.eng[1]), (what, e.tag, r)
+                    else:
+                        assert not refused(r) or i_op == "setMinPointPerVoxel", (what, e.tag, r)
+                    m.apply(i_op, i_k)
+                    after = table_check(rig, e, m, what)
+                    if i_op in ("resolution", "setMinPointPerVoxel") and m.kind == "SINGLE":
+                        assert after == reference(p_op, p_k, i_op, i_k), "%s on the %s engine: the rebuilt grid is not the fresh one" % (what, e.tag)
+                    if i_op == "removeTarget" and was != "UNION":
+                        assert after == before, "%s on the %s engine: removeTarget touched a target that is no union" % (what, e.tag)
+                    n += 1
+        assert n == 2 * len(TABLE_PRODUCERS) * len(TABLE_INVALIDATORS)
+    finally:
+        ref.close()
+    print("transition table: %d producer-invalidator pairs in %.2f s" % (n, time.perf_counter() - t0))
