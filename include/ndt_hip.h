@@ -838,6 +838,51 @@ int ndt_map_carve(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes
 int ndt_map_carve_keyframe(ndt_handle* h, int64_t id, const float origin[3], const double pose16_colmajor[16],
                            const ndt_map_carve_params* params, ndt_map_carve_result* out_or_null);
 
+/* Re-pose the map: after a pose-graph correction or a loop closure the frame a map was accumulated in moves.  The map
+ * has no points to move, but it keeps exactly the sums that move exactly: with p' = R p + t, sum p' and sum p' p'^T are
+ * linear in a voxel's count, its three first and its six second moments.  ndt_map_transform moves every voxel of the map
+ * by a pose, ndt_map_import_state_posed / _device merge records that were accumulated in another frame (a submap) under
+ * the pose that takes that frame to the map's.  Both rest on ONE per-record rule, every operation rounded as written
+ * (IEEE f64 unless said otherwise, no contraction):
+ *    R_ab = P[a + 4 b], t_a = P[12 + a]: the upper 3 x 4 of the column-major pose AS GIVEN -- there is no orthonormality
+ *    check (a scale or a reflection is applied as it stands), and the bottom row is not read beyond the finiteness check,
+ *    as with ndt_map_add.  n = (double)count.  lin(a, v) = (R_a0 v0 + R_a1 v1) + R_a2 v2.
+ *    float sums  s'_a = (float)(lin(a, (double)s) + n t_a): the one f32 rounding; the intensity sum and the count stay.
+ *    moments     u_a = lin(a, m1), m1'_a = u_a + n t_a; with M the symmetric 3 x 3 of {xx, xy, xz, yy, yz, zz}:
+ *                A_ab = (R_a0 M_0b + R_a1 M_1b) + R_a2 M_2b, B_ab = (A_a0 R_b0 + A_a1 R_b1) + A_a2 R_b2 for a <= b,
+ *                m2'_ab = ((B_ab + u_a t_b) + t_a u_b) + (n t_a) t_b.
+ *    voxel       the one ndt_map_add would give a point at the moved FLOAT centroid: c_a = s'_a / (float)count (f32
+ *                division), ijk'_a = floor(c_a * inv_leaf) in f32 -- in maps with and without moments alike (the float
+ *                centroid is what ndt_map_export shows).  The record's own ijk is not read.
+ *    merge       the moved records are merged by ndt_map_import_state's rule: per destination voxel its records in input
+ *                order, every field old + record, one rounding.
+ * What is exact is the affine map of the sums of one record (up to the roundings written above).  What is not: a moved
+ * voxel is assigned as a whole to the voxel of its mean, so points that the new lattice would separate stay together and
+ * voxels whose means meet are merged (NDT-OM's map fusion does the same); a moved Gaussian is not split.
+ *  - ndt_map_transform: the records are the map's occupied voxels in ascending (k, j, i) order (ndt_map_export_state's
+ *    order, so the result does not depend on the table's slot layout); they are merged into a fresh, empty table of the
+ *    smallest power-of-two capacity >= 2 x (voxels before) that is not below the capacity ndt_map_reset gave the map, and
+ *    the old table is freed only once the new one stands.  Afterwards n_points, n_points_dropped, n_adds and n_grows are
+ *    unchanged, n_voxels <= its value before (*n_voxels_after_or_null receives it), min_ijk / max_ijk are the tight box
+ *    of the new voxels, the moments and intensity settings are kept.  An empty map is NDT_OK and untouched.  The call
+ *    gives up the map's founding property: afterwards ndt_map_export is no longer pcl::VoxelGrid of any concatenation of
+ *    clouds.  The identity pose is NOT special-cased: a voxel whose float centroid has rounded out of its own voxel moves
+ *    to the voxel the centroid is in.  No record leaves the device.
+ *  - ndt_map_import_state_posed / _device: ndt_map_import_state / _device with every record passed through the rule
+ *    first (arguments, n = 0, counters, growth and the caller's arrays as there; ijk must not be NULL but is not read).
+ * Refusals, each of the whole call with the map exactly as it was, decided before anything is written:
+ * NDT_ERR_INVALID_ARG for no map, a NULL pose, a non-finite value in the pose and ndt_map_import_state's own checks
+ * (leaf, moments9 on a map with moments, count < 1); NDT_ERR_GRID_OVERFLOW when a moved centroid is not finite or
+ * leaves |ijk| < 2^20 (the message names how many); NDT_ERR_ALLOC when an allocation fails.  The target (also one made
+ * from this map before), source, align state, iteration history, evaluation counters and the keyframe archive are left
+ * untouched.  Complete when they return. */
+int ndt_map_transform(ndt_handle* h, const double pose16_colmajor[16], int64_t* n_voxels_after_or_null);
+int ndt_map_import_state_posed(ndt_handle* h, float leaf, const int32_t* ijk, const int32_t* count, const float* sums4,
+                               const double* moments9, size_t n, const double pose16_colmajor[16]);
+int ndt_map_import_state_posed_device(ndt_handle* h, float leaf, const int32_t* ijk, const int32_t* count,
+                                      const float* sums4, const double* moments9, size_t n,
+                                      const double pose16_colmajor[16]);
+
 /* setRegularizationPose (ref: run/pipeline_ligo_tc.cpp:531) */
 int ndt_set_regularization_pose(ndt_handle* h, const float pose_colmajor[16]);
 int ndt_clear_regularization_pose(ndt_handle* h);

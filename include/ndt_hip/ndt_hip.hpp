@@ -156,6 +156,11 @@ inline std::vector<double> pack_poses(const Poses& poses) {
   for (size_t k = 0; k < poses.size(); ++k) to_colmajor(poses[k], 4, 4, &p[16 * k]);
   return p;
 }
+// anything with matrix() (gtsam::Pose3) as 16 column-major doubles
+template <class Pose>
+inline auto pose_colmajor(const Pose& p, double a[16]) -> decltype((void)p.matrix()) {
+  to_colmajor(p.matrix(), 4, 4, a);
+}
 }  // namespace detail
 
 inline Matrix4f identity4f() {
@@ -820,6 +825,53 @@ class NormalDistributionsTransform
     }
     status_ = ndt_map_import_state(h_, s.leaf, s.ijk.data(), s.counts.data(), s.sums.data(),
                                    s.moments.empty() ? nullptr : s.moments.data(), n);
+  }
+
+  // ---- the map under a changed pose (ndt_map_transform, ndt_map_import_state_posed): every voxel's sums are moved as
+  // the sums of its points would be and re-binned by the moved float centroid.  Pose: 16 column-major doubles, Matrix4d, or gtsam::Pose3
+  // (anything with matrix()).  mapTransform returns the number of voxels afterwards. ----
+  int64_t mapTransform(const double* pose_colmajor) {
+    int64_t after = 0;
+    status_ = h_ ? ndt_map_transform(h_, pose_colmajor, &after) : NDT_ERR_NO_DEVICE;
+    return status_ == NDT_OK ? after : 0;
+  }
+  int64_t mapTransform(const Matrix4d& pose) {
+    double a[16];
+    detail::to_colmajor(pose, 4, 4, a);
+    return mapTransform(static_cast<const double*>(a));
+  }
+  template <class Pose>
+  auto mapTransform(const Pose& pose) -> decltype((void)pose.matrix(), int64_t()) {
+    double a[16];
+    detail::pose_colmajor(pose, a);
+    return mapTransform(static_cast<const double*>(a));
+  }
+  // a state accumulated in another frame (a submap), merged under the pose that takes that frame to the map's
+  void mapImportStatePosed(const MapState& s, const double* pose_colmajor) {
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return; }
+    const size_t n = s.counts.size();
+    if (s.ijk.size() != 3 * n || s.sums.size() != 4 * n || (!s.moments.empty() && s.moments.size() != 9 * n)) {
+      status_ = NDT_ERR_INVALID_ARG;
+      return;
+    }
+    status_ = ndt_map_import_state_posed(h_, s.leaf, s.ijk.data(), s.counts.data(), s.sums.data(),
+                                         s.moments.empty() ? nullptr : s.moments.data(), n, pose_colmajor);
+  }
+  void mapImportStatePosed(const MapState& s, const Matrix4d& pose) {
+    double a[16];
+    detail::to_colmajor(pose, 4, 4, a);
+    mapImportStatePosed(s, static_cast<const double*>(a));
+  }
+  template <class Pose>
+  auto mapImportStatePosed(const MapState& s, const Pose& pose) -> decltype((void)pose.matrix()) {
+    double a[16];
+    detail::pose_colmajor(pose, a);
+    mapImportStatePosed(s, static_cast<const double*>(a));
+  }
+  void mapImportStatePosedDevice(float leaf, const int32_t* d_ijk, const int32_t* d_count, const float* d_sums4,
+                                 const double* d_moments9, size_t n, const double* pose_colmajor) {
+    status_ = h_ ? ndt_map_import_state_posed_device(h_, leaf, d_ijk, d_count, d_sums4, d_moments9, n, pose_colmajor)
+                 : NDT_ERR_NO_DEVICE;
   }
 
   // ---- device-resident keyframe archive (ref: run/pipeline_ligo_tc.cpp:519-529, run/pipeline.cpp:554-557,784) ----

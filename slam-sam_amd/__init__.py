@@ -311,6 +311,7 @@ ABI_SYMBOLS = [
     "ndt_unproject_packet_frame_device", "ndt_unproject_packet_frame", "ndt_keyframe_put_from_packets",
     "ndt_map_crop", "ndt_map_export_state", "ndt_map_export_state_device", "ndt_map_import_state", "ndt_map_import_state_device",
     "ndt_map_carve_default_params", "ndt_map_carve_device", "ndt_map_carve", "ndt_map_carve_keyframe",
+    "ndt_map_transform", "ndt_map_import_state_posed", "ndt_map_import_state_posed_device",
 ]
 
 _lib = None
@@ -436,6 +437,9 @@ def lib():
         L.ndt_map_export_state_device.argtypes = [vp, fp, fp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ndt_map_import_state.argtypes = [vp, C.c_float, vp, vp, vp, vp, C.c_size_t]
         L.ndt_map_import_state_device.argtypes = [vp, C.c_float, vp, vp, vp, vp, C.c_size_t]
+        L.ndt_map_transform.argtypes = [vp, dp, C.POINTER(C.c_int64)]
+        L.ndt_map_import_state_posed.argtypes = [vp, C.c_float, vp, vp, vp, vp, C.c_size_t, dp]
+        L.ndt_map_import_state_posed_device.argtypes = [vp, C.c_float, vp, vp, vp, vp, C.c_size_t, dp]
         L.ndt_map_carve_default_params.restype = None
         L.ndt_map_carve_default_params.argtypes = [C.POINTER(MapCarveParams)]
         L.ndt_map_carve_device.argtypes = [vp, vp, vp, vp, C.c_size_t, fp, dp, C.POINTER(MapCarveParams),
@@ -1308,9 +1312,10 @@ class NormalDistributionsTransform:
                                                       d_ijk, d_count, d_sums, d_moments, int(cap), C.byref(m)))
         return int(m.value)
 
-    def mapImportState(self, state=None, leaf=None, ijk=None, count=None, sums=None, moments=None):
-        """Merge voxel records into the map: a dict as mapExportState returns it, or leaf and the arrays themselves
-        (ijk [n, 3], count [n], sums [n, 4], moments [n, 9] or None)."""
+    @staticmethod
+    def _state_arrays(state, leaf, ijk, count, sums, moments):
+        """(leaf, ijk int32 [n, 3], count int32 [n], sums float32 [n, 4], moments float64 [n, 9] or None, n) of a state
+        given as a dict or as its arrays; ValueError on a missing or ragged one"""
         if state is not None:
             leaf, ijk, count, sums, moments = state["leaf"], state["ijk"], state["count"], state["sums"], state.get("moments")
         if leaf is None or ijk is None or count is None or sums is None:
@@ -1325,7 +1330,13 @@ class NormalDistributionsTransform:
             moments = np.ascontiguousarray(moments, dtype=np.float64)
             if moments.shape != (n, 9):
                 raise ValueError("moments must be n x 9")
-        self._check(lib().ndt_map_import_state(self._h, float(leaf), ijk.ctypes.data if n else None, count.ctypes.data if n else None,
+        return float(leaf), ijk, count, sums, moments, n
+
+    def mapImportState(self, state=None, leaf=None, ijk=None, count=None, sums=None, moments=None):
+        """Merge voxel records into the map: a dict as mapExportState returns it, or leaf and the arrays themselves
+        (ijk [n, 3], count [n], sums [n, 4], moments [n, 9] or None)."""
+        leaf, ijk, count, sums, moments, n = self._state_arrays(state, leaf, ijk, count, sums, moments)
+        self._check(lib().ndt_map_import_state(self._h, leaf, ijk.ctypes.data if n else None, count.ctypes.data if n else None,
                                                sums.ctypes.data if n else None,
                                                moments.ctypes.data if moments is not None and n else None, n))
 
@@ -1802,6 +1813,44 @@ class NormalDistributionsTransform:
                     ms_last_build=t.ms_last_build, n_eval_launches=t.n_eval_launches,
                     ms_eval_kernel_total=t.ms_eval_kernel_total,
                     ms_reduce_kernel_total=t.ms_reduce_kernel_total, n_timed_evals=t.n_timed_evals)
+
+
+# --- the map under a changed pose: every voxel's sums moved as the sums of its points would be (ndt_map_transform,
+# ndt_map_import_state_posed).  Functions on an engine, not methods of it: `ndt` is a
+# NormalDistributionsTransform that holds a map. ---
+def _finite_pose16(pose):
+    """a 4x4 double pose as 16 column-major doubles; ValueError on another shape or a non-finite value"""
+    if pose is None:
+        raise ValueError("a pose is needed")
+    p = np.asarray(pose, dtype=np.float64)
+    if p.shape != (4, 4) or not np.isfinite(p).all():
+        raise ValueError("pose must be 4 x 4 and finite")
+    return np.ascontiguousarray(p.T).ravel()
+
+
+def mapTransform(ndt, pose):
+    """Move the whole map of `ndt` by the 4x4 double `pose` (its upper 3 x 4 as given): every voxel's sums are moved
+    exactly and re-binned by the moved float centroid, voxels that meet are merged in ascending (k, j, i) order.
+    Returns the number of voxels afterwards."""
+    p = _finite_pose16(pose)
+    after = C.c_int64(0)
+    ndt._check(lib().ndt_map_transform(ndt._h, _dp(p), C.byref(after)))
+    return int(after.value)
+
+
+def mapImportStatePosed(ndt, state=None, pose=None, leaf=None, ijk=None, count=None, sums=None, moments=None):
+    """ndt.mapImportState of records accumulated in another frame: `pose` (4x4 double) takes that frame to the map's."""
+    leaf, ijk, count, sums, moments, n = ndt._state_arrays(state, leaf, ijk, count, sums, moments)
+    p = _finite_pose16(pose)
+    ndt._check(lib().ndt_map_import_state_posed(ndt._h, leaf, ijk.ctypes.data if n else None,
+                                                count.ctypes.data if n else None, sums.ctypes.data if n else None,
+                                                moments.ctypes.data if moments is not None and n else None, n, _dp(p)))
+
+
+def mapImportStatePosedDevice(ndt, leaf, d_ijk, d_count, d_sums, d_moments, n, pose):
+    """As mapImportStatePosed, from device arrays (integer addresses; d_moments None for a map without moments)."""
+    p = _finite_pose16(pose)
+    ndt._check(lib().ndt_map_import_state_posed_device(ndt._h, float(leaf), d_ijk, d_count, d_sums, d_moments, int(n), _dp(p)))
 
 
 def comm_unique_id():

@@ -8,6 +8,7 @@
 //                      the host side of every compaction (the device side: ndt_compact_device.h)
 //   ndt_map.hip        the sparse voxel map accumulated scan by scan (ndt_map_*), its kernels included
 //   ndt_map_state.hip  the map's crop, full-state export / import and merge (k_mapstate_* kernels)
+//   ndt_map_repose.hip the map moved by a pose, and records merged under one (k_maprepose_* kernels)
 //   ndt_map_carve.hip  free-space carving of the map: voxels that a scan's rays pass through go (k_mapcarve_* kernels)
 //   ndt_deskew.hip     motion compensation of a scan along a pose trajectory + the acquisition filter (its kernels included)
 //   ndt_unproject.hip  a lidar range image -> points through the scan model's tables, fused with that filter and deskew
@@ -277,7 +278,7 @@ struct VoxelMap {
   DevBuf<float> px, py, pz;            // the batch moved by its pose
   DevBuf<float> ux, uy, uz, ui;        // a host batch on the device
   DevBuf<int> stats;                   // per add: {finite, out of range, min ijk, max ijk, probe failures}
-  DevBuf<unsigned long long> nvox;     // occupied slots (cumulative)
+  DevBuf<unsigned long long> nvox;     // occupied slots (cumulative); [1]: those a re-pose creates in its fresh table
   PinBuf<int> stats_h;                 // [0..15] read-back, [16..31] the neutral words
   PinBuf<unsigned long long> nvox_h;
   PinBuf<BuildGeom> plan_h;            // sort plans: [0] add, [1] / [2] export (low / high word)
@@ -626,19 +627,37 @@ int map_box_floor(float v, float inv_leaf);
 bool pose_finite(const double p[16]);
 bool finite3(const float v[3]);
 int map_alloc_table(ndt_handle* h, int64_t cap, bool with_moments, MapTable* t);
-// The map's table is replaced by a fresh one of new_cap slots that `launch` fills from the old one (the caller's one
-// kernel launch on the engine's stream; awaited here).  kept < 0: growth, every voxel moves.  kept >= 0: a selective move
-// that keeps `kept` voxels -- tsel is reset in front of the launch and read back behind it, the device's voxel counter,
-// n_voxels and (kept > 0) the ijk box follow.  On any error the map is as it was and `what` heads the text.
-int map_replace_table(ndt_handle* h, int64_t new_cap, const char* what, const std::function<void(const MapTable&)>& launch,
+// The map's table is replaced by a fresh one of new_cap slots that `launch` fills from the old one (the caller's launches
+// on the engine's stream, awaited here; a launch that returns an error has reported it).  kept == -1: growth, every voxel
+// moves.  kept >= 0: a selective move that keeps `kept` voxels -- tsel is reset in front of the launch and read back
+// behind it, the device's voxel counter, n_voxels and (kept > 0) the ijk box follow.  kept == MAP_KEPT_COUNTED: the launch
+// counts the voxels it creates in nvox[1] (zeroed in front of it); the device's voxel counter and n_voxels follow, the ijk
+// box is the caller's.  On any error the map is as it was and `what` heads the text.
+constexpr int64_t MAP_KEPT_COUNTED = -2;
+int map_replace_table(ndt_handle* h, int64_t new_cap, const char* what, const std::function<int(const MapTable&)>& launch,
                       int64_t kept);
-int map_grow_table(ndt_handle* h, int64_t new_cap);
+// what fills the fresh table in place of growth's move (map_grow_table)
+struct MapRefill {
+  const char* what;
+  std::function<int(const MapTable&)> launch;
+};
+int map_grow_table(ndt_handle* h, int64_t new_cap, const MapRefill* refill = nullptr);
 int map_sort_scratch(ndt_handle* h, size_t n);
 int map_refresh_voxel_count(ndt_handle* h);
-int map_group_batch(ndt_handle* h, size_t n, const uint32_t** keys_sorted, const uint32_t** vals_sorted);
+int map_group_batch(ndt_handle* h, size_t n, const MapTable& t, unsigned long long* d_nvox, const uint32_t** keys_sorted,
+                    const uint32_t** vals_sorted);
 int map_export_count(ndt_handle* h, const MapSel& sel, bool box, size_t* total);
 int map_export_order(ndt_handle* h, const MapSel& sel, bool box_sel, size_t total, const int mn[3], const int mx[3],
                      const uint32_t** order_out, const uint32_t** slots_out);
+// ndt_map_state.hip's host side as ndt_map_repose.hip uses it: the state export into device arrays (awaited), the checks
+// of an import once the map is known, the import behind its key pass (one host wait, refusals, growth, counters, merge;
+// awaited) and the merge itself into a given table (enqueued)
+int map_export_state(ndt_handle* h, const float* box_min, const float* box_max, int32_t* d_ijk, int32_t* d_count, float* d_sums,
+                     double* d_mom, size_t cap, size_t* total_out);
+int map_import_checks(ndt_handle* h, float leaf, const double* moments9, size_t n, bool* go);
+int map_import_tail(ndt_handle* h, const int32_t* d_count, const float* d_sums, const double* d_mom, size_t n);
+int map_merge_records(ndt_handle* h, const MapTable& t, unsigned long long* d_nvox, const int32_t* d_count, const float* d_sums,
+                      const double* d_mom, size_t n);
 void fill_pose_consts(const double p[6], const float T[16], PoseConsts* pc);
 unsigned long long process_item_salt();
 EvalConsts make_eval_consts(const ndt_handle* h, bool need_h);

@@ -14,8 +14,8 @@
 //            voxel's points to; ndt_set_target_from_map_moments selects the voxels of a box with the export's count / scan /
 //            compaction / key sort under a predicate (ONE host wait: selection count, ijk box and point total decide the
 //            refusals and size the grid) and hands each to the ordinary build's finalize_leaf (launch_map_finalize).
-// Crop, state export and state import are in ndt_map_state.hip, the carve in ndt_map_carve.hip; the constants and device
-// helpers the three files use (key, probes, box reduction, a slot's move) are in ndt_map_device.h, and the host functions
+// Crop, state export and state import are in ndt_map_state.hip, the carve in ndt_map_carve.hip, the re-pose in
+// ndt_map_repose.hip; the constants and device helpers these files use (key, probes, box reduction, a slot's move) are in ndt_map_device.h, and the host functions
 // of this file that the others call -- map_replace_table, the one way a table is replaced, among them -- are declared in
 // ndt_engine.h.
 #include "ndt_engine.h"
@@ -406,23 +406,33 @@ int map_refresh_voxel_count(ndt_handle* h) {
   return NDT_OK;
 }
 
-int map_replace_table(ndt_handle* h, int64_t new_cap, const char* what, const std::function<void(const MapTable&)>& launch,
+int map_replace_table(ndt_handle* h, int64_t new_cap, const char* what, const std::function<int(const MapTable&)>& launch,
                       int64_t kept) {
   VoxelMap& m = *h->map;
   hipStream_t s = h->stream;
+  const bool counted = kept == MAP_KEPT_COUNTED;   // the launch counts the voxels it creates in nvox[1]
   const bool selective = kept >= 0;
   MapTable fresh;
   int rc = map_alloc_table(h, new_cap, m.moments, &fresh);
   if (rc) return rc;   // the map is as it was
   hipError_t e = hipSuccess;
   if (selective) e = hipMemcpyAsync(m.tsel.p, m.tsel_h.h + TS_WORDS, TS_WORDS * sizeof(int), hipMemcpyHostToDevice, s);
+  if (counted) e = hipMemsetAsync(m.nvox.p + 1, 0, sizeof(unsigned long long), s);
   if (e == hipSuccess) {
-    launch(fresh);
+    rc = launch(fresh);
+    if (rc) {   // (the launch has reported it; what it enqueued may still write to the fresh table)
+      (void)hipStreamSynchronize(s);
+      (void)hipGetLastError();
+      map_free_table(fresh);
+      return rc;
+    }
     e = hipGetLastError();
   }
   if (e == hipSuccess && selective) e = hipMemcpyAsync(m.tsel_h.h, m.tsel.p, TS_WORDS * sizeof(int), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && counted) e = hipMemcpyAsync(m.nvox_h.h + 1, m.nvox.p + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);   // (a replacement is rare: the old table is freed behind its last reader)
-  if (e == hipSuccess && selective) {   // the next add reads the device's counter
+  if (e == hipSuccess && counted) kept = (int64_t)m.nvox_h.h[1];
+  if (e == hipSuccess && (selective || counted)) {   // the next add reads the device's counter
     m.nvox_h.h[0] = (unsigned long long)kept;
     e = hipMemcpy(m.nvox.p, m.nvox_h.h, sizeof(unsigned long long), hipMemcpyHostToDevice);
   }
@@ -433,36 +443,43 @@ int map_replace_table(ndt_handle* h, int64_t new_cap, const char* what, const st
   }
   map_free_table(m.tab);
   m.tab = fresh;
-  if (selective) {
+  if (selective || counted) {
     m.n_voxels = kept;
     m.nvox_stale = false;
-    if (kept > 0)
+    if (selective && kept > 0)
       for (int a = 0; a < 3; ++a) { m.mn[a] = m.tsel_h.h[TS_MIN + a]; m.mx[a] = m.tsel_h.h[TS_MAX + a]; }
   }
   return NDT_OK;
 }
 
-int map_grow_table(ndt_handle* h, int64_t new_cap) {
+// Growth (refill == nullptr): every voxel moves as it is into a table of new_cap slots, and n_grows counts it.  With a
+// refill the fresh table is filled by the caller's own launches instead, which count the voxels they create (the re-pose
+// of ndt_map_repose.hip: the voxels do not move as they are); that is no growth, and the ijk box is the caller's to set.
+int map_grow_table(ndt_handle* h, int64_t new_cap, const MapRefill* refill) {
   VoxelMap& m = *h->map;
-  const int rc = map_replace_table(h, new_cap, "voxel map growth: ", [&](const MapTable& fresh) {
+  const std::function<int(const MapTable&)> rehash = [&](const MapTable& fresh) {
     hipLaunchKernelGGL(k_map_rehash, dim3((unsigned)((m.tab.capacity + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0,
                        h->stream, m.tab, fresh, m.stats.p);
-  }, -1);
-  if (rc == NDT_OK) ++m.n_grows;
+    return (int)NDT_OK;
+  };
+  const int rc = map_replace_table(h, new_cap, refill ? refill->what : "voxel map growth: ", refill ? refill->launch : rehash,
+                                   refill ? MAP_KEPT_COUNTED : -1);
+  if (rc == NDT_OK && !refill) ++m.n_grows;
   return rc;
 }
 
-// The batch's n keys (m.pkey; MAP_EMPTY: skipped) get their slots (k_map_insert: the device's voxel counter goes up by
-// the voxels created), then the stable sort of (slot, index) and the run search: run r of *keys_sorted / *vals_sorted is one
+// The batch's n keys (m.pkey; MAP_EMPTY: skipped) get their slots in table `t` (k_map_insert: *d_nvox -- for the map's own
+// table the device's voxel counter -- goes up by the voxels created), then the stable sort of (slot, index) and the run search: run r of *keys_sorted / *vals_sorted is one
 // voxel's entries in input order (h->nleaf, h->leaf_start, h->leaf_cnt).  After map_sort_scratch(n); enqueued, not awaited.
-int map_group_batch(ndt_handle* h, size_t n, const uint32_t** keys_sorted, const uint32_t** vals_sorted) {
+int map_group_batch(ndt_handle* h, size_t n, const MapTable& t, unsigned long long* d_nvox, const uint32_t** keys_sorted,
+                    const uint32_t** vals_sorted) {
   VoxelMap& m = *h->map;
   hipStream_t s = h->stream;
   const unsigned blocks = (unsigned)((n + MAP_THREADS - 1) / MAP_THREADS);
-  hipLaunchKernelGGL(k_map_insert, dim3(blocks), dim3(MAP_THREADS), 0, s, m.pkey.p, (int)n, m.tab.keys,
-                     (unsigned long long)(m.tab.capacity - 1), h->keys.p, m.nvox.p, m.stats.p);
+  hipLaunchKernelGGL(k_map_insert, dim3(blocks), dim3(MAP_THREADS), 0, s, m.pkey.p, (int)n, t.keys,
+                     (unsigned long long)(t.capacity - 1), h->keys.p, d_nvox, m.stats.p);
   int passes = 0;
-  int rc = map_put_plan(h, 0, map_bits_for(m.tab.capacity), (int)m.tab.capacity, &passes);   // (the sentinel `capacity` sorts behind every slot)
+  int rc = map_put_plan(h, 0, map_bits_for(t.capacity), (int)t.capacity, &passes);   // (the sentinel `capacity` sorts behind every slot)
   if (rc) return rc;
   launch_sort_first_count(h->keys.p, n, h->gd.p, h->sort_tmp.p, s);
   bool in_b = false;
@@ -528,7 +545,7 @@ int map_add_device(ndt_handle* h, const float* dx, const float* dy, const float*
   m.n_points += n_finite;
   m.nvox_stale = true;
   const uint32_t *keys_sorted = nullptr, *vals_sorted = nullptr;
-  rc = map_group_batch(h, n, &keys_sorted, &vals_sorted);
+  rc = map_group_batch(h, n, m.tab, m.nvox.p, &keys_sorted, &vals_sorted);
   if (rc) return rc;
   if (m.moments)
     hipLaunchKernelGGL(k_map_accumulate<true>, dim3(blocks), dim3(MAP_THREADS), 0, s, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p,
@@ -783,7 +800,7 @@ int ndt_map_reset(ndt_handle* h, float leaf, int with_intensity, int64_t initial
   if (rc) return undo(rc);
   m.reset_capacity = cap;
   hipError_t e = m.stats.ensure(MS_WORDS);
-  if (e == hipSuccess) e = m.nvox.ensure(1);
+  if (e == hipSuccess) e = m.nvox.ensure(2);   // [1]: the voxels a re-pose creates in its fresh table
   if (e == hipSuccess) e = m.stats_h.ensure(2 * MS_WORDS);
   if (e == hipSuccess) e = m.nvox_h.ensure(2);
   if (e == hipSuccess) e = m.plan_h.ensure(3);

@@ -246,6 +246,7 @@ int map_carve_device(ndt_handle* h, const float* dx, const float* dy, const floa
   rc = map_replace_table(h, new_cap, "voxel map carve: ", [&](const MapTable& fresh) {
     hipLaunchKernelGGL(k_mapcarve_move, dim3(slot_blocks), dim3(MAP_THREADS), 0, s, m.tab, m.cmarks.p, prm.min_misses,
                        prm.protect_min_count, fresh, m.stats.p, m.tsel.p);
+    return NDT_OK;
   }, kept);
   if (rc) return rc;
   m.n_points -= pts_removed;

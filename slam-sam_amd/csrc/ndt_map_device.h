@@ -1,8 +1,9 @@
 // ndt_map_device.h -- what the voxel map's kernels share across translation units (ndt_map.hip, ndt_map_state.hip,
-// ndt_map_carve.hip; ndt_target.hip for the key alone): the table's constants, the words of VoxelMap::stats / tsel, the
+// ndt_map_carve.hip, ndt_map_repose.hip; ndt_target.hip for the key alone): the table's constants, the words of VoxelMap::stats / tsel, the
 // 63-bit key and its inverse (map_key / map_ijk: the only place that knows the layout), the hash, the probe that claims
 // a slot and the one that only looks, the box predicate of a selection, the wave reductions, the block's reduction of an
-// ijk box (map_box_waves / map_box_commit around the kernel's barrier) and one slot's move into a fresh table
+// ijk box (map_box_waves / map_box_commit around the kernel's barrier), the statistics of a batch of records
+// (map_record_stats) and one slot's move into a fresh table
 // (map_move_slot: what growth, crop and carve do with a voxel that stays).  Device code only.
 #pragma once
 
@@ -18,6 +19,8 @@ constexpr int MAP_BIAS = 1 << 20;                      // |ijk| < 2^20 per axis:
 constexpr float MAP_LIMIT = 1048576.0f;
 // words of VoxelMap::stats
 enum { MS_FINITE = 0, MS_OOR = 1, MS_MIN = 2, MS_MAX = 5, MS_PROBE_FAIL = 8, MS_WORDS = 16 };
+// ... and those a batch of voxel RECORDS adds (the state import's key pass, the re-pose's record pass)
+enum { MS_BAD_COUNT = 9, MS_POINTS = 10 /* 64 bits */ };
 // words of VoxelMap::tsel: ijk box, number and point total (64 bits) of the occupied voxels a selection's box holds,
 // and the leaves its finalize launch accepted
 enum { TS_MIN = 0, TS_MAX = 3, TS_VOXELS = 6, TS_POINTS = 8, TS_VALID = 10, TS_WORDS = 16 };
@@ -130,6 +133,36 @@ __device__ __forceinline__ void map_box_commit(const int (&box)[MAP_WAVES][6], i
     for (int w = 1; w < MAP_WAVES; ++w) v = t < 3 ? min(v, box[w][t]) : max(v, box[w][t]);
     if (t < 3) { if (v != INT_MAX) atomicMin(bmin + t, v); }
     else if (v != INT_MIN) atomicMax(bmax + (t - 3), v);
+  }
+}
+
+// The statistics of a batch of voxel records, as the host reads them under the import's one wait: how many records are
+// out of the coordinate range (oor) and how many have count < 1 (bad), the ijk box (mn / mx) and the 64-bit point total
+// (pts) of the valid ones -- every thread of the block brings its record's (a thread without one: 0, 0, 0 and the empty
+// box); one integer atomic per word and block.  Holds the block's barrier: every thread calls it, once.
+__device__ __forceinline__ void map_record_stats(int oor, int bad, unsigned long long pts, const int (&mn)[3], const int (&mx)[3],
+                                                 int* __restrict__ stats) {
+  __shared__ int red[MAP_WAVES][2], box[MAP_WAVES][6];
+  __shared__ unsigned long long red_pts[MAP_WAVES];
+  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+  oor = wave_sum(oor);
+  bad = wave_sum(bad);
+  pts = wave_sum_u64(pts);
+  if (lane == 0) { red[wave][0] = oor; red[wave][1] = bad; red_pts[wave] = pts; }
+  map_box_waves(mn, mx, box);
+  __syncthreads();
+  map_box_commit(box, stats + MS_MIN, stats + MS_MAX);
+  if (threadIdx.x == 6 || threadIdx.x == 7) {
+    const int t = (int)threadIdx.x - 6;
+    int v = 0;
+#pragma unroll
+    for (int w = 0; w < MAP_WAVES; ++w) v += red[w][t];
+    if (v) atomicAdd(stats + (t == 0 ? MS_OOR : MS_BAD_COUNT), v);
+  } else if (threadIdx.x == 8) {
+    unsigned long long v = 0;
+#pragma unroll
+    for (int w = 0; w < MAP_WAVES; ++w) v += red_pts[w];
+    if (v) atomicAdd(reinterpret_cast<unsigned long long*>(stats + MS_POINTS), v);
   }
 }
 

@@ -11,6 +11,8 @@
 // A fresh slot holds +0 in every field and 0 + s == s bit for bit for every s but -0.0, which a map never holds (its
 // sums start at +0, and +0 + x is -0 for no x; x + y is -0 only for x = y = -0): a voxel new to the map receives its
 // record exactly, and export -> import into an empty map reproduces the table's content.
+// The import behind its key pass (map_import_tail) and the merge into a given table (map_merge_records) also serve the
+// re-pose of ndt_map_repose.hip, whose record pass stands in for k_mapstate_keys; both share map_record_stats.
 // The rules of ndt_map.hip hold: wave64, integer atomics only (one per word and block), no kernel waits for another
 // block, every probe loop is bounded by the capacity.
 #include "ndt_engine.h"
@@ -19,9 +21,6 @@
 namespace ndt {
 
 namespace {
-
-// words of VoxelMap::stats the import's key pass adds to those of the add's (MS_OOR, MS_MIN, MS_MAX as there)
-enum { MS_BAD_COUNT = 9, MS_POINTS = 10 /* 64 bits */ };
 
 // Crop: every occupied slot of the old table whose voxel is inside the box (remove_inside == 0) or outside it
 // (remove_inside != 0) moves to the new table (map_move_slot); the survivors' ijk box goes to tsel (TS_MIN / TS_MAX).
@@ -75,10 +74,7 @@ __global__ void __launch_bounds__(MAP_THREADS) k_mapstate_gather(const uint32_t*
 __global__ void __launch_bounds__(MAP_THREADS) k_mapstate_keys(const int32_t* __restrict__ ijk, const int32_t* __restrict__ count,
                                                               int n, unsigned long long* __restrict__ pkey,
                                                               int* __restrict__ stats) {
-  __shared__ int red[MAP_WAVES][2], box[MAP_WAVES][6];
-  __shared__ unsigned long long red_pts[MAP_WAVES];
   const int i = (int)(blockIdx.x * MAP_THREADS + threadIdx.x);
-  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
   int oor = 0, bad = 0;
   int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
   unsigned long long pts = 0;
@@ -96,25 +92,7 @@ __global__ void __launch_bounds__(MAP_THREADS) k_mapstate_keys(const int32_t* __
     }
     pkey[i] = key;
   }
-  oor = wave_sum(oor);
-  bad = wave_sum(bad);
-  pts = wave_sum_u64(pts);
-  if (lane == 0) { red[wave][0] = oor; red[wave][1] = bad; red_pts[wave] = pts; }
-  map_box_waves(mn, mx, box);
-  __syncthreads();
-  map_box_commit(box, stats + MS_MIN, stats + MS_MAX);
-  if (threadIdx.x == 6 || threadIdx.x == 7) {
-    const int t = (int)threadIdx.x - 6;
-    int v = 0;
-#pragma unroll
-    for (int w = 0; w < MAP_WAVES; ++w) v += red[w][t];
-    if (v) atomicAdd(stats + (t == 0 ? MS_OOR : MS_BAD_COUNT), v);
-  } else if (threadIdx.x == 8) {
-    unsigned long long v = 0;
-#pragma unroll
-    for (int w = 0; w < MAP_WAVES; ++w) v += red_pts[w];
-    if (v) atomicAdd(reinterpret_cast<unsigned long long*>(stats + MS_POINTS), v);
-  }
+  map_record_stats(oor, bad, pts, mn, mx, stats);
 }
 
 // Run r of the slot-sorted batch = records vals_sorted[start .. start + cnt) of one voxel, in input order (the radix sort
@@ -192,11 +170,14 @@ int map_crop(ndt_handle* h, const float* box_min, const float* box_max, int remo
   rc = map_replace_table(h, new_cap, "voxel map crop: ", [&](const MapTable& fresh) {
     hipLaunchKernelGGL(k_mapstate_crop, dim3((unsigned)((m.tab.capacity + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0,
                        h->stream, m.tab, sel, remove_inside, fresh, m.stats.p, m.tsel.p);
+    return NDT_OK;
   }, kept);
   if (rc) return rc;
   m.n_points = remove_inside ? m.n_points - (int64_t)pts_inside : (int64_t)pts_inside;
   return NDT_OK;
 }
+
+}  // namespace
 
 // the selection's records, the first min(total, cap) of them, into device arrays (any may be null); *n_out = total
 int map_export_state(ndt_handle* h, const float* box_min, const float* box_max, int32_t* d_ijk, int32_t* d_count, float* d_sums,
@@ -222,18 +203,34 @@ int map_export_state(ndt_handle* h, const float* box_min, const float* box_max, 
   return NDT_OK;
 }
 
-// n records in device memory (d_mom may be null in a map without moments), behind the argument checks
-int map_import_state(ndt_handle* h, const int32_t* d_ijk, const int32_t* d_count, const float* d_sums, const double* d_mom, size_t n) {
+// The n records' keys (m.pkey), grouped by their slot in table `t` (map_group_batch; *d_nvox goes up by the voxels they
+// create there), continue the sums `t` holds: per voxel its records in input order, old + record.field.  After
+// map_sort_scratch(n); enqueued, not awaited.
+int map_merge_records(ndt_handle* h, const MapTable& t, unsigned long long* d_nvox, const int32_t* d_count, const float* d_sums,
+                      const double* d_mom, size_t n) {
   VoxelMap& m = *h->map;
   hipStream_t s = h->stream;
-  // every allocation of the import except the table's growth, before anything is written
-  HIP_TRY(h, m.pkey.ensure(n));
-  int rc = map_sort_scratch(h, n);
-  if (rc) return rc;
   const unsigned blocks = (unsigned)((n + MAP_THREADS - 1) / MAP_THREADS);
-  HIP_TRY(h, hipMemcpyAsync(m.stats.p, m.stats_h.h + MS_WORDS, MS_WORDS * sizeof(int), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_mapstate_keys, dim3(blocks), dim3(MAP_THREADS), 0, s, d_ijk, d_count, (int)n, m.pkey.p, m.stats.p);
+  const uint32_t *keys_sorted = nullptr, *vals_sorted = nullptr;
+  const int rc = map_group_batch(h, n, t, d_nvox, &keys_sorted, &vals_sorted);
+  if (rc) return rc;
+  if (m.moments)
+    hipLaunchKernelGGL(k_mapstate_accumulate<true>, dim3(blocks), dim3(MAP_THREADS), 0, s, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p,
+                       keys_sorted, vals_sorted, d_count, d_sums, d_mom, m.with_intensity, t.sums, t.cnt, t.mom);
+  else
+    hipLaunchKernelGGL(k_mapstate_accumulate<false>, dim3(blocks), dim3(MAP_THREADS), 0, s, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p,
+                       keys_sorted, vals_sorted, d_count, d_sums, static_cast<const double*>(nullptr), m.with_intensity,
+                       t.sums, t.cnt, static_cast<double*>(nullptr));
   HIP_TRY(h, hipGetLastError());
+  return NDT_OK;
+}
+
+// The import behind its key pass (k_mapstate_keys, or the re-pose's record pass: m.pkey and m.stats are enqueued on the
+// stream): the one host wait, the refusals, the growth, the counters and the merge of the n records; awaited.
+int map_import_tail(ndt_handle* h, const int32_t* d_count, const float* d_sums, const double* d_mom, size_t n) {
+  VoxelMap& m = *h->map;
+  hipStream_t s = h->stream;
+  int rc = NDT_OK;
   HIP_TRY(h, hipMemcpyAsync(m.stats_h.h, m.stats.p, MS_WORDS * sizeof(int), hipMemcpyDeviceToHost, s));
   HIP_TRY(h, hipMemcpyAsync(m.nvox_h.h, m.nvox.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   HIP_TRY(h, hipStreamSynchronize(s));   // the import's one host wait: refusals and growth decision
@@ -260,25 +257,34 @@ int map_import_state(ndt_handle* h, const int32_t* d_ijk, const int32_t* d_count
   }
   m.n_points += (int64_t)pts;
   m.nvox_stale = true;
-  const uint32_t *keys_sorted = nullptr, *vals_sorted = nullptr;
-  rc = map_group_batch(h, n, &keys_sorted, &vals_sorted);
+  rc = map_merge_records(h, m.tab, m.nvox.p, d_count, d_sums, d_mom, n);
   if (rc) return rc;
-  if (m.moments)
-    hipLaunchKernelGGL(k_mapstate_accumulate<true>, dim3(blocks), dim3(MAP_THREADS), 0, s, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p,
-                       keys_sorted, vals_sorted, d_count, d_sums, d_mom, m.with_intensity, m.tab.sums, m.tab.cnt,
-                       m.tab.mom);
-  else
-    hipLaunchKernelGGL(k_mapstate_accumulate<false>, dim3(blocks), dim3(MAP_THREADS), 0, s, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p,
-                       keys_sorted, vals_sorted, d_count, d_sums, static_cast<const double*>(nullptr), m.with_intensity,
-                       m.tab.sums, m.tab.cnt, static_cast<double*>(nullptr));
-  HIP_TRY(h, hipGetLastError());
   // the caller's arrays (and the engine's scratch) are free again when the call returns
   HIP_TRY(h, hipStreamSynchronize(s));
   return NDT_OK;
 }
 
-// what both import forms check once the map is known; *go: there is something to import
-int import_checks(ndt_handle* h, float leaf, const double* moments9, size_t n, bool* go) {
+namespace {
+
+// n records in device memory (d_mom may be null in a map without moments), behind the argument checks
+int map_import_state(ndt_handle* h, const int32_t* d_ijk, const int32_t* d_count, const float* d_sums, const double* d_mom, size_t n) {
+  VoxelMap& m = *h->map;
+  hipStream_t s = h->stream;
+  // every allocation of the import except the table's growth, before anything is written
+  HIP_TRY(h, m.pkey.ensure(n));
+  const int rc = map_sort_scratch(h, n);
+  if (rc) return rc;
+  const unsigned blocks = (unsigned)((n + MAP_THREADS - 1) / MAP_THREADS);
+  HIP_TRY(h, hipMemcpyAsync(m.stats.p, m.stats_h.h + MS_WORDS, MS_WORDS * sizeof(int), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_mapstate_keys, dim3(blocks), dim3(MAP_THREADS), 0, s, d_ijk, d_count, (int)n, m.pkey.p, m.stats.p);
+  HIP_TRY(h, hipGetLastError());
+  return map_import_tail(h, d_count, d_sums, d_mom, n);
+}
+
+}  // namespace
+
+// what every import form checks once the map is known; *go: there is something to import
+int map_import_checks(ndt_handle* h, float leaf, const double* moments9, size_t n, bool* go) {
   *go = false;
   if (!h->map) return no_map(h);
   VoxelMap& m = *h->map;
@@ -289,6 +295,8 @@ int import_checks(ndt_handle* h, float leaf, const double* moments9, size_t n, b
   *go = n > 0;
   return NDT_OK;
 }
+
+namespace {
 
 int export_checks(ndt_handle* h, const float* box_min, const float* box_max, const double* moments9) {
   if (!h->map) return no_map(h);
@@ -370,7 +378,7 @@ int ndt_map_import_state_device(ndt_handle* h, float leaf, const int32_t* ijk, c
   int rc = bind_device(h);
   if (rc) return rc;
   bool go = false;
-  rc = import_checks(h, leaf, moments9, n, &go);
+  rc = map_import_checks(h, leaf, moments9, n, &go);
   if (rc || !go) return rc;
   settle_discard_keep_grid(h);
   return map_import_state(h, ijk, count, sums4, h->map->moments ? moments9 : nullptr, n);
@@ -382,7 +390,7 @@ int ndt_map_import_state(ndt_handle* h, float leaf, const int32_t* ijk, const in
   int rc = bind_device(h);
   if (rc) return rc;
   bool go = false;
-  rc = import_checks(h, leaf, moments9, n, &go);
+  rc = map_import_checks(h, leaf, moments9, n, &go);
   if (rc || !go) return rc;
   VoxelMap& m = *h->map;
   settle_discard_keep_grid(h);
