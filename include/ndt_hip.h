@@ -883,6 +883,58 @@ int ndt_map_import_state_posed_device(ndt_handle* h, float leaf, const int32_t* 
                                       const float* sums4, const double* moments9, size_t n,
                                       const double pose16_colmajor[16]);
 
+/* Distribution-to-distribution NDT (D2D; Stoyanov et al. 2012): register a submap's voxels -- Gaussians, not points --
+ * to the target's.  It estimates the pose that ndt_map_import_state_posed / ndt_map_transform take, from the two maps'
+ * own f64 moments; the chain export -> pose -> posed import runs without a record leaving the device.
+ * THE DISTRIBUTION SOURCE is separate from the point source (ndt_set_source*): neither disturbs the other.
+ *  - ndt_set_source_distributions / _device take `count` (n) and `moments9` (n x 9: sums of x, y, z, xx, xy, xz, yy, yz,
+ *    zz) exactly as ndt_map_export_state / _device write them (host / device memory).  Record r becomes a source Gaussian
+ *    when it passes the target build's own leaf rule under the handle's parameters: count >= max(3, min_points_per_voxel),
+ *    then the build's finalize step (cov_mode's covariance formula, eigenvalue floor eig_inflation_ratio, the inverse
+ *    checks); its mean and its REGULARISED covariance are that leaf's mean and cov as ndt_export_leaves shows them for a
+ *    target built from the same moments.  Rejected records are dropped and counted; accepted ones keep input order.
+ *    n == 0 clears the source (pointers may be NULL).  NDT_ERR_INVALID_ARG for a NULL pointer with n > 0, a count < 1 or
+ *    a non-finite moment: the previous source stays.  The records are kept: when ndt_set_params has changed the leaf rule
+ *    the Gaussians are re-derived from them by the next call that uses them.  Complete when they return.
+ *  - ndt_source_distributions_info: records handed over and Gaussians accepted (0, 0 without a source).
+ *  - ndt_export_source_distributions: the accepted Gaussians -- mean3 (m x 3), cov6 (m x 6: xx, xy, xz, yy, yz, zz), count
+ *    and the index of the record each came from (any output may be NULL); returns m, or < 0 (cap < m: INVALID_ARG).
+ * THE EVALUATION ndt_eval_derivatives_d2d: K poses p = [x, y, z, roll, pitch, yaw] -> K x NDT_EVAL_WORDS words in the
+ * layout of ndt_eval_derivatives (ndt_unpack_eval applies; ridge / regularisation as there).  Per pose, IEEE f64:
+ *    rotation    R = Rx(roll) Ry(pitch) Rz(yaw) and its first and second angle derivatives, built on the host from the
+ *                sin / cos of poses6 (not from an f32 matrix, no small-angle snap) and handed to the kernel.
+ *    moved mean  m_a = ((R_a0 mu_0 + R_a1 mu_1) + R_a2 mu_2) + t_a, rounded as written, no contraction.
+ *    neighbours  the target leaves ndt_score_points gives a point at ((float)m_x, (float)m_y, (float)m_z): DIRECT1 or
+ *                DIRECT7 by the handle's search method, in the same pair order.
+ *    pair (i, j) mu = m - mu_j, C = R Sigma_i R^T + Sigma_j (Sigma_j: the leaf's cov of ndt_export_leaves; of both Sigmas
+ *                the triangle xx, xy, xz, yy, yz, zz is what is read), B = C^-1 (by cofactors), q = mu^T B mu, e = exp(-d2 q / 2), score = -d1 e; d1, d2: ndt_gauss_constants of the handle's
+ *                resolution and outlier ratio.  A pair whose e is not finite or outside [0, 1] contributes nothing and
+ *                is not counted.
+ *    gradient    j_a = dm/dp_a, Z_a = (dR/dp_a) Sigma_i R^T + its transpose (0 for translations),
+ *                q_a = 2 mu^T B j_a - mu^T B Z_a B mu,  g_a = (d1 d2 / 2) e q_a.
+ *    Hessian     H_ab = d2m/dp_a dp_b, Z_ab = (d2R) Sigma_i R^T + (d_a R) Sigma_i (d_b R)^T + transpose,
+ *                q_ab = 2 j_b^T B j_a - 2 mu^T B Z_b B j_a + 2 mu^T B H_ab - 2 j_b^T B Z_a B mu + 2 mu^T B Z_b B Z_a B mu
+ *                       - mu^T B Z_ab B mu,   Hess_ab = (d1 d2 / 2) e (q_ab - (d2 / 2) q_a q_b):
+ *                the exact derivatives of the score (always the full Hessian: hessian_mode is not read).
+ *    the rest    nvtl_sum: the sum over Gaussians of their best pair score; n_points_with_neighbors: Gaussians with a
+ *                counted pair; n_pairs: counted pairs.  compute_hessian == 0: the Hessian words are zero, score and
+ *                gradient are the bits of the Hessian call.
+ * Sums are made in a fixed order without float atomics: a call gives the same bits every time, and a pose in a batch of
+ * K the bits it gives alone.  NDT_ERR_UNSUPPORTED for NDT_KDTREE / NDT_DIRECT26, a multi-grid union target and a reducer
+ * other than NDT_REDUCE_NONE; NDT_ERR_NO_TARGET without a target, NDT_ERR_NO_SOURCE without an accepted Gaussian.
+ * THE ALIGN ndt_align_d2d: ndt_newton_align's loop (the ndt_align product path) over that evaluation with the handle's
+ * parameters and regularisation pose, n_source_total = the accepted Gaussians; `out` as ndt_align fills it (ms_device 0).
+ * Without a target, a distribution source or an accepted Gaussian the guess comes back with converged = 0 and the call
+ * returns the code above.  The handle's align state, iteration history, pre-launch state and point source are left alone,
+ * as by ndt_align_batch: an ndt_align afterwards gives the bits it gave before. */
+int ndt_set_source_distributions(ndt_handle* h, const int32_t* count, const double* moments9, size_t n);
+int ndt_set_source_distributions_device(ndt_handle* h, const int32_t* count, const double* moments9, size_t n);
+int ndt_source_distributions_info(ndt_handle* h, int64_t* n_records, int64_t* n_accepted);
+int64_t ndt_export_source_distributions(ndt_handle* h, double* mean3, double* cov6, int32_t* count, int32_t* record_index,
+                                        size_t cap);
+int ndt_eval_derivatives_d2d(ndt_handle* h, const double* poses6, int K, int compute_hessian, double* out);
+int ndt_align_d2d(ndt_handle* h, const float guess_colmajor[16], ndt_result* out);
+
 /* setRegularizationPose (ref: run/pipeline_ligo_tc.cpp:531) */
 int ndt_set_regularization_pose(ndt_handle* h, const float pose_colmajor[16]);
 int ndt_clear_regularization_pose(ndt_handle* h);

@@ -874,6 +874,80 @@ class NormalDistributionsTransform
                  : NDT_ERR_NO_DEVICE;
   }
 
+  // ---- distribution-to-distribution NDT (ndt_set_source_distributions, ndt_eval_derivatives_d2d, ndt_align_d2d): a
+  // submap's voxels -- the counts and moments of a MapState -- registered to the target's leaves.  The distribution
+  // source is separate from the point source; the adapter's own result (getFinalTransformation, getResult) stays that
+  // of the last align().  The pose found is what mapImportStatePosed takes. ----
+  void setInputSourceDistributions(const std::vector<int32_t>& counts, const std::vector<double>& moments) {
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return; }
+    const size_t n = counts.size();
+    if (moments.size() != 9 * n) { status_ = NDT_ERR_INVALID_ARG; return; }
+    status_ = ndt_set_source_distributions(h_, n ? counts.data() : nullptr, n ? moments.data() : nullptr, n);
+  }
+  void setInputSourceDistributions(const MapState& s) { setInputSourceDistributions(s.counts, s.moments); }
+  void setInputSourceDistributionsDevice(const int32_t* d_count, const double* d_moments9, size_t n) {
+    status_ = h_ ? ndt_set_source_distributions_device(h_, d_count, d_moments9, n) : NDT_ERR_NO_DEVICE;
+  }
+  // the accepted source Gaussians in input order
+  struct SourceDistributions {
+    std::vector<double> mean;            // 3 per Gaussian
+    std::vector<double> cov;             // 6 per Gaussian: xx, xy, xz, yy, yz, zz
+    std::vector<int32_t> counts, record_index;
+    int64_t n_records = 0;               // records handed over, the rejected ones included
+    size_t size() const { return counts.size(); }
+  };
+  SourceDistributions getSourceDistributions() {
+    SourceDistributions out;
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return out; }
+    int64_t n_acc = 0;
+    status_ = ndt_source_distributions_info(h_, &out.n_records, &n_acc);
+    if (status_ != NDT_OK || n_acc <= 0) return out;
+    const size_t m = (size_t)n_acc;
+    out.mean.resize(3 * m); out.cov.resize(6 * m); out.counts.resize(m); out.record_index.resize(m);
+    const int64_t got = ndt_export_source_distributions(h_, out.mean.data(), out.cov.data(), out.counts.data(),
+                                                        out.record_index.data(), m);
+    if (got != n_acc) { status_ = got < 0 ? (int)got : NDT_ERR_INVALID_ARG; out = SourceDistributions(); }
+    return out;
+  }
+  // score, gradient and Hessian of the D2D objective at p = [x, y, z, roll, pitch, yaw] (one launch)
+  template <class Vec6, class Mat6>
+  double computeDerivativesD2D(Vec6& score_gradient, Mat6& hessian, const Vec6& p, bool compute_hessian = true) {
+    double pose[6], words[NDT_EVAL_WORDS], score = 0.0, g[6], H[36];
+    for (int i = 0; i < 6; ++i) { pose[i] = p[i]; score_gradient[i] = 0.0; }
+    for (int r = 0; r < 6; ++r)
+      for (int c = 0; c < 6; ++c) hessian(r, c) = 0.0;
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return 0.0; }
+    status_ = ndt_eval_derivatives_d2d(h_, pose, 1, compute_hessian ? 1 : 0, words);
+    if (status_ != NDT_OK) return 0.0;
+    ndt_unpack_eval(words, &score, g, H);
+    for (int i = 0; i < 6; ++i) score_gradient[i] = g[i];
+    if (compute_hessian)
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) hessian(r, c) = H[6 * r + c];
+    return score;
+  }
+  // the result as alignMany gives one: `pose` takes the submap's frame to the target's; on an error it holds the guess.
+  // converged_or_null receives ndt_result::converged.
+  NdtResult alignDistributions(const Matrix4f& guess, bool* converged_or_null = nullptr) {
+    float g[16];
+    detail::to_colmajor(guess, 4, 4, g);
+    ndt_result raw;
+    std::memset(&raw, 0, sizeof(raw));
+    status_ = h_ ? ndt_align_d2d(h_, g, &raw) : NDT_ERR_NO_DEVICE;
+    if (status_ != NDT_OK) {
+      std::memset(&raw, 0, sizeof(raw));
+      std::memcpy(raw.final_transformation, g, sizeof(g));
+    }
+    if (converged_or_null) *converged_or_null = raw.converged != 0;
+    NdtResult out;
+    out.pose = detail::from_colmajor<Matrix4f>(raw.final_transformation, 4, 4);
+    out.transform_probability = (float)raw.transform_probability;
+    out.nearest_voxel_transformation_likelihood = (float)raw.nearest_voxel_transformation_likelihood;
+    out.iteration_num = raw.iterations;
+    out.hessian = detail::from_rowmajor<Matrix6d>(raw.hessian, 6, 6);
+    return out;
+  }
+
   // ---- device-resident keyframe archive (ref: run/pipeline_ligo_tc.cpp:519-529, run/pipeline.cpp:554-557,784) ----
   // not part of pclomp: the body-frame scans stay in HBM, the sliding-window target is assembled
   // there from ids + poses (column-major 4x4 doubles, e.g. gtsam::Pose3::matrix().data())

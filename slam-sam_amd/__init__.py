@@ -312,6 +312,8 @@ ABI_SYMBOLS = [
     "ndt_map_crop", "ndt_map_export_state", "ndt_map_export_state_device", "ndt_map_import_state", "ndt_map_import_state_device",
     "ndt_map_carve_default_params", "ndt_map_carve_device", "ndt_map_carve", "ndt_map_carve_keyframe",
     "ndt_map_transform", "ndt_map_import_state_posed", "ndt_map_import_state_posed_device",
+    "ndt_set_source_distributions", "ndt_set_source_distributions_device", "ndt_source_distributions_info",
+    "ndt_export_source_distributions", "ndt_eval_derivatives_d2d", "ndt_align_d2d",
 ]
 
 _lib = None
@@ -440,6 +442,13 @@ def lib():
         L.ndt_map_transform.argtypes = [vp, dp, C.POINTER(C.c_int64)]
         L.ndt_map_import_state_posed.argtypes = [vp, C.c_float, vp, vp, vp, vp, C.c_size_t, dp]
         L.ndt_map_import_state_posed_device.argtypes = [vp, C.c_float, vp, vp, vp, vp, C.c_size_t, dp]
+        L.ndt_set_source_distributions.argtypes = [vp, vp, vp, C.c_size_t]
+        L.ndt_set_source_distributions_device.argtypes = [vp, vp, vp, C.c_size_t]
+        L.ndt_source_distributions_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.ndt_export_source_distributions.argtypes = [vp, dp, dp, vp, vp, C.c_size_t]
+        L.ndt_export_source_distributions.restype = C.c_int64
+        L.ndt_eval_derivatives_d2d.argtypes = [vp, dp, C.c_int, C.c_int, dp]
+        L.ndt_align_d2d.argtypes = [vp, fp, C.POINTER(Result)]
         L.ndt_map_carve_default_params.restype = None
         L.ndt_map_carve_default_params.argtypes = [C.POINTER(MapCarveParams)]
         L.ndt_map_carve_device.argtypes = [vp, vp, vp, vp, C.c_size_t, fp, dp, C.POINTER(MapCarveParams),
@@ -1851,6 +1860,79 @@ def mapImportStatePosedDevice(ndt, leaf, d_ijk, d_count, d_sums, d_moments, n, p
     """As mapImportStatePosed, from device arrays (integer addresses; d_moments None for a map without moments)."""
     p = _finite_pose16(pose)
     ndt._check(lib().ndt_map_import_state_posed_device(ndt._h, float(leaf), d_ijk, d_count, d_sums, d_moments, int(n), _dp(p)))
+
+
+# --- distribution-to-distribution NDT: a submap's voxels (mapExportState's records) registered to the target's leaves
+# (ndt_set_source_distributions, ndt_eval_derivatives_d2d, ndt_align_d2d; DESIGN 7l).  Functions on an engine, as above. ---
+def setSourceDistributions(ndt, state=None, count=None, moments=None):
+    """The distribution source of `ndt`: the records of mapExportState (its dict as `state`, or `count` [n] and
+    `moments` [n, 9]).  Each record that passes the target build's leaf rule becomes a source Gaussian.  n = 0 clears
+    the source.  Returns (records, accepted)."""
+    if state is not None:
+        count, moments = state.get("count"), state.get("moments")
+    if count is None or moments is None:
+        raise ValueError("count and moments (the state of a map with moments) are needed")
+    count = np.ascontiguousarray(count, dtype=np.int32)
+    moments = np.ascontiguousarray(moments, dtype=np.float64)
+    n = len(count)
+    if count.ndim != 1 or moments.shape != (n, 9):
+        raise ValueError("count must be [n] and moments [n, 9]")
+    ndt._check(lib().ndt_set_source_distributions(ndt._h, count.ctypes.data if n else None, moments.ctypes.data if n else None, n))
+    return sourceDistributionsInfo(ndt)
+
+
+def setSourceDistributionsDevice(ndt, d_count, d_moments, n):
+    """As setSourceDistributions, from device arrays (integer addresses) as mapExportStateDevice wrote them."""
+    if int(n) and (not d_count or not d_moments):
+        raise ValueError("device pointers are needed")
+    ndt._check(lib().ndt_set_source_distributions_device(ndt._h, d_count, d_moments, int(n)))
+    return sourceDistributionsInfo(ndt)
+
+
+def sourceDistributionsInfo(ndt):
+    """(records handed over, Gaussians accepted) of the distribution source"""
+    a, b = C.c_int64(0), C.c_int64(0)
+    ndt._check(lib().ndt_source_distributions_info(ndt._h, C.byref(a), C.byref(b)))
+    return int(a.value), int(b.value)
+
+
+def getSourceDistributions(ndt):
+    """The accepted source Gaussians in input order: dict(mean [m, 3], cov6 [m, 6] (xx, xy, xz, yy, yz, zz), cov
+    [m, 3, 3], count [m], record_index [m])."""
+    m = sourceDistributionsInfo(ndt)[1]
+    mean, cov6 = np.zeros((m, 3)), np.zeros((m, 6))
+    count, index = np.zeros(m, np.int32), np.zeros(m, np.int32)
+    got = lib().ndt_export_source_distributions(ndt._h, _dp(mean), _dp(cov6), count.ctypes.data, index.ctypes.data, m) if m else 0
+    if got < 0:
+        ndt._check(int(got))
+    cov = cov6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(m, 3, 3)
+    return dict(mean=mean, cov6=cov6, cov=cov, count=count, record_index=index)
+
+
+def evalDerivativesD2D(ndt, poses6, compute_hessian=True, raw=False):
+    """The D2D score, gradient and Hessian at K poses [x, y, z, roll, pitch, yaw] (K x 6): a list of dicts as
+    evalDerivatives gives them; raw=True: the K x 32 packed words."""
+    p = np.ascontiguousarray(np.atleast_2d(poses6), dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 6 or not np.isfinite(p).all():
+        raise ValueError("poses6 must be K x 6 and finite")
+    K = p.shape[0]
+    out = np.zeros((K, EVAL_WORDS))
+    ndt._check(lib().ndt_eval_derivatives_d2d(ndt._h, _dp(p), K, int(bool(compute_hessian)), _dp(out)))
+    return out if raw else [unpack_eval(out[k]) for k in range(K)]
+
+
+computeDerivativesD2D = evalDerivativesD2D
+
+
+def alignDistributions(ndt, guess=None):
+    """ndt_align_d2d: the distribution source registered to the target from `guess` (4x4, default identity).  Returns
+    (final 4x4, result dict as getResult() gives it); getResult() keeps reporting the last align()."""
+    g = _colmajor(np.eye(4) if guess is None else guess)
+    r = Result()
+    ndt._check(lib().ndt_align_d2d(ndt._h, _fp(g), C.byref(r)))
+    d = result_to_dict(r)
+    d["iteration_num"] = d["iterations"]
+    return d["T"], d
 
 
 def comm_unique_id():

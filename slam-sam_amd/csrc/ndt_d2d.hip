@@ -1,0 +1,662 @@
+// ndt_d2d.hip -- distribution-to-distribution NDT (Stoyanov et al. 2012): a submap's voxels registered to the target's
+// (see ndt_engine.h; the rule is stated in include/ndt_hip.h).
+//   ndt_set_source_distributions*   the records of ndt_map_export_state* are kept; k_d2d_finalize puts each through the
+//                                   target build's own finalize_leaf (ndt_leaf_device.h) and counts what it accepts per
+//                                   block, k_filter_scan turns the counts into offsets, k_d2d_emit writes the accepted
+//                                   Gaussians {mean 3, cov 6} in input order (ndt_compact_device.h)
+//   ndt_eval_derivatives_d2d        k_d2d_gather_target once per published target (mean 3 + cov 6 per leaf slot, from
+//                                   `stats`), then per pose one launch of k_d2d_eval<HESSIAN> -- one source Gaussian per
+//                                   lane -- and one launch of k_d2d_sum over all poses
+//   ndt_align_d2d                   newton_align over that evaluation
+// Sums: lane -> wave (xor butterfly) -> block (LDS, wave order) -> one row per block -> k_d2d_sum in fixed order.  No
+// float atomics; a pose's launch and its rows do not depend on the other poses of a call, so it gives the bits it gives
+// alone.  The point source, the align state and the iteration history of the handle are not touched.
+#include "ndt_engine.h"
+#include "ndt_compact_device.h"
+#include "ndt_leaf_device.h"
+
+namespace ndt {
+
+namespace {
+
+constexpr int D2D_THREADS = 256, D2D_WAVES = D2D_THREADS / 64;
+constexpr int SUM_SEGS = D2D_THREADS / EV_WORDS;   // k_d2d_sum: threads per word
+
+// R = Rx(roll) Ry(pitch) Rz(yaw) and its first and second angle derivatives, row-major, f64 from exact sin / cos
+struct D2dPose {
+  double R[9];
+  double dR[3][9];    // by roll, pitch, yaw
+  double d2R[6][9];   // rr, rp, ry, pp, py, yy
+  double t[3];
+};
+
+struct Sym3 {
+  double xx, xy, xz, yy, yz, zz;
+};
+
+__device__ __forceinline__ void sym_mul(const Sym3& S, const double v[3], double o[3]) {
+  o[0] = (S.xx * v[0] + S.xy * v[1]) + S.xz * v[2];
+  o[1] = (S.xy * v[0] + S.yy * v[1]) + S.yz * v[2];
+  o[2] = (S.xz * v[0] + S.yz * v[1]) + S.zz * v[2];
+}
+__device__ __forceinline__ double dot3(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+__device__ __forceinline__ void mat_vec(const double* A, const double v[3], double o[3]) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) o[a] = (A[3 * a] * v[0] + A[3 * a + 1] * v[1]) + A[3 * a + 2] * v[2];
+}
+// M = A S B^T (A, B row-major 3 x 3, S symmetric)
+__device__ __forceinline__ void a_s_bt(const double* A, const Sym3& S, const double* B, double M[9]) {
+  double T[9];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    T[3 * a + 0] = (A[3 * a] * S.xx + A[3 * a + 1] * S.xy) + A[3 * a + 2] * S.xz;
+    T[3 * a + 1] = (A[3 * a] * S.xy + A[3 * a + 1] * S.yy) + A[3 * a + 2] * S.yz;
+    T[3 * a + 2] = (A[3 * a] * S.xz + A[3 * a + 1] * S.yz) + A[3 * a + 2] * S.zz;
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) M[3 * a + b] = (T[3 * a] * B[3 * b] + T[3 * a + 1] * B[3 * b + 1]) + T[3 * a + 2] * B[3 * b + 2];
+}
+// M + M^T
+__device__ __forceinline__ Sym3 sym_of(const double M[9]) {
+  Sym3 Z;
+  Z.xx = M[0] + M[0]; Z.xy = M[1] + M[3]; Z.xz = M[2] + M[6];
+  Z.yy = M[4] + M[4]; Z.yz = M[5] + M[7]; Z.zz = M[8] + M[8];
+  return Z;
+}
+// sum_ab Z_ab W_ab of two symmetric matrices
+__device__ __forceinline__ double sym_inner(const Sym3& Z, const Sym3& W) {
+  return ((Z.xx * W.xx + Z.yy * W.yy) + Z.zz * W.zz) + 2.0 * ((Z.xy * W.xy + Z.xz * W.xz) + Z.yz * W.yz);
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
+  return v;   // (a + b and b + a are the same bits: every lane holds the same sum)
+}
+
+// a record of the setters' input that cannot be a voxel: count < 1 or a non-finite sum
+__global__ void __launch_bounds__(D2D_THREADS) k_d2d_check(const int32_t* __restrict__ count, const double* __restrict__ mom, int n,
+                                                          int* __restrict__ bad) {
+  const int r = (int)(blockIdx.x * D2D_THREADS + threadIdx.x);
+  if (r >= n) return;
+  bool b = count[r] < 1;
+#pragma unroll
+  for (int a = 0; a < 9; ++a) b = b || !isfinite(mom[(size_t)r * 9 + a]);
+  if (b) atomicOr(bad, 1);
+}
+
+// record r -> a leaf through the target build's rule (cell = slot = r: cell2leaf[r] = r marks an accepted record, the
+// array is -1 before the launch); counts[block] = records the block accepted
+__global__ void __launch_bounds__(D2D_THREADS) k_d2d_finalize(const int32_t* __restrict__ count, const double* __restrict__ mom, int n,
+                                                             int min_pts, FinalizeParams fp, VoxelRecord* __restrict__ rec,
+                                                             float4* __restrict__ cent, LeafStats* __restrict__ stats,
+                                                             int* __restrict__ cell2leaf, unsigned int* __restrict__ counts) {
+  __shared__ unsigned int s_w[D2D_WAVES];
+  const int r = (int)(blockIdx.x * D2D_THREADS + threadIdx.x);
+  bool ok = false;
+  if (r < n) {
+    const int cnt = count[r];
+    if (cnt >= min_pts) ok = finalize_leaf(r, r, cnt, mom + (size_t)r * 9, fp, rec, cent, stats, cell2leaf);
+  }
+  compact_ballot(ok, s_w);
+  __syncthreads();
+  compact_block_count(s_w, counts);
+}
+
+__global__ void __launch_bounds__(D2D_THREADS) k_d2d_emit(const int* __restrict__ cell2leaf, const LeafStats* __restrict__ stats, int n,
+                                                         const unsigned int* __restrict__ offsets, double* __restrict__ gauss,
+                                                         int32_t* __restrict__ gcount, int32_t* __restrict__ gindex) {
+  __shared__ unsigned int s_w[D2D_WAVES];
+  const int r = (int)(blockIdx.x * D2D_THREADS + threadIdx.x);
+  const bool keep = r < n && cell2leaf[r] >= 0;
+  const unsigned long long bal = compact_ballot(keep, s_w);
+  __syncthreads();
+  const unsigned int pos = compact_position(bal, s_w, offsets);
+  if (!keep) return;   // (pos <= r < n: the outputs hold n Gaussians)
+  const LeafStats& L = stats[r];
+  double* g = gauss + (size_t)pos * 9;
+  g[0] = L.mean[0]; g[1] = L.mean[1]; g[2] = L.mean[2];
+  g[3] = L.cov[0]; g[4] = L.cov[1]; g[5] = L.cov[2]; g[6] = L.cov[4]; g[7] = L.cov[5]; g[8] = L.cov[8];
+  gcount[pos] = L.count;
+  gindex[pos] = r;
+}
+
+// leaf slot s of the target -> {mean 3, cov xx xy xz yy yz zz}: 72 bytes per pair in place of a 296-byte LeafStats
+__global__ void __launch_bounds__(D2D_THREADS) k_d2d_gather_target(const LeafStats* __restrict__ stats, int n_slots,
+                                                                  double* __restrict__ tleaf) {
+  const int s = (int)(blockIdx.x * D2D_THREADS + threadIdx.x);
+  if (s >= n_slots) return;
+  const LeafStats& L = stats[s];
+  double* g = tleaf + (size_t)s * 9;
+  g[0] = L.mean[0]; g[1] = L.mean[1]; g[2] = L.mean[2];
+  g[3] = L.cov[0]; g[4] = L.cov[1]; g[5] = L.cov[2]; g[6] = L.cov[4]; g[7] = L.cov[5]; g[8] = L.cov[8];
+}
+
+// What a lane keeps over its <= 7 pairs.  The Hessian's terms that are linear in a pair's f v and f v v^T (v = B mu,
+// f = (d1 d2 / 2) e) are summed as w and W and meet the second derivatives of the pose once per lane, behind the pairs:
+//   q_ab = 2 u_b^T B u_a + 2 v^T H_ab - v^T Z_ab v,   u_a = j_a - Z_a v,   q_a = v^T (j_a + u_a)
+// (the six products of the rule's q_ab in j, Z, B and v fold into u_b^T B u_a).
+template <bool HESSIAN>
+struct D2dAcc {
+  double score, best;
+  int npairs;
+  double g[6];
+  double H[HESSIAN ? 21 : 1];
+  double w[3];
+  Sym3 W;
+};
+
+template <bool HESSIAN>
+__device__ __forceinline__ void d2d_pair(D2dAcc<HESSIAN>& acc, const double* __restrict__ T, const double m[3], const Sym3& A,
+                                         const double (&j)[3][3], const Sym3 (&Z)[3], double d1, double d2) {
+  const double mu[3] = {m[0] - T[0], m[1] - T[1], m[2] - T[2]};
+  Sym3 C;
+  C.xx = A.xx + T[3]; C.xy = A.xy + T[4]; C.xz = A.xz + T[5]; C.yy = A.yy + T[6]; C.yz = A.yz + T[7]; C.zz = A.zz + T[8];
+  // B = C^-1 by cofactors
+  const double c00 = C.yy * C.zz - C.yz * C.yz;
+  const double c01 = C.xz * C.yz - C.xy * C.zz;
+  const double c02 = C.xy * C.yz - C.xz * C.yy;
+  const double det = (C.xx * c00 + C.xy * c01) + C.xz * c02;
+  const double id = 1.0 / det;
+  Sym3 B;
+  B.xx = c00 * id; B.xy = c01 * id; B.xz = c02 * id;
+  B.yy = (C.xx * C.zz - C.xz * C.xz) * id;
+  B.yz = (C.xy * C.xz - C.xx * C.yz) * id;
+  B.zz = (C.xx * C.yy - C.xy * C.xy) * id;
+  double v[3];
+  sym_mul(B, mu, v);
+  const double q = dot3(mu, v);
+  const double e = exp(-d2 * q * 0.5);
+  if (!(e >= 0.0 && e <= 1.0)) return;   // the evaluation's guard (a NaN fails both compares)
+  const double sc = -d1 * e;
+  acc.score += sc;
+  acc.best = fmax(acc.best, sc);
+  acc.npairs += 1;
+  const double f = (d1 * d2 * 0.5) * e;
+  double u[3][3], qa[6];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    double zv[3];
+    sym_mul(Z[c], v, zv);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) u[c][a] = j[c][a] - zv[a];
+    const double ju[3] = {j[c][0] + u[c][0], j[c][1] + u[c][1], j[c][2] + u[c][2]};
+    qa[c] = 2.0 * v[c];
+    qa[3 + c] = dot3(v, ju);
+  }
+#pragma unroll
+  for (int a = 0; a < 6; ++a) acc.g[a] += f * qa[a];
+  if (HESSIAN) {
+    // B u_a: the columns of B for the translations, then the three rotations
+    double Bu[6][3] = {{B.xx, B.xy, B.xz}, {B.xy, B.yy, B.yz}, {B.xz, B.yz, B.zz}};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) sym_mul(B, u[c], Bu[3 + c]);
+    const double hd = 0.5 * d2;
+    int w = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+      for (int b = a; b < 6; ++b) {
+        // u_b^T B u_a (u of a translation is a unit vector)
+        const double ubu = b < 3 ? Bu[a][b] : dot3(u[b - 3], Bu[a]);
+        acc.H[w] += f * (2.0 * ubu - hd * qa[a] * qa[b]);
+        ++w;
+      }
+    acc.w[0] += f * v[0]; acc.w[1] += f * v[1]; acc.w[2] += f * v[2];
+    acc.W.xx += f * v[0] * v[0]; acc.W.xy += f * v[0] * v[1]; acc.W.xz += f * v[0] * v[2];
+    acc.W.yy += f * v[1] * v[1]; acc.W.yz += f * v[1] * v[2]; acc.W.zz += f * v[2] * v[2];
+  }
+}
+
+// One source Gaussian per lane: the moved mean, its neighbours as k_point_scores finds them for the f32-rounded moved
+// mean (DIRECT1 / DIRECT7, the same pair order), the pairs, and the block's row of EV_WORDS sums (word 31 = 0).
+template <bool HESSIAN, bool D7>
+__global__ void __launch_bounds__(D2D_THREADS)
+k_d2d_eval(const double* __restrict__ gauss, int n, GridGeom g, const int* __restrict__ cell2leaf, const double* __restrict__ tleaf,
+           D2dPose P, double d1, double d2, double* __restrict__ rows) {
+  __shared__ double s_part[D2D_WAVES][EV_WORDS];
+  const int i = (int)(blockIdx.x * D2D_THREADS + threadIdx.x);
+  const bool active = i < n;
+  D2dAcc<HESSIAN> acc;
+  acc.score = 0.0; acc.best = 0.0; acc.npairs = 0;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) acc.g[a] = 0.0;
+#pragma unroll
+  for (int a = 0; a < (HESSIAN ? 21 : 1); ++a) acc.H[a] = 0.0;
+  acc.w[0] = acc.w[1] = acc.w[2] = 0.0;
+  acc.W.xx = acc.W.xy = acc.W.xz = acc.W.yy = acc.W.yz = acc.W.zz = 0.0;
+  if (active) {
+    const double* G = gauss + (size_t)i * 9;
+    const double mu[3] = {G[0], G[1], G[2]};
+    Sym3 S;
+    S.xx = G[3]; S.xy = G[4]; S.xz = G[5]; S.yy = G[6]; S.yz = G[7]; S.zz = G[8];
+    double m[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) m[a] = ((P.R[3 * a] * mu[0] + P.R[3 * a + 1] * mu[1]) + P.R[3 * a + 2] * mu[2]) + P.t[a];
+    const float xt = (float)m[0], yt = (float)m[1], zt = (float)m[2];
+    const bool finite = isfinite(xt) && isfinite(yt) && isfinite(zt);
+    // the classification of k_point_scores (ndt_derivs.hip), operation for operation
+    const float w = g.leaf;
+    const float cx[3] = {xt, xt + w, xt - w}, cy[3] = {yt, yt + w, yt - w}, cz[3] = {zt, zt + w, zt - w};
+    bool inx[3], iny[3], inz[3];
+    unsigned int ix[3], iy[3], iz[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      inx[k] = cx[k] >= g.lo[0] && cx[k] < g.hi[0];
+      iny[k] = cy[k] >= g.lo[1] && cy[k] < g.hi[1];
+      inz[k] = cz[k] >= g.lo[2] && cz[k] < g.hi[2];
+      ix[k] = (unsigned int)(int)(floorf(cx[k] * g.inv_leaf) - (float)g.min_b[0]);
+      iy[k] = (unsigned int)(int)(floorf(cy[k] * g.inv_leaf) - (float)g.min_b[1]) * (unsigned int)g.mul1;
+      iz[k] = (unsigned int)(int)(floorf(cz[k] * g.inv_leaf) - (float)g.min_b[2]) * (unsigned int)g.mul2;
+    }
+    int cell[7];
+    {
+      const int idx0 = (int)(ix[0] + iy[0] + iz[0]);
+      cell[0] = (inx[0] && iny[0] && inz[0] && idx0 >= 0 && idx0 < g.ncells) ? idx0 : -1;
+    }
+#pragma unroll
+    for (int k = 1; k < 3; ++k) {
+      const int ax = (int)(ix[k] + iy[0] + iz[0]), ay = (int)(ix[0] + iy[k] + iz[0]), az = (int)(ix[0] + iy[0] + iz[k]);
+      cell[k] = (D7 && inx[k] && iny[0] && inz[0] && ax >= 0 && ax < g.ncells) ? ax : -1;
+      cell[2 + k] = (D7 && inx[0] && iny[k] && inz[0] && ay >= 0 && ay < g.ncells) ? ay : -1;
+      cell[4 + k] = (D7 && inx[0] && iny[0] && inz[k] && az >= 0 && az < g.ncells) ? az : -1;
+    }
+    int slot[7];
+#pragma unroll
+    for (int k = 0; k < (D7 ? 7 : 1); ++k) slot[k] = (finite && cell[k] >= 0) ? cell2leaf[cell[k]] : -1;
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < (D7 ? 7 : 1); ++k) any = any || slot[k] >= 0;
+    if (any) {
+      // what depends on the pose and the source Gaussian alone, once per lane
+      double M[9];
+      a_s_bt(P.R, S, P.R, M);
+      Sym3 A;
+      A.xx = M[0]; A.xy = M[1]; A.xz = M[2]; A.yy = M[4]; A.yz = M[5]; A.zz = M[8];
+      double j[3][3];
+      Sym3 Z[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        mat_vec(P.dR[c], mu, j[c]);
+        a_s_bt(P.dR[c], S, P.R, M);
+        Z[c] = sym_of(M);
+      }
+#pragma unroll
+      for (int k = 0; k < (D7 ? 7 : 1); ++k)
+        if (slot[k] >= 0) d2d_pair<HESSIAN>(acc, tleaf + (size_t)slot[k] * 9, m, A, j, Z, d1, d2);
+      if (HESSIAN && acc.npairs > 0) {
+        // the rotation block's second-derivative terms: 2 w^T H_cd - <Z_cd, W>, Z_cd = N + N^T,
+        // N = (d2R_cd) S R^T + (dR_c) S (dR_d)^T
+        int q = 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+          for (int d = c; d < 3; ++d) {
+            double hcd[3], N[9], N2[9];
+            mat_vec(P.d2R[q], mu, hcd);
+            a_s_bt(P.d2R[q], S, P.R, N);
+            a_s_bt(P.dR[c], S, P.dR[d], N2);
+#pragma unroll
+            for (int a = 0; a < 9; ++a) N[a] += N2[a];
+            const Sym3 Zcd = sym_of(N);
+            // word of (3 + c, 3 + d) in the upper triangle row by row: rows 0 .. 2 hold 6 + 5 + 4 = 15 words
+            const int word = 15 + (c == 0 ? d : c == 1 ? 3 + (d - 1) : 5);
+            acc.H[word] += 2.0 * dot3(acc.w, hcd) - sym_inner(Zcd, acc.W);
+            ++q;
+          }
+      }
+    }
+  }
+  // lane -> wave -> block
+  double words[EV_WORDS];
+  words[EV_SCORE] = acc.score;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) words[EV_G + a] = acc.g[a];
+#pragma unroll
+  for (int a = 0; a < 21; ++a) words[EV_H + a] = HESSIAN ? acc.H[a] : 0.0;
+  words[EV_NVTL] = acc.best;
+  words[EV_NWITH] = acc.npairs > 0 ? 1.0 : 0.0;
+  words[EV_NPAIRS] = (double)acc.npairs;
+  words[EV_FAIL] = 0.0;
+  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+#pragma unroll
+  for (int k = 0; k < EV_WORDS; ++k) {
+    if (!HESSIAN && k >= EV_H && k < EV_H + 21) continue;
+    if (k == EV_FAIL) continue;
+    const double s = wave_sum(words[k]);
+    if (lane == 0) s_part[wave][k] = s;
+  }
+  if (lane == 0) {
+    s_part[wave][EV_FAIL] = 0.0;
+    if (!HESSIAN)
+#pragma unroll
+      for (int k = 0; k < 21; ++k) s_part[wave][EV_H + k] = 0.0;
+  }
+  __syncthreads();
+  if (threadIdx.x < EV_WORDS) {
+    double s = s_part[0][threadIdx.x];
+#pragma unroll
+    for (int wv = 1; wv < D2D_WAVES; ++wv) s += s_part[wv][threadIdx.x];
+    rows[(size_t)blockIdx.x * EV_WORDS + threadIdx.x] = s;
+  }
+}
+
+// out[k] = the nb rows of pose k added in a fixed order: SUM_SEGS strided partial sums per word, then those in order
+__global__ void __launch_bounds__(D2D_THREADS) k_d2d_sum(const double* __restrict__ rows, int nb, double* __restrict__ out) {
+  __shared__ double s_seg[SUM_SEGS][EV_WORDS];
+  const int word = (int)(threadIdx.x % EV_WORDS), seg = (int)(threadIdx.x / EV_WORDS);
+  const double* r = rows + (size_t)blockIdx.x * (size_t)nb * EV_WORDS;
+  double s = 0.0;
+  for (int b = seg; b < nb; b += SUM_SEGS) s += r[(size_t)b * EV_WORDS + word];
+  s_seg[seg][word] = s;
+  __syncthreads();
+  if (threadIdx.x < EV_WORDS) {
+    double t = s_seg[0][word];
+#pragma unroll
+    for (int k = 1; k < SUM_SEGS; ++k) t += s_seg[k][word];
+    out[(size_t)blockIdx.x * EV_WORDS + word] = t;
+  }
+}
+
+void rot_x(double a, int order, double M[9]) {   // order-th derivative of Rx(a)
+  const double s = std::sin(a), c = std::cos(a);
+  const double f[3][2] = {{c, s}, {-s, c}, {-c, -s}};   // {cos, sin} and their derivatives
+  const double C = f[order][0], Sn = f[order][1], one = order == 0 ? 1.0 : 0.0;
+  const double m[9] = {one, 0, 0, 0, C, -Sn, 0, Sn, C};
+  std::memcpy(M, m, sizeof(m));
+}
+void rot_y(double a, int order, double M[9]) {
+  const double s = std::sin(a), c = std::cos(a);
+  const double f[3][2] = {{c, s}, {-s, c}, {-c, -s}};
+  const double C = f[order][0], Sn = f[order][1], one = order == 0 ? 1.0 : 0.0;
+  const double m[9] = {C, 0, Sn, 0, one, 0, -Sn, 0, C};
+  std::memcpy(M, m, sizeof(m));
+}
+void rot_z(double a, int order, double M[9]) {
+  const double s = std::sin(a), c = std::cos(a);
+  const double f[3][2] = {{c, s}, {-s, c}, {-c, -s}};
+  const double C = f[order][0], Sn = f[order][1], one = order == 0 ? 1.0 : 0.0;
+  const double m[9] = {C, -Sn, 0, Sn, C, 0, 0, 0, one};
+  std::memcpy(M, m, sizeof(m));
+}
+void mul3(const double* A, const double* B, double* C) {
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) C[3 * a + b] = (A[3 * a] * B[b] + A[3 * a + 1] * B[3 + b]) + A[3 * a + 2] * B[6 + b];
+}
+// (d/droll)^o0 (d/dpitch)^o1 (d/dyaw)^o2 of Rx Ry Rz
+void rot_product(const double p[6], int o0, int o1, int o2, double M[9]) {
+  double X[9], Y[9], Zm[9], XY[9];
+  rot_x(p[3], o0, X);
+  rot_y(p[4], o1, Y);
+  rot_z(p[5], o2, Zm);
+  mul3(X, Y, XY);
+  mul3(XY, Zm, M);
+}
+void fill_d2d_pose(const double p[6], D2dPose* P) {
+  rot_product(p, 0, 0, 0, P->R);
+  rot_product(p, 1, 0, 0, P->dR[0]);
+  rot_product(p, 0, 1, 0, P->dR[1]);
+  rot_product(p, 0, 0, 1, P->dR[2]);
+  rot_product(p, 2, 0, 0, P->d2R[0]);
+  rot_product(p, 1, 1, 0, P->d2R[1]);
+  rot_product(p, 1, 0, 1, P->d2R[2]);
+  rot_product(p, 0, 2, 0, P->d2R[3]);
+  rot_product(p, 0, 1, 1, P->d2R[4]);
+  rot_product(p, 0, 0, 2, P->d2R[5]);
+  for (int a = 0; a < 3; ++a) P->t[a] = p[a];
+}
+
+int blocks_for(size_t n) { return (int)((n + D2D_THREADS - 1) / D2D_THREADS); }
+
+}  // namespace
+
+namespace engine {
+namespace {
+
+int d2d_min_points(const ndt_handle* h) { return std::max(3, h->prm.min_points_per_voxel); }   // the ordinary build's rule (build_begin)
+
+// the kept records -> the accepted Gaussians under the handle's leaf rule, in input order; awaited
+int d2d_derive(ndt_handle* h) {
+  D2dBufs& d = h->d2d;
+  const size_t n = d.n_records;
+  const int nb = blocks_for(n);
+  HIP_TRY(h, d.frec.ensure(n));
+  HIP_TRY(h, d.fcent.ensure(4 * n));
+  HIP_TRY(h, d.fstats.ensure(n));
+  HIP_TRY(h, d.fcell.ensure(n));
+  HIP_TRY(h, d.gauss.ensure(9 * n));
+  HIP_TRY(h, d.gcount.ensure(n));
+  HIP_TRY(h, d.gindex.ensure(n));
+  if (int rc = compact_scratch(h, nb)) return rc;
+  hipStream_t s = h->stream;
+  const int min_pts = d2d_min_points(h);
+  const FinalizeParams fp{h->prm.eig_inflation_ratio, h->prm.cov_mode};
+  HIP_TRY(h, hipMemsetAsync(d.fcell.p, 0xff, n * sizeof(int), s));
+  unsigned int* counts = h->compact.counts.p;
+  hipLaunchKernelGGL(k_d2d_finalize, dim3((unsigned)nb), dim3(D2D_THREADS), 0, s, d.rcount.p, d.rmom.p, (int)n, min_pts, fp, d.frec.p,
+                     reinterpret_cast<float4*>(d.fcent.p), d.fstats.p, d.fcell.p, counts);
+  launch_filter_scan(counts, nb, h->compact.d_total(nb), s);
+  hipLaunchKernelGGL(k_d2d_emit, dim3((unsigned)nb), dim3(D2D_THREADS), 0, s, d.fcell.p, d.fstats.p, (int)n, counts, d.gauss.p,
+                     d.gcount.p, d.gindex.p);
+  size_t kept = 0;
+  if (int rc = compact_total(h, nb, n, &kept)) return rc;
+  d.n_accepted = kept;
+  d.rule_min_pts = min_pts;
+  d.rule_cov_mode = h->prm.cov_mode;
+  d.rule_eig = h->prm.eig_inflation_ratio;
+  return NDT_OK;
+}
+
+// the Gaussians follow the handle's leaf rule: ndt_set_params may have changed it since they were derived
+int d2d_source_fresh(ndt_handle* h) {
+  const D2dBufs& d = h->d2d;
+  if (!d.have || d.n_records == 0) return NDT_OK;
+  if (d.rule_min_pts == d2d_min_points(h) && d.rule_cov_mode == h->prm.cov_mode && d.rule_eig == h->prm.eig_inflation_ratio)
+    return NDT_OK;
+  return d2d_derive(h);
+}
+
+void d2d_clear(ndt_handle* h) {
+  h->d2d.have = false;
+  h->d2d.n_records = h->d2d.n_accepted = 0;
+}
+
+bool d2d_too_many(size_t n) { return n > (size_t)std::numeric_limits<int>::max() / 16; }
+
+// what a D2D evaluation can work with: DIRECT1 / DIRECT7 on a single grid, one rank
+int d2d_supported(ndt_handle* h) {
+  if (h->red.mode() != NDT_REDUCE_NONE) return fail(h, NDT_ERR_UNSUPPORTED, "D2D: multi-rank evaluation is not supported");
+  if (h->prm.search_method != NDT_DIRECT1 && h->prm.search_method != NDT_DIRECT7)
+    return fail(h, NDT_ERR_UNSUPPORTED, "D2D: the search method must be DIRECT1 or DIRECT7");
+  if (h->tgt.is_union()) return fail(h, NDT_ERR_UNSUPPORTED, "D2D: a multi-grid union target is not supported");
+  return NDT_OK;
+}
+
+// target, then distribution source: what ndt_align_d2d answers with the guess
+int d2d_ready(ndt_handle* h) {
+  if (int rc = settle(h)) return rc;
+  if (int rc = d2d_supported(h)) return rc;
+  if (!h->tgt.have_grid() || h->tgt.n_valid() <= 0) return fail(h, NDT_ERR_NO_TARGET, "no target voxel grid (setInputTarget first)");
+  if (int rc = d2d_source_fresh(h)) return rc;
+  if (!h->d2d.have || h->d2d.n_accepted == 0)
+    return fail(h, NDT_ERR_NO_SOURCE, "no source Gaussians (ndt_set_source_distributions first)");
+  D2dBufs& d = h->d2d;
+  if (!d.tleaf_valid || d.tleaf_gen != h->tgt.gen()) {
+    const int n_slots = h->tgt.n_slots();
+    HIP_TRY(h, d.tleaf.ensure(9 * (size_t)n_slots));
+    hipLaunchKernelGGL(k_d2d_gather_target, dim3((unsigned)blocks_for((size_t)n_slots)), dim3(D2D_THREADS), 0, h->stream, h->stats.p,
+                       n_slots, d.tleaf.p);
+    HIP_TRY(h, hipGetLastError());
+    d.tleaf_gen = h->tgt.gen();
+    d.tleaf_valid = true;
+  }
+  return NDT_OK;
+}
+
+// K poses -> K x EV_WORDS raw sums in `out`; d2d_ready has passed
+int d2d_eval_raw(ndt_handle* h, const double* poses6, int K, bool need_h, double* out) {
+  D2dBufs& d = h->d2d;
+  const int n = (int)d.n_accepted, nb = blocks_for(d.n_accepted);
+  HIP_TRY(h, d.rows.ensure((size_t)K * (size_t)nb * EV_WORDS));
+  HIP_TRY(h, d.out.ensure((size_t)K * EV_WORDS));
+  HIP_TRY(h, d.out_h.ensure((size_t)K * EV_WORDS));
+  double d1, d2;
+  gauss_constants((double)h->prm.resolution, h->prm.outlier_ratio, &d1, &d2);
+  const bool d7 = h->prm.search_method == NDT_DIRECT7;
+  hipStream_t s = h->stream;
+  const dim3 grid((unsigned)nb), block(D2D_THREADS);
+  for (int k = 0; k < K; ++k) {   // one launch per pose: a pose's rows are what they are alone
+    D2dPose P;
+    fill_d2d_pose(poses6 + 6 * (size_t)k, &P);
+    double* rows = d.rows.p + (size_t)k * (size_t)nb * EV_WORDS;
+#define NDT_D2D_LAUNCH(H, D7) \
+  hipLaunchKernelGGL((k_d2d_eval<H, D7>), grid, block, 0, s, d.gauss.p, n, h->geom, h->cell2leaf.p, d.tleaf.p, P, d1, d2, rows)
+    if (need_h) { if (d7) NDT_D2D_LAUNCH(true, true); else NDT_D2D_LAUNCH(true, false); }
+    else { if (d7) NDT_D2D_LAUNCH(false, true); else NDT_D2D_LAUNCH(false, false); }
+#undef NDT_D2D_LAUNCH
+  }
+  hipLaunchKernelGGL(k_d2d_sum, dim3((unsigned)K), block, 0, s, d.rows.p, nb, d.out.p);
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipMemcpyAsync(d.out_h.h, d.out.p, (size_t)K * EV_WORDS * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  std::memcpy(out, d.out_h.h, (size_t)K * EV_WORDS * sizeof(double));
+  for (int k = 0; k < K; ++k)
+    if (!std::isfinite(out[(size_t)k * EV_WORDS + EV_SCORE])) return fail(h, NDT_ERR_HIP, "D2D evaluation returned a non-finite score");
+  return NDT_OK;
+}
+
+}  // namespace
+}  // namespace engine
+}  // namespace ndt
+
+extern "C" {
+
+int ndt_set_source_distributions(ndt_handle* h, const int32_t* count, const double* moments9, size_t n) {
+  if (!h || (n && (!count || !moments9)) || d2d_too_many(n)) return NDT_ERR_INVALID_ARG;
+  for (size_t r = 0; r < n; ++r) {   // (before the handle is looked at: a refused call leaves the previous source)
+    if (count[r] < 1) return NDT_ERR_INVALID_ARG;
+    for (int a = 0; a < 9; ++a)
+      if (!std::isfinite(moments9[9 * r + a])) return NDT_ERR_INVALID_ARG;
+  }
+  if (n == 0) { d2d_clear(h); return NDT_OK; }
+  if (int rc = bind_device(h)) return rc;
+  D2dBufs& d = h->d2d;
+  HIP_TRY(h, d.rcount.ensure(n));
+  HIP_TRY(h, d.rmom.ensure(9 * n));
+  d2d_clear(h);   // (from here on the previous source is gone)
+  HIP_TRY(h, hipMemcpyAsync(d.rcount.p, count, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(d.rmom.p, moments9, 9 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  d.n_records = n;
+  if (int rc = d2d_derive(h)) { d2d_clear(h); return rc; }
+  d.have = true;
+  return NDT_OK;
+}
+
+int ndt_set_source_distributions_device(ndt_handle* h, const int32_t* d_count, const double* d_moments9, size_t n) {
+  if (!h || (n && (!d_count || !d_moments9)) || d2d_too_many(n)) return NDT_ERR_INVALID_ARG;
+  if (n == 0) { d2d_clear(h); return NDT_OK; }
+  if (int rc = bind_device(h)) return rc;
+  D2dBufs& d = h->d2d;
+  HIP_TRY(h, d.bad.ensure(1));
+  HIP_TRY(h, d.bad_h.ensure(4));
+  hipStream_t s = h->stream;
+  HIP_TRY(h, hipMemsetAsync(d.bad.p, 0, sizeof(int), s));
+  hipLaunchKernelGGL(k_d2d_check, dim3((unsigned)blocks_for(n)), dim3(D2D_THREADS), 0, s, d_count, d_moments9, (int)n, d.bad.p);
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipMemcpyAsync(d.bad_h.h, d.bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  if (d.bad_h.h[0]) return fail(h, NDT_ERR_INVALID_ARG, "source distributions: a count < 1 or a non-finite moment");
+  if (d_count != d.rcount.p) {   // (the handle's own kept records may be handed back)
+    HIP_TRY(h, d.rcount.ensure(n));
+    HIP_TRY(h, d.rmom.ensure(9 * n));
+    d2d_clear(h);
+    HIP_TRY(h, hipMemcpyAsync(d.rcount.p, d_count, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(d.rmom.p, d_moments9, 9 * n * sizeof(double), hipMemcpyDeviceToDevice, s));
+  }
+  d.n_records = n;
+  if (int rc = d2d_derive(h)) { d2d_clear(h); return rc; }
+  d.have = true;
+  return NDT_OK;
+}
+
+int ndt_source_distributions_info(ndt_handle* h, int64_t* n_records, int64_t* n_accepted) {
+  if (!h) return NDT_ERR_INVALID_ARG;
+  if (h->d2d.have) {
+    if (int rc = bind_device(h)) return rc;
+    if (int rc = d2d_source_fresh(h)) return rc;
+  }
+  if (n_records) *n_records = h->d2d.have ? (int64_t)h->d2d.n_records : 0;
+  if (n_accepted) *n_accepted = h->d2d.have ? (int64_t)h->d2d.n_accepted : 0;
+  return NDT_OK;
+}
+
+int64_t ndt_export_source_distributions(ndt_handle* h, double* mean3, double* cov6, int32_t* count, int32_t* record_index,
+                                        size_t cap) {
+  if (!h) return NDT_ERR_INVALID_ARG;
+  const D2dBufs& d = h->d2d;
+  if (!d.have) return 0;
+  if (int rc = bind_device(h)) return rc;
+  if (int rc = d2d_source_fresh(h)) return rc;
+  const size_t m = d.n_accepted;
+  if (m > cap) return over_capacity(h, m);
+  if (m == 0) return 0;
+  std::vector<double> g(9 * m);
+  hipStream_t s = h->stream;
+  HIP_TRY(h, hipMemcpyAsync(g.data(), d.gauss.p, 9 * m * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (count) HIP_TRY(h, hipMemcpyAsync(count, d.gcount.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (record_index) HIP_TRY(h, hipMemcpyAsync(record_index, d.gindex.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  for (size_t i = 0; i < m; ++i) {
+    if (mean3) std::memcpy(mean3 + 3 * i, &g[9 * i], 3 * sizeof(double));
+    if (cov6) std::memcpy(cov6 + 6 * i, &g[9 * i + 3], 6 * sizeof(double));
+  }
+  return (int64_t)m;
+}
+
+int ndt_eval_derivatives_d2d(ndt_handle* h, const double* poses6, int K, int compute_hessian, double* out) {
+  if (!h || !poses6 || !out || K <= 0) return NDT_ERR_INVALID_ARG;
+  for (int i = 0; i < 6 * K; ++i)
+    if (!std::isfinite(poses6[i])) return NDT_ERR_INVALID_ARG;
+  if (int rc = bind_device(h)) return rc;
+  if (int rc = d2d_ready(h)) return rc;
+  if (int rc = d2d_eval_raw(h, poses6, K, compute_hessian != 0, out)) return rc;
+  // ridge / regularisation / guards as ndt_eval_derivatives applies them, then repacked
+  for (int k = 0; k < K; ++k) {
+    double* w = out + (size_t)k * EV_WORDS;
+    Eval e;
+    unpack_eval(w, &e);
+    finish_eval(h->prm, h->have_reg ? h->reg_pose : nullptr, poses6 + 6 * (size_t)k, compute_hessian != 0, &e);
+    w[EV_SCORE] = e.score;
+    for (int i = 0; i < 6; ++i) w[EV_G + i] = e.g[i];
+    if (compute_hessian) {
+      int idx = EV_H;
+      for (int i = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j) w[idx++] = e.H[6 * i + j];
+    }
+  }
+  return NDT_OK;
+}
+
+int ndt_align_d2d(ndt_handle* h, const float guess[16], ndt_result* out) {
+  if (!h || !guess || !out) return NDT_ERR_INVALID_ARG;
+  std::memset(out, 0, sizeof(*out));   // what every failure before the loop leaves: the guess, not converged
+  std::memcpy(out->final_transformation, guess, sizeof(float) * 16);
+  if (int rc = bind_device(h)) return rc;
+  h->keepwarm.touch();
+  if (int rc = d2d_ready(h)) return rc;
+  EvalFn fn = [h](const double* p, const float*, bool need_h, Eval* e) {
+    double words[EV_WORDS];
+    if (int r = d2d_eval_raw(h, p, 1, need_h, words)) return r;
+    unpack_eval(words, e);
+    finish_eval(h->prm, h->have_reg ? h->reg_pose : nullptr, p, need_h, e);
+    return 0;
+  };
+  // the product path of ndt_align (the Hessian in every trial, the memo on); no iteration history
+  const int rc = newton_align(h->prm, (int64_t)h->d2d.n_accepted, guess, fn, out, /*hessian_in_trials=*/true);
+  h->keepwarm.touch();
+  return rc;
+}
+
+}  // extern "C"

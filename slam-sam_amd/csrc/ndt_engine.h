@@ -9,6 +9,8 @@
 //   ndt_map.hip        the sparse voxel map accumulated scan by scan (ndt_map_*), its kernels included
 //   ndt_map_state.hip  the map's crop, full-state export / import and merge (k_mapstate_* kernels)
 //   ndt_map_repose.hip the map moved by a pose, and records merged under one (k_maprepose_* kernels)
+//   ndt_d2d.hip        distribution-to-distribution registration: a source of Gaussians from map records, its evaluation
+//                      and align against the target's leaves (k_d2d_* kernels)
 //   ndt_map_carve.hip  free-space carving of the map: voxels that a scan's rays pass through go (k_mapcarve_* kernels)
 //   ndt_deskew.hip     motion compensation of a scan along a pose trajectory + the acquisition filter (its kernels included)
 //   ndt_unproject.hip  a lidar range image -> points through the scan model's tables, fused with that filter and deskew
@@ -249,6 +251,40 @@ struct PacketBufs {
   }
 };
 
+// The distribution source of the D2D registration and what its evaluations need (ndt_d2d.hip).  The records are kept as
+// handed over: the Gaussians are derived from them under the handle's leaf rule and re-derived when that rule has changed
+// (d2d_source_fresh).  The target's leaves as the kernel reads them (mean 3 + cov 6 per leaf slot) are gathered from
+// `stats` by the first D2D evaluation after a target was published; target_retire and target_drop invalidate them.
+struct D2dBufs {
+  DevBuf<int32_t> rcount;            // the records: counts ...
+  DevBuf<double> rmom;               // ... and nine f64 sums each
+  size_t n_records = 0;
+  bool have = false;                 // a distribution source is set
+  int rule_min_pts = 0, rule_cov_mode = 0;   // the leaf rule the Gaussians below were derived under
+  double rule_eig = 0.0;
+  DevBuf<double> gauss;              // the accepted Gaussians in input order: {mean xyz, cov xx xy xz yy yz zz}
+  DevBuf<int32_t> gcount, gindex;    // ... their counts and their records
+  size_t n_accepted = 0;
+  DevBuf<VoxelRecord> frec;          // finalize_leaf's outputs for the records (scratch of the derivation)
+  DevBuf<float> fcent;
+  DevBuf<LeafStats> fstats;
+  DevBuf<int> fcell;                 // record r -> r if it was accepted, else -1
+  DevBuf<int> bad;                   // the device setter's argument check
+  PinBuf<int> bad_h;
+  DevBuf<double> tleaf;              // the target's leaves, 9 doubles per slot
+  uint64_t tleaf_gen = 0;            // TargetState::gen() of the target they were gathered from
+  bool tleaf_valid = false;
+  DevBuf<double> rows, out;          // per-block rows of K poses, their K x EV_WORDS sums
+  PinBuf<double> out_h;
+  void release() {
+    rcount.release(); rmom.release(); gauss.release(); gcount.release(); gindex.release(); frec.release(); fcent.release();
+    fstats.release(); fcell.release(); bad.release(); bad_h.release(); tleaf.release(); rows.release(); out.release();
+    out_h.release();
+    n_records = n_accepted = 0;
+    have = tleaf_valid = false;
+  }
+};
+
 // The voxel map's table, as its kernels take it (by value) and as growth, crop and carve replace it (map_replace_table).
 struct MapTable {
   unsigned long long* keys = nullptr;  // capacity words, ~0 = empty
@@ -367,6 +403,7 @@ struct ndt_handle {
   // source
   DevBuf<float> sx, sy, sz;
   size_t n_src = 0;
+  D2dBufs d2d;                       // the distribution source of ndt_*_d2d and the target's leaves for it (ndt_d2d.hip)
   // the same points in block order of the target grid (see sort_source_by_blocks); valid until
   // the source or the target changes
   DevBuf<float> ox, oy, oz;

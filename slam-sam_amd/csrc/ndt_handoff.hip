@@ -101,6 +101,7 @@ IndexReuse target_retire(ndt_handle* h, size_t kept_cloud_n) {
   const IndexReuse reuse = h->tgt.retire(kept_cloud_n);
   h->src_sorted = false;
   h->prec_valid = false;
+  h->d2d.tleaf_valid = false;   // (the D2D evaluation's copy of the leaves goes with the target)
   h->build_pending = false;
   h->deferred_rc = 0;
   h->deferred_msg.clear();
@@ -125,7 +126,10 @@ int target_publish(ndt_handle* h, TargetKind kind, const GridGeom& geom, const i
   return h->record_format == NDT_RECORDS_PACKED48 ? pack_records(h, false) : NDT_OK;
 }
 
-void target_drop(ndt_handle* h) { h->tgt.drop(); }
+void target_drop(ndt_handle* h) {
+  h->tgt.drop();
+  h->d2d.tleaf_valid = false;
+}
 
 // everything of a build that does not depend on the attempt: state reset, allocations, constants
 int build_begin(ndt_handle* h, const float* x, const float* y, const float* z, size_t n, ndt_handle::BuildRun& br) {
