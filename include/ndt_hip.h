@@ -935,6 +935,76 @@ int64_t ndt_export_source_distributions(ndt_handle* h, double* mean3, double* co
 int ndt_eval_derivatives_d2d(ndt_handle* h, const double* poses6, int K, int compute_hessian, double* out);
 int ndt_align_d2d(ndt_handle* h, const float guess_colmajor[16], ndt_result* out);
 
+/* Scan Context place recognition (Kim & Kim, IROS 2018) over the device keyframe archive: which archived scan shows this
+ * place again, and under which heading -- the question in front of ndt_align_batch / ndt_align_d2d (the relative pose) and
+ * ndt_map_transform / ndt_map_import_state_posed (the correction).  A scan becomes an n_rings x n_sectors matrix of
+ * maximum heights around the sensor; two matrices are compared by the mean cosine distance of their columns, minimised
+ * over ALL cyclic column shifts, against EVERY descriptor of the bank in one launch (no ring key, no k-d tree).  The best
+ * shift is the relative yaw.  Everything below is IEEE arithmetic rounded as written, no contraction; the results equal a
+ * NumPy restatement bit for bit (tests/test_scan_context_cpu.py).
+ * PARAMETERS (R = n_rings, S = n_sectors): 1 <= R <= 32, 3 <= S <= 128, max_radius finite and > 0, z_sign exactly +1 or
+ * -1, lift finite, min_points_per_bin >= 1; anything else is NDT_ERR_INVALID_ARG and the previous state stays.  Defaults:
+ * 20, 60, 80.0f, +1.0f, 2.0f, 1.  ndt_scan_context_set_params with a CHANGE clears the descriptor bank (its entries were
+ * made under other parameters); the same parameters again change nothing.
+ * THE DESCRIPTOR RULE
+ *    sector table  dir[k] = ((float)cos(2 pi k / S), (float)sin(2 pi k / S)), cosine and sine computed by the host in f64
+ *                  and rounded to f32 once.  ndt_scan_context_sector_table (host only, S x 2 floats) returns it and the
+ *                  engine uploads this very table.
+ *    a point       (x, y, z) in f32 is SKIPPED when a coordinate is not finite, when x == 0 && y == 0, or when it fails
+ *                  the ring gate below.
+ *    sector        c_k = (double)dir[k].x * (double)y - (double)dir[k].y * (double)x; both products are exact in f64, so
+ *                  the sign of c_k is exact.  The sector is the one s with c_s >= 0 and c_{(s+1) mod S} < 0 (for S >= 3
+ *                  it exists and is unique off the origin).  The kernel guesses s with atan2f and settles it with these
+ *                  tests.
+ *    ring          r2 = (double)x * (double)x + (double)y * (double)y, rho = sqrt(r2); the point is skipped unless
+ *                  rho < (double)max_radius; ring = min((int)(rho * (double)R / (double)max_radius), R - 1).
+ *    height        hgt = z_sign * z + lift in f32 (the product is exact: one rounding).
+ *    bin (ring, s) count = the unskipped points of the bin (int32); desc = the maximum over them of max(hgt, +0.0f), and
+ *                  +0.0f when count < min_points_per_bin.
+ *    layout        desc[ring * S + s], count likewise.
+ * Maximum and integer sum do not depend on order: the kernel's integer atomics (on the bit pattern of the non-negative
+ * floats, and on the counts) are deterministic, and the host, device and keyframe forms give the same bits.  n == 0 gives
+ * the all-zero descriptor.
+ * THE MATCH RULE (Q the query, C a bank entry, both R x S f32; all arithmetic f64)
+ *    nQ[j] = sqrt(sum_r (double)Q[r][j]^2), r ascending, one rounding per addition; nC likewise.
+ *    for each shift n = 0 .. S-1: sum = 0, m = 0; for j = 0 .. S-1 ascending, jj = (j + n) mod S: the column is skipped
+ *    when nQ[j] == 0 or nC[jj] == 0, otherwise dot = sum_r (double)Q[r][j] * (double)C[r][jj] (r ascending),
+ *    sum += 1.0 - dot / (nQ[j] * nC[jj]), m += 1;  d(n) = m > 0 ? sum / m : 1.0.
+ *    distance = min_n d(n) (d(0) first, then every d(n) < the best so far), shift = the smallest n that attains it,
+ *    columns = that shift's m.
+ * yaw = shift * 2 pi / S wrapped to (-pi, pi]; Rz(yaw) about the frame's own z axis is the guess for aligning the QUERY
+ * scan (source) to the CANDIDATE scan (target): a sensor yawed by +psi sees the world at azimuth alpha - psi, so
+ * Q[:, j] ~ C[:, j + psi S / 2 pi].  Fixed order, no float atomics: an entry matched in a bank of 10 000 has the bits it has
+ * when matched alone.
+ * THE CALLS.  A NULL handle or a NULL required pointer is NDT_ERR_INVALID_ARG before the handle is read.  Every call is
+ * complete when it returns and is ordered on the handle's stream like the other blocking calls.
+ *  - ndt_scan_context (host cloud, xyz + stride as ndt_set_source) / _device (three device arrays; d_desc, d_count device
+ *    memory of R x S words) / _keyframe (the archived scan `id`; the descriptor goes into the bank under the same id,
+ *    replacing an entry, and optionally to the host): desc R x S floats, count R x S int32 (may be NULL).  An unknown
+ *    keyframe id is NDT_ERR_INVALID_ARG.
+ *  - the bank: _bank_put stores a saved descriptor under `id` (replacing), _bank_get reads one back, _bank_erase drops one,
+ *    _bank_clear all, _bank_count counts; an unknown id in get / erase is NDT_ERR_INVALID_ARG.  ndt_keyframe_erase does not
+ *    touch the bank.
+ *  - ndt_scan_context_match (query from the host) / _match_keyframe (query = bank entry `id`, read on the device; its own
+ *    entry is among the results; an unknown id is NDT_ERR_INVALID_ARG): return m, the number of bank entries, and fill ids,
+ *    distance, shift, columns (each may be NULL) for all m entries in ascending id order; cap < m is NDT_ERR_INVALID_ARG;
+ *    an empty bank returns 0. */
+typedef struct { int32_t n_rings, n_sectors; float max_radius, z_sign, lift; int32_t min_points_per_bin; } ndt_scan_context_params;
+void    ndt_scan_context_default_params(ndt_scan_context_params* p);
+int     ndt_scan_context_set_params(ndt_handle* h, const ndt_scan_context_params* p);
+int     ndt_scan_context_get_params(const ndt_handle* h, ndt_scan_context_params* p);
+int     ndt_scan_context_sector_table(int n_sectors, float* dir_xy);
+int     ndt_scan_context(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, float* desc, int32_t* count_or_null);
+int     ndt_scan_context_device(ndt_handle* h, const float* dx, const float* dy, const float* dz, size_t n, float* d_desc, int32_t* d_count_or_null);
+int     ndt_scan_context_keyframe(ndt_handle* h, int64_t id, float* desc_or_null, int32_t* count_or_null);
+int     ndt_scan_context_bank_put(ndt_handle* h, int64_t id, const float* desc);
+int     ndt_scan_context_bank_get(ndt_handle* h, int64_t id, float* desc);
+int     ndt_scan_context_bank_erase(ndt_handle* h, int64_t id);
+int     ndt_scan_context_bank_clear(ndt_handle* h);
+int64_t ndt_scan_context_bank_count(const ndt_handle* h);
+int64_t ndt_scan_context_match(ndt_handle* h, const float* desc, int64_t* ids, double* distance, int32_t* shift, int32_t* columns, size_t cap);
+int64_t ndt_scan_context_match_keyframe(ndt_handle* h, int64_t id, int64_t* ids, double* distance, int32_t* shift, int32_t* columns, size_t cap);
+
 /* setRegularizationPose (ref: run/pipeline_ligo_tc.cpp:531) */
 int ndt_set_regularization_pose(ndt_handle* h, const float pose_colmajor[16]);
 int ndt_clear_regularization_pose(ndt_handle* h);

@@ -968,6 +968,104 @@ class NormalDistributionsTransform
     if (status_ == NDT_OK) n_src_ = 0;  // align()'s output cloud is not filled on this path
   }
 
+  // ---- Scan Context place recognition over the keyframe archive (ndt_scan_context* in ndt_hip.h): a scan's
+  // rings x sectors descriptor of maximum heights, the descriptor bank beside the archive, and the match of one query with
+  // every entry at every column shift.  Not part of pclomp.  A descriptor is n_rings * n_sectors floats, row = ring. ----
+  void setScanContextParams(const ndt_scan_context_params& p) {   // a change clears the bank
+    status_ = h_ ? ndt_scan_context_set_params(h_, &p) : NDT_ERR_NO_DEVICE;
+  }
+  ndt_scan_context_params getScanContextParams() {
+    ndt_scan_context_params p;
+    ndt_scan_context_default_params(&p);
+    status_ = h_ ? ndt_scan_context_get_params(h_, &p) : NDT_ERR_NO_DEVICE;
+    return p;
+  }
+  // the descriptor of a cloud in the sensor's frame; counts_or_null receives the points per bin.  Empty on error.
+  template <class Cloud>
+  std::vector<float> scanContext(const Cloud& cloud, std::vector<int32_t>* counts_or_null = nullptr) {
+    std::vector<float> desc;
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return desc; }
+    const ndt_scan_context_params p = getScanContextParams();
+    if (status_ != NDT_OK) return desc;
+    const size_t bins = (size_t)p.n_rings * (size_t)p.n_sectors;
+    desc.assign(bins, 0.0f);
+    if (counts_or_null) counts_or_null->assign(bins, 0);
+    int32_t* cnt = counts_or_null ? counts_or_null->data() : nullptr;
+    status_ = cloud.points.empty()
+                  ? ndt_scan_context(h_, nullptr, 0, 12, desc.data(), cnt)
+                  : ndt_scan_context(h_, &cloud.points[0].x, cloud.points.size(), sizeof(cloud.points[0]), desc.data(), cnt);
+    if (status_ != NDT_OK) desc.clear();
+    return desc;
+  }
+  // device arrays in, device memory of n_rings * n_sectors words out (d_count may be null)
+  void scanContextDevice(const float* dx, const float* dy, const float* dz, size_t n, float* d_desc, int32_t* d_count = nullptr) {
+    status_ = h_ ? ndt_scan_context_device(h_, dx, dy, dz, n, d_desc, d_count) : NDT_ERR_NO_DEVICE;
+  }
+  // the archived scan `id`: its descriptor goes into the bank under the same id and comes back
+  std::vector<float> scanContextKeyframe(int64_t id, std::vector<int32_t>* counts_or_null = nullptr) {
+    std::vector<float> desc;
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return desc; }
+    const ndt_scan_context_params p = getScanContextParams();
+    if (status_ != NDT_OK) return desc;
+    const size_t bins = (size_t)p.n_rings * (size_t)p.n_sectors;
+    desc.assign(bins, 0.0f);
+    if (counts_or_null) counts_or_null->assign(bins, 0);
+    status_ = ndt_scan_context_keyframe(h_, id, desc.data(), counts_or_null ? counts_or_null->data() : nullptr);
+    if (status_ != NDT_OK) desc.clear();
+    return desc;
+  }
+  void scanContextBankPut(int64_t id, const std::vector<float>& desc) {
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return; }
+    const ndt_scan_context_params p = getScanContextParams();
+    if (status_ != NDT_OK) return;
+    if (desc.size() != (size_t)p.n_rings * (size_t)p.n_sectors) { status_ = NDT_ERR_INVALID_ARG; return; }
+    status_ = ndt_scan_context_bank_put(h_, id, desc.data());
+  }
+  std::vector<float> scanContextBankGet(int64_t id) {
+    std::vector<float> desc;
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return desc; }
+    const ndt_scan_context_params p = getScanContextParams();
+    if (status_ != NDT_OK) return desc;
+    desc.assign((size_t)p.n_rings * (size_t)p.n_sectors, 0.0f);
+    status_ = ndt_scan_context_bank_get(h_, id, desc.data());
+    if (status_ != NDT_OK) desc.clear();
+    return desc;
+  }
+  void scanContextBankErase(int64_t id) { status_ = h_ ? ndt_scan_context_bank_erase(h_, id) : NDT_ERR_NO_DEVICE; }
+  void scanContextBankClear() { status_ = h_ ? ndt_scan_context_bank_clear(h_) : NDT_ERR_NO_DEVICE; }
+  int64_t scanContextBankCount() const { return h_ ? ndt_scan_context_bank_count(h_) : 0; }
+  // one element per bank entry, ascending ids; best(): the entry of least distance (-1: the bank is empty)
+  struct ScanContextMatches {
+    std::vector<int64_t> ids;
+    std::vector<double> distance;
+    std::vector<int32_t> shift, columns;
+    size_t size() const { return ids.size(); }
+    long best() const {
+      long at = -1;
+      for (size_t i = 0; i < distance.size(); ++i)
+        if (at < 0 || distance[i] < distance[(size_t)at]) at = (long)i;
+      return at;
+    }
+  };
+  ScanContextMatches scanContextMatch(const std::vector<float>& desc) {
+    ScanContextMatches out;
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return out; }
+    const ndt_scan_context_params p = getScanContextParams();
+    if (status_ != NDT_OK) return out;
+    if (desc.size() != (size_t)p.n_rings * (size_t)p.n_sectors) { status_ = NDT_ERR_INVALID_ARG; return out; }
+    return scan_context_matches_(true, desc.data(), 0);
+  }
+  // the query is the bank entry `id`, read on the device; it is among the results
+  ScanContextMatches scanContextMatchKeyframe(int64_t id) {
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return ScanContextMatches(); }
+    return scan_context_matches_(false, nullptr, id);
+  }
+  // yaw = shift * 2 pi / n_sectors wrapped to (-pi, pi]: Rz(yaw) is the guess that aligns the query scan to the candidate
+  static double scanContextYaw(int shift, int n_sectors) {
+    const double two_pi = 6.283185307179586476925286766559;
+    return (double)(2 * shift > n_sectors ? shift - n_sectors : shift) * (two_pi / (double)n_sectors);
+  }
+
   // ---- deskew: a scan expressed in one pose, from per-point times and a pose trajectory (ndt_deskew* in ndt_hip.h:
   // position blended linearly, attitude by slerp, times clamped to the knots; ref_pose null = the last knot), with the
   // acquisition filter of the lidar callback in the same pass (filter null: every point comes back, a non-finite one
@@ -1421,6 +1519,22 @@ class NormalDistributionsTransform
       output.points[i].y = xyz[3 * i + 1];
       output.points[i].z = xyz[3 * i + 2];
     }
+  }
+
+  // both match calls: the bank's size, then every entry's result (h_ is set)
+  ScanContextMatches scan_context_matches_(bool from_host, const float* desc, int64_t id) {
+    ScanContextMatches out;
+    const int64_t n = ndt_scan_context_bank_count(h_);
+    if (n < 0) { status_ = (int)n; return out; }
+    const size_t m = (size_t)n;
+    out.ids.resize(m); out.distance.resize(m); out.shift.resize(m); out.columns.resize(m);
+    const int64_t got = from_host ? ndt_scan_context_match(h_, desc, out.ids.data(), out.distance.data(), out.shift.data(),
+                                                           out.columns.data(), m)
+                                  : ndt_scan_context_match_keyframe(h_, id, out.ids.data(), out.distance.data(),
+                                                                    out.shift.data(), out.columns.data(), m);
+    status_ = got < 0 ? (int)got : NDT_OK;
+    if (got != n) out = ScanContextMatches();
+    return out;
   }
 
   ndt_params prm_{};

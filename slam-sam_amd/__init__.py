@@ -114,6 +114,12 @@ class MapCarveParams(C.Structure):
                 ("dry_run", C.c_int), ("reserved", C.c_int * 3)]
 
 
+class ScanContextParams(C.Structure):
+    """ndt_scan_context_params (ndt_scan_context_default_params: 20, 60, 80.0, +1.0, 2.0, 1)"""
+    _fields_ = [("n_rings", C.c_int32), ("n_sectors", C.c_int32), ("max_radius", C.c_float), ("z_sign", C.c_float),
+                ("lift", C.c_float), ("min_points_per_bin", C.c_int32)]
+
+
 class MapCarveResult(C.Structure):
     _fields_ = [("n_rays", C.c_int64), ("n_rays_skipped", C.c_int64), ("n_steps", C.c_int64), ("n_voxels_crossed", C.c_int64),
                 ("n_voxels_hit", C.c_int64), ("n_removed", C.c_int64), ("n_points_removed", C.c_int64)]
@@ -314,6 +320,10 @@ ABI_SYMBOLS = [
     "ndt_map_transform", "ndt_map_import_state_posed", "ndt_map_import_state_posed_device",
     "ndt_set_source_distributions", "ndt_set_source_distributions_device", "ndt_source_distributions_info",
     "ndt_export_source_distributions", "ndt_eval_derivatives_d2d", "ndt_align_d2d",
+    "ndt_scan_context_default_params", "ndt_scan_context_set_params", "ndt_scan_context_get_params",
+    "ndt_scan_context_sector_table", "ndt_scan_context", "ndt_scan_context_device", "ndt_scan_context_keyframe",
+    "ndt_scan_context_bank_put", "ndt_scan_context_bank_get", "ndt_scan_context_bank_erase", "ndt_scan_context_bank_clear",
+    "ndt_scan_context_bank_count", "ndt_scan_context_match", "ndt_scan_context_match_keyframe",
 ]
 
 _lib = None
@@ -449,6 +459,25 @@ def lib():
         L.ndt_export_source_distributions.restype = C.c_int64
         L.ndt_eval_derivatives_d2d.argtypes = [vp, dp, C.c_int, C.c_int, dp]
         L.ndt_align_d2d.argtypes = [vp, fp, C.POINTER(Result)]
+        scp, i64 = C.POINTER(ScanContextParams), C.c_int64
+        L.ndt_scan_context_default_params.restype = None
+        L.ndt_scan_context_default_params.argtypes = [scp]
+        L.ndt_scan_context_set_params.argtypes = [vp, scp]
+        L.ndt_scan_context_get_params.argtypes = [vp, scp]
+        L.ndt_scan_context_sector_table.argtypes = [C.c_int, fp]
+        L.ndt_scan_context.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, vp]
+        L.ndt_scan_context_device.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp]
+        L.ndt_scan_context_keyframe.argtypes = [vp, i64, fp, vp]
+        L.ndt_scan_context_bank_put.argtypes = [vp, i64, fp]
+        L.ndt_scan_context_bank_get.argtypes = [vp, i64, fp]
+        L.ndt_scan_context_bank_erase.argtypes = [vp, i64]
+        L.ndt_scan_context_bank_clear.argtypes = [vp]
+        L.ndt_scan_context_bank_count.argtypes = [vp]
+        L.ndt_scan_context_bank_count.restype = i64
+        L.ndt_scan_context_match.argtypes = [vp, fp, vp, dp, vp, vp, C.c_size_t]
+        L.ndt_scan_context_match.restype = i64
+        L.ndt_scan_context_match_keyframe.argtypes = [vp, i64, vp, dp, vp, vp, C.c_size_t]
+        L.ndt_scan_context_match_keyframe.restype = i64
         L.ndt_map_carve_default_params.restype = None
         L.ndt_map_carve_default_params.argtypes = [C.POINTER(MapCarveParams)]
         L.ndt_map_carve_device.argtypes = [vp, vp, vp, vp, C.c_size_t, fp, dp, C.POINTER(MapCarveParams),
@@ -1933,6 +1962,151 @@ def alignDistributions(ndt, guess=None):
     d = result_to_dict(r)
     d["iteration_num"] = d["iterations"]
     return d["T"], d
+
+
+# --- Scan Context place recognition over the keyframe archive (ndt_scan_context*).  Functions on an engine, as
+# above.  A descriptor is [n_rings, n_sectors] float32, its counts int32 of the same shape. ---
+def scanContextDefaultParams():
+    p = ScanContextParams()
+    lib().ndt_scan_context_default_params(C.byref(p))
+    return p
+
+
+def getScanContextParams(ndt):
+    """dict(n_rings, n_sectors, max_radius, z_sign, lift, min_points_per_bin) of the engine"""
+    p = ScanContextParams()
+    ndt._check(lib().ndt_scan_context_get_params(ndt._h, C.byref(p)))
+    return {k: getattr(p, k) for k, _ in ScanContextParams._fields_}
+
+
+def setScanContextParams(ndt, **kw):
+    """Changes the named parameters (the others stay); a change clears the descriptor bank."""
+    unknown = set(kw) - {k for k, _ in ScanContextParams._fields_}
+    if unknown:
+        raise ValueError("unknown Scan Context parameter(s): %s" % sorted(unknown))
+    for k in ("n_rings", "n_sectors", "min_points_per_bin"):
+        if k in kw and int(kw[k]) != kw[k]:
+            raise ValueError("%s must be an integer" % k)
+    p = ScanContextParams(**{k: (float(v) if k in ("max_radius", "z_sign", "lift") else int(v))
+                             for k, v in dict(getScanContextParams(ndt), **kw).items()})
+    ndt._check(lib().ndt_scan_context_set_params(ndt._h, C.byref(p)))
+
+
+def scanContextSectorTable(n_sectors):
+    """dir [S, 2] float32: ((float)cos(2 pi k / S), (float)sin(2 pi k / S)) as the engine uploads it (host only)"""
+    if int(n_sectors) != n_sectors or not 3 <= int(n_sectors) <= 128:
+        raise ValueError("n_sectors must be an integer in 3 .. 128")
+    d = np.zeros((int(n_sectors), 2), np.float32)
+    rc = lib().ndt_scan_context_sector_table(int(n_sectors), _fp(d))
+    if rc != 0:
+        raise NdtError(rc, "ndt_scan_context_sector_table")
+    return d
+
+
+def scanContextYaw(shift, n_sectors):
+    """yaw = shift * 2 pi / S wrapped to (-pi, pi]: Rz(yaw) is the guess that aligns the query scan to the candidate"""
+    s, S = int(shift), int(n_sectors)
+    if S < 3 or not 0 <= s < S:
+        raise ValueError("shift must lie in 0 .. n_sectors - 1")
+    return (s - S if 2 * s > S else s) * (2.0 * np.pi / S)
+
+
+def _sc_shape(ndt):
+    p = getScanContextParams(ndt)
+    return p["n_rings"], p["n_sectors"]
+
+
+def _sc_desc(ndt, desc):
+    d = np.asarray(desc)
+    if d.ndim != 2 or d.dtype.kind not in "fiu":
+        raise ValueError("a descriptor must be a [n_rings, n_sectors] array of numbers")
+    d = np.ascontiguousarray(d, dtype=np.float32)
+    if d.shape != _sc_shape(ndt):
+        raise ValueError("the descriptor is %s, the engine's parameters say %s" % (d.shape, _sc_shape(ndt)))
+    return d
+
+
+def scanContext(ndt, cloud, with_count=False):
+    """The Scan Context descriptor of a host cloud (N x >= 3 float32, the sensor at the origin): desc [R, S] float32, with
+    with_count also the points per bin [R, S] int32."""
+    a = ndt._xyz(cloud)
+    R, S = _sc_shape(ndt)
+    desc, count = np.zeros((R, S), np.float32), np.zeros((R, S), np.int32)
+    stride = a.strides[0] if len(a) else a.itemsize * a.shape[1]
+    ndt._check(lib().ndt_scan_context(ndt._h, a.ctypes.data if len(a) else None, len(a), stride, _fp(desc),
+                                      count.ctypes.data if with_count else None))
+    return (desc, count) if with_count else desc
+
+
+def scanContextDevice(ndt, dx, dy, dz, n, d_desc, d_count=None):
+    """As scanContext from three device arrays (integer addresses) into device memory of R x S words."""
+    if int(n) < 0 or not d_desc or (int(n) and (not dx or not dy or not dz)):
+        raise ValueError("device pointers are needed")
+    ndt._check(lib().ndt_scan_context_device(ndt._h, dx, dy, dz, int(n), d_desc, d_count))
+
+
+def scanContextKeyframe(ndt, kf_id, with_count=False):
+    """The descriptor of the archived scan `kf_id`, stored in the bank under the same id and returned."""
+    kf_id = _sc_id(kf_id)
+    R, S = _sc_shape(ndt)
+    desc, count = np.zeros((R, S), np.float32), np.zeros((R, S), np.int32)
+    ndt._check(lib().ndt_scan_context_keyframe(ndt._h, kf_id, _fp(desc), count.ctypes.data if with_count else None))
+    return (desc, count) if with_count else desc
+
+
+def _sc_id(i):
+    if isinstance(i, (bool, float)) or int(i) != i:
+        raise ValueError("an id must be an integer")
+    return int(i)
+
+
+def scanContextBankPut(ndt, bank_id, desc):
+    bank_id = _sc_id(bank_id)
+    d = _sc_desc(ndt, desc)
+    ndt._check(lib().ndt_scan_context_bank_put(ndt._h, bank_id, _fp(d)))
+
+
+def scanContextBankGet(ndt, bank_id):
+    bank_id = _sc_id(bank_id)
+    d = np.zeros(_sc_shape(ndt), np.float32)
+    ndt._check(lib().ndt_scan_context_bank_get(ndt._h, bank_id, _fp(d)))
+    return d
+
+
+def scanContextBankErase(ndt, bank_id):
+    ndt._check(lib().ndt_scan_context_bank_erase(ndt._h, _sc_id(bank_id)))
+
+
+def scanContextBankClear(ndt):
+    ndt._check(lib().ndt_scan_context_bank_clear(ndt._h))
+
+
+def scanContextBankCount(ndt):
+    return int(lib().ndt_scan_context_bank_count(ndt._h))
+
+
+def _sc_match(ndt, call):
+    m = scanContextBankCount(ndt)
+    ids, dist = np.zeros(m, np.int64), np.zeros(m, np.float64)
+    shift, cols = np.zeros(m, np.int32), np.zeros(m, np.int32)
+    got = call(ids.ctypes.data, _dp(dist), shift.ctypes.data, cols.ctypes.data, m)
+    if got < 0:
+        ndt._check(int(got))
+    assert got == m
+    return dict(ids=ids, distance=dist, shift=shift, columns=cols)
+
+
+def scanContextMatch(ndt, desc):
+    """The query descriptor against every bank entry at every column shift: dict(ids, distance, shift, columns), one
+    element per entry in ascending id order."""
+    d = _sc_desc(ndt, desc)
+    return _sc_match(ndt, lambda *a: lib().ndt_scan_context_match(ndt._h, _fp(d), *a))
+
+
+def scanContextMatchKeyframe(ndt, bank_id):
+    """As scanContextMatch with the bank entry `bank_id` as the query (read on the device; it is among the results)."""
+    bank_id = _sc_id(bank_id)
+    return _sc_match(ndt, lambda *a: lib().ndt_scan_context_match_keyframe(ndt._h, bank_id, *a))
 
 
 def comm_unique_id():

@@ -11,6 +11,8 @@
 //   ndt_map_repose.hip the map moved by a pose, and records merged under one (k_maprepose_* kernels)
 //   ndt_d2d.hip        distribution-to-distribution registration: a source of Gaussians from map records, its evaluation
 //                      and align against the target's leaves (k_d2d_* kernels)
+//   ndt_scan_context.hip  Scan Context place recognition: a scan's rings x sectors descriptor, the descriptor bank beside
+//                      the keyframe archive and the all-shifts match against it (k_sc_* kernels)
 //   ndt_map_carve.hip  free-space carving of the map: voxels that a scan's rays pass through go (k_mapcarve_* kernels)
 //   ndt_deskew.hip     motion compensation of a scan along a pose trajectory + the acquisition filter (its kernels included)
 //   ndt_unproject.hip  a lidar range image -> points through the scan model's tables, fused with that filter and deskew
@@ -285,6 +287,35 @@ struct D2dBufs {
   }
 };
 
+// Scan Context (ndt_scan_context.hip): the parameters, the sector table they imply, the scratch of a descriptor call and
+// the descriptor bank -- slots of n_rings x n_sectors floats in one device array, `ids` naming the slot of every entry
+// (ascending ids: the order of a match's outputs).  ndt_keyframe_erase leaves the bank alone; a parameter change clears it.
+struct ScanContextBufs {
+  ndt_scan_context_params prm{20, 60, 80.0f, 1.0f, 2.0f, 1};
+  bool table_valid = false;          // `dir` holds the table of prm.n_sectors
+  DevBuf<float> dir;                 // S x 2: ndt_scan_context_sector_table's floats
+  DevBuf<uint32_t> acc;              // [desc bits (R x S) | counts (R x S)]: what the blocks' LDS copies merge into
+  DevBuf<float> ux, uy, uz;          // a host scan on the device
+  DevBuf<float> desc;                // a descriptor on its way to the host, or a query on its way up
+  DevBuf<int32_t> count;
+  DevBuf<float> bank;                // bank_slots() slots of bins() floats
+  std::map<int64_t, int> ids;        // entry -> slot
+  std::vector<int> free_slots;
+  DevBuf<int> order;                 // the slots in ascending id order, as the match kernel reads them
+  bool order_valid = false;
+  DevBuf<double> mdist;              // a match's outputs, one per entry
+  DevBuf<int32_t> mshift, mcols;
+  size_t bins() const { return (size_t)prm.n_rings * (size_t)prm.n_sectors; }
+  size_t bank_slots() const { return bank.cap / bins(); }
+  void clear_bank() { ids.clear(); free_slots.clear(); order_valid = false; }
+  void release() {
+    dir.release(); acc.release(); ux.release(); uy.release(); uz.release(); desc.release(); count.release(); bank.release();
+    order.release(); mdist.release(); mshift.release(); mcols.release();
+    table_valid = false;
+    clear_bank();
+  }
+};
+
 // The voxel map's table, as its kernels take it (by value) and as growth, crop and carve replace it (map_replace_table).
 struct MapTable {
   unsigned long long* keys = nullptr;  // capacity words, ~0 = empty
@@ -403,6 +434,7 @@ struct ndt_handle {
   // source
   DevBuf<float> sx, sy, sz;
   size_t n_src = 0;
+  ScanContextBufs sc;                // Scan Context: parameters, sector table, descriptor bank (ndt_scan_context.hip)
   D2dBufs d2d;                       // the distribution source of ndt_*_d2d and the target's leaves for it (ndt_d2d.hip)
   // the same points in block order of the target grid (see sort_source_by_blocks); valid until
   // the source or the target changes
