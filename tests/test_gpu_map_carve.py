@@ -72,11 +72,11 @@ def build(pkg, pieces, pose=None, moments=True, intensities=None, capacity=0):
     return ndt
 
 
-def check_carve(ndt, cloud, origin, pose, reset_cap, moments=True, call=None, **params):
+def check_carve(ndt, cloud, origin, pose, reset_cap, moments=True, call=None, leaf=LEAF, **params):
     """One carve against the restatement: result, exported state, info.  Returns (state before, restatement)."""
     before, info0 = ndt.mapExportState(), ndt.mapInfo()
     prm = dict(DEFAULTS, **params)
-    want = carve_numpy(before["ijk"], before["count"], cloud, origin, LEAF, pose, **prm)
+    want = carve_numpy(before["ijk"], before["count"], cloud, origin, leaf, pose, **prm)
     got = (call or ndt.mapCarve)(cloud, origin, pose=pose, **params)
     print("carve: %s" % got)
     assert got == result_of(want)

@@ -172,7 +172,7 @@ def test_growth_and_collisions(pkg):
 
 
 def test_one_crowded_voxel_and_the_edges_of_the_index(pkg):
-    leaf = 0.5                                                               # inv_leaf = 2 exactly: faces are exact
+    leaf = 0.5                       # inv_leaf = 2 exactly, so every arithmetic agrees on a face; inexact leaves: test_gpu_map_sweep.py
     rng = np.random.default_rng(7)
     crowd = rng.uniform([-0.5, -0.5, -0.5], [-0.001, -0.001, -0.001], (5000, 3)).astype(np.float32)   # voxel (-1, -1, -1)
     around = rng.uniform([-6, -6, -2], [6, 6, 2], (400, 3)).astype(np.float32)
