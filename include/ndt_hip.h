@@ -883,6 +883,69 @@ int ndt_map_import_state_posed_device(ndt_handle* h, float leaf, const int32_t* 
                                       const float* sums4, const double* moments9, size_t n,
                                       const double pose16_colmajor[16]);
 
+/* Levels: the map at leaf * 2^L, made from its own sums, and coarse-to-fine alignment over them.  The points are not
+ * kept, but a coarse voxel's sums are the sums of its children's sums, and for a power-of-two factor the parent of a fine
+ * voxel is the voxel the point rule gives at the coarse leaf: 1.0f / (leaf * 2^L) is inv_leaf / 2^L exactly and
+ * p * (inv_leaf / 2^L) is fl(p * inv_leaf) / 2^L exactly (a division by a power of two does not round a normal f32), so
+ * floor(p * inv_leaf_L) == floor_div(floor(p * inv_leaf), 2^L).  A factor that is no power of two has no such identity.
+ * THE RULE.  Level L (1 <= L <= NDT_MAP_MAX_LEVEL) of a map with leaf l is a map with leaf_L = (float)(l * 2^L) and
+ * inv_leaf_L = 1.0f / leaf_L; a level whose leaf_L is not finite is refused (NDT_ERR_INVALID_ARG).
+ *    voxel       every occupied voxel (i, j, k) belongs to the level voxel (i >> L, j >> L, k >> L), an arithmetic shift
+ *                (floor_div by 2^L).  That is floor(p * inv_leaf_L) in f32 for every point p of the fine voxel whose
+ *                scaled coordinate p * inv_leaf is zero or a normal f32 (a subnormal one, |p| ~ 1e-45, may differ).
+ *    count       the sum of the children's counts.  A level voxel whose count would exceed INT32_MAX refuses the level
+ *                as a whole (NDT_ERR_GRID_OVERFLOW; nothing is cached, map and target are as they were).
+ *    sums        each of the four float sums in f32 and each of the nine moments in f64 starts from +0 and adds the
+ *                children's values one at a time in ascending child (k, j, i) order, one rounding per add.  In a map
+ *                without intensity the intensity sum is 0; without moments there are no moments.
+ * This is ndt_map_import_state of the map's ndt_map_export_state records with ijk shifted, into an empty map of leaf
+ * leaf_L, bit for bit.  A level is derived on the device when a call first needs it (no record passes through the host)
+ * and cached until the map's content changes (an add, an import, crop, carve, transform, ndt_map_enable_moments);
+ * ndt_map_reset, ndt_map_clear and ndt_destroy free the levels.  The level's table has the smallest power-of-two capacity
+ * >= 2 x (the map's voxels), at least 64.
+ * `level` == 0 is valid in every call below and means the map itself: bit for bit ndt_map_get_info /
+ * ndt_map_export_state / _device / ndt_set_target_from_map_moments.  A level outside 0 .. NDT_MAP_MAX_LEVEL is
+ * NDT_ERR_INVALID_ARG.  Boxes select level voxels with the level's own inv_leaf_L, as the box rule above reads.
+ *  - ndt_map_level_info: derives if stale; leaf, with_intensity, n_voxels, n_points, capacity and the tight min_ijk /
+ *    max_ijk are the level's (capacity 0 for a level of an empty map), n_points_dropped, n_adds and n_grows the map's.
+ *  - ndt_map_export_state_level / _device: ndt_map_export_state / _device of the level.
+ *  - ndt_set_target_from_map_level: ndt_set_target_from_map_moments of the level; ndt_params::resolution must be
+ *    bit-equal to leaf_L, and the map must keep moments.
+ *  - ndt_map_coarsen: the map BECOMES its level: the level's table replaces the map's, leaf = leaf_L, min_ijk / max_ijk /
+ *    n_voxels are the level's, the cached levels are dropped; n_points, n_points_dropped, n_adds, n_grows and the
+ *    moments / intensity settings are kept.  Later adds continue as on a map of that leaf.  Level 0 is a no-op.
+ *  - ndt_map_levels_drop: frees the cached levels; the map is untouched.
+ *  - ndt_align_map_levels (host code): for each of the n_steps (1 .. NDT_MAP_LEVEL_STEPS_MAX) steps in order --
+ *    ndt_set_params with resolution = leaf_L of the step's level, the step's max_iterations and step_size (0 / 0.0: the
+ *    handle's value); ndt_set_target_from_map_level with the box guess translation +- half_extent (NULL: the whole
+ *    level), guess being the previous step's final transform; ndt_align into results[s].  A step that fails stops the call
+ *    with its code; earlier results stay written.  On return, success or failure, the handle's ndt_params are the
+ *    caller's again, restored through ndt_set_params: THE TARGET IS THE LAST STEP'S TARGET when the caller's resolution
+ *    (and the other grid parameters) are that step's, as after a sequence that ends at level 0 of a map whose leaf is
+ *    ndt_params::resolution; otherwise ndt_set_params' own rule applies and the target is dropped (no cloud is kept to
+ *    re-voxelise).  A NULL pointer or n_steps out of range is NDT_ERR_INVALID_ARG with nothing touched.
+ * Every refusal leaves the target and the map as they were.  Source, align state (except through ndt_align_map_levels),
+ * iteration history, evaluation counters and the keyframe archive are untouched; only ndt_set_target_from_map_level and
+ * ndt_align_map_levels replace the target.  Complete when they return. */
+#define NDT_MAP_MAX_LEVEL 6
+#define NDT_MAP_LEVEL_STEPS_MAX 8
+typedef struct ndt_map_level_step {
+  int level;
+  int max_iterations;        /* 0: the handle's */
+  double step_size;          /* 0.0: the handle's */
+} ndt_map_level_step;
+int ndt_map_level_info(ndt_handle* h, int level, ndt_map_info* out);
+int ndt_map_export_state_level(ndt_handle* h, int level, const float box_min[3], const float box_max[3], int32_t* ijk,
+                               int32_t* count, float* sums4, double* moments9, size_t cap, size_t* n_out);
+int ndt_map_export_state_level_device(ndt_handle* h, int level, const float box_min[3], const float box_max[3],
+                                      int32_t* ijk, int32_t* count, float* sums4, double* moments9, size_t cap,
+                                      size_t* n_out);
+int ndt_set_target_from_map_level(ndt_handle* h, int level, const float box_min[3], const float box_max[3]);
+int ndt_map_coarsen(ndt_handle* h, int level);
+int ndt_map_levels_drop(ndt_handle* h);
+int ndt_align_map_levels(ndt_handle* h, const ndt_map_level_step* steps, int n_steps, const float half_extent_or_null[3],
+                         const float guess_colmajor[16], ndt_result* results);
+
 /* Distribution-to-distribution NDT (D2D; Stoyanov et al. 2012): register a submap's voxels -- Gaussians, not points --
  * to the target's.  It estimates the pose that ndt_map_import_state_posed / ndt_map_transform take, from the two maps'
  * own f64 moments; the chain export -> pose -> posed import runs without a record leaving the device.

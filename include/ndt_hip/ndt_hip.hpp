@@ -874,6 +874,63 @@ class NormalDistributionsTransform
                  : NDT_ERR_NO_DEVICE;
   }
 
+  // ---- levels (ndt_map_level_*, ndt_set_target_from_map_level, ndt_map_coarsen, ndt_align_map_levels): the map at
+  // leaf * 2^level made from its own sums on the device, cached until the map changes; level 0 is the map itself.
+  // alignMapLevels runs one align() per step, coarse to fine, each against its level as the target and from the step
+  // before; the adapter's own result (getFinalTransformation, getResult) stays that of the last align(). ----
+  ndt_map_info mapLevelInfo(int level) {
+    ndt_map_info mi{};
+    status_ = h_ ? ndt_map_level_info(h_, level, &mi) : NDT_ERR_NO_DEVICE;
+    return status_ == NDT_OK ? mi : ndt_map_info{};
+  }
+  void mapExportStateLevel(int level, MapState& out, const float* box_min = nullptr, const float* box_max = nullptr) {
+    out = MapState{};
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return; }
+    ndt_map_info mi{};
+    status_ = ndt_map_level_info(h_, level, &mi);
+    if (status_ != NDT_OK) return;
+    out.leaf = mi.leaf;
+    out.with_intensity = mi.with_intensity != 0;
+    const bool mom = mapHasMoments();
+    const size_t cap = (size_t)mi.n_voxels;   // (no selection holds more)
+    out.ijk.resize(3 * cap); out.counts.resize(cap); out.sums.resize(4 * cap); out.moments.resize(mom ? 9 * cap : 0);
+    size_t m = 0;
+    status_ = ndt_map_export_state_level(h_, level, box_min, box_max, out.ijk.data(), out.counts.data(), out.sums.data(),
+                                         mom ? out.moments.data() : nullptr, cap, &m);
+    if (status_ != NDT_OK) m = 0;
+    out.ijk.resize(3 * m); out.counts.resize(m); out.sums.resize(4 * m); out.moments.resize(mom ? 9 * m : 0);
+  }
+  size_t mapExportStateLevelDevice(int level, int32_t* d_ijk, int32_t* d_count, float* d_sums4, double* d_moments9, size_t cap,
+                                   const float* box_min = nullptr, const float* box_max = nullptr) {
+    size_t m = 0;
+    status_ = h_ ? ndt_map_export_state_level_device(h_, level, box_min, box_max, d_ijk, d_count, d_sums4, d_moments9, cap, &m)
+                 : NDT_ERR_NO_DEVICE;
+    return m;
+  }
+  void setInputTargetFromMapLevel(int level, const float* box_min = nullptr, const float* box_max = nullptr) {
+    status_ = h_ ? ndt_set_target_from_map_level(h_, level, box_min, box_max) : NDT_ERR_NO_DEVICE;
+  }
+  void mapCoarsen(int level) { status_ = h_ ? ndt_map_coarsen(h_, level) : NDT_ERR_NO_DEVICE; }
+  void mapLevelsDrop() { status_ = h_ ? ndt_map_levels_drop(h_) : NDT_ERR_NO_DEVICE; }
+  // one ndt_result per step that ran (fewer than steps.size() when a step failed: lastStatus() is its code)
+  std::vector<ndt_result> alignMapLevels(const std::vector<ndt_map_level_step>& steps, const Matrix4f& guess,
+                                         const float* half_extent_or_null = nullptr) {
+    std::vector<ndt_result> out;
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return out; }
+    if (steps.empty() || steps.size() > (size_t)NDT_MAP_LEVEL_STEPS_MAX) { status_ = NDT_ERR_INVALID_ARG; return out; }
+    float g[16];
+    detail::to_colmajor(guess, 4, 4, g);
+    out.resize(steps.size());
+    for (ndt_result& r : out) { std::memset(&r, 0, sizeof(r)); r.iterations = -1; }
+    status_ = ndt_align_map_levels(h_, steps.data(), (int)steps.size(), half_extent_or_null, g, out.data());
+    if (status_ != NDT_OK) {   // keep the steps that were written
+      size_t done = 0;
+      while (done < out.size() && out[done].iterations >= 0) ++done;
+      out.resize(done);
+    }
+    return out;
+  }
+
   // ---- distribution-to-distribution NDT (ndt_set_source_distributions, ndt_eval_derivatives_d2d, ndt_align_d2d): a
   // submap's voxels -- the counts and moments of a MapState -- registered to the target's leaves.  The distribution
   // source is separate from the point source; the adapter's own result (getFinalTransformation, getResult) stays that

@@ -108,6 +108,10 @@ class MapInfo(C.Structure):
                 ("max_ijk", C.c_int * 3), ("n_adds", C.c_int64), ("n_grows", C.c_int64)]
 
 
+class MapLevelStep(C.Structure):
+    _fields_ = [("level", C.c_int), ("max_iterations", C.c_int), ("step_size", C.c_double)]
+
+
 class MapCarveParams(C.Structure):
     """ndt_map_carve_params (ndt_map_carve_default_params: 2, 1, 4096, 0, 0)"""
     _fields_ = [("min_misses", C.c_int), ("keep_last", C.c_int), ("max_steps", C.c_int), ("protect_min_count", C.c_int),
@@ -318,6 +322,8 @@ ABI_SYMBOLS = [
     "ndt_map_crop", "ndt_map_export_state", "ndt_map_export_state_device", "ndt_map_import_state", "ndt_map_import_state_device",
     "ndt_map_carve_default_params", "ndt_map_carve_device", "ndt_map_carve", "ndt_map_carve_keyframe",
     "ndt_map_transform", "ndt_map_import_state_posed", "ndt_map_import_state_posed_device",
+    "ndt_map_level_info", "ndt_map_export_state_level", "ndt_map_export_state_level_device", "ndt_set_target_from_map_level",
+    "ndt_map_coarsen", "ndt_map_levels_drop", "ndt_align_map_levels",
     "ndt_set_source_distributions", "ndt_set_source_distributions_device", "ndt_source_distributions_info",
     "ndt_export_source_distributions", "ndt_eval_derivatives_d2d", "ndt_align_d2d",
     "ndt_scan_context_default_params", "ndt_scan_context_set_params", "ndt_scan_context_get_params",
@@ -452,6 +458,13 @@ def lib():
         L.ndt_map_transform.argtypes = [vp, dp, C.POINTER(C.c_int64)]
         L.ndt_map_import_state_posed.argtypes = [vp, C.c_float, vp, vp, vp, vp, C.c_size_t, dp]
         L.ndt_map_import_state_posed_device.argtypes = [vp, C.c_float, vp, vp, vp, vp, C.c_size_t, dp]
+        L.ndt_map_level_info.argtypes = [vp, C.c_int, C.POINTER(MapInfo)]
+        L.ndt_map_export_state_level.argtypes = [vp, C.c_int, fp, fp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ndt_map_export_state_level_device.argtypes = [vp, C.c_int, fp, fp, vp, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ndt_set_target_from_map_level.argtypes = [vp, C.c_int, fp, fp]
+        L.ndt_map_coarsen.argtypes = [vp, C.c_int]
+        L.ndt_map_levels_drop.argtypes = [vp]
+        L.ndt_align_map_levels.argtypes = [vp, C.POINTER(MapLevelStep), C.c_int, fp, fp, C.POINTER(Result)]
         L.ndt_set_source_distributions.argtypes = [vp, vp, vp, C.c_size_t]
         L.ndt_set_source_distributions_device.argtypes = [vp, vp, vp, C.c_size_t]
         L.ndt_source_distributions_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -1889,6 +1902,103 @@ def mapImportStatePosedDevice(ndt, leaf, d_ijk, d_count, d_sums, d_moments, n, p
     """As mapImportStatePosed, from device arrays (integer addresses; d_moments None for a map without moments)."""
     p = _finite_pose16(pose)
     ndt._check(lib().ndt_map_import_state_posed_device(ndt._h, float(leaf), d_ijk, d_count, d_sums, d_moments, int(n), _dp(p)))
+
+
+# --- levels: the map at leaf * 2^L made from its own sums, and coarse-to-fine alignment over them (ndt_map_level_*,
+# ndt_set_target_from_map_level, ndt_map_coarsen, ndt_align_map_levels; DESIGN 7n).  Functions on an engine, as above.
+# level 0 is the map itself in every one of them. ---
+MAP_MAX_LEVEL = 6
+MAP_LEVEL_STEPS_MAX = 8
+
+
+def mapLevelInfo(ndt, level):
+    """mapInfo() of the map's level (derived if stale): leaf, n_voxels, n_points, capacity and the tight ijk box are the
+    level's, the other counters the map's."""
+    mi = MapInfo()
+    ndt._check(lib().ndt_map_level_info(ndt._h, int(level), C.byref(mi)))
+    return dict(leaf=mi.leaf, with_intensity=bool(mi.with_intensity), n_voxels=mi.n_voxels, n_points=mi.n_points,
+                n_points_dropped=mi.n_points_dropped, capacity=mi.capacity, min_ijk=tuple(mi.min_ijk),
+                max_ijk=tuple(mi.max_ijk), n_adds=mi.n_adds, n_grows=mi.n_grows)
+
+
+def mapExportStateLevel(ndt, level, box_min=None, box_max=None):
+    """ndt.mapExportState of the map's level: the same dict, leaf being the level's; the box selects level voxels."""
+    lo, hi = ndt._box_or_none(box_min, box_max)
+    info = mapLevelInfo(ndt, level)
+    cap = info["n_voxels"]                        # (no selection holds more)
+    with_mom = ndt.mapHasMoments()
+    ijk = np.zeros((cap, 3), dtype=np.int32)
+    cnt = np.zeros(cap, dtype=np.int32)
+    sums = np.zeros((cap, 4), dtype=np.float32)
+    mom = np.zeros((cap, 9), dtype=np.float64) if with_mom else None
+    m = C.c_size_t(0)
+    ndt._check(lib().ndt_map_export_state_level(ndt._h, int(level), None if lo is None else _fp(lo),
+                                                None if hi is None else _fp(hi), ijk.ctypes.data if cap else None,
+                                                cnt.ctypes.data if cap else None, sums.ctypes.data if cap else None,
+                                                mom.ctypes.data if with_mom and cap else None, cap, C.byref(m)))
+    k = m.value
+    return dict(leaf=info["leaf"], with_intensity=info["with_intensity"], ijk=ijk[:k], count=cnt[:k], sums=sums[:k],
+                moments=None if mom is None else mom[:k])
+
+
+def mapExportStateLevelDevice(ndt, level, d_ijk, d_count, d_sums, d_moments, cap, box_min=None, box_max=None):
+    """Into device arrays of `cap` records (integer addresses, any may be None); returns the number of level voxels."""
+    lo, hi = ndt._box_or_none(box_min, box_max)
+    m = C.c_size_t(0)
+    ndt._check(lib().ndt_map_export_state_level_device(ndt._h, int(level), None if lo is None else _fp(lo),
+                                                       None if hi is None else _fp(hi), d_ijk, d_count, d_sums, d_moments,
+                                                       int(cap), C.byref(m)))
+    return int(m.value)
+
+
+def setInputTargetFromMapLevel(ndt, level, box_min=None, box_max=None):
+    """ndt.setInputTargetFromMapMoments of the map's level; the engine's resolution must be the level's leaf."""
+    lo, hi = ndt._box_or_none(box_min, box_max)
+    ndt._check(lib().ndt_set_target_from_map_level(ndt._h, int(level), None if lo is None else _fp(lo),
+                                                   None if hi is None else _fp(hi)))
+
+
+def mapCoarsen(ndt, level):
+    """The map becomes its level: leaf * 2^level, the level's voxels; the counters of its history are kept."""
+    ndt._check(lib().ndt_map_coarsen(ndt._h, int(level)))
+
+
+def mapLevelsDrop(ndt):
+    """Free the cached levels; the map is untouched (the next use derives them again)."""
+    ndt._check(lib().ndt_map_levels_drop(ndt._h))
+
+
+def alignMapLevels(ndt, steps, guess=None, half_extent=None):
+    """ndt_align_map_levels: coarse-to-fine align()s against the map's levels.  `steps`: a sequence of levels, or of
+    (level, max_iterations, step_size) / dict(level=, max_iterations=, step_size=) with 0 for the engine's value; every
+    step sets resolution to its level's leaf, makes the level (the box guess translation +- half_extent, or all of it)
+    the target and aligns from the previous step's result.  Returns the list of result dicts, one per step; raises at
+    the first step that fails.  The engine's parameters are the caller's again afterwards."""
+    arr = (MapLevelStep * max(len(steps), 1))()
+    for i, st in enumerate(steps):
+        if isinstance(st, dict):
+            st = (st["level"], st.get("max_iterations", 0), st.get("step_size", 0.0))
+        elif np.isscalar(st):
+            st = (st, 0, 0.0)
+        arr[i].level, arr[i].max_iterations, arr[i].step_size = int(st[0]), int(st[1]), float(st[2])
+    if guess is not None and np.shape(guess) != (4, 4):
+        raise ValueError("guess must be 4 x 4")
+    if not 1 <= len(steps) <= MAP_LEVEL_STEPS_MAX:
+        raise ValueError("1 to %d steps" % MAP_LEVEL_STEPS_MAX)
+    g = _colmajor(np.eye(4) if guess is None else guess)
+    he = None
+    if half_extent is not None:
+        he = np.ascontiguousarray(half_extent, dtype=np.float32)
+        if he.shape != (3,):
+            raise ValueError("half_extent must be three numbers")
+    res = (Result * max(len(steps), 1))()
+    ndt._check(lib().ndt_align_map_levels(ndt._h, arr, len(steps), None if he is None else _fp(he), _fp(g), res))
+    out = []
+    for i in range(len(steps)):
+        d = result_to_dict(res[i])
+        d["iteration_num"] = d["iterations"]
+        out.append(d)
+    return out
 
 
 # --- distribution-to-distribution NDT: a submap's voxels (mapExportState's records) registered to the target's leaves

@@ -9,6 +9,8 @@
 //   ndt_map.hip        the sparse voxel map accumulated scan by scan (ndt_map_*), its kernels included
 //   ndt_map_state.hip  the map's crop, full-state export / import and merge (k_mapstate_* kernels)
 //   ndt_map_repose.hip the map moved by a pose, and records merged under one (k_maprepose_* kernels)
+//   ndt_map_levels.hip the map at leaf * 2^L derived from its own sums and cached beside it, a level as the target, the map
+//                      coarsened to a level, coarse-to-fine align over the levels (k_maplevel_* kernels)
 //   ndt_d2d.hip        distribution-to-distribution registration: a source of Gaussians from map records, its evaluation
 //                      and align against the target's leaves (k_d2d_* kernels)
 //   ndt_scan_context.hip  Scan Context place recognition: a scan's rings x sectors descriptor, the descriptor bank beside
@@ -341,6 +343,11 @@ struct VoxelMap {
   int64_t n_voxels = 0, n_points = 0, n_dropped = 0, n_adds = 0, n_grows = 0;
   int mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
   bool nvox_stale = false;             // the device's voxel counter is ahead of n_voxels
+  // Levels (ndt_map_levels.hip).  The map: `change` goes up wherever the table's content changes (add, import, every
+  // table replacement, enable_moments).  A level (ndt_handle::map_level): `derived_at` is the map's `change` it was
+  // derived at, `lchild` its derivation's table position per ordered fine voxel.
+  uint64_t change = 0, derived_at = 0;
+  DevBuf<uint32_t> lchild;
   DevBuf<unsigned long long> pkey;     // the batch's voxel keys
   DevBuf<float> px, py, pz;            // the batch moved by its pose
   DevBuf<float> ux, uy, uz, ui;        // a host batch on the device
@@ -366,7 +373,7 @@ struct VoxelMap {
     pkey.release(); px.release(); py.release(); pz.release(); ux.release(); uy.release(); uz.release(); ui.release();
     stats.release(); nvox.release(); stats_h.release(); nvox_h.release(); plan_h.release(); xcounts.release();
     xslot.release(); xslot2.release(); xhi.release(); xout.release(); xcnt.release(); xijk.release(); xmom.release();
-    tsel.release(); tsel_h.release(); cmarks.release(); cstat.release(); cstat_h.release();
+    tsel.release(); tsel_h.release(); cmarks.release(); cstat.release(); cstat_h.release(); lchild.release();
   }
 };
 
@@ -519,6 +526,8 @@ struct ndt_handle {
   std::vector<Keyframe> keyframe_pool;
 
   VoxelMap* map = nullptr;            // ndt_map_reset .. ndt_map_clear (ndt_map.hip); survives target builds and ndt_set_params
+  VoxelMap* map_level[NDT_MAP_MAX_LEVEL] = {};   // [L - 1]: the map at leaf * 2^L, derived from the moments on demand and cached
+                                                 // until the map changes (ndt_map_levels.hip); freed with the map
 
   // multi-grid target [RECALLED] (tier4 MultiGridNormalDistributionsTransform): the valid leaves of
   // every separately voxelised cloud, on the host (adding a map tile is not a per-scan operation);
@@ -703,26 +712,35 @@ int map_alloc_table(ndt_handle* h, int64_t cap, bool with_moments, MapTable* t);
 // counts the voxels it creates in nvox[1] (zeroed in front of it); the device's voxel counter and n_voxels follow, the ijk
 // box is the caller's.  On any error the map is as it was and `what` heads the text.
 constexpr int64_t MAP_KEPT_COUNTED = -2;
-int map_replace_table(ndt_handle* h, int64_t new_cap, const char* what, const std::function<int(const MapTable&)>& launch,
-                      int64_t kept);
+int map_replace_table(ndt_handle* h, VoxelMap& m, int64_t new_cap, const char* what,
+                      const std::function<int(const MapTable&)>& launch, int64_t kept);
 // what fills the fresh table in place of growth's move (map_grow_table)
 struct MapRefill {
   const char* what;
   std::function<int(const MapTable&)> launch;
 };
-int map_grow_table(ndt_handle* h, int64_t new_cap, const MapRefill* refill = nullptr);
+int map_grow_table(ndt_handle* h, VoxelMap& m, int64_t new_cap, const MapRefill* refill = nullptr);
 int map_sort_scratch(ndt_handle* h, size_t n);
-int map_refresh_voxel_count(ndt_handle* h);
-int map_group_batch(ndt_handle* h, size_t n, const MapTable& t, unsigned long long* d_nvox, const uint32_t** keys_sorted,
-                    const uint32_t** vals_sorted);
-int map_export_count(ndt_handle* h, const MapSel& sel, bool box, size_t* total);
-int map_export_order(ndt_handle* h, const MapSel& sel, bool box_sel, size_t total, const int mn[3], const int mx[3],
+// (the VoxelMap a function takes is the map, *h->map, or one of its levels, h->map_level[]: ndt_map_levels.hip)
+int map_init_buffers(ndt_handle* h, VoxelMap& m);   // the small device / pinned words every VoxelMap works with
+int map_refresh_voxel_count(ndt_handle* h, VoxelMap& m);
+int map_group_batch(ndt_handle* h, VoxelMap& m, size_t n, const MapTable& t, unsigned long long* d_nvox,
+                    const uint32_t** keys_sorted, const uint32_t** vals_sorted);
+int map_export_count(ndt_handle* h, VoxelMap& m, const MapSel& sel, bool box, size_t* total);
+int map_export_order(ndt_handle* h, VoxelMap& m, const MapSel& sel, bool box_sel, size_t total, const int mn[3], const int mx[3],
                      const uint32_t** order_out, const uint32_t** slots_out);
+int no_moments(ndt_handle* h);
+// ndt_set_target_from_map_moments behind its argument checks, for the map or a level of it
+int target_from_moments(ndt_handle* h, VoxelMap& m, const float* box_min, const float* box_max);
+void map_levels_release(ndt_handle* h);   // ndt_map_levels.hip: frees the cached levels (the stream is idle)
 // ndt_map_state.hip's host side as ndt_map_repose.hip uses it: the state export into device arrays (awaited), the checks
 // of an import once the map is known, the import behind its key pass (one host wait, refusals, growth, counters, merge;
 // awaited) and the merge itself into a given table (enqueued)
-int map_export_state(ndt_handle* h, const float* box_min, const float* box_max, int32_t* d_ijk, int32_t* d_count, float* d_sums,
-                     double* d_mom, size_t cap, size_t* total_out);
+int map_export_state(ndt_handle* h, VoxelMap& m, const float* box_min, const float* box_max, int32_t* d_ijk, int32_t* d_count,
+                     float* d_sums, double* d_mom, size_t cap, size_t* total_out);
+// both public export forms behind the handle checks (box, moments, outputs as ndt_map_export_state[_device] takes them)
+int map_export_state_public(ndt_handle* h, VoxelMap& m, bool device_out, const float* box_min, const float* box_max, int32_t* ijk,
+                            int32_t* count, float* sums4, double* moments9, size_t cap, size_t* n_out);
 int map_import_checks(ndt_handle* h, float leaf, const double* moments9, size_t n, bool* go);
 int map_import_tail(ndt_handle* h, const int32_t* d_count, const float* d_sums, const double* d_mom, size_t n);
 int map_merge_records(ndt_handle* h, const MapTable& t, unsigned long long* d_nvox, const int32_t* d_count, const float* d_sums,

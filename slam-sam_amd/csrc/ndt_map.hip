@@ -383,8 +383,7 @@ int map_sort_scratch(ndt_handle* h, size_t n) {
 }
 
 // a sort plan for keys of `bits` bits in pinned slot `which`, copied to the build's device-side BuildGeom on the stream
-int map_put_plan(ndt_handle* h, int which, int bits, int ncells, int* passes) {
-  VoxelMap& m = *h->map;
+int map_put_plan(ndt_handle* h, VoxelMap& m, int which, int bits, int ncells, int* passes) {
   BuildGeom& b = m.plan_h.h[which];
   b = BuildGeom{};
   fill_sort_plan(&b, bits);
@@ -396,8 +395,7 @@ int map_put_plan(ndt_handle* h, int which, int bits, int ncells, int* passes) {
 }
 
 // n_voxels as the device counts it (the insert launches before this point have run when the call returns)
-int map_refresh_voxel_count(ndt_handle* h) {
-  VoxelMap& m = *h->map;
+int map_refresh_voxel_count(ndt_handle* h, VoxelMap& m) {
   if (!m.nvox_stale) return NDT_OK;
   HIP_TRY(h, hipMemcpyAsync(m.nvox_h.h, m.nvox.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -406,9 +404,8 @@ int map_refresh_voxel_count(ndt_handle* h) {
   return NDT_OK;
 }
 
-int map_replace_table(ndt_handle* h, int64_t new_cap, const char* what, const std::function<int(const MapTable&)>& launch,
-                      int64_t kept) {
-  VoxelMap& m = *h->map;
+int map_replace_table(ndt_handle* h, VoxelMap& m, int64_t new_cap, const char* what,
+                      const std::function<int(const MapTable&)>& launch, int64_t kept) {
   hipStream_t s = h->stream;
   const bool counted = kept == MAP_KEPT_COUNTED;   // the launch counts the voxels it creates in nvox[1]
   const bool selective = kept >= 0;
@@ -443,6 +440,7 @@ int map_replace_table(ndt_handle* h, int64_t new_cap, const char* what, const st
   }
   map_free_table(m.tab);
   m.tab = fresh;
+  ++m.change;
   if (selective || counted) {
     m.n_voxels = kept;
     m.nvox_stale = false;
@@ -455,14 +453,13 @@ int map_replace_table(ndt_handle* h, int64_t new_cap, const char* what, const st
 // Growth (refill == nullptr): every voxel moves as it is into a table of new_cap slots, and n_grows counts it.  With a
 // refill the fresh table is filled by the caller's own launches instead, which count the voxels they create (the re-pose
 // of ndt_map_repose.hip: the voxels do not move as they are); that is no growth, and the ijk box is the caller's to set.
-int map_grow_table(ndt_handle* h, int64_t new_cap, const MapRefill* refill) {
-  VoxelMap& m = *h->map;
+int map_grow_table(ndt_handle* h, VoxelMap& m, int64_t new_cap, const MapRefill* refill) {
   const std::function<int(const MapTable&)> rehash = [&](const MapTable& fresh) {
     hipLaunchKernelGGL(k_map_rehash, dim3((unsigned)((m.tab.capacity + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0,
                        h->stream, m.tab, fresh, m.stats.p);
     return (int)NDT_OK;
   };
-  const int rc = map_replace_table(h, new_cap, refill ? refill->what : "voxel map growth: ", refill ? refill->launch : rehash,
+  const int rc = map_replace_table(h, m, new_cap, refill ? refill->what : "voxel map growth: ", refill ? refill->launch : rehash,
                                    refill ? MAP_KEPT_COUNTED : -1);
   if (rc == NDT_OK && !refill) ++m.n_grows;
   return rc;
@@ -471,15 +468,14 @@ int map_grow_table(ndt_handle* h, int64_t new_cap, const MapRefill* refill) {
 // The batch's n keys (m.pkey; MAP_EMPTY: skipped) get their slots in table `t` (k_map_insert: *d_nvox -- for the map's own
 // table the device's voxel counter -- goes up by the voxels created), then the stable sort of (slot, index) and the run search: run r of *keys_sorted / *vals_sorted is one
 // voxel's entries in input order (h->nleaf, h->leaf_start, h->leaf_cnt).  After map_sort_scratch(n); enqueued, not awaited.
-int map_group_batch(ndt_handle* h, size_t n, const MapTable& t, unsigned long long* d_nvox, const uint32_t** keys_sorted,
-                    const uint32_t** vals_sorted) {
-  VoxelMap& m = *h->map;
+int map_group_batch(ndt_handle* h, VoxelMap& m, size_t n, const MapTable& t, unsigned long long* d_nvox,
+                    const uint32_t** keys_sorted, const uint32_t** vals_sorted) {
   hipStream_t s = h->stream;
   const unsigned blocks = (unsigned)((n + MAP_THREADS - 1) / MAP_THREADS);
   hipLaunchKernelGGL(k_map_insert, dim3(blocks), dim3(MAP_THREADS), 0, s, m.pkey.p, (int)n, t.keys,
                      (unsigned long long)(t.capacity - 1), h->keys.p, d_nvox, m.stats.p);
   int passes = 0;
-  int rc = map_put_plan(h, 0, map_bits_for(t.capacity), (int)t.capacity, &passes);   // (the sentinel `capacity` sorts behind every slot)
+  int rc = map_put_plan(h, m, 0, map_bits_for(t.capacity), (int)t.capacity, &passes);   // (the sentinel `capacity` sorts behind every slot)
   if (rc) return rc;
   launch_sort_first_count(h->keys.p, n, h->gd.p, h->sort_tmp.p, s);
   bool in_b = false;
@@ -531,10 +527,11 @@ int map_add_device(ndt_handle* h, const float* dx, const float* dy, const float*
   const int64_t want = map_pow2_at_least(2 * (m.n_voxels + (int64_t)n));
   if (want > m.tab.capacity) {
     if (want > MAP_MAX_CAPACITY) return fail(h, NDT_ERR_ALLOC, "voxel map: more than 2^30 table slots needed");
-    rc = map_grow_table(h, want);
+    rc = map_grow_table(h, m, want);
     if (rc) return rc;
   }
   // from here on the map changes
+  ++m.change;
   ++m.n_adds;
   m.n_dropped += (int64_t)n - n_finite;
   if (n_finite == 0) return NDT_OK;
@@ -545,7 +542,7 @@ int map_add_device(ndt_handle* h, const float* dx, const float* dy, const float*
   m.n_points += n_finite;
   m.nvox_stale = true;
   const uint32_t *keys_sorted = nullptr, *vals_sorted = nullptr;
-  rc = map_group_batch(h, n, m.tab, m.nvox.p, &keys_sorted, &vals_sorted);
+  rc = map_group_batch(h, m, n, m.tab, m.nvox.p, &keys_sorted, &vals_sorted);
   if (rc) return rc;
   if (m.moments)
     hipLaunchKernelGGL(k_map_accumulate<true>, dim3(blocks), dim3(MAP_THREADS), 0, s, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p,
@@ -571,10 +568,9 @@ MapSel sel_all(int min_points) {
 
 // the voxels a selection takes (count + scan, awaited); the block offsets stay in xcounts.  box: the selection is
 // limited to sel.lo .. sel.hi, and tsel_h receives the TS_* words of the occupied voxels inside (same wait)
-int map_export_count(ndt_handle* h, const MapSel& sel, bool box, size_t* total) {
-  VoxelMap& m = *h->map;
+int map_export_count(ndt_handle* h, VoxelMap& m, const MapSel& sel, bool box, size_t* total) {
   *total = 0;
-  int rc = map_refresh_voxel_count(h);
+  int rc = map_refresh_voxel_count(h, m);
   if (rc) return rc;
   if (m.n_voxels == 0) return NDT_OK;
   hipStream_t s = h->stream;
@@ -600,9 +596,8 @@ int map_export_count(ndt_handle* h, const MapSel& sel, bool box, size_t* total) 
 // after map_export_count(sel, box) = total > 0: the selected slots compacted and ordered by ascending (k, j, i) -- output
 // voxel r is table position (*slots)[(*order)[r]].  mn / mx: an ijk box that holds every selected voxel (the sort key is
 // relative to it).  Enqueued, not awaited.
-int map_export_order(ndt_handle* h, const MapSel& sel, bool box_sel, size_t total, const int mn[3], const int mx[3],
+int map_export_order(ndt_handle* h, VoxelMap& m, const MapSel& sel, bool box_sel, size_t total, const int mn[3], const int mx[3],
                      const uint32_t** order_out, const uint32_t** slots_out) {
-  VoxelMap& m = *h->map;
   hipStream_t s = h->stream;
   int rc = map_sort_scratch(h, total);
   if (rc) return rc;
@@ -626,7 +621,7 @@ int map_export_order(ndt_handle* h, const MapSel& sel, bool box_sel, size_t tota
                        m.xcounts.p, box, m.xslot.p, h->keys.p, two_words ? m.xhi.p : nullptr);
   HIP_TRY(h, hipGetLastError());
   int passes = 0;
-  rc = map_put_plan(h, 1, std::min(bits, 32), 0, &passes);
+  rc = map_put_plan(h, m, 1, std::min(bits, 32), 0, &passes);
   if (rc) return rc;
   launch_sort_first_count(h->keys.p, total, h->gd.p, h->sort_tmp.p, s);
   bool in_b = false;
@@ -637,7 +632,7 @@ int map_export_order(ndt_handle* h, const MapSel& sel, bool box_sel, size_t tota
     const unsigned tb = (unsigned)((total + MAP_THREADS - 1) / MAP_THREADS);
     hipLaunchKernelGGL(k_map_xgather, dim3(tb), dim3(MAP_THREADS), 0, s, order, m.xhi.p, m.xslot.p, (int)total, h->keys.p, m.xslot2.p);
     HIP_TRY(h, hipGetLastError());
-    rc = map_put_plan(h, 2, bits - 32, 0, &passes);
+    rc = map_put_plan(h, m, 2, bits - 32, 0, &passes);
     if (rc) return rc;
     launch_sort_first_count(h->keys.p, total, h->gd.p, h->sort_tmp.p, s);
     HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, total, passes, h->gd.p, s, &in_b));
@@ -659,7 +654,7 @@ int map_export_write(ndt_handle* h, int min_points, size_t total, float* ox, flo
   const size_t w = std::min(total, cap);
   if (w == 0) return NDT_OK;
   const uint32_t *order = nullptr, *slots = nullptr;
-  int rc = map_export_order(h, sel_all(min_points), false, total, m.mn, m.mx, &order, &slots);
+  int rc = map_export_order(h, m, sel_all(min_points), false, total, m.mn, m.mx, &order, &slots);
   if (rc) return rc;
   hipLaunchKernelGGL(k_map_xcentroids, dim3((unsigned)((w + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0, s, order, slots,
                      (int)w, m.tab.sums, m.tab.cnt, ox, oy, oz, m.with_intensity ? oi : nullptr, oc);
@@ -670,6 +665,27 @@ int map_export_write(ndt_handle* h, int min_points, size_t total, float* ox, flo
 }
 
 }  // namespace
+
+// the counters, read-back words and sort plans of a VoxelMap (the map's at ndt_map_reset, a level's at its first derivation)
+int map_init_buffers(ndt_handle* h, VoxelMap& m) {
+  hipError_t e = m.stats.ensure(MS_WORDS);
+  if (e == hipSuccess) e = m.nvox.ensure(2);   // [1]: the voxels a re-pose creates in its fresh table
+  if (e == hipSuccess) e = m.stats_h.ensure(2 * MS_WORDS);
+  if (e == hipSuccess) e = m.nvox_h.ensure(2);
+  if (e == hipSuccess) e = m.plan_h.ensure(3);
+  if (e == hipSuccess) e = m.tsel.ensure(TS_WORDS);
+  if (e == hipSuccess) e = m.tsel_h.ensure(2 * TS_WORDS);
+  if (e == hipSuccess) e = hipMemsetAsync(m.nvox.p, 0, sizeof(unsigned long long), h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) return fail(h, e == hipErrorOutOfMemory ? NDT_ERR_ALLOC : NDT_ERR_HIP, hipGetErrorString(e));
+  int* neutral = m.stats_h.h + MS_WORDS;
+  for (int i = 0; i < MS_WORDS; ++i) neutral[i] = 0;
+  for (int a = 0; a < 3; ++a) { neutral[MS_MIN + a] = INT_MAX; neutral[MS_MAX + a] = INT_MIN; }
+  int* tneutral = m.tsel_h.h + TS_WORDS;
+  for (int i = 0; i < TS_WORDS; ++i) tneutral[i] = 0;
+  for (int a = 0; a < 3; ++a) { tneutral[TS_MIN + a] = INT_MAX; tneutral[TS_MAX + a] = INT_MIN; }
+  return NDT_OK;
+}
 
 int no_map(ndt_handle* h) { return fail(h, NDT_ERR_INVALID_ARG, "no map (ndt_map_reset creates one)"); }
 
@@ -687,13 +703,11 @@ bool pose_finite(const double p[16]) {
 
 bool finite3(const float v[3]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
-namespace {
-
 int no_moments(ndt_handle* h) { return fail(h, NDT_ERR_INVALID_ARG, "the map keeps no moments (ndt_map_enable_moments right after ndt_map_reset)"); }
 
-// ndt_set_target_from_map_moments behind its argument checks.  Up to the one host wait nothing of the target is touched.
-int target_from_moments(ndt_handle* h, const float* box_min, const float* box_max) {
-  VoxelMap& m = *h->map;
+// ndt_set_target_from_map_moments behind its argument checks, on the map or on one of its levels (m.leaf is bit-equal to
+// ndt_params::resolution).  Up to the one host wait nothing of the target is touched.
+int target_from_moments(ndt_handle* h, VoxelMap& m, const float* box_min, const float* box_max) {
   settle_discard_keep_grid(h);   // (the pending build borrows the sort scratch; its verdict is dropped once this call replaces it)
   const auto t0 = std::chrono::steady_clock::now();
   MapSel sel{};
@@ -703,7 +717,7 @@ int target_from_moments(ndt_handle* h, const float* box_min, const float* box_ma
     sel.hi[a] = box_max ? map_box_floor(box_max[a], m.inv_leaf) : MAP_BIAS;
   }
   size_t total = 0;
-  int rc = map_export_count(h, sel, true, &total);
+  int rc = map_export_count(h, m, sel, true, &total);
   if (rc) return rc;
   const int* ts = m.tsel_h.h;
   if (m.n_voxels == 0 || ts[TS_VOXELS] == 0) return fail(h, NDT_ERR_NO_TARGET, "the map holds no occupied voxel inside the box");
@@ -750,7 +764,7 @@ int target_from_moments(ndt_handle* h, const float* box_min, const float* box_ma
   int n_valid = 0;
   if (total > 0) {
     const uint32_t *order = nullptr, *slots = nullptr;
-    rc = map_export_order(h, sel, true, total, mn, mx, &order, &slots);
+    rc = map_export_order(h, m, sel, true, total, mn, mx, &order, &slots);
     if (rc) return rc;
     FinalizeParams fp{h->prm.eig_inflation_ratio, h->prm.cov_mode};
     launch_map_finalize(order, slots, total, m.tab.keys, m.tab.cnt, m.tab.mom, mn, g.mul1, g.mul2, fp, h->rec.p, h->cent.p, h->stats.p,
@@ -768,11 +782,10 @@ int target_from_moments(ndt_handle* h, const float* box_min, const float* box_ma
   return target_publish(h, TargetKind::SINGLE, g, mx, (size_t)n_points, (int)total, n_valid, ms);
 }
 
-}  // namespace
-
 void map_release(ndt_handle* h) {
   if (!h->map) return;
   if (h->stream) (void)hipStreamSynchronize(h->stream);
+  map_levels_release(h);
   h->map->release();
   delete h->map;
   h->map = nullptr;
@@ -799,22 +812,8 @@ int ndt_map_reset(ndt_handle* h, float leaf, int with_intensity, int64_t initial
   rc = map_alloc_table(h, cap, false, &m.tab);
   if (rc) return undo(rc);
   m.reset_capacity = cap;
-  hipError_t e = m.stats.ensure(MS_WORDS);
-  if (e == hipSuccess) e = m.nvox.ensure(2);   // [1]: the voxels a re-pose creates in its fresh table
-  if (e == hipSuccess) e = m.stats_h.ensure(2 * MS_WORDS);
-  if (e == hipSuccess) e = m.nvox_h.ensure(2);
-  if (e == hipSuccess) e = m.plan_h.ensure(3);
-  if (e == hipSuccess) e = m.tsel.ensure(TS_WORDS);
-  if (e == hipSuccess) e = m.tsel_h.ensure(2 * TS_WORDS);
-  if (e == hipSuccess) e = hipMemsetAsync(m.nvox.p, 0, sizeof(unsigned long long), h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return undo(fail(h, e == hipErrorOutOfMemory ? NDT_ERR_ALLOC : NDT_ERR_HIP, hipGetErrorString(e)));
-  int* neutral = m.stats_h.h + MS_WORDS;
-  for (int i = 0; i < MS_WORDS; ++i) neutral[i] = 0;
-  for (int a = 0; a < 3; ++a) { neutral[MS_MIN + a] = INT_MAX; neutral[MS_MAX + a] = INT_MIN; }
-  int* tneutral = m.tsel_h.h + TS_WORDS;
-  for (int i = 0; i < TS_WORDS; ++i) tneutral[i] = 0;
-  for (int a = 0; a < 3; ++a) { tneutral[TS_MIN + a] = INT_MAX; tneutral[TS_MAX + a] = INT_MIN; }
+  rc = map_init_buffers(h, m);
+  if (rc) return undo(rc);
   return NDT_OK;
 }
 
@@ -907,7 +906,7 @@ int ndt_map_export_device(ndt_handle* h, int min_points, float* ox, float* oy, f
   if (!h->map) return no_map(h);
   settle_discard_keep_grid(h);
   size_t total = 0;
-  rc = map_export_count(h, sel_all(min_points), false, &total);
+  rc = map_export_count(h, *h->map, sel_all(min_points), false, &total);
   if (rc) return rc;
   *n_out = total;
   if (total == 0) return NDT_OK;
@@ -929,7 +928,7 @@ int ndt_map_export(ndt_handle* h, int min_points, float* out, size_t stride_byte
   VoxelMap& m = *h->map;
   settle_discard_keep_grid(h);
   size_t total = 0;
-  rc = map_export_count(h, sel_all(min_points), false, &total);
+  rc = map_export_count(h, *h->map, sel_all(min_points), false, &total);
   if (rc) return rc;
   *n_out = total;
   if (total == 0) return NDT_OK;
@@ -962,7 +961,7 @@ int ndt_set_target_from_map(ndt_handle* h, int min_points) {
   if (!h->map) return no_map(h);
   settle_discard(h);
   size_t total = 0;
-  rc = map_export_count(h, sel_all(min_points), false, &total);
+  rc = map_export_count(h, *h->map, sel_all(min_points), false, &total);
   if (rc) return rc;
   if (total == 0) return fail(h, NDT_ERR_NO_TARGET, "the map holds no voxel with that many points");
   h->tgt.claim_cloud();
@@ -994,6 +993,7 @@ int ndt_map_enable_moments(ndt_handle* h) {
     return fail(h, e == hipErrorOutOfMemory ? NDT_ERR_ALLOC : NDT_ERR_HIP, std::string("voxel map moments: ") + hipGetErrorString(e));
   }
   m.moments = true;
+  ++m.change;
   return NDT_OK;
 }
 
@@ -1011,7 +1011,7 @@ int ndt_map_export_moments(ndt_handle* h, int min_points, int32_t* ijk, int32_t*
   if (!m.moments) return no_moments(h);
   settle_discard_keep_grid(h);
   size_t total = 0;
-  rc = map_export_count(h, sel_all(min_points), false, &total);
+  rc = map_export_count(h, *h->map, sel_all(min_points), false, &total);
   if (rc) return rc;
   *n_out = total;
   if (total == 0) return NDT_OK;
@@ -1021,7 +1021,7 @@ int ndt_map_export_moments(ndt_handle* h, int min_points, int32_t* ijk, int32_t*
     HIP_TRY(h, m.xcnt.ensure(w));
     HIP_TRY(h, m.xmom.ensure(9 * w));
     const uint32_t *order = nullptr, *slots = nullptr;
-    rc = map_export_order(h, sel_all(min_points), false, total, m.mn, m.mx, &order, &slots);
+    rc = map_export_order(h, m, sel_all(min_points), false, total, m.mn, m.mx, &order, &slots);
     if (rc) return rc;
     launch_map_gather_moments(order, slots, w, m.tab.keys, m.tab.cnt, m.tab.mom, m.xijk.p, m.xcnt.p, m.xmom.p, h->stream);
     HIP_TRY(h, hipGetLastError());
@@ -1044,7 +1044,7 @@ int ndt_set_target_from_map_moments(ndt_handle* h, const float box_min[3], const
   if (std::memcmp(&m.leaf, &h->prm.resolution, sizeof(float)) != 0)
     return fail(h, NDT_ERR_INVALID_ARG, "the map's leaf size is not ndt_params::resolution: a voxel of the map is not a voxel of the grid");
   if (box_min && !(finite3(box_min) && finite3(box_max))) return fail(h, NDT_ERR_INVALID_ARG, "non-finite box");
-  return target_from_moments(h, box_min, box_max);
+  return target_from_moments(h, m, box_min, box_max);
 }
 
 }  // extern "C"

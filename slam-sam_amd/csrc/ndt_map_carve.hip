@@ -210,7 +210,7 @@ int map_carve_device(ndt_handle* h, const float* dx, const float* dy, const floa
   }
   settle_discard_keep_grid(h);
   hipStream_t s = h->stream;
-  int rc = map_refresh_voxel_count(h);
+  int rc = map_refresh_voxel_count(h, *h->map);
   if (rc) return rc;
   HIP_TRY(h, m.cmarks.ensure((size_t)m.tab.capacity));
   HIP_TRY(h, m.cstat.ensure(CS_WORDS));
@@ -243,7 +243,7 @@ int map_carve_device(ndt_handle* h, const float* dx, const float* dy, const floa
 
   const int64_t kept = m.n_voxels - removed;
   const int64_t new_cap = std::max(map_pow2_at_least(2 * kept), m.reset_capacity);
-  rc = map_replace_table(h, new_cap, "voxel map carve: ", [&](const MapTable& fresh) {
+  rc = map_replace_table(h, m, new_cap, "voxel map carve: ", [&](const MapTable& fresh) {
     hipLaunchKernelGGL(k_mapcarve_move, dim3(slot_blocks), dim3(MAP_THREADS), 0, s, m.tab, m.cmarks.p, prm.min_misses,
                        prm.protect_min_count, fresh, m.stats.p, m.tsel.p);
     return NDT_OK;

@@ -141,7 +141,7 @@ int repose_records(ndt_handle* h, const double* pose16, const int32_t* d_count, 
 int map_transform(ndt_handle* h, const double* pose16, int64_t* n_after) {
   VoxelMap& m = *h->map;
   hipStream_t s = h->stream;
-  int rc = map_refresh_voxel_count(h);
+  int rc = map_refresh_voxel_count(h, m);
   if (rc) return rc;
   if (m.n_voxels == 0) {   // untouched
     if (n_after) *n_after = 0;
@@ -160,7 +160,7 @@ int map_transform(ndt_handle* h, const double* pose16, int64_t* n_after) {
   if (rc) return rc;
   // the records in export-state order, in the staging arrays
   size_t total = 0;
-  rc = map_export_state(h, nullptr, nullptr, nullptr, m.xcnt.p, m.xout.p, m.moments ? m.xmom.p : nullptr, n, &total);
+  rc = map_export_state(h, m, nullptr, nullptr, nullptr, m.xcnt.p, m.xout.p, m.moments ? m.xmom.p : nullptr, n, &total);
   if (rc) return rc;
   if (total != n) return fail(h, NDT_ERR_HIP, "voxel map transform: the table holds " + std::to_string(total) + " voxels, the counter says " + std::to_string(n));
   rc = repose_records(h, pose16, m.xcnt.p, m.xout.p, m.moments ? m.xmom.p : nullptr, n, m.xout.p, m.moments ? m.xmom.p : nullptr);
@@ -174,7 +174,7 @@ int map_transform(ndt_handle* h, const double* pose16, int64_t* n_after) {
   const MapRefill refill{"voxel map transform: ", [&](const MapTable& fresh) {
     return map_merge_records(h, fresh, m.nvox.p + 1, m.xcnt.p, m.xout.p, m.moments ? m.xmom.p : nullptr, n);
   }};
-  rc = map_grow_table(h, new_cap, &refill);
+  rc = map_grow_table(h, m, new_cap, &refill);
   if (rc) return rc;
   for (int a = 0; a < 3; ++a) { m.mn[a] = mn[a]; m.mx[a] = mx[a]; }
   if (n_after) *n_after = m.n_voxels;

@@ -156,7 +156,7 @@ int map_crop(ndt_handle* h, const float* box_min, const float* box_max, int remo
   VoxelMap& m = *h->map;
   const MapSel sel = sel_box(m, box_min, box_max);
   size_t inside = 0;
-  int rc = map_export_count(h, sel, true, &inside);   // (settles nvox_stale first; one host wait)
+  int rc = map_export_count(h, m, sel, true, &inside);   // (settles nvox_stale first; one host wait)
   if (rc) return rc;
   unsigned long long pts_inside = 0;
   if (m.n_voxels > 0) std::memcpy(&pts_inside, m.tsel_h.h + TS_POINTS, sizeof(pts_inside));
@@ -167,7 +167,7 @@ int map_crop(ndt_handle* h, const float* box_min, const float* box_max, int remo
   if (removed == 0) return NDT_OK;   // the table is as it was
 
   const int64_t new_cap = std::max(map_pow2_at_least(2 * kept), m.reset_capacity);
-  rc = map_replace_table(h, new_cap, "voxel map crop: ", [&](const MapTable& fresh) {
+  rc = map_replace_table(h, m, new_cap, "voxel map crop: ", [&](const MapTable& fresh) {
     hipLaunchKernelGGL(k_mapstate_crop, dim3((unsigned)((m.tab.capacity + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0,
                        h->stream, m.tab, sel, remove_inside, fresh, m.stats.p, m.tsel.p);
     return NDT_OK;
@@ -180,12 +180,11 @@ int map_crop(ndt_handle* h, const float* box_min, const float* box_max, int remo
 }  // namespace
 
 // the selection's records, the first min(total, cap) of them, into device arrays (any may be null); *n_out = total
-int map_export_state(ndt_handle* h, const float* box_min, const float* box_max, int32_t* d_ijk, int32_t* d_count, float* d_sums,
-                     double* d_mom, size_t cap, size_t* total_out) {
-  VoxelMap& m = *h->map;
+int map_export_state(ndt_handle* h, VoxelMap& m, const float* box_min, const float* box_max, int32_t* d_ijk, int32_t* d_count,
+                     float* d_sums, double* d_mom, size_t cap, size_t* total_out) {
   const MapSel sel = sel_box(m, box_min, box_max);
   size_t total = 0;
-  int rc = map_export_count(h, sel, true, &total);
+  int rc = map_export_count(h, m, sel, true, &total);
   if (rc) return rc;
   *total_out = total;
   const size_t w = std::min(total, cap);
@@ -194,7 +193,7 @@ int map_export_state(ndt_handle* h, const float* box_min, const float* box_max, 
   const int* ts = m.tsel_h.h;
   const int mn[3] = {ts[TS_MIN], ts[TS_MIN + 1], ts[TS_MIN + 2]}, mx[3] = {ts[TS_MAX], ts[TS_MAX + 1], ts[TS_MAX + 2]};
   const uint32_t *order = nullptr, *slots = nullptr;
-  rc = map_export_order(h, sel, true, total, mn, mx, &order, &slots);
+  rc = map_export_order(h, m, sel, true, total, mn, mx, &order, &slots);
   if (rc) return rc;
   hipLaunchKernelGGL(k_mapstate_gather, dim3((unsigned)((w + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0, h->stream, order,
                      slots, (int)w, m.tab.keys, m.tab.sums, m.tab.cnt, m.tab.mom, d_ijk, d_count, d_sums, d_mom);
@@ -212,7 +211,7 @@ int map_merge_records(ndt_handle* h, const MapTable& t, unsigned long long* d_nv
   hipStream_t s = h->stream;
   const unsigned blocks = (unsigned)((n + MAP_THREADS - 1) / MAP_THREADS);
   const uint32_t *keys_sorted = nullptr, *vals_sorted = nullptr;
-  const int rc = map_group_batch(h, n, t, d_nvox, &keys_sorted, &vals_sorted);
+  const int rc = map_group_batch(h, m, n, t, d_nvox, &keys_sorted, &vals_sorted);
   if (rc) return rc;
   if (m.moments)
     hipLaunchKernelGGL(k_mapstate_accumulate<true>, dim3(blocks), dim3(MAP_THREADS), 0, s, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p,
@@ -244,10 +243,11 @@ int map_import_tail(ndt_handle* h, const int32_t* d_count, const float* d_sums, 
   const int64_t want = map_pow2_at_least(2 * (m.n_voxels + (int64_t)n));
   if (want > m.tab.capacity) {
     if (want > MAP_MAX_CAPACITY) return fail(h, NDT_ERR_ALLOC, "voxel map: more than 2^30 table slots needed");
-    rc = map_grow_table(h, want);
+    rc = map_grow_table(h, m, want);
     if (rc) return rc;
   }
   // from here on the map changes
+  ++m.change;
   unsigned long long pts = 0;
   std::memcpy(&pts, st + MS_POINTS, sizeof(pts));
   ++m.n_adds;
@@ -296,17 +296,46 @@ int map_import_checks(ndt_handle* h, float leaf, const double* moments9, size_t 
   return NDT_OK;
 }
 
-namespace {
-
-int export_checks(ndt_handle* h, const float* box_min, const float* box_max, const double* moments9) {
-  if (!h->map) return no_map(h);
-  if (moments9 && !h->map->moments)
-    return fail(h, NDT_ERR_INVALID_ARG, "the map keeps no moments (ndt_map_enable_moments right after ndt_map_reset)");
+// Both public forms of the state export on `m` -- the map or one of its levels -- behind the handle checks: the
+// refusals, then the records into the caller's device arrays (device_out) or through m's staging arrays to the host.
+int map_export_state_public(ndt_handle* h, VoxelMap& m, bool device_out, const float* box_min, const float* box_max, int32_t* ijk,
+                            int32_t* count, float* sums4, double* moments9, size_t cap, size_t* n_out) {
+  if (moments9 && !m.moments) return no_moments(h);
   if (box_min && !(finite3(box_min) && finite3(box_max))) return fail(h, NDT_ERR_INVALID_ARG, "non-finite box");
+  settle_discard_keep_grid(h);
+  int rc = NDT_OK;
+  size_t total = 0;
+  if (device_out) {
+    rc = map_export_state(h, m, box_min, box_max, ijk, count, sums4, moments9, cap, &total);
+    if (rc) return rc;
+    *n_out = total;
+  } else {
+    rc = map_refresh_voxel_count(h, m);
+    if (rc) return rc;
+    // (no selection holds more than the map: the device-side outputs are sized before the selection is counted)
+    const size_t w = std::min((size_t)m.n_voxels, cap);
+    if (w) {
+      if (ijk) HIP_TRY(h, m.xijk.ensure(3 * w));
+      if (count) HIP_TRY(h, m.xcnt.ensure(w));
+      if (sums4) HIP_TRY(h, m.xout.ensure(4 * w));
+      if (moments9) HIP_TRY(h, m.xmom.ensure(9 * w));
+    }
+    rc = map_export_state(h, m, box_min, box_max, ijk && w ? m.xijk.p : nullptr, count && w ? m.xcnt.p : nullptr,
+                          sums4 && w ? m.xout.p : nullptr, moments9 && w ? m.xmom.p : nullptr, w, &total);
+    if (rc) return rc;
+    *n_out = total;
+    const size_t got = std::min(total, w);
+    if (got) {
+      if (ijk) HIP_TRY(h, hipMemcpy(ijk, m.xijk.p, 3 * got * sizeof(int32_t), hipMemcpyDeviceToHost));
+      if (count) HIP_TRY(h, hipMemcpy(count, m.xcnt.p, got * sizeof(int32_t), hipMemcpyDeviceToHost));
+      if (sums4) HIP_TRY(h, hipMemcpy(sums4, m.xout.p, 4 * got * sizeof(float), hipMemcpyDeviceToHost));
+      if (moments9) HIP_TRY(h, hipMemcpy(moments9, m.xmom.p, 9 * got * sizeof(double), hipMemcpyDeviceToHost));
+    }
+  }
+  if (total > cap) return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(total) + " voxels");
   return NDT_OK;
 }
 
-}  // namespace
 }  // namespace engine
 }  // namespace ndt
 
@@ -326,15 +355,8 @@ int ndt_map_export_state_device(ndt_handle* h, const float box_min[3], const flo
   if (!h || !n_out || (box_min == nullptr) != (box_max == nullptr)) return NDT_ERR_INVALID_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  rc = export_checks(h, box_min, box_max, moments9);
-  if (rc) return rc;
-  settle_discard_keep_grid(h);
-  size_t total = 0;
-  rc = map_export_state(h, box_min, box_max, ijk, count, sums4, moments9, cap, &total);
-  if (rc) return rc;
-  *n_out = total;
-  if (total > cap) return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(total) + " voxels");
-  return NDT_OK;
+  if (!h->map) return no_map(h);
+  return map_export_state_public(h, *h->map, true, box_min, box_max, ijk, count, sums4, moments9, cap, n_out);
 }
 
 int ndt_map_export_state(ndt_handle* h, const float box_min[3], const float box_max[3], int32_t* ijk, int32_t* count, float* sums4,
@@ -342,34 +364,8 @@ int ndt_map_export_state(ndt_handle* h, const float box_min[3], const float box_
   if (!h || !n_out || (box_min == nullptr) != (box_max == nullptr)) return NDT_ERR_INVALID_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
-  rc = export_checks(h, box_min, box_max, moments9);
-  if (rc) return rc;
-  VoxelMap& m = *h->map;
-  settle_discard_keep_grid(h);
-  rc = map_refresh_voxel_count(h);
-  if (rc) return rc;
-  // (no selection holds more than the map: the device-side outputs are sized before the selection is counted)
-  const size_t w = std::min((size_t)m.n_voxels, cap);
-  if (w) {
-    if (ijk) HIP_TRY(h, m.xijk.ensure(3 * w));
-    if (count) HIP_TRY(h, m.xcnt.ensure(w));
-    if (sums4) HIP_TRY(h, m.xout.ensure(4 * w));
-    if (moments9) HIP_TRY(h, m.xmom.ensure(9 * w));
-  }
-  size_t total = 0;
-  rc = map_export_state(h, box_min, box_max, ijk && w ? m.xijk.p : nullptr, count && w ? m.xcnt.p : nullptr,
-                        sums4 && w ? m.xout.p : nullptr, moments9 && w ? m.xmom.p : nullptr, w, &total);
-  if (rc) return rc;
-  *n_out = total;
-  const size_t got = std::min(total, w);
-  if (got) {
-    if (ijk) HIP_TRY(h, hipMemcpy(ijk, m.xijk.p, 3 * got * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (count) HIP_TRY(h, hipMemcpy(count, m.xcnt.p, got * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (sums4) HIP_TRY(h, hipMemcpy(sums4, m.xout.p, 4 * got * sizeof(float), hipMemcpyDeviceToHost));
-    if (moments9) HIP_TRY(h, hipMemcpy(moments9, m.xmom.p, 9 * got * sizeof(double), hipMemcpyDeviceToHost));
-  }
-  if (total > cap) return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(total) + " voxels");
-  return NDT_OK;
+  if (!h->map) return no_map(h);
+  return map_export_state_public(h, *h->map, false, box_min, box_max, ijk, count, sums4, moments9, cap, n_out);
 }
 
 int ndt_map_import_state_device(ndt_handle* h, float leaf, const int32_t* ijk, const int32_t* count, const float* sums4,
