@@ -4,6 +4,7 @@
 //   ndt_handoff.hip    host hand-off (repack + pull kernels), the target voxel-grid build's orchestration, grid accessors
 //   ndt_evaluate.hip   derivative evaluations (ordinary, pre-launched, batched), align, scoring
 //   ndt_keyframes.hip  multi-grid targets, the device-resident keyframe archive, voxel downsample
+//   ndt_sort.hip       the keyed sort every subsystem shares: radix sort kernels, plan writer, sort call, run-search scratch
 //   ndt_point_scores.hip  per-point scores and the score-based source filter; the engine's one scan of block counts and
 //                      the host side of every compaction (the device side: ndt_compact_device.h)
 //   ndt_map.hip        the sparse voxel map accumulated scan by scan (ndt_map_*), its kernels included
@@ -141,6 +142,16 @@ struct EvalLogEntry {
 };
 static_assert(sizeof(EvalLogEntry) == 464, "EvalLogEntry layout is read from Python");
 
+// The five arrays of one stable radix sort of (key, index) pairs (ndt_sort.hip): the keys go into `keys`, sort_keyed
+// ping-pongs between the two pairs of arrays and says where the result is.  Three instances, each with its own memory: the
+// handle's (the build, the downsample, the voxel map, ndt_debug_sort_pairs), the fitness index's and the source ordering's.
+struct SortScratch {
+  DevBuf<uint32_t> keys, vals, keys2, vals2;
+  DevBuf<char> tmp;                  // sort_temp_bytes(n): tile histograms of the digit in flight + bin totals
+  hipError_t ensure(size_t n);       // n pairs
+  void release() { keys.release(); vals.release(); keys2.release(); vals2.release(); tmp.release(); }
+};
+
 // Geometry of the point-level nearest-neighbour index (ndt_fitness.hip): cells of edge `c` on the bounding box of the
 // target's finite points, cell (i, j, k) = floor((p - lo) * inv_c) per axis in f32, key i + dims0 * (j + dims1 * k).
 struct FitGeom {
@@ -160,10 +171,8 @@ struct FitIndex {
   FitGeom g{};
   DevBuf<float> pts;                 // the finite target points as float4, sorted by cell (stable)
   DevBuf<uint32_t> tab;              // hash table, 4 words per slot: {cell key, first point, end point, 0}
-  DevBuf<uint32_t> keys, vals, keys2, vals2;
-  DevBuf<char> sort_tmp;
-  DevBuf<BuildGeom> plan;
-  BuildGeom plan_h{};
+  SortScratch sort;
+  DevBuf<BuildGeom> plan;            // its sort plan (sort_put_plan)
   DevBuf<float> bslab;               // per-block bounds {min xyz, max xyz}
   DevBuf<int> cslab;                 // ... and finite counts
   PinBuf<float> bslab_h;
@@ -175,8 +184,7 @@ struct FitIndex {
   DevBuf<double> slab;               // K x blocks x 3: {sum d^2, inliers, finite points}
   PinBuf<double> slab_h;
   void release() {
-    pts.release(); tab.release(); keys.release(); vals.release(); keys2.release(); vals2.release(); sort_tmp.release();
-    plan.release(); bslab.release(); cslab.release(); bslab_h.release(); cslab_h.release(); dist.release(); work.release();
+    pts.release(); tab.release(); sort.release(); plan.release(); bslab.release(); cslab.release(); bslab_h.release(); cslab_h.release(); dist.release(); work.release();
     poses.release(); slab.release(); slab_h.release();
     valid = false;
   }
@@ -355,7 +363,6 @@ struct VoxelMap {
   DevBuf<unsigned long long> nvox;     // occupied slots (cumulative); [1]: those a re-pose creates in its fresh table
   PinBuf<int> stats_h;                 // [0..15] read-back, [16..31] the neutral words
   PinBuf<unsigned long long> nvox_h;
-  PinBuf<BuildGeom> plan_h;            // sort plans: [0] add, [1] / [2] export (low / high word)
   DevBuf<unsigned int> xcounts;        // export: per-block counts / offsets, their sum, then the scan's total (nb + 2 words)
   DevBuf<uint32_t> xslot, xslot2, xhi; // export: compacted slots (and in low-word order), high key words
   DevBuf<float> xout;                  // host export: [x | y | z | intensity] ...
@@ -371,7 +378,7 @@ struct VoxelMap {
     map_free_table(tab);
     moments = false;
     pkey.release(); px.release(); py.release(); pz.release(); ux.release(); uy.release(); uz.release(); ui.release();
-    stats.release(); nvox.release(); stats_h.release(); nvox_h.release(); plan_h.release(); xcounts.release();
+    stats.release(); nvox.release(); stats_h.release(); nvox_h.release(); xcounts.release();
     xslot.release(); xslot2.release(); xhi.release(); xout.release(); xcnt.release(); xijk.release(); xmom.release();
     tsel.release(); tsel_h.release(); cmarks.release(); cstat.release(); cstat_h.release(); lchild.release();
   }
@@ -401,8 +408,9 @@ struct ndt_handle {
   FitIndex fit;                      // point-level nearest-neighbour index of getFitnessScore (ndt_fitness.hip)
   GridGeom geom{};
   int max_b[3] = {0, 0, 0};
-  DevBuf<uint32_t> keys, vals, keys2, vals2;
-  DevBuf<char> sort_tmp;
+  SortScratch sort;                  // the build's pair sort; the downsample, the voxel map and ndt_debug_sort_pairs reuse it
+  PinBuf<BuildGeom> plan_h;          // host-written sort plans on their way to the device (sort_put_plan)
+  unsigned plan_next = 0;            // ... and the next free slot of them
   DevBuf<int> nleaf;                 // [0] slots, [1] valid
   DevBuf<int> leaf_start, leaf_cnt, run_counts, run_offsets, fin_counts;
   std::unique_ptr<RepackPool> pool;   // repack workers of the host hand-off, created on first use
@@ -446,9 +454,8 @@ struct ndt_handle {
   // the same points in block order of the target grid (see sort_source_by_blocks); valid until
   // the source or the target changes
   DevBuf<float> ox, oy, oz;
-  DevBuf<uint32_t> skeys, skeys2, svals, svals2;
-  DevBuf<char> ssort_tmp;
-  DevBuf<BuildGeom> splan;
+  SortScratch ssort;                 // the source ordering's own pair sort ...
+  DevBuf<BuildGeom> splan;           // ... and its plan, written by k_source_keys
   bool src_sorted = false;
   int64_t n_src_global = -1;
 
@@ -658,6 +665,27 @@ GridGeom grid_geom_from_box(float leaf, const I mn[3], const I mx[3]) {
   g.ncells = g.mul2 * g.div_b[2];
   return g;
 }
+// ---- the keyed sort on a handle (ndt_sort.hip) ----
+// A plan for `bits`-bit keys (1 .. 32) and `ncells`, status BG_OK, copied to the device plan `d_plan` on the engine's
+// stream; *passes: its digit passes.  The copy's source must live until the copy has run, so it is one of SORT_PLAN_SLOTS
+// pinned slots of the handle (h->plan_h) taken in turn, and the writer waits for the stream whenever it starts the
+// round again: no slot is rewritten while a copy out of it can still be pending, however many plans a call enqueues.
+constexpr unsigned SORT_PLAN_SLOTS = 8;
+int sort_put_plan(ndt_handle* h, BuildGeom* d_plan, int bits, int ncells, int* passes);
+// The one sort call: the n pairs (sc.keys, identity) stably sorted on the key bits of the plan in *d_plan (device memory;
+// nothing runs unless its status is BG_OK) in `passes` digit passes, enqueued on s.  The passes need the first digit's tile
+// histograms in sc.tmp: SORT_FIRST_COUNTED says the kernel that wrote the keys counted them on its way (launch_cell_keys,
+// k_source_keys), SORT_COUNT_FIRST makes this call launch the count.  *out: where the sorted keys and values are.
+enum SortFirstDigit { SORT_COUNT_FIRST = 0, SORT_FIRST_COUNTED = 1 };
+hipError_t sort_keyed(SortScratch& sc, size_t n, const BuildGeom* d_plan, int passes, SortFirstDigit first, hipStream_t s,
+                      SortedPairs* out);
+// What a sort on the handle's scratch and the run search behind it work in, for n pairs and at most max_runs runs: the
+// build's BuildGeom (device + pinned), the tickets (zero), the plan slots, h->sort, the leaf counters and lists, the run
+// search's block counts.  The build passes its max_leaves, everyone else n + 1.
+int group_scratch(ndt_handle* h, size_t n, size_t max_runs);
+// launch_find_runs on the handle's buffers (after group_scratch): runs of equal keys with >= min_pts entries -> h->nleaf,
+// h->leaf_start, h->leaf_cnt; fused: count and emit in one launch (the build with ndt_tuning::fused_sort on)
+hipError_t find_runs(ndt_handle* h, const uint32_t* keys_sorted, size_t n, int min_pts, bool fused);
 int build_begin(ndt_handle* h, const float* x, const float* y, const float* z, size_t n, ndt_handle::BuildRun& br);
 int build_enqueue(ndt_handle* h, ndt_handle::BuildRun& br);
 int build_collect(ndt_handle* h, ndt_handle::BuildRun& br);
@@ -699,7 +727,6 @@ void map_release(ndt_handle* h);   // ndt_map.hip: frees the voxel map, if any (
 // ndt_map.hip's host side as ndt_map_state.hip uses it (the kernels stay where they are)
 constexpr int64_t MAP_MAX_CAPACITY = 1ll << 30;   // slots are 32-bit sort keys with one sentinel above them
 int no_map(ndt_handle* h);
-int map_bits_for(long long v);
 int64_t map_pow2_at_least(int64_t v);
 int map_box_floor(float v, float inv_leaf);
 bool pose_finite(const double p[16]);
@@ -720,7 +747,6 @@ struct MapRefill {
   std::function<int(const MapTable&)> launch;
 };
 int map_grow_table(ndt_handle* h, VoxelMap& m, int64_t new_cap, const MapRefill* refill = nullptr);
-int map_sort_scratch(ndt_handle* h, size_t n);
 // (the VoxelMap a function takes is the map, *h->map, or one of its levels, h->map_level[]: ndt_map_levels.hip)
 int map_init_buffers(ndt_handle* h, VoxelMap& m);   // the small device / pinned words every VoxelMap works with
 int map_refresh_voxel_count(ndt_handle* h, VoxelMap& m);

@@ -114,19 +114,15 @@ int maybe_sort_source(ndt_handle* h, const float T[16]) {
   HIP_TRY(h, h->ox.ensure(n));
   HIP_TRY(h, h->oy.ensure(n));
   HIP_TRY(h, h->oz.ensure(n));
-  HIP_TRY(h, h->skeys.ensure(n));
-  HIP_TRY(h, h->skeys2.ensure(n));
-  HIP_TRY(h, h->svals.ensure(n));
-  HIP_TRY(h, h->svals2.ensure(n));
-  HIP_TRY(h, h->ssort_tmp.ensure(sort_temp_bytes(n)));
+  HIP_TRY(h, h->ssort.ensure(n));
   HIP_TRY(h, h->splan.ensure(1));
   PoseConsts pc{};
   for (int i = 0; i < 3; ++i) {
     for (int j = 0; j < 3; ++j) pc.R[3 * i + j] = T[4 * j + i];
     pc.t[i] = T[12 + i];
   }
-  HIP_TRY(h, sort_source_by_blocks(h->vx, h->vy, h->vz, n, h->geom, pc, h->splan.p, h->ssort_tmp.p, h->skeys.p,
-                                   h->skeys2.p, h->svals.p, h->svals2.p, h->ox.p, h->oy.p, h->oz.p, h->stream));
+  HIP_TRY(h, sort_source_by_blocks(h->vx, h->vy, h->vz, n, h->geom, pc, h->splan.p, h->ssort, h->ox.p, h->oy.p, h->oz.p,
+                                   h->stream));
   h->src_sorted = true;
   return NDT_OK;
 }

@@ -95,14 +95,14 @@ __global__ void __launch_bounds__(FIT_THREADS) k_fit_keys(const float* __restric
 
 // the finite points in cell order as float4; the first point of every cell claims a hash slot and records itself
 __global__ void __launch_bounds__(FIT_THREADS) k_fit_gather(const float* __restrict__ x, const float* __restrict__ y,
-                                                            const float* __restrict__ z, const uint32_t* __restrict__ skeys,
-                                                            const uint32_t* __restrict__ svals, int nf, uint32_t mask,
+                                                            const float* __restrict__ z, const uint32_t* __restrict__ sorted_keys,
+                                                            const uint32_t* __restrict__ sorted_vals, int nf, uint32_t mask,
                                                             float4* __restrict__ pts, uint32_t* __restrict__ tab) {
   const int i = blockIdx.x * FIT_THREADS + threadIdx.x;
   if (i >= nf) return;
-  const uint32_t key = skeys[i], idx = svals[i];
+  const uint32_t key = sorted_keys[i], idx = sorted_vals[i];
   pts[i] = make_float4(x[idx], y[idx], z[idx], 0.0f);
-  if (i > 0 && skeys[i - 1] == key) return;
+  if (i > 0 && sorted_keys[i - 1] == key) return;
   uint32_t slot = fit_hash(key, mask);
   for (;;) {   // (the table has at least twice as many slots as there are cells)
     if (atomicCAS(&tab[4 * (size_t)slot], FIT_EMPTY, key) == FIT_EMPTY) { tab[4 * (size_t)slot + 1] = (uint32_t)i; return; }
@@ -122,12 +122,12 @@ __device__ __forceinline__ int fit_find(const uint4* __restrict__ tab, uint32_t 
 }
 
 // the last point of every cell writes the cell's end (the slots were all claimed by the previous launch)
-__global__ void __launch_bounds__(FIT_THREADS) k_fit_ends(const uint32_t* __restrict__ skeys, int nf, uint32_t mask,
+__global__ void __launch_bounds__(FIT_THREADS) k_fit_ends(const uint32_t* __restrict__ sorted_keys, int nf, uint32_t mask,
                                                           uint32_t* __restrict__ tab) {
   const int i = blockIdx.x * FIT_THREADS + threadIdx.x;
   if (i >= nf) return;
-  const uint32_t key = skeys[i];
-  if (i + 1 < nf && skeys[i + 1] == key) return;
+  const uint32_t key = sorted_keys[i];
+  if (i + 1 < nf && sorted_keys[i + 1] == key) return;
   uint32_t slot = fit_hash(key, mask);
   while (tab[4 * (size_t)slot] != key) slot = (slot + 1) & mask;
   tab[4 * (size_t)slot + 2] = (uint32_t)(i + 1);
@@ -359,26 +359,16 @@ int fit_build(ndt_handle* h) {
   while (slots < 2 * (uint64_t)nf) slots <<= 1;
   g.hash_mask = slots - 1;
   // stable sort of (cell key, point) -- non-finite points carry the key ncells and sort behind the finite ones
-  HIP_TRY(h, f.keys.ensure(n));
-  HIP_TRY(h, f.vals.ensure(n));
-  HIP_TRY(h, f.keys2.ensure(n));
-  HIP_TRY(h, f.vals2.ensure(n));
-  HIP_TRY(h, f.sort_tmp.ensure(sort_temp_bytes(n)));
+  HIP_TRY(h, f.sort.ensure(n));
   HIP_TRY(h, f.plan.ensure(1));
   HIP_TRY(h, f.pts.ensure(4 * (size_t)nf));
   HIP_TRY(h, f.tab.ensure(4 * (size_t)slots));
-  int end_bit = 1;
-  while (end_bit < 32 && (g.ncells >> end_bit) != 0) ++end_bit;
-  f.plan_h = BuildGeom{};
-  fill_sort_plan(&f.plan_h, end_bit);
-  f.plan_h.status = BG_OK;
-  HIP_TRY(h, hipMemcpyAsync(f.plan.p, &f.plan_h, sizeof(BuildGeom), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_fit_keys, dim3(grid1(n)), dim3(FIT_THREADS), 0, s, x, y, z, (int)n, g, f.keys.p);
-  launch_sort_first_count(f.keys.p, n, f.plan.p, f.sort_tmp.p, s);
-  bool in_b = false;
-  HIP_TRY(h, sort_pairs(f.sort_tmp.p, f.keys.p, f.keys2.p, f.vals.p, f.vals2.p, n, f.plan_h.passes, f.plan.p, s, &in_b));
-  const uint32_t* sk = in_b ? f.keys2.p : f.keys.p;
-  const uint32_t* sv = in_b ? f.vals2.p : f.vals.p;
+  int passes = 0;
+  if (int rc = sort_put_plan(h, f.plan.p, sort_key_bits(g.ncells), 0, &passes)) return rc;   // (the last key is `ncells`)
+  hipLaunchKernelGGL(k_fit_keys, dim3(grid1(n)), dim3(FIT_THREADS), 0, s, x, y, z, (int)n, g, f.sort.keys.p);
+  SortedPairs sorted;
+  HIP_TRY(h, sort_keyed(f.sort, n, f.plan.p, passes, SORT_COUNT_FIRST, s, &sorted));
+  const uint32_t *sk = sorted.keys, *sv = sorted.vals;
   HIP_TRY(h, hipMemsetAsync(f.tab.p, 0xff, 4 * (size_t)slots * sizeof(uint32_t), s));
   hipLaunchKernelGGL(k_fit_gather, dim3(grid1((size_t)nf)), dim3(FIT_THREADS), 0, s, x, y, z, sk, sv, (int)nf, g.hash_mask,
                      reinterpret_cast<float4*>(f.pts.p), f.tab.p);

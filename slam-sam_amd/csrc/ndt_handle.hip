@@ -169,8 +169,7 @@ int ndt_destroy(ndt_handle* h) {
   h->dsk.release();
   h->scan.release();
   h->pkt.release();
-  h->keys.release(); h->vals.release(); h->keys2.release(); h->vals2.release();
-  h->sort_tmp.release(); h->nleaf.release(); h->leaf_start.release(); h->leaf_cnt.release();
+  h->sort.release(); h->plan_h.release(); h->nleaf.release(); h->leaf_start.release(); h->leaf_cnt.release();
   h->cell2leaf.release(); h->rec.release(); h->prec.release(); h->prec_valid = false; h->cent.release(); h->stats.release();
   h->run_counts.release(); h->run_offsets.release(); h->fin_counts.release(); h->bucket_tab.release(); h->bnd.release(); h->sort_tags.release(); h->run_tags.release(); h->xyz4.release(); h->leaf_sums.release();
   h->brows.release(); h->tickets.release(); h->gd.release(); h->gdh.release();
@@ -180,8 +179,7 @@ int ndt_destroy(ndt_handle* h) {
   h->keyframe_pool.clear();
   map_release(h);
   h->sx.release(); h->sy.release(); h->sz.release();
-  h->ox.release(); h->oy.release(); h->oz.release(); h->skeys.release(); h->skeys2.release();
-  h->svals.release(); h->svals2.release(); h->ssort_tmp.release(); h->splan.release();
+  h->ox.release(); h->oy.release(); h->oz.release(); h->ssort.release(); h->splan.release();
   h->result.release(); h->small.release(); h->partials.release();
   h->dres.release(); h->dposes.release(); h->hposes.release(); h->counters.release(); h->flag.release();
   if (h->mbox) (void)hipFree(h->mbox);
@@ -512,22 +510,16 @@ int ndt_debug_sort_pairs(ndt_handle* h, const uint32_t* keys, size_t n, int end_
   if (rc) return rc;
   settle_discard(h);
   hipStream_t s = h->stream;
-  HIP_TRY(h, h->keys.ensure(n));
-  HIP_TRY(h, h->vals.ensure(n));
-  HIP_TRY(h, h->keys2.ensure(n));
-  HIP_TRY(h, h->vals2.ensure(n));
-  HIP_TRY(h, h->sort_tmp.ensure(sort_temp_bytes(n)));
+  HIP_TRY(h, h->sort.ensure(n));
   HIP_TRY(h, h->gd.ensure(1));
-  BuildGeom plan{};
-  fill_sort_plan(&plan, end_bit);
-  plan.status = BG_OK;
-  HIP_TRY(h, hipMemcpyAsync(h->gd.p, &plan, sizeof(plan), hipMemcpyHostToDevice, s));
-  HIP_TRY(h, hipMemcpyAsync(h->keys.p, keys, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  launch_sort_first_count(h->keys.p, n, h->gd.p, h->sort_tmp.p, s);
-  bool in_b = false;
-  HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, n, plan.passes, h->gd.p, s, &in_b));
-  HIP_TRY(h, hipMemcpyAsync(keys_out, in_b ? h->keys2.p : h->keys.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(h, hipMemcpyAsync(vals_out, in_b ? h->vals2.p : h->vals.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  int passes = 0;
+  rc = sort_put_plan(h, h->gd.p, end_bit, 0, &passes);
+  if (rc) return rc;
+  HIP_TRY(h, hipMemcpyAsync(h->sort.keys.p, keys, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  SortedPairs sorted;
+  HIP_TRY(h, sort_keyed(h->sort, n, h->gd.p, passes, SORT_COUNT_FIRST, s, &sorted));
+  HIP_TRY(h, hipMemcpyAsync(keys_out, sorted.keys, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipMemcpyAsync(vals_out, sorted.vals, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(h, hipStreamSynchronize(s));
   target_drop(h);  // the build's scratch was overwritten
   return NDT_OK;

@@ -157,29 +157,14 @@ int build_begin(ndt_handle* h, const float* x, const float* y, const float* z, s
     int rc = neutral_bounds(h);
     if (rc) return rc;
   }
-  HIP_TRY(h, h->gd.ensure(1));
-  HIP_TRY(h, h->gdh.ensure(1));
-  if (!h->tickets.p) {
-    HIP_TRY(h, h->tickets.ensure(6));
-    HIP_TRY(h, hipMemsetAsync(h->tickets.p, 0, h->tickets.cap * sizeof(unsigned int), s));
-  }
-  HIP_TRY(h, h->nleaf.ensure(4));  // [0] slots, [1] valid, [2] buckets that declined (two-launch build)
+  if (int rc = group_scratch(h, n, (size_t)max_leaves)) return rc;
   // a re-allocation of `stats` would lose the cells the previous build published
   if ((size_t)max_leaves > h->stats.cap) br.clean_cap = 0;
-  HIP_TRY(h, h->keys.ensure(n));
   HIP_TRY(h, h->xyz4.ensure(4 * n));
-  HIP_TRY(h, h->vals.ensure(n));
-  HIP_TRY(h, h->keys2.ensure(n));
-  HIP_TRY(h, h->vals2.ensure(n));
-  HIP_TRY(h, h->leaf_start.ensure((size_t)max_leaves));
-  HIP_TRY(h, h->leaf_cnt.ensure((size_t)max_leaves));
   HIP_TRY(h, h->rec.ensure((size_t)max_leaves));
   HIP_TRY(h, h->cent.ensure((size_t)max_leaves * 4));
   HIP_TRY(h, h->leaf_sums.ensure((size_t)max_leaves * 9));
-  HIP_TRY(h, h->run_counts.ensure((size_t)runs_blocks(n)));
-  HIP_TRY(h, h->run_offsets.ensure((size_t)runs_blocks(n)));
   HIP_TRY(h, h->fin_counts.ensure((size_t)finalize_blocks(max_leaves)));
-  HIP_TRY(h, h->sort_tmp.ensure(sort_temp_bytes(n)));
   // fused = launches that wait, inside the kernel, for sibling blocks (k_sort_pass, k_runs<RUNS_FUSED>)
   br.fused = br.tn.fused_sort != 0;
   br.fused_sort = br.fused && fused_sort_fits(n, h->n_cus);
@@ -268,21 +253,17 @@ int build_enqueue(ndt_handle* h, ndt_handle::BuildRun& br) {
       HIP_TRY(h, hipMemsetAsync(h->cell2leaf.p, 0xFF, h->cell2leaf.cap * sizeof(int), s));
     }
     HIP_TRY(h, h->stats.ensure((size_t)max_leaves));
-    bool in_b = false;
+    SortedPairs sorted;
     if (br.fused && br.fused_sort) {
-      HIP_TRY(h, sort_cloud_fused(x, y, z, n, fused_tile_for(n, h->n_cus), h->gd.p, h->gdh.d, h->xyz4.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p,
-                                  passes, h->sort_tags.p, &h->sort_seq, s, &in_b));
+      HIP_TRY(h, sort_cloud_fused(x, y, z, n, fused_tile_for(n, h->n_cus), h->gd.p, h->gdh.d, h->xyz4.p, h->sort, passes,
+                                  h->sort_tags.p, &h->sort_seq, s, &sorted));
     } else {
-      launch_cell_keys(x, y, z, n, h->gd.p, h->keys.p, h->xyz4.p, h->sort_tmp.p, s);
-      HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, n, passes, h->gd.p, s, &in_b));
+      launch_cell_keys(x, y, z, n, h->gd.p, h->sort.keys.p, h->xyz4.p, h->sort.tmp.p, s);
+      HIP_TRY(h, sort_keyed(h->sort, n, h->gd.p, passes, SORT_FIRST_COUNTED, s, &sorted));
     }
-    const uint32_t* keys_sorted = in_b ? h->keys2.p : h->keys.p;
-    const uint32_t* vals_sorted = in_b ? h->vals2.p : h->vals.p;
-    HIP_TRY(h, launch_find_runs(keys_sorted, n, h->gd.p, h->gdh.d, min_pts, h->nleaf.p, h->run_counts.p, h->run_offsets.p,
-                                h->tickets.p + 1, br.fused ? h->run_tags.p : nullptr, h->run_tags.cap, &h->run_seq,
-                                h->leaf_start.p, h->leaf_cnt.p, s));
+    HIP_TRY(h, find_runs(h, sorted.keys, n, min_pts, br.fused));
     FinalizeParams fp{h->prm.eig_inflation_ratio, h->prm.cov_mode};
-    launch_finalize_leaves(br.tn, h->xyz4.p, keys_sorted, vals_sorted, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p, max_leaves,
+    launch_finalize_leaves(br.tn, h->xyz4.p, sorted.keys, sorted.vals, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p, max_leaves,
                            fp, h->leaf_sums.p, h->rec.p, h->cent.p, h->stats.p, h->cell2leaf.p, h->fin_counts.p, h->tickets.p + 2,
                            h->small.d + 8, done_tag, s);
   }  // (sort-based pipeline)

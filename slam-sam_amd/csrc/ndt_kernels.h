@@ -3,8 +3,11 @@
 
 #include "../../include/ndt_hip.h"
 #include "ndt_device.h"
+#include "ndt_sort_plan.h"
 
 namespace ndt {
+
+namespace engine { struct SortScratch; }  // ndt_engine.h: the five arrays of a pair sort
 
 // ---- target voxel-grid build (ndt_target.hip) ------------------------------
 struct FinalizeParams {
@@ -33,15 +36,12 @@ void launch_bounds_geometry(const ndt_tuning& tn, const float* x, const float* y
 void launch_cell_keys(const float* x, const float* y, const float* z, size_t n, const BuildGeom* gd,
                       uint32_t* keys, float* xyz4, void* sort_temp, hipStream_t s);
 
-// Stable LSD radix sort of (key, point index) on the key bits of the plan in *gd; values start
-// as the identity.  Ping-pongs between the a and b buffers; *result_in_b tells where the result is.
+// Stable LSD radix sort of (key, point index) on the key bits of the plan in *gd; values start as the identity
+// (ndt_sort.hip; the call itself is sort_keyed, ndt_engine.h).  sort_tiles(n) tiles of pairs, sort_temp_bytes(n) of
+// histogram scratch; a sort hands its result back as SortedPairs.
+int sort_tiles(size_t n);
 size_t sort_temp_bytes(size_t n);
-hipError_t sort_pairs(void* temp, uint32_t* keys_a, uint32_t* keys_b, uint32_t* vals_a, uint32_t* vals_b,
-                      size_t n, int passes, const BuildGeom* gd, hipStream_t s, bool* result_in_b);
-// test seam: a plan for keys of end_bit bits (host struct), and the first digit's histograms
-// for keys that did not come from launch_cell_keys
-void fill_sort_plan(BuildGeom* b, int end_bit);
-void launch_sort_first_count(const uint32_t* keys, size_t n, const BuildGeom* gd, void* sort_temp, hipStream_t s);
+struct SortedPairs { const uint32_t *keys, *vals; };
 
 // One launch per digit, straight from the cloud (no launch_cell_keys): see k_sort_pass.  Only for
 // clouds with fused_sort_fits(n, CUs of the device); `table`: fused_table_words() words, zero at allocation; a build
@@ -51,9 +51,8 @@ bool fused_sort_fits(size_t n, int compute_units);
 int fused_tile_for(size_t n, int compute_units);  // pairs per tile (8192 up to 2 M points on 256 CUs, 16384 up to 4 M), 0 = classic passes
 size_t fused_table_words();
 hipError_t sort_cloud_fused(const float* x, const float* y, const float* z, size_t n, int tile, BuildGeom* gd,
-                            BuildGeom* gd_host, float* xyz4, uint32_t* keys_a, uint32_t* keys_b, uint32_t* vals_a,
-                            uint32_t* vals_b, int passes, uint32_t* table, uint32_t* seq, hipStream_t s,
-                            bool* result_in_b);
+                            BuildGeom* gd_host, float* xyz4, engine::SortScratch& sc, int passes, uint32_t* table,
+                            uint32_t* seq, hipStream_t s, SortedPairs* out);
 
 // The whole build in TWO launches (k_bucket_pass + k_bucket_leaves, ndt_target.hip): steady state only --
 // every buffer exists and the dense grid holds nothing but the `dirty_slots` cells of old_stats.  tab: the
@@ -142,12 +141,11 @@ void launch_transform_append(const float* x, const float* y, const float* z, siz
 
 // Source ordering: the source cloud stably sorted by the 8 x 8 x 4-voxel block of the target grid
 // its points fall into under the transform P (keys + first histogram, the digit passes, gather).
-// keys/vals a, b: n uint32 each; temp: sort_temp_bytes(n); plan: one BuildGeom of scratch in
-// device memory; ox/oy/oz: the sorted copy.
+// sc: the source's own sort scratch, ensured for n pairs; plan: one BuildGeom of scratch in device memory;
+// ox/oy/oz: the sorted copy.
 int source_sort_passes(const GridGeom& g);
 hipError_t sort_source_by_blocks(const float* x, const float* y, const float* z, size_t n, const GridGeom& g,
-                                 const PoseConsts& P, BuildGeom* plan, void* temp, uint32_t* keys_a,
-                                 uint32_t* keys_b, uint32_t* vals_a, uint32_t* vals_b, float* ox, float* oy,
+                                 const PoseConsts& P, BuildGeom* plan, engine::SortScratch& sc, float* ox, float* oy,
                                  float* oz, hipStream_t s);
 
 // ---- derivative evaluation (ndt_derivs.hip) ---------------------------------

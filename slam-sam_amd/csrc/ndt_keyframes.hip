@@ -259,23 +259,8 @@ static int voxel_downsample_device_impl(ndt_handle* h, const float* dx, const fl
   hipStream_t s = h->stream;
   const ndt_tuning tn = tuning_snapshot();   // (the bounds launch below and the rows it writes: one configuration)
   HIP_TRY(h, h->brows.ensure(8 * (size_t)std::max(bounds_rows(tn, n), bucket_build_tiles(tn, n))));
-  HIP_TRY(h, h->gd.ensure(1));
-  HIP_TRY(h, h->gdh.ensure(1));
-  if (!h->tickets.p) {
-    HIP_TRY(h, h->tickets.ensure(6));
-    HIP_TRY(h, hipMemsetAsync(h->tickets.p, 0, h->tickets.cap * sizeof(unsigned int), s));
-  }
-  HIP_TRY(h, h->nleaf.ensure(4));
-  HIP_TRY(h, h->keys.ensure(n));
+  if (int rc = group_scratch(h, n, n + 1)) return rc;
   HIP_TRY(h, h->xyz4.ensure(4 * n));
-  HIP_TRY(h, h->vals.ensure(n));
-  HIP_TRY(h, h->keys2.ensure(n));
-  HIP_TRY(h, h->vals2.ensure(n));
-  HIP_TRY(h, h->leaf_start.ensure(n + 1));
-  HIP_TRY(h, h->leaf_cnt.ensure(n + 1));
-  HIP_TRY(h, h->run_counts.ensure((size_t)runs_blocks(n)));
-  HIP_TRY(h, h->run_offsets.ensure((size_t)runs_blocks(n)));
-  HIP_TRY(h, h->sort_tmp.ensure(sort_temp_bytes(n)));
   HIP_TRY(h, h->small.ensure(16));
   h->gdh.h->status = -1;
   // the geometry is awaited (its pass count sizes the sort): a full, launch-per-phase pipeline that never waits
@@ -288,14 +273,11 @@ static int voxel_downsample_device_impl(ndt_handle* h, const float* dx, const fl
   if (bg.status == BG_NO_FINITE) return NDT_OK;   // nothing finite: an empty output, as PCL's filter leaves it
   if (bg.status != BG_OK)
     return fail(h, NDT_ERR_GRID_OVERFLOW, "leaf size too small for the cloud's extent (index overflow; PCL's VoxelGrid refuses the same cloud)");
-  launch_cell_keys(dx, dy, dz, n, h->gd.p, h->keys.p, h->xyz4.p, h->sort_tmp.p, s);
-  bool in_b = false;
-  HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, n, bg.passes, h->gd.p, s, &in_b));
-  const uint32_t* keys_sorted = in_b ? h->keys2.p : h->keys.p;
-  const uint32_t* vals_sorted = in_b ? h->vals2.p : h->vals.p;
-  HIP_TRY(h, launch_find_runs(keys_sorted, n, h->gd.p, h->gdh.d, /*min_pts=*/1, h->nleaf.p, h->run_counts.p, h->run_offsets.p,
-                              h->tickets.p + 1, nullptr, 0, &h->run_seq, h->leaf_start.p, h->leaf_cnt.p, s));
-  launch_voxel_centroids(h->xyz4.p, di, vals_sorted, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p, n, cap, ox, oy, oz, oi, s);
+  launch_cell_keys(dx, dy, dz, n, h->gd.p, h->sort.keys.p, h->xyz4.p, h->sort.tmp.p, s);
+  SortedPairs sorted;
+  HIP_TRY(h, sort_keyed(h->sort, n, h->gd.p, bg.passes, SORT_FIRST_COUNTED, s, &sorted));
+  HIP_TRY(h, find_runs(h, sorted.keys, n, /*min_pts=*/1, /*fused=*/false));
+  launch_voxel_centroids(h->xyz4.p, di, sorted.vals, h->nleaf.p, h->leaf_start.p, h->leaf_cnt.p, n, cap, ox, oy, oz, oi, s);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(h->small.h + 12, h->nleaf.p, sizeof(int), hipMemcpyDeviceToHost, s));
   HIP_TRY(h, hipStreamSynchronize(s));

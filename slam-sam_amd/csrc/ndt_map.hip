@@ -320,12 +320,6 @@ constexpr int64_t MAP_DEFAULT_CAPACITY = 1ll << 18;
 
 // ---- the host side ndt_map_state.hip shares (declared in ndt_engine.h) ----
 
-int map_bits_for(long long v) {  // bits that hold 0 .. v
-  int b = 0;
-  while (b < 62 && (1ll << b) <= v) ++b;
-  return b;
-}
-
 void map_free_table(MapTable& t) {
   if (t.keys) (void)hipFree(t.keys);
   if (t.sums) (void)hipFree(t.sums);
@@ -359,39 +353,6 @@ int64_t map_pow2_at_least(int64_t v) {
   int64_t c = 64;
   while (c < v) c <<= 1;
   return c;
-}
-
-// the scratch of the build that the sort and the run search work in, for n pairs
-int map_sort_scratch(ndt_handle* h, size_t n) {
-  HIP_TRY(h, h->gd.ensure(1));
-  HIP_TRY(h, h->gdh.ensure(1));
-  if (!h->tickets.p) {
-    HIP_TRY(h, h->tickets.ensure(6));
-    HIP_TRY(h, hipMemsetAsync(h->tickets.p, 0, h->tickets.cap * sizeof(unsigned int), h->stream));
-  }
-  HIP_TRY(h, h->nleaf.ensure(4));
-  HIP_TRY(h, h->keys.ensure(n));
-  HIP_TRY(h, h->vals.ensure(n));
-  HIP_TRY(h, h->keys2.ensure(n));
-  HIP_TRY(h, h->vals2.ensure(n));
-  HIP_TRY(h, h->leaf_start.ensure(n + 1));
-  HIP_TRY(h, h->leaf_cnt.ensure(n + 1));
-  HIP_TRY(h, h->run_counts.ensure((size_t)runs_blocks(n)));
-  HIP_TRY(h, h->run_offsets.ensure((size_t)runs_blocks(n)));
-  HIP_TRY(h, h->sort_tmp.ensure(sort_temp_bytes(n)));
-  return NDT_OK;
-}
-
-// a sort plan for keys of `bits` bits in pinned slot `which`, copied to the build's device-side BuildGeom on the stream
-int map_put_plan(ndt_handle* h, VoxelMap& m, int which, int bits, int ncells, int* passes) {
-  BuildGeom& b = m.plan_h.h[which];
-  b = BuildGeom{};
-  fill_sort_plan(&b, bits);
-  b.g.ncells = ncells;
-  b.status = BG_OK;
-  *passes = b.passes;
-  HIP_TRY(h, hipMemcpyAsync(h->gd.p, &b, sizeof(BuildGeom), hipMemcpyHostToDevice, h->stream));
-  return NDT_OK;
 }
 
 // n_voxels as the device counts it (the insert launches before this point have run when the call returns)
@@ -467,23 +428,21 @@ int map_grow_table(ndt_handle* h, VoxelMap& m, int64_t new_cap, const MapRefill*
 
 // The batch's n keys (m.pkey; MAP_EMPTY: skipped) get their slots in table `t` (k_map_insert: *d_nvox -- for the map's own
 // table the device's voxel counter -- goes up by the voxels created), then the stable sort of (slot, index) and the run search: run r of *keys_sorted / *vals_sorted is one
-// voxel's entries in input order (h->nleaf, h->leaf_start, h->leaf_cnt).  After map_sort_scratch(n); enqueued, not awaited.
+// voxel's entries in input order (h->nleaf, h->leaf_start, h->leaf_cnt).  After group_scratch(n, n + 1); enqueued, not awaited.
 int map_group_batch(ndt_handle* h, VoxelMap& m, size_t n, const MapTable& t, unsigned long long* d_nvox,
                     const uint32_t** keys_sorted, const uint32_t** vals_sorted) {
   hipStream_t s = h->stream;
   const unsigned blocks = (unsigned)((n + MAP_THREADS - 1) / MAP_THREADS);
   hipLaunchKernelGGL(k_map_insert, dim3(blocks), dim3(MAP_THREADS), 0, s, m.pkey.p, (int)n, t.keys,
-                     (unsigned long long)(t.capacity - 1), h->keys.p, d_nvox, m.stats.p);
+                     (unsigned long long)(t.capacity - 1), h->sort.keys.p, d_nvox, m.stats.p);
   int passes = 0;
-  int rc = map_put_plan(h, m, 0, map_bits_for(t.capacity), (int)t.capacity, &passes);   // (the sentinel `capacity` sorts behind every slot)
+  int rc = sort_put_plan(h, h->gd.p, sort_key_bits(t.capacity), (int)t.capacity, &passes);   // (the sentinel `capacity` sorts behind every slot)
   if (rc) return rc;
-  launch_sort_first_count(h->keys.p, n, h->gd.p, h->sort_tmp.p, s);
-  bool in_b = false;
-  HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, n, passes, h->gd.p, s, &in_b));
-  *keys_sorted = in_b ? h->keys2.p : h->keys.p;
-  *vals_sorted = in_b ? h->vals2.p : h->vals.p;
-  HIP_TRY(h, launch_find_runs(*keys_sorted, n, h->gd.p, h->gdh.d, /*min_pts=*/1, h->nleaf.p, h->run_counts.p, h->run_offsets.p,
-                              h->tickets.p + 1, nullptr, 0, &h->run_seq, h->leaf_start.p, h->leaf_cnt.p, s));
+  SortedPairs sorted;
+  HIP_TRY(h, sort_keyed(h->sort, n, h->gd.p, passes, SORT_COUNT_FIRST, s, &sorted));
+  *keys_sorted = sorted.keys;
+  *vals_sorted = sorted.vals;
+  HIP_TRY(h, find_runs(h, sorted.keys, n, /*min_pts=*/1, /*fused=*/false));
   return NDT_OK;
 }
 
@@ -504,7 +463,7 @@ int map_add_device(ndt_handle* h, const float* dx, const float* dy, const float*
     HIP_TRY(h, m.py.ensure(n));
     HIP_TRY(h, m.pz.ensure(n));
   }
-  int rc = map_sort_scratch(h, n);
+  int rc = group_scratch(h, n, n + 1);
   if (rc) return rc;
   const float *qx = dx, *qy = dy, *qz = dz;
   if (pose16) {
@@ -599,13 +558,13 @@ int map_export_count(ndt_handle* h, VoxelMap& m, const MapSel& sel, bool box, si
 int map_export_order(ndt_handle* h, VoxelMap& m, const MapSel& sel, bool box_sel, size_t total, const int mn[3], const int mx[3],
                      const uint32_t** order_out, const uint32_t** slots_out) {
   hipStream_t s = h->stream;
-  int rc = map_sort_scratch(h, total);
+  int rc = group_scratch(h, total, total + 1);
   if (rc) return rc;
   MapKeyBox box;
   for (int a = 0; a < 3; ++a) box.mn[a] = mn[a];
-  box.bx = map_bits_for((long long)mx[0] - mn[0]);
-  box.by = map_bits_for((long long)mx[1] - mn[1]);
-  const int bits = box.bx + box.by + map_bits_for((long long)mx[2] - mn[2]);
+  box.bx = sort_key_bits((long long)mx[0] - mn[0]);
+  box.by = sort_key_bits((long long)mx[1] - mn[1]);
+  const int bits = box.bx + box.by + sort_key_bits((long long)mx[2] - mn[2]);
   const bool two_words = bits > 32;
   HIP_TRY(h, m.xslot.ensure(total));
   if (two_words) {
@@ -615,28 +574,26 @@ int map_export_order(ndt_handle* h, VoxelMap& m, const MapSel& sel, bool box_sel
   const int nb = (int)((m.tab.capacity + MAP_XTILE - 1) / MAP_XTILE);
   if (box_sel)
     hipLaunchKernelGGL(k_map_xemit<true>, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.tab.keys, m.tab.cnt, (long long)m.tab.capacity, sel,
-                       m.xcounts.p, box, m.xslot.p, h->keys.p, two_words ? m.xhi.p : nullptr);
+                       m.xcounts.p, box, m.xslot.p, h->sort.keys.p, two_words ? m.xhi.p : nullptr);
   else
     hipLaunchKernelGGL(k_map_xemit<false>, dim3((unsigned)nb), dim3(MAP_THREADS), 0, s, m.tab.keys, m.tab.cnt, (long long)m.tab.capacity, sel,
-                       m.xcounts.p, box, m.xslot.p, h->keys.p, two_words ? m.xhi.p : nullptr);
+                       m.xcounts.p, box, m.xslot.p, h->sort.keys.p, two_words ? m.xhi.p : nullptr);
   HIP_TRY(h, hipGetLastError());
   int passes = 0;
-  rc = map_put_plan(h, m, 1, std::min(bits, 32), 0, &passes);
+  rc = sort_put_plan(h, h->gd.p, std::min(bits, 32), 0, &passes);
   if (rc) return rc;
-  launch_sort_first_count(h->keys.p, total, h->gd.p, h->sort_tmp.p, s);
-  bool in_b = false;
-  HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, total, passes, h->gd.p, s, &in_b));
-  const uint32_t* order = in_b ? h->vals2.p : h->vals.p;
+  SortedPairs sorted;
+  HIP_TRY(h, sort_keyed(h->sort, total, h->gd.p, passes, SORT_COUNT_FIRST, s, &sorted));
+  const uint32_t* order = sorted.vals;
   const uint32_t* slots = m.xslot.p;
   if (two_words) {   // stable: the order of the low words survives among equal high words
     const unsigned tb = (unsigned)((total + MAP_THREADS - 1) / MAP_THREADS);
-    hipLaunchKernelGGL(k_map_xgather, dim3(tb), dim3(MAP_THREADS), 0, s, order, m.xhi.p, m.xslot.p, (int)total, h->keys.p, m.xslot2.p);
+    hipLaunchKernelGGL(k_map_xgather, dim3(tb), dim3(MAP_THREADS), 0, s, order, m.xhi.p, m.xslot.p, (int)total, h->sort.keys.p, m.xslot2.p);
     HIP_TRY(h, hipGetLastError());
-    rc = map_put_plan(h, m, 2, bits - 32, 0, &passes);
+    rc = sort_put_plan(h, h->gd.p, bits - 32, 0, &passes);
     if (rc) return rc;
-    launch_sort_first_count(h->keys.p, total, h->gd.p, h->sort_tmp.p, s);
-    HIP_TRY(h, sort_pairs(h->sort_tmp.p, h->keys.p, h->keys2.p, h->vals.p, h->vals2.p, total, passes, h->gd.p, s, &in_b));
-    order = in_b ? h->vals2.p : h->vals.p;
+    HIP_TRY(h, sort_keyed(h->sort, total, h->gd.p, passes, SORT_COUNT_FIRST, s, &sorted));
+    order = sorted.vals;
     slots = m.xslot2.p;
   }
   *order_out = order;
@@ -672,7 +629,6 @@ int map_init_buffers(ndt_handle* h, VoxelMap& m) {
   if (e == hipSuccess) e = m.nvox.ensure(2);   // [1]: the voxels a re-pose creates in its fresh table
   if (e == hipSuccess) e = m.stats_h.ensure(2 * MS_WORDS);
   if (e == hipSuccess) e = m.nvox_h.ensure(2);
-  if (e == hipSuccess) e = m.plan_h.ensure(3);
   if (e == hipSuccess) e = m.tsel.ensure(TS_WORDS);
   if (e == hipSuccess) e = m.tsel_h.ensure(2 * TS_WORDS);
   if (e == hipSuccess) e = hipMemsetAsync(m.nvox.p, 0, sizeof(unsigned long long), h->stream);

@@ -153,7 +153,7 @@ int level_get(ndt_handle* h, int level, VoxelMap** out) {
     hipError_t e = lv->pkey.ensure(n);
     if (e == hipSuccess) e = lv->lchild.ensure(n);
     if (e != hipSuccess) return drop_level(h, lv, fail(h, e == hipErrorOutOfMemory ? NDT_ERR_ALLOC : NDT_ERR_HIP, hipGetErrorString(e)));
-    rc = map_sort_scratch(h, n);
+    rc = group_scratch(h, n, n + 1);
     if (rc) return drop_level(h, lv, rc);
     MapSel sel{};
     sel.min_points = INT_MIN;   // every occupied voxel

@@ -156,7 +156,7 @@ int map_transform(ndt_handle* h, const double* pose16, int64_t* n_after) {
   HIP_TRY(h, m.xout.ensure(4 * n));
   if (m.moments) HIP_TRY(h, m.xmom.ensure(9 * n));
   HIP_TRY(h, m.pkey.ensure(n));
-  rc = map_sort_scratch(h, n);
+  rc = group_scratch(h, n, n + 1);
   if (rc) return rc;
   // the records in export-state order, in the staging arrays
   size_t total = 0;
@@ -189,7 +189,7 @@ int map_import_posed(ndt_handle* h, const double* pose16, const int32_t* d_count
   HIP_TRY(h, m.xout.ensure(4 * n));
   if (m.moments) HIP_TRY(h, m.xmom.ensure(9 * n));
   HIP_TRY(h, m.pkey.ensure(n));
-  int rc = map_sort_scratch(h, n);
+  int rc = group_scratch(h, n, n + 1);
   if (rc) return rc;
   rc = repose_records(h, pose16, d_count, d_sums, m.moments ? d_mom : nullptr, n, m.xout.p, m.moments ? m.xmom.p : nullptr);
   if (rc) return rc;

@@ -204,7 +204,7 @@ int map_export_state(ndt_handle* h, VoxelMap& m, const float* box_min, const flo
 
 // The n records' keys (m.pkey), grouped by their slot in table `t` (map_group_batch; *d_nvox goes up by the voxels they
 // create there), continue the sums `t` holds: per voxel its records in input order, old + record.field.  After
-// map_sort_scratch(n); enqueued, not awaited.
+// group_scratch(n, n + 1); enqueued, not awaited.
 int map_merge_records(ndt_handle* h, const MapTable& t, unsigned long long* d_nvox, const int32_t* d_count, const float* d_sums,
                       const double* d_mom, size_t n) {
   VoxelMap& m = *h->map;
@@ -272,7 +272,7 @@ int map_import_state(ndt_handle* h, const int32_t* d_ijk, const int32_t* d_count
   hipStream_t s = h->stream;
   // every allocation of the import except the table's growth, before anything is written
   HIP_TRY(h, m.pkey.ensure(n));
-  const int rc = map_sort_scratch(h, n);
+  const int rc = group_scratch(h, n, n + 1);
   if (rc) return rc;
   const unsigned blocks = (unsigned)((n + MAP_THREADS - 1) / MAP_THREADS);
   HIP_TRY(h, hipMemcpyAsync(m.stats.p, m.stats_h.h + MS_WORDS, MS_WORDS * sizeof(int), hipMemcpyHostToDevice, s));

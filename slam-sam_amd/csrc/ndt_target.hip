@@ -21,9 +21,10 @@
 //                      inverse; publishes an 80-byte VoxelRecord and the dense
 //                      cell -> leaf index.
 // Compiled with -ffp-contract=off: f32 index arithmetic must round as written.
-#include "ndt_kernels.h"
+#include "ndt_engine.h"       // SortScratch, sort_keyed
 #include "ndt_leaf_device.h"  // finalize_leaf
 #include "ndt_map_device.h"  // the voxel map's key (k_map_finalize, k_map_gather_moments)
+#include "ndt_sort_device.h" // the radix sort's tile shape (k_cell_keys, k_sort_pass, k_source_keys, the bucketed build)
 
 #include <climits>
 #include <cstdlib>
@@ -133,19 +134,12 @@ __device__ void derive_geometry(const int mnmx[6], int n_finite, float leaf, flo
         g.mul2 = g.div_b[0] * g.div_b[1];
         g.ncells = (int)ncells;
         if (ncells > cell_capacity) b.status = BG_CAPACITY;
-        int bits = 1;
-        while (bits < 32 && (1ull << bits) <= (unsigned long long)ncells) ++bits;  // the sentinel key is `ncells`
+        const int bits = sort_key_bits(ncells);  // the sentinel key is `ncells`: 1 <= ncells < 2^31, so 1 .. 31 bits
         b.bits = bits;
-        const int need = (bits + 7) / 8;
+        const int need = sort_passes_for_bits(bits);
         if (planned_passes <= 0) b.passes = need;
         else if (need > planned_passes && b.status == BG_OK) b.status = BG_PASSES;
-        const int base = bits / b.passes, rem = bits % b.passes;
-        int sh = 0;
-        for (int i = 0; i < b.passes && i < 4; ++i) {
-          b.width[i] = base + (i < rem ? 1 : 0);
-          b.shift[i] = sh;
-          sh += b.width[i];
-        }
+        sort_split_bits(bits, b.passes, b.width, b.shift);
       }
     }
   }
@@ -278,30 +272,6 @@ __device__ __forceinline__ int cell_of(float px, float py, float pz, const GridG
   return i0 + i1 * g.mul1 + i2 * g.mul2;
 }
 
-// ---- stable LSD radix sort of (cell key, point index) ---------------------------------
-// One tile = 2048 consecutive pairs per 256-thread block; wave w owns the contiguous
-// quarter [w*512, (w+1)*512) of the tile and walks it in 8 rounds of 64, so "tile order"
-// is (wave, round, lane).  Per digit pass: count (per-tile histogram, bin-major), scan (one
-// block per bin over the tiles + bin totals), scatter (rank of a pair among the equal
-// digits before it in the tile: equal-digit lanes of a round find each other with 8
-// ballots, rounds chain through a per-wave LDS counter, waves through a 4-entry prefix).
-// No atomics on global memory, no look-back chain between tiles: every launch is a
-// streaming pass, and the result does not depend on scheduling.
-constexpr int SORT_THREADS = 256;
-constexpr int SORT_ROUNDS = 8;
-constexpr int SORT_WAVES = SORT_THREADS / 64;
-constexpr int SORT_TILE = SORT_THREADS * SORT_ROUNDS;
-constexpr int SORT_BINS = 256;
-// (Round 2 tried to let scatter pass p count the tile histogram of pass p + 1 with integer atomics
-// on a global table -- one launch per pass less.  A million device-scope atomicAdds spread over
-// 125 k counters took 88-248 us per pass: across eight XCDs they are served at the memory side.
-// Reverted; the per-tile LDS histogram of k_sort_count costs 6 us.)
-
-__device__ __forceinline__ int sort_index(int tile, int wave, int round, int lane) {
-  return tile * SORT_TILE + wave * (SORT_TILE / SORT_WAVES) + round * 64 + lane;
-}
-
-
 // Cell key per point (+ the packed float4 copy the per-voxel gather reads) and, in the same
 // pass, the tile histograms of the first sort digit.
 __global__ void __launch_bounds__(SORT_THREADS) k_cell_keys(const float* __restrict__ x, const float* __restrict__ y,
@@ -339,137 +309,6 @@ __global__ void __launch_bounds__(SORT_THREADS) k_cell_keys(const float* __restr
   }
   __syncthreads();
   hist[threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
-}
-
-__global__ void __launch_bounds__(SORT_THREADS) k_sort_count(const uint32_t* __restrict__ keys, int n, int pass,
-                                                            const BuildGeom* __restrict__ gd, int ntiles,
-                                                            int* __restrict__ hist) {
-  __shared__ int h[SORT_BINS];
-  if (gd->status != BG_OK) return;
-  const int shift = gd->shift[pass];
-  const uint32_t digit_mask = (1u << gd->width[pass]) - 1u;
-  h[threadIdx.x] = 0;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t key[SORT_ROUNDS];
-#pragma unroll
-  for (int r = 0; r < SORT_ROUNDS; ++r) {
-    const int i = sort_index(blockIdx.x, wave, r, lane);
-    key[r] = keys[i < n ? i : 0];
-  }
-#pragma unroll
-  for (int r = 0; r < SORT_ROUNDS; ++r)
-    if (sort_index(blockIdx.x, wave, r, lane) < n) atomicAdd(&h[(key[r] >> shift) & digit_mask], 1);
-  __syncthreads();
-  hist[threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
-}
-
-__device__ __forceinline__ int wave_inclusive_scan(int v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    int t = __shfl_up(v, off);
-    if (lane >= off) v += t;
-  }
-  return v;
-}
-
-// one block per bin: exclusive scan of that bin's counts over the tiles (in place) + total
-__global__ void __launch_bounds__(SORT_THREADS) k_sort_scan(int* __restrict__ hist, int ntiles, int* __restrict__ totals) {
-  __shared__ int wsum[SORT_WAVES];
-  __shared__ int carry;
-  int* row = hist + (size_t)blockIdx.x * ntiles;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int base = 0; base < ntiles; base += SORT_THREADS) {
-    const int i = base + threadIdx.x;
-    const int v = i < ntiles ? row[i] : 0;
-    const int incl = wave_inclusive_scan(v, lane);
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int before = carry;
-    for (int w = 0; w < wave; ++w) before += wsum[w];
-    if (i < ntiles) row[i] = before + incl - v;
-    __syncthreads();
-    if (threadIdx.x == SORT_THREADS - 1) carry = before + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) totals[blockIdx.x] = carry;
-}
-
-// FIRST: the values are the identity permutation and are synthesised instead of read
-template <bool FIRST>
-__global__ void __launch_bounds__(SORT_THREADS) k_sort_scatter(const uint32_t* __restrict__ keys_in,
-                                                              const uint32_t* __restrict__ vals_in, int n, int pass,
-                                                              const BuildGeom* __restrict__ gd, int ntiles,
-                                                              const int* __restrict__ hist,
-                                                              const int* __restrict__ totals,
-                                                              uint32_t* __restrict__ keys_out,
-                                                              uint32_t* __restrict__ vals_out) {
-  __shared__ int cnt[SORT_WAVES][SORT_BINS];
-  __shared__ int gbase[SORT_BINS];
-  __shared__ int wsum[SORT_WAVES];
-  if (gd->status != BG_OK) return;
-  const int shift = gd->shift[pass];
-  const uint32_t digit_mask = (1u << gd->width[pass]) - 1u;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  {  // first output slot of every digit for this tile: bins before it + same bin in earlier tiles
-    const int t = totals[threadIdx.x];
-    const int incl = wave_inclusive_scan(t, lane);
-    if (lane == 63) wsum[wave] = incl;
-#pragma unroll
-    for (int w = 0; w < SORT_WAVES; ++w) cnt[w][threadIdx.x] = 0;
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < wave; ++w) before += wsum[w];
-    gbase[threadIdx.x] = before + incl - t + hist[threadIdx.x * ntiles + blockIdx.x];
-  }
-  uint32_t key[SORT_ROUNDS], val[SORT_ROUNDS];
-  int rank[SORT_ROUNDS];
-#pragma unroll
-  for (int r = 0; r < SORT_ROUNDS; ++r) {
-    const int i = sort_index(blockIdx.x, wave, r, lane);
-    key[r] = i < n ? keys_in[i] : 0u;
-    val[r] = FIRST ? (uint32_t)i : (i < n ? vals_in[i] : 0u);
-  }
-  const unsigned long long lt_mask = (1ull << lane) - 1ull;
-#pragma unroll
-  for (int r = 0; r < SORT_ROUNDS; ++r) {
-    const bool valid = sort_index(blockIdx.x, wave, r, lane) < n;
-    const uint32_t d = (key[r] >> shift) & digit_mask;
-    unsigned long long same = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const unsigned long long bal = __ballot(bit);
-      same &= bit ? bal : ~bal;
-    }
-    const int before = cnt[wave][d];
-    const int lower = __popcll(same & lt_mask);
-    rank[r] = before + lower;
-    __builtin_amdgcn_wave_barrier();
-    if (valid && lower == 0) cnt[wave][d] = before + __popcll(same);
-    __builtin_amdgcn_wave_barrier();
-  }
-  __syncthreads();
-  {
-    int run = 0;
-#pragma unroll
-    for (int w = 0; w < SORT_WAVES; ++w) {
-      const int t = cnt[w][threadIdx.x];
-      cnt[w][threadIdx.x] = run;
-      run += t;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < SORT_ROUNDS; ++r) {
-    if (sort_index(blockIdx.x, wave, r, lane) >= n) break;
-    const uint32_t d = (key[r] >> shift) & digit_mask;
-    const int pos = gbase[d] + cnt[wave][d] + rank[r];
-    keys_out[pos] = key[r];
-    vals_out[pos] = val[r];
-  }
 }
 
 // ---- one launch per digit ("fused pass") -------------------------------------------------
@@ -2065,10 +1904,8 @@ __host__ __device__ inline SourceBlocks source_blocks(const GridGeom& g) {
   b.nbx = (g.div_b[0] + 7) >> 3;
   b.nby = (g.div_b[1] + 7) >> 3;
   b.nbz = (g.div_b[2] + 3) >> 2;
-  const long long nb = (long long)b.nbx * b.nby * b.nbz;
-  int bits = 1;
-  while (bits < 31 && (1ll << bits) < nb) ++bits;
-  b.bits = bits;
+  const int bits = sort_key_bits((long long)b.nbx * b.nby * b.nbz - 1);   // keys 0 .. blocks - 1
+  b.bits = bits < 1 ? 1 : (bits > 31 ? 31 : bits);
   return b;
 }
 
@@ -2082,17 +1919,8 @@ __global__ void __launch_bounds__(SORT_THREADS) k_source_keys(const float* __res
   // the sort plan of these keys, for the passes that follow (every block derives the same one)
   BuildGeom plan;
   plan.bits = sb.bits;
-  plan.passes = (sb.bits + 7) / 8;
-  {
-    const int base = sb.bits / plan.passes, rem = sb.bits % plan.passes;
-    int sh = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      plan.width[i] = i < plan.passes ? base + (i < rem ? 1 : 0) : 0;
-      plan.shift[i] = sh;
-      sh += plan.width[i];
-    }
-  }
+  plan.passes = sort_passes_for_bits(sb.bits);
+  sort_split_bits(plan.bits, plan.passes, plan.width, plan.shift);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     plan_out->bits = plan.bits;
     plan_out->passes = plan.passes;
@@ -2139,25 +1967,22 @@ __global__ void __launch_bounds__(256) k_gather_soa(const uint32_t* __restrict__
 
 }  // namespace
 
-int sort_tiles(size_t n);
-
-int source_sort_passes(const GridGeom& g) { return (source_blocks(g).bits + 7) / 8; }
+int source_sort_passes(const GridGeom& g) { return sort_passes_for_bits(source_blocks(g).bits); }
 
 // keys + first histogram, `passes` sort passes, gather: the source in block order of the target
-// grid under the transform P.  keys/vals a,b: n uint32 each; temp: sort_temp_bytes(n); plan: one
+// grid under the transform P.  sc: the source's sort scratch, ensured for n pairs; plan: one
 // BuildGeom in device memory (scratch).
 hipError_t sort_source_by_blocks(const float* x, const float* y, const float* z, size_t n, const GridGeom& g,
-                                 const PoseConsts& P, BuildGeom* plan, void* temp, uint32_t* keys_a,
-                                 uint32_t* keys_b, uint32_t* vals_a, uint32_t* vals_b, float* ox, float* oy,
+                                 const PoseConsts& P, BuildGeom* plan, SortScratch& sc, float* ox, float* oy,
                                  float* oz, hipStream_t s) {
   if (n == 0) return hipSuccess;
   const int ntiles = sort_tiles(n);
-  hipLaunchKernelGGL(k_source_keys, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, s, x, y, z, (int)n, g, P, plan, keys_a,
-                     ntiles, static_cast<int*>(temp));
-  bool in_b = false;
-  hipError_t e = sort_pairs(temp, keys_a, keys_b, vals_a, vals_b, n, source_sort_passes(g), plan, s, &in_b);
+  hipLaunchKernelGGL(k_source_keys, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, s, x, y, z, (int)n, g, P, plan, sc.keys.p,
+                     ntiles, reinterpret_cast<int*>(sc.tmp.p));
+  SortedPairs sorted;
+  hipError_t e = sort_keyed(sc, n, plan, source_sort_passes(g), SORT_FIRST_COUNTED, s, &sorted);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_gather_soa, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in_b ? vals_b : vals_a, x, y, z,
+  hipLaunchKernelGGL(k_gather_soa, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sorted.vals, x, y, z,
                      (int)n, ox, oy, oz);
   return hipGetLastError();
 }
@@ -2260,12 +2085,6 @@ int bounds_rows(const ndt_tuning& tn, size_t n) {
   return (int)std::max<size_t>(1, std::min(most, (n + 255) / 256));
 }
 
-int sort_passes_for_cells(long long ncells) {
-  int bits = 1;
-  while (bits < 32 && (1ull << bits) <= (unsigned long long)ncells) ++bits;
-  return (bits + 7) / 8;
-}
-
 void launch_bounds_geometry(const ndt_tuning& tn, const float* x, const float* y, const float* z, size_t n, float leaf,
                             float inv_leaf, long long cell_capacity, int planned_passes, int* rows, unsigned int* ticket,
                             BuildGeom* gd, BuildGeom* gd_host, const LeafStats* old_stats, int dirty_slots,
@@ -2280,67 +2099,12 @@ void launch_bounds_geometry(const ndt_tuning& tn, const float* x, const float* y
                        d_nleaf);
 }
 
-int sort_tiles(size_t n) { return (int)((n + SORT_TILE - 1) / SORT_TILE); }
-
-// scratch of the sort: the bin-major tile histograms + the bin totals
-size_t sort_temp_bytes(size_t n) { return ((size_t)SORT_BINS * sort_tiles(n) + SORT_BINS) * sizeof(int); }
-
-void fill_sort_plan(BuildGeom* b, int end_bit) {
-  if (end_bit < 1) end_bit = 1;
-  if (end_bit > 32) end_bit = 32;
-  b->bits = end_bit;
-  b->passes = (end_bit + 7) / 8;
-  const int base = end_bit / b->passes, rem = end_bit % b->passes;
-  int sh = 0;
-  for (int i = 0; i < 4; ++i) {
-    b->width[i] = i < b->passes ? base + (i < rem ? 1 : 0) : 0;
-    b->shift[i] = sh;
-    sh += b->width[i];
-  }
-}
-
 void launch_cell_keys(const float* x, const float* y, const float* z, size_t n, const BuildGeom* gd,
                       uint32_t* keys, float* xyz4, void* sort_temp, hipStream_t s) {
   if (n == 0) return;
   const int ntiles = sort_tiles(n);
   hipLaunchKernelGGL(k_cell_keys, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, s, x, y, z, (int)n, gd, keys,
                      reinterpret_cast<float4*>(xyz4), ntiles, static_cast<int*>(sort_temp));
-}
-
-void launch_sort_first_count(const uint32_t* keys, size_t n, const BuildGeom* gd, void* sort_temp, hipStream_t s) {
-  if (n == 0) return;
-  const int ntiles = sort_tiles(n);
-  hipLaunchKernelGGL(k_sort_count, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, s, keys, (int)n, 0, gd, ntiles,
-                     static_cast<int*>(sort_temp));
-}
-
-// Sorts (keys_a, identity) by the key bits of the plan in *gd (device memory), stable, in
-// `passes` digit passes.  The first digit's tile histograms must already be in `temp`
-// (launch_cell_keys).  The passes ping-pong between the a and b buffers; *result_in_b says
-// where the sorted pairs ended up.
-hipError_t sort_pairs(void* temp, uint32_t* keys_a, uint32_t* keys_b, uint32_t* vals_a, uint32_t* vals_b,
-                      size_t n, int passes, const BuildGeom* gd, hipStream_t s, bool* result_in_b) {
-  *result_in_b = false;
-  if (n == 0) return hipSuccess;
-  const int ntiles = sort_tiles(n);
-  int* hist = static_cast<int*>(temp);
-  int* totals = hist + (size_t)SORT_BINS * ntiles;
-  uint32_t *kin = keys_a, *kout = keys_b, *vin = vals_a, *vout = vals_b;
-  for (int p = 0; p < passes; ++p) {
-    if (p > 0)
-      hipLaunchKernelGGL(k_sort_count, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, s, kin, (int)n, p, gd, ntiles, hist);
-    hipLaunchKernelGGL(k_sort_scan, dim3(SORT_BINS), dim3(SORT_THREADS), 0, s, hist, ntiles, totals);
-    if (p == 0)
-      hipLaunchKernelGGL(k_sort_scatter<true>, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, s, kin, vin, (int)n, p, gd,
-                         ntiles, hist, totals, kout, vout);
-    else
-      hipLaunchKernelGGL(k_sort_scatter<false>, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, s, kin, vin, (int)n, p, gd,
-                         ntiles, hist, totals, kout, vout);
-    uint32_t* t = kin; kin = kout; kout = t;
-    t = vin; vin = vout; vout = t;
-  }
-  *result_in_b = (passes & 1) != 0;
-  return hipGetLastError();
 }
 
 // sized for the smaller tile, whatever the tuning
@@ -2363,8 +2127,8 @@ size_t fused_table_words() { return (size_t)FUSED_MAX_TILES * SORT_BINS; }
 
 // Cell keys + stable sort by cell in `passes` launches, straight from the cloud.  `tile`: fused_tile_for();
 // `table` (fused_table_words() words, zeroed at allocation and whenever *seq wraps) carries the tagged
-// tile counts; *seq is the engine's launch tag counter.  The result lands in (keys_b, vals_b) for an
-// odd number of passes, (keys_a, vals_a) otherwise.
+// tile counts; *seq is the engine's launch tag counter.  The passes ping-pong between sc's two pairs of arrays
+// (sc.tmp is not used); *out: where the result is.
 template <int ROUNDS>
 static void launch_sort_pass(bool from_points, int ntiles, hipStream_t s, const float* x, const float* y, const float* z,
                              float* xyz4, const uint32_t* kin, const uint32_t* vin, int n, int p, BuildGeom* gd,
@@ -2381,10 +2145,9 @@ static void launch_sort_pass(bool from_points, int ntiles, hipStream_t s, const 
 }
 
 hipError_t sort_cloud_fused(const float* x, const float* y, const float* z, size_t n, int tile, BuildGeom* gd,
-                            BuildGeom* gd_host, float* xyz4, uint32_t* keys_a, uint32_t* keys_b, uint32_t* vals_a,
-                            uint32_t* vals_b, int passes, uint32_t* table, uint32_t* seq, hipStream_t s,
-                            bool* result_in_b) {
-  *result_in_b = false;
+                            BuildGeom* gd_host, float* xyz4, SortScratch& sc, int passes, uint32_t* table,
+                            uint32_t* seq, hipStream_t s, SortedPairs* out) {
+  *out = SortedPairs{sc.keys.p, sc.vals.p};
   if (n == 0) return hipSuccess;
   if (tile != FUSED_TILE && tile != FUSED_BIG_TILE) return hipErrorInvalidValue;
   const int ntiles = fused_tiles(n, tile);
@@ -2394,7 +2157,7 @@ hipError_t sort_cloud_fused(const float* x, const float* y, const float* z, size
 #else
   constexpr int mute_tile = -1;
 #endif
-  uint32_t *kin = keys_a, *kout = keys_b, *vin = vals_a, *vout = vals_b;
+  uint32_t *kin = sc.keys.p, *kout = sc.keys2.p, *vin = sc.vals.p, *vout = sc.vals2.p;
   for (int p = 0; p < passes; ++p) {
     uint32_t tag = (*seq + 1u) & 0xffffu;
     if (tag == 0u) {  // wrapped: forget every old tag before tag 1 is handed out again
@@ -2411,7 +2174,7 @@ hipError_t sort_cloud_fused(const float* x, const float* y, const float* z, size
     uint32_t* t = kin; kin = kout; kout = t;
     t = vin; vin = vout; vout = t;
   }
-  *result_in_b = (passes & 1) != 0;
+  *out = SortedPairs{kin, vin};   // (the buffers the last pass wrote)
   return hipGetLastError();
 }
 

@@ -11,9 +11,12 @@
 //   * the host half of the asynchronous cloud hand-off (stage_cloud): every layout and stride against a scalar
 //     restatement, the caller's cloud in an exactly-sized heap block (no byte beyond the last point's z is read)
 //     that is overwritten and freed THE MOMENT the call returns -- the staging copy must already be complete.
+//   * the radix sort's plan rule (ndt_sort_plan.h): key bits of a range, and the split of 1 .. 32 bits into digits with
+//     derived and with planned pass counts, against the rule's properties and a recorded table.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <unistd.h>
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -31,6 +34,7 @@
 #include "../../slam-sam_amd/csrc/ndt_newton.h"
 #include "../../slam-sam_amd/csrc/ndt_repack_pool.h"
 #include "../../slam-sam_amd/csrc/ndt_se3.h"
+#include "../../slam-sam_amd/csrc/ndt_sort_plan.h"
 
 static int fails = 0;
 #define CHECK(c)                                                        \
@@ -362,6 +366,55 @@ int main() {
     std::vector<double> w = words(NDT_EVAL_WORDS - 1, nan, 0.0);
     ndt::mark_lost_rows(w.data());
     CHECK(std::isnan(w[NDT_EVAL_WORDS - 1]));
+  }
+
+  // ---- the radix sort's plan rule (ndt_sort_plan.h) ---------------------------------------------------
+  {
+    // every split: the widths sum to `bits`, never grow, differ by at most one; shift = the widths before; zero from `passes` on
+    auto split_ok = [](int bits, int passes) {
+      int w[ndt::SORT_MAX_PASSES], sh[ndt::SORT_MAX_PASSES];
+      for (int i = 0; i < ndt::SORT_MAX_PASSES; ++i) w[i] = sh[i] = -1;
+      ndt::sort_split_bits(bits, passes, w, sh);
+      bool ok = true;
+      int sum = 0;
+      for (int i = 0; i < ndt::SORT_MAX_PASSES; ++i) {
+        if (i < passes) {
+          ok = ok && sh[i] == sum && w[i] >= 0 && w[i] <= 8 && (i == 0 || (w[i] <= w[i - 1] && w[i - 1] - w[i] <= 1));
+          sum += w[i];
+        } else {
+          ok = ok && w[i] == 0 && sh[i] == 0;
+        }
+      }
+      return ok && sum == bits && w[0] - w[passes - 1] <= 1;
+    };
+    for (int bits = 1; bits <= 32; ++bits) {
+      const int need = ndt::sort_passes_for_bits(bits);
+      CHECK(need == (bits + 7) / 8 && need >= 1 && need <= ndt::SORT_MAX_PASSES);
+      CHECK(split_ok(bits, need));                                                      // derived passes
+      for (int planned = need; planned <= ndt::SORT_MAX_PASSES; ++planned) CHECK(split_ok(bits, planned));   // planned: ceil(bits / 8) .. 4
+    }
+    // the derived plans as the host's plan writer gave them before the rule had one home
+    struct Row { int bits, passes, w[4]; };
+    const Row table[] = {{1, 1, {1, 0, 0, 0}},  {8, 1, {8, 0, 0, 0}},  {9, 2, {5, 4, 0, 0}},  {16, 2, {8, 8, 0, 0}}, {17, 3, {6, 6, 5, 0}},
+                         {23, 3, {8, 8, 7, 0}}, {24, 3, {8, 8, 8, 0}}, {25, 4, {7, 6, 6, 6}}, {31, 4, {8, 8, 8, 7}}, {32, 4, {8, 8, 8, 8}}};
+    for (const Row& r : table) {
+      int w[4], sh[4];
+      CHECK(ndt::sort_passes_for_bits(r.bits) == r.passes);
+      ndt::sort_split_bits(r.bits, r.passes, w, sh);
+      for (int i = 0; i < 4; ++i) CHECK(w[i] == r.w[i]);
+    }
+    {  // three planned passes over 9 bits
+      int w[4], sh[4];
+      ndt::sort_split_bits(9, 3, w, sh);
+      CHECK(w[0] == 3 && w[1] == 3 && w[2] == 3 && w[3] == 0 && sh[0] == 0 && sh[1] == 3 && sh[2] == 6 && sh[3] == 0);
+    }
+    // bits that hold 0 .. v = floor(log2 v) + 1; 0 (and below) needs none: the voxel map's axis extents take that 0, a sort
+    // key has at least one bit (the build's cells, the fitness cells and the source's blocks clamp to 1)
+    const long long vs[] = {1, 2, 255, 256, (1ll << 30) - 1, 1ll << 30, (1ll << 31) - 1};
+    for (long long v : vs) CHECK(ndt::sort_key_bits(v) == (int)std::floor(std::log2((double)v)) + 1);
+    CHECK(ndt::sort_key_bits(0) == 0 && ndt::sort_key_bits(-1) == 0);
+    CHECK(std::max(1, ndt::sort_key_bits(0)) == 1);
+    CHECK(ndt::sort_key_bits((1ll << 31) - 1) == 31 && ndt::sort_key_bits(1ll << 31) == 32 && ndt::sort_key_bits(1ll << 61) == 62);
   }
 
   // ---- SE(3) ---------------------------------------------------------------------------------------

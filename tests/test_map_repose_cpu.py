@@ -334,7 +334,7 @@ def test_map_repose_kernels_do_not_spill(tmp_path):
     # not copied: no sort, run search or accumulate launch of its own
     assert not re.search(r"atomic\w*\(|\basm\b", src)
     assert "map_import_tail(" in src and "map_merge_records(" in src and "map_record_stats(" in src
-    assert not re.search(r"sort_pairs\(|launch_find_runs\(|hipLaunchKernelGGL\(k_(?!maprepose_)", src)
+    assert not re.search(r"sort_keyed\(|sort_pairs\(|find_runs\(|hipLaunchKernelGGL\(k_(?!maprepose_)", src)
     # ndt_map_state.hip gained no kernel (its own test pins the set) and shares the statistics helper
     state = open(os.path.join(ROOT, "slam-sam_amd", "csrc", "ndt_map_state.hip")).read()
     assert "map_record_stats(" in state
