@@ -998,6 +998,91 @@ int64_t ndt_export_source_distributions(ndt_handle* h, double* mean3, double* co
 int ndt_eval_derivatives_d2d(ndt_handle* h, const double* poses6, int K, int compute_hessian, double* out);
 int ndt_align_d2d(ndt_handle* h, const float guess_colmajor[16], ndt_result* out);
 
+/* Continuous-time NDT (CT): align a scan that was captured in motion.  Every other registration call moves the whole
+ * scan by one pose; here every point has its own, blended between the scan's known BEGIN pose b (the previous scan's end
+ * pose: ndt_result.final_pose of the previous align) and its unknown END pose p = [x, y, z, roll, pitch, yaw] (the pose
+ * the drivers attach to a frame) by the point's time factor alpha_i -- one float per point, the reference's pointsAlpha:
+ * 0 at the start of the frame, 1 at its end.  ndt_deskew* undoes motion from a trajectory somebody else supplies; here the
+ * motion within the scan is part of what the registration estimates.
+ * THE TIMES belong to the current point source, in the order the source was handed over.  ndt_set_source_times (host
+ * array) / _device (device array, copied; consumed during the call): n must equal ndt_source_size, otherwise
+ * NDT_ERR_INVALID_ARG and the previous times stay; n == 0 clears them (the pointer may be NULL).  Values are not checked
+ * (see a_i below).  Every call that replaces or re-declares the source drops them: ndt_set_source*, _device,
+ * _device_view, ndt_set_source_from_keyframe and ndt_source_changed.  No other call notices the times.
+ * ndt_source_times_info: the number of times attached, 0 = none.  Without times (or without a source) the _ct calls
+ * return NDT_ERR_NO_SOURCE.  The _ct calls read the source as handed over: source_order is not read, the cached
+ * block-ordered copy is neither used nor disturbed.
+ * THE EVALUATION ndt_eval_derivatives_ct: K end poses -> K x NDT_EVAL_WORDS words in the layout of ndt_eval_derivatives
+ * (ndt_unpack_eval applies; ridge / regularisation as there).  Per pose and point, IEEE f64, no contraction:
+ *    a_i         alpha_i clamped to [0, 1].  A point whose alpha or coordinates are not finite contributes nothing and
+ *                is not counted.
+ *    begin pose  THE FIT, the same in every _ct call: the blend below is linear in the angles, so the begin pose's angles
+ *                are first brought onto the Euler branch of the end pose's.  Of the two triples of the begin rotation
+ *                -- (r, p, y) as given and (r + pi, pi - p, y + pi) -- each angle is shifted by round((angle - end's
+ *                angle) / 2 pi) turns (nothing is subtracted for 0 turns), and the triple whose three absolute
+ *                differences to the end pose's angles then add up to less is taken (a tie keeps the first).  A begin
+ *                pose already on the branch is used bit for bit; the translation is never touched.  b below is the
+ *                fitted begin pose.  This is what lets the previous result's final_pose be handed in as it is: those
+ *                angles come out of ndt_newton_align's matrix-to-pose conversion, which folds the roll into [0, pi], so
+ *                a roll that changes sign between two scans -- or a yaw that crosses pi -- puts two consecutive results
+ *                on different triples of nearly the same rotation.
+ *    pose        p_i = b + a_i (p - b), component by component, rounded as written; a_i == 1 uses p itself, a_i == 0 uses
+ *                b itself.  The end pose's angles are used as given.
+ *    moved point R_i = Rx(roll) Ry(pitch) Rz(yaw) of p_i's angles (the convention of ndt_eval_derivatives_d2d), sin and
+ *                cos per point in f64, applied one rotation after the other, every operation rounded as written:
+ *                  u = (cy x0 - sy x1, sy x0 + cy x1, x2)        v = (cp u0 + sp u2, u1, cp u2 - sp u0)
+ *                  w = (v0, cr v1 - sr v2, sr v1 + cr v2)        x'_i = w + t_i
+ *    neighbours  the target leaves ndt_score_points gives a point at ((float)x', (float)y', (float)z'): DIRECT1 or
+ *                DIRECT7 by the handle's search method, in the same pair order.
+ *    pair (i, j) mu = x'_i - mean_j, B = the leaf's icov as ndt_export_leaves shows it (its triangle xx, xy, xz, yy, yz,
+ *                zz is what is read), q = mu^T B mu, e = exp(-d2 q / 2); a pair whose e is not finite or outside [0, 1]
+ *                contributes nothing and is not counted; score += -d1 e; d1, d2: ndt_gauss_constants of the handle's
+ *                resolution and outlier ratio.
+ *    derivatives with j_c = d x'_i / d (p_i)_c (a unit vector for a translation, (dR/d angle_c) x_i for a rotation) and
+ *                h_cd its second derivative (non-zero for rotation pairs only), and because d p_i / d p = a_i I:
+ *                  g_c  += a_i d1 d2 e (mu^T B j_c)
+ *                  H_cd += a_i^2 d1 d2 e ( -d2 (mu^T B j_c)(mu^T B j_d) + mu^T B h_cd + j_d^T B j_c )
+ *                the exact gradient and Hessian of the score (always the full Hessian: hessian_mode is not read).
+ *    the rest    nvtl_sum, n_points_with_neighbors and n_pairs as in ndt_eval_derivatives.  compute_hessian == 0: the
+ *                Hessian words are zero, score and gradient are the bits of the Hessian call.
+ * With every alpha_i = 1 this is the ordinary point-to-distribution evaluation at p, in f64.  With b == p every point
+ * lands where that evaluation puts it, so score, nvtl_sum and the counters do not depend on the times; gradient and
+ * Hessian still do -- they are derivatives with respect to the END pose, of which point i follows the share a_i, so they
+ * are the a_i- and a_i^2-weighted sums of that evaluation's per-point terms.  Sums are made in a fixed order without float atomics: a call gives the same bits
+ * every time, and a pose in a batch of K the bits it gives alone.
+ * NDT_ERR_INVALID_ARG, before the handle is looked at, for a NULL pointer, K <= 0 or a non-finite pose entry;
+ * NDT_ERR_UNSUPPORTED for NDT_KDTREE / NDT_DIRECT26, a multi-grid union target and a reducer other than
+ * NDT_REDUCE_NONE; NDT_ERR_NO_TARGET as for ndt_align; NDT_ERR_NO_SOURCE without a source or without times.
+ * THE ALIGN ndt_align_ct: ndt_newton_align's loop (the ndt_align product path: the Hessian in every trial, the memo on)
+ * over that evaluation with the handle's parameters and regularisation pose, n_source_total = the source size; `out` as
+ * ndt_align fills it (ms_device 0), final_pose being the END pose.  The begin pose is fitted ONCE, before the loop, to
+ * the guess's pose -- the one ndt_newton_align derives from the matrix, on whose branch final_pose then lies -- and not
+ * again per evaluation, so the objective does not change under the loop.  On a failure before the loop `out` holds the
+ * guess with converged = 0.  The handle's align state, iteration history, pre-launch state and evaluation counters are left alone:
+ * an ndt_align afterwards gives the bits it gave before.
+ * THE DESKEWED SCAN ndt_transform_source_ct (host output, n x 3 floats) / _device (three device arrays): the source
+ * under begin pose b (fitted to e as above: a begin pose and a result on different Euler triples deskew as the align
+ * saw them) and end pose e, out[i] belonging to in[i].
+ *    frame == 1  the points in the target's frame: y = x'_i as above.
+ *    frame == 0  the points in the END pose's frame -- what goes into ndt_keyframe_put or ndt_map_add with the result:
+ *                y = R(e)^T (x'_i - t(e)), the three rotations of e undone one after the other (Rx^T, Ry^T, Rz^T).  A
+ *                point whose pose p_i equals e in all six numbers (a_i == 1, or b == e) comes back bit for bit: "no
+ *                motion" is exact, as in ndt_deskew.
+ * Everything is computed in f64 and rounded to f32 once.  A non-finite point or time gives NaN in x, y and z.
+ * cap < n is NDT_ERR_INVALID_ARG and nothing is written; frame other than 0 / 1 and a non-finite pose entry likewise.
+ * The blend is linear in the Euler parameters, not a slerp: exact for a constant-rate yaw, second-order different from
+ * ndt_deskew's trajectory model otherwise. */
+int     ndt_set_source_times(ndt_handle* h, const float* alpha, size_t n);
+int     ndt_set_source_times_device(ndt_handle* h, const float* d_alpha, size_t n);
+int64_t ndt_source_times_info(const ndt_handle* h);
+int     ndt_eval_derivatives_ct(ndt_handle* h, const double begin_pose6[6], const double* poses6, int K,
+                                int compute_hessian, double* out);
+int     ndt_align_ct(ndt_handle* h, const double begin_pose6[6], const float guess_colmajor[16], ndt_result* out);
+int     ndt_transform_source_ct(ndt_handle* h, const double begin_pose6[6], const double end_pose6[6], int frame,
+                                float* out_xyz, size_t cap_points);
+int     ndt_transform_source_ct_device(ndt_handle* h, const double begin_pose6[6], const double end_pose6[6], int frame,
+                                       float* ox, float* oy, float* oz, size_t cap);
+
 /* Scan Context place recognition (Kim & Kim, IROS 2018) over the device keyframe archive: which archived scan shows this
  * place again, and under which heading -- the question in front of ndt_align_batch / ndt_align_d2d (the relative pose) and
  * ndt_map_transform / ndt_map_import_state_posed (the correction).  A scan becomes an n_rings x n_sectors matrix of

@@ -1005,6 +1005,104 @@ class NormalDistributionsTransform
     return out;
   }
 
+  // ---- continuous-time NDT (ndt_set_source_times, ndt_eval_derivatives_ct, ndt_align_ct, ndt_transform_source_ct): a scan
+  // captured in motion, every point with its own pose between the scan's begin pose (the previous scan's end pose) and
+  // the end pose being estimated.  The times are PCLPointCloud::pointsAlpha, one per point of the input source, set AFTER
+  // setInputSource (every source setter drops them).  `begin` is [x, y, z, roll, pitch, yaw] or a 4 x 4 -- a previous
+  // getFinalTransformation() or ContinuousTimeResult::pose can be passed straight in.  Any Euler triple of the begin
+  // rotation serves, in every call below: the engine fits the begin pose's angles to the branch of the end pose's (of the
+  // guess's, in the align) before it blends -- THE FIT of ndt_hip.h -- so poseOfMatrix need not be, and is not, the
+  // engine's own matrix-to-pose conversion (whose roll lies in [0, pi]).  The adapter's own result
+  // (getFinalTransformation, getResult) stays that of the last align(). ----
+  using Pose6 = std::array<double, 6>;
+  template <class Mat4>
+  static Pose6 poseOfMatrix(const Mat4& T) {   // the angles of R = Rx Ry Rz, pitch in [-pi/2, pi/2]
+    Pose6 p;
+    p[0] = T(0, 3); p[1] = T(1, 3); p[2] = T(2, 3);
+    p[3] = std::atan2(-(double)T(1, 2), (double)T(2, 2));
+    p[4] = std::atan2((double)T(0, 2), std::sqrt((double)T(0, 0) * (double)T(0, 0) + (double)T(0, 1) * (double)T(0, 1)));
+    p[5] = std::atan2(-(double)T(0, 1), (double)T(0, 0));
+    return p;
+  }
+  void setInputSourceTimes(const float* alpha, size_t n) { status_ = h_ ? ndt_set_source_times(h_, alpha, n) : NDT_ERR_NO_DEVICE; }
+  void setInputSourceTimes(const std::vector<float>& alpha) { setInputSourceTimes(alpha.empty() ? nullptr : alpha.data(), alpha.size()); }
+  int64_t sourceTimesCount() const { return h_ ? ndt_source_times_info(h_) : 0; }
+  // score, gradient and Hessian of the continuous-time objective at the END pose p (one launch)
+  template <class Vec6, class Mat6>
+  double computeDerivativesCT(Vec6& score_gradient, Mat6& hessian, const Pose6& begin, const Vec6& p, bool compute_hessian = true) {
+    double pose[6], words[NDT_EVAL_WORDS], score = 0.0, g[6], H[36];
+    for (int i = 0; i < 6; ++i) { pose[i] = p[i]; score_gradient[i] = 0.0; }
+    for (int r = 0; r < 6; ++r)
+      for (int c = 0; c < 6; ++c) hessian(r, c) = 0.0;
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return 0.0; }
+    status_ = ndt_eval_derivatives_ct(h_, begin.data(), pose, 1, compute_hessian ? 1 : 0, words);
+    if (status_ != NDT_OK) return 0.0;
+    ndt_unpack_eval(words, &score, g, H);
+    for (int i = 0; i < 6; ++i) score_gradient[i] = g[i];
+    if (compute_hessian)
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) hessian(r, c) = H[6 * r + c];
+    return score;
+  }
+  template <class Vec6, class Mat6>
+  double computeDerivativesCT(Vec6& score_gradient, Mat6& hessian, const Matrix4f& begin, const Vec6& p, bool compute_hessian = true) {
+    return computeDerivativesCT(score_gradient, hessian, poseOfMatrix(begin), p, compute_hessian);
+  }
+  // the result as alignDistributions gives one, with the end pose as six numbers -- the next scan's `begin`; on an error
+  // `pose` holds the guess and end_pose its angles
+  struct ContinuousTimeResult : NdtResult {
+    Pose6 end_pose{};
+    bool converged = false;
+  };
+  ContinuousTimeResult alignContinuousTime(const Pose6& begin, const Matrix4f& guess) {
+    float g[16];
+    detail::to_colmajor(guess, 4, 4, g);
+    ndt_result raw;
+    std::memset(&raw, 0, sizeof(raw));
+    status_ = h_ ? ndt_align_ct(h_, begin.data(), g, &raw) : NDT_ERR_NO_DEVICE;
+    ContinuousTimeResult out;
+    if (status_ != NDT_OK) {
+      std::memset(&raw, 0, sizeof(raw));
+      std::memcpy(raw.final_transformation, g, sizeof(g));
+      out.end_pose = poseOfMatrix(guess);
+    } else {
+      for (int i = 0; i < 6; ++i) out.end_pose[i] = raw.final_pose[i];
+    }
+    out.converged = raw.converged != 0;
+    out.pose = detail::from_colmajor<Matrix4f>(raw.final_transformation, 4, 4);
+    out.transform_probability = (float)raw.transform_probability;
+    out.nearest_voxel_transformation_likelihood = (float)raw.nearest_voxel_transformation_likelihood;
+    out.iteration_num = raw.iterations;
+    out.hessian = detail::from_rowmajor<Matrix6d>(raw.hessian, 6, 6);
+    return out;
+  }
+  ContinuousTimeResult alignContinuousTime(const Matrix4f& begin, const Matrix4f& guess) {
+    return alignContinuousTime(poseOfMatrix(begin), guess);
+  }
+  // the deskewed scan under begin and end pose: frame 0 in the end pose's frame (what putKeyframe / mapAdd take with the
+  // result), frame 1 in the target's frame; out.points[i] belongs to source point i (NaN for a non-finite point or time).
+  // On error: an empty cloud, lastStatus() says why.
+  template <class Cloud>
+  void getDeskewedSource(const Pose6& begin, const Pose6& end, Cloud& out, int frame = 0) {
+    out.points.clear();
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return; }
+    const int64_t n = ndt_source_size(h_);
+    if (n < 0) { status_ = (int)n; return; }
+    std::vector<float> xyz(3 * (size_t)n + 3);
+    status_ = ndt_transform_source_ct(h_, begin.data(), end.data(), frame, xyz.data(), (size_t)n);
+    if (status_ != NDT_OK) return;
+    out.points.resize((size_t)n);   // value-initialised points: the fields the engine does not write keep their defaults
+    for (size_t i = 0; i < (size_t)n; ++i) {
+      out.points[i].x = xyz[3 * i];
+      out.points[i].y = xyz[3 * i + 1];
+      out.points[i].z = xyz[3 * i + 2];
+    }
+  }
+  template <class Cloud>
+  void getDeskewedSource(const Matrix4f& begin, const Pose6& end, Cloud& out, int frame = 0) {
+    getDeskewedSource(poseOfMatrix(begin), end, out, frame);
+  }
+
   // ---- device-resident keyframe archive (ref: run/pipeline_ligo_tc.cpp:519-529, run/pipeline.cpp:554-557,784) ----
   // not part of pclomp: the body-frame scans stay in HBM, the sliding-window target is assembled
   // there from ids + poses (column-major 4x4 doubles, e.g. gtsam::Pose3::matrix().data())

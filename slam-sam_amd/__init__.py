@@ -326,6 +326,8 @@ ABI_SYMBOLS = [
     "ndt_map_coarsen", "ndt_map_levels_drop", "ndt_align_map_levels",
     "ndt_set_source_distributions", "ndt_set_source_distributions_device", "ndt_source_distributions_info",
     "ndt_export_source_distributions", "ndt_eval_derivatives_d2d", "ndt_align_d2d",
+    "ndt_set_source_times", "ndt_set_source_times_device", "ndt_source_times_info", "ndt_eval_derivatives_ct", "ndt_align_ct",
+    "ndt_transform_source_ct", "ndt_transform_source_ct_device",
     "ndt_scan_context_default_params", "ndt_scan_context_set_params", "ndt_scan_context_get_params",
     "ndt_scan_context_sector_table", "ndt_scan_context", "ndt_scan_context_device", "ndt_scan_context_keyframe",
     "ndt_scan_context_bank_put", "ndt_scan_context_bank_get", "ndt_scan_context_bank_erase", "ndt_scan_context_bank_clear",
@@ -472,6 +474,14 @@ def lib():
         L.ndt_export_source_distributions.restype = C.c_int64
         L.ndt_eval_derivatives_d2d.argtypes = [vp, dp, C.c_int, C.c_int, dp]
         L.ndt_align_d2d.argtypes = [vp, fp, C.POINTER(Result)]
+        L.ndt_set_source_times.argtypes = [vp, vp, C.c_size_t]
+        L.ndt_set_source_times_device.argtypes = [vp, vp, C.c_size_t]
+        L.ndt_source_times_info.restype = C.c_int64
+        L.ndt_source_times_info.argtypes = [vp]
+        L.ndt_eval_derivatives_ct.argtypes = [vp, dp, dp, C.c_int, C.c_int, dp]
+        L.ndt_align_ct.argtypes = [vp, dp, fp, C.POINTER(Result)]
+        L.ndt_transform_source_ct.argtypes = [vp, dp, dp, C.c_int, vp, C.c_size_t]
+        L.ndt_transform_source_ct_device.argtypes = [vp, dp, dp, C.c_int, vp, vp, vp, C.c_size_t]
         scp, i64 = C.POINTER(ScanContextParams), C.c_int64
         L.ndt_scan_context_default_params.restype = None
         L.ndt_scan_context_default_params.argtypes = [scp]
@@ -2072,6 +2082,94 @@ def alignDistributions(ndt, guess=None):
     d = result_to_dict(r)
     d["iteration_num"] = d["iterations"]
     return d["T"], d
+
+
+# --- continuous-time NDT: a scan captured in motion, one pose per point blended between the begin pose and the end pose by
+# the point's time factor (ndt_set_source_times, ndt_eval_derivatives_ct, ndt_align_ct, ndt_transform_source_ct).
+# Functions on an engine, as above.  `begin`, `end`: [x, y, z, roll, pitch, yaw]. ---
+def _pose6(p, what):
+    a = np.ascontiguousarray(p, dtype=np.float64)
+    if a.shape != (6,) or not np.isfinite(a).all():
+        raise ValueError("%s must be 6 finite numbers [x, y, z, roll, pitch, yaw]" % what)
+    return a
+
+
+def setSourceTimes(ndt, alpha):
+    """One time factor per point of the current source, in the source's order (0: start of the frame, 1: its end; the
+    reference's pointsAlpha).  An empty array clears the times.  Returns the number attached."""
+    a = np.ascontiguousarray(alpha, dtype=np.float32)
+    if a.ndim != 1:
+        raise ValueError("alpha must be [n]")
+    ndt._check(lib().ndt_set_source_times(ndt._h, a.ctypes.data if len(a) else None, len(a)))
+    return sourceTimesInfo(ndt)
+
+
+def setSourceTimesDevice(ndt, d_alpha, n):
+    """As setSourceTimes, from a device array of n floats (integer address); copied during the call."""
+    if int(n) < 0 or (int(n) and not d_alpha):
+        raise ValueError("a device pointer is needed")
+    ndt._check(lib().ndt_set_source_times_device(ndt._h, d_alpha, int(n)))
+    return sourceTimesInfo(ndt)
+
+
+def sourceTimesInfo(ndt):
+    """The number of times attached to the source, 0 = none"""
+    n = int(lib().ndt_source_times_info(ndt._h))
+    if n < 0:
+        ndt._check(n)
+    return n
+
+
+def evalDerivativesCT(ndt, begin, poses6, compute_hessian=True, raw=False):
+    """The continuous-time score, gradient and Hessian at K END poses (K x 6) with the begin pose `begin`: a list of
+    dicts as evalDerivatives gives them; raw=True: the K x 32 packed words."""
+    b = _pose6(begin, "begin")
+    p = np.ascontiguousarray(np.atleast_2d(poses6), dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 6 or not np.isfinite(p).all():
+        raise ValueError("poses6 must be K x 6 and finite")
+    K = p.shape[0]
+    out = np.zeros((K, EVAL_WORDS))
+    ndt._check(lib().ndt_eval_derivatives_ct(ndt._h, _dp(b), _dp(p), K, int(bool(compute_hessian)), _dp(out)))
+    return out if raw else [unpack_eval(out[k]) for k in range(K)]
+
+
+computeDerivativesCT = evalDerivativesCT
+
+
+def alignContinuousTime(ndt, begin, guess=None):
+    """ndt_align_ct: the END pose of the source captured in motion, from `guess` (4x4, default identity), the begin pose
+    being known.  Returns (final 4x4, result dict as getResult() gives it -- its `pose` is the end pose to hand on as
+    the next scan's begin); getResult() keeps reporting the last align()."""
+    b = _pose6(begin, "begin")
+    g = np.asarray(np.eye(4) if guess is None else guess, dtype=np.float64)
+    if g.shape != (4, 4) or not np.isfinite(g).all():
+        raise ValueError("guess must be a finite 4 x 4 matrix")
+    g = _colmajor(g)
+    r = Result()
+    ndt._check(lib().ndt_align_ct(ndt._h, _dp(b), _fp(g), C.byref(r)))
+    d = result_to_dict(r)
+    d["iteration_num"] = d["iterations"]
+    return d["T"], d
+
+
+def transformSourceCT(ndt, begin, end, frame=0):
+    """The deskewed scan under begin pose `begin` and end pose `end` [n, 3] float32: frame 0 in the end pose's frame (what
+    keyframePut / mapAdd take with the result), frame 1 in the target's frame.  NaN rows for non-finite points or times."""
+    b, e = _pose6(begin, "begin"), _pose6(end, "end")
+    if frame not in (0, 1):
+        raise ValueError("frame must be 0 (the end pose's frame) or 1 (the target's frame)")
+    n = ndt.sourceSize()
+    out = np.zeros((n, 3), np.float32)
+    ndt._check(lib().ndt_transform_source_ct(ndt._h, _dp(b), _dp(e), int(frame), out.ctypes.data, n))
+    return out
+
+
+def transformSourceCTDevice(ndt, begin, end, d_x, d_y, d_z, cap, frame=0):
+    """As transformSourceCT, into three device arrays of `cap` floats (integer addresses)."""
+    b, e = _pose6(begin, "begin"), _pose6(end, "end")
+    if frame not in (0, 1) or not d_x or not d_y or not d_z or int(cap) < 0:
+        raise ValueError("frame must be 0 or 1 and the three device pointers are needed")
+    ndt._check(lib().ndt_transform_source_ct_device(ndt._h, _dp(b), _dp(e), int(frame), d_x, d_y, d_z, int(cap)))
 
 
 # --- Scan Context place recognition over the keyframe archive (ndt_scan_context*; DESIGN 7m).  Functions on an engine, as

@@ -413,6 +413,11 @@ int blocks_for(size_t n) { return (int)((n + D2D_THREADS - 1) / D2D_THREADS); }
 }  // namespace
 
 namespace engine {
+
+void d2d_launch_sum(const double* rows, int nb, int K, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_d2d_sum, dim3((unsigned)K), dim3(D2D_THREADS), 0, s, rows, nb, out);
+}
+
 namespace {
 
 int d2d_min_points(const ndt_handle* h) { return std::max(3, h->prm.min_points_per_voxel); }   // the ordinary build's rule (build_begin)
@@ -517,7 +522,7 @@ int d2d_eval_raw(ndt_handle* h, const double* poses6, int K, bool need_h, double
     else { if (d7) NDT_D2D_LAUNCH(false, true); else NDT_D2D_LAUNCH(false, false); }
 #undef NDT_D2D_LAUNCH
   }
-  hipLaunchKernelGGL(k_d2d_sum, dim3((unsigned)K), block, 0, s, d.rows.p, nb, d.out.p);
+  d2d_launch_sum(d.rows.p, nb, K, d.out.p, s);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipMemcpyAsync(d.out_h.h, d.out.p, (size_t)K * EV_WORDS * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(h, hipStreamSynchronize(s));

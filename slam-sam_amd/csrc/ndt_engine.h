@@ -14,6 +14,8 @@
 //                      coarsened to a level, coarse-to-fine align over the levels (k_maplevel_* kernels)
 //   ndt_d2d.hip        distribution-to-distribution registration: a source of Gaussians from map records, its evaluation
 //                      and align against the target's leaves (k_d2d_* kernels)
+//   ndt_ct.hip         continuous-time registration: per-point times of the point source, the evaluation with one pose per
+//                      point, its align and the deskewed scan under a result (k_ct_* kernels)
 //   ndt_scan_context.hip  Scan Context place recognition: a scan's rings x sectors descriptor, the descriptor bank beside
 //                      the keyframe archive and the all-shifts match against it (k_sc_* kernels)
 //   ndt_map_carve.hip  free-space carving of the map: voxels that a scan's rays pass through go (k_mapcarve_* kernels)
@@ -297,6 +299,20 @@ struct D2dBufs {
   }
 };
 
+// The times of the point source for the continuous-time calls (ndt_ct.hip) and their scratch.  The times belong to the
+// source they were set behind: every call that replaces or re-declares the source sets n back to 0.
+struct CtBufs {
+  DevBuf<float> alpha;               // one factor per source point, in the source's order
+  size_t n = 0;                      // times attached (== n_src), 0 = none
+  DevBuf<double> rows, out;          // per-block rows of K poses, their K x EV_WORDS sums
+  PinBuf<double> out_h;
+  DevBuf<float> xyz;                 // [x | y | z] of ndt_transform_source_ct's host form
+  void release() {
+    alpha.release(); rows.release(); out.release(); out_h.release(); xyz.release();
+    n = 0;
+  }
+};
+
 // Scan Context (ndt_scan_context.hip): the parameters, the sector table they imply, the scratch of a descriptor call and
 // the descriptor bank -- slots of n_rings x n_sectors floats in one device array, `ids` naming the slot of every entry
 // (ascending ids: the order of a match's outputs).  ndt_keyframe_erase leaves the bank alone; a parameter change clears it.
@@ -451,6 +467,7 @@ struct ndt_handle {
   size_t n_src = 0;
   ScanContextBufs sc;                // Scan Context: parameters, sector table, descriptor bank (ndt_scan_context.hip)
   D2dBufs d2d;                       // the distribution source of ndt_*_d2d and the target's leaves for it (ndt_d2d.hip)
+  CtBufs ct;                         // the source's times and the scratch of ndt_*_ct (ndt_ct.hip)
   // the same points in block order of the target grid (see sort_source_by_blocks); valid until
   // the source or the target changes
   DevBuf<float> ox, oy, oz;
@@ -771,6 +788,9 @@ int map_import_checks(ndt_handle* h, float leaf, const double* moments9, size_t 
 int map_import_tail(ndt_handle* h, const int32_t* d_count, const float* d_sums, const double* d_mom, size_t n);
 int map_merge_records(ndt_handle* h, const MapTable& t, unsigned long long* d_nvox, const int32_t* d_count, const float* d_sums,
                       const double* d_mom, size_t n);
+// ndt_d2d.hip: k_d2d_sum on rows of K poses x nb blocks x EV_WORDS -> out (K x EV_WORDS), enqueued on s; the CT evaluation's
+// rows have the same layout and take the same fixed-order sum
+void d2d_launch_sum(const double* rows, int nb, int K, double* out, hipStream_t s);
 void fill_pose_consts(const double p[6], const float T[16], PoseConsts* pc);
 unsigned long long process_item_salt();
 EvalConsts make_eval_consts(const ndt_handle* h, bool need_h);

@@ -163,6 +163,7 @@ int ndt_destroy(ndt_handle* h) {
   h->tx.release(); h->ty.release(); h->tz.release();
   h->fit.release();
   h->d2d.release();
+  h->ct.release();
   h->sc.release();
   h->compact.release(); h->knots.release();
   h->ps.release();

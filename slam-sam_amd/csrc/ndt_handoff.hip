@@ -579,6 +579,7 @@ int ndt_set_source(ndt_handle* h, const float* xyz, size_t n, size_t stride_byte
   if (rc) return rc;
   h->vx = h->vy = h->vz = nullptr;
   h->n_src = 0;
+  h->ct.n = 0;   // the times go with the source they were set for
   // asynchronous hand-off: on the source lane's own stream, so that its copies run beside the target's build; the
   // engine's streams are ordered behind it by the first call that evaluates (settle_source)
   const bool async = h->handoff_mode == NDT_HANDOFF_ASYNC;
@@ -599,6 +600,7 @@ int ndt_set_source_soa(ndt_handle* h, const float* x, const float* y, const floa
   if (rc) return rc;
   h->vx = h->vy = h->vz = nullptr;
   h->n_src = 0;
+  h->ct.n = 0;   // the times go with the source they were set for
   const bool async = h->handoff_mode == NDT_HANDOFF_ASYNC;
   rc = source_behind_target_transfer(h, async);
   if (rc) return rc;
@@ -628,6 +630,7 @@ int ndt_set_source_device(ndt_handle* h, const float* dx, const float* dy, const
   h->vx = h->sx.p; h->vy = h->sy.p; h->vz = h->sz.p;
   h->n_src = n;
   h->src_sorted = false;
+  h->ct.n = 0;
   return NDT_OK;
 }
 
@@ -640,6 +643,7 @@ int ndt_set_source_device_view(ndt_handle* h, const float* dx, const float* dy, 
   h->vx = dx; h->vy = dy; h->vz = dz;
   h->n_src = n;
   h->src_sorted = false;
+  h->ct.n = 0;
   return NDT_OK;
 }
 
@@ -648,6 +652,7 @@ int ndt_set_source_device_view(ndt_handle* h, const float* dx, const float* dy, 
 int ndt_source_changed(ndt_handle* h) {
   if (!h) return NDT_ERR_INVALID_ARG;
   h->src_sorted = false;
+  h->ct.n = 0;   // rewritten points: the times of the previous ones do not describe them
   return NDT_OK;
 }
 

@@ -18,6 +18,7 @@ ndt_handle::Keyframe& keyframe_claim(ndt_handle* h, int64_t id, size_t n) {
   if (kf.x.p && h->vx == kf.x.p) {   // the keyframe being replaced is the viewed source: it has to be set again
     h->vx = h->vy = h->vz = nullptr;
     h->n_src = 0;
+    h->ct.n = 0;
   }
   return kf;
 }
@@ -204,6 +205,7 @@ int ndt_keyframe_erase(ndt_handle* h, int64_t id) {
   if (it->second.x.p && h->vx == it->second.x.p) {   // the viewed source goes with its keyframe
     h->vx = h->vy = h->vz = nullptr;
     h->n_src = 0;
+    h->ct.n = 0;
   }
   if (h->keyframe_pool.size() < 4 && it->second.x.p) {
     // (whatever still reads these arrays was enqueued on the engine's stream before this call; the next put writes
