@@ -3,16 +3,19 @@
 // include/ndt_hip.h).
 //   ndt_set_source_times*           one float per point of the current point source, kept on the device
 //   ndt_eval_derivatives_ct         per pose one launch of k_ct_eval<HESSIAN, D7> -- one point per lane: its own pose, three
-//                                   sincos in f64, the moved point, its neighbours as k_point_scores finds them -- and one
-//                                   launch of D2D's fixed-order sum over all poses (d2d_launch_sum)
+//                                   sincos in f64, the moved point, its neighbours by ndt_neighbors_device.h as every
+//                                   evaluator's -- and one launch of the fixed-order sum over all poses (lane_eval_rows)
 //   ndt_align_ct                    newton_align over that evaluation
 //   ndt_transform_source_ct*        k_ct_apply: the deskewed scan under a result
 // What a pair adds to gradient and Hessian is linear in f v and f (B - d2 v v^T) (v = B mu, f = d1 d2 e) once the point's
 // j_c and h_cd are fixed, so a lane sums those nine numbers over its <= 7 pairs and meets j and h once, behind the pairs.
-// Sums: lane -> wave (xor butterfly) -> block (LDS, wave order) -> one row per block -> the sum kernel in fixed order.  No
-// float atomics; a pose's launch and its rows do not depend on the other poses of a call.  The source is read as handed
-// over (vx / vy / vz); the block-ordered copy, the align state and the iteration history of the handle are not touched.
+// Sums: lane -> wave -> block -> one row per block (eval_block_row, ndt_evalrows_device.h) -> k_eval_rows_sum in fixed
+// order; the host side around the launches (lane_eval_rows, finish_words, lane_align) is ndt_eval_rows.hip's, shared with
+// D2D.  The source is read as handed over (vx / vy / vz); the block-ordered copy, the align state and the iteration
+// history of the handle are not touched.
 #include "ndt_engine.h"
+#include "ndt_evalrows_device.h"
+#include "ndt_neighbors_device.h"
 
 namespace ndt {
 
@@ -71,14 +74,8 @@ __device__ __forceinline__ void ct_rxry(const CtMoved& M, const double c[3], dou
 
 __device__ __forceinline__ double ct_dot(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 
-__device__ __forceinline__ double ct_wave_sum(double v) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
-  return v;   // (a + b and b + a are the same bits: every lane holds the same sum)
-}
-
-// One point per lane: its pose, the moved point, its neighbours as k_point_scores finds them for the f32-rounded moved
-// point (DIRECT1 / DIRECT7, the same pair order), the pairs, and the block's row of EV_WORDS sums (word 31 = 0).
+// One point per lane: its pose, the moved point, the neighbours of the f32-rounded moved point (neighbor_cells7: DIRECT1 /
+// DIRECT7, the pair order of every evaluator), the pairs, and the block's row of EV_WORDS sums (word 31 = 0).
 template <bool HESSIAN, bool D7>
 __global__ void __launch_bounds__(CT_THREADS)
 k_ct_eval(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, const float* __restrict__ alpha,
@@ -103,38 +100,15 @@ k_ct_eval(const float* __restrict__ sx, const float* __restrict__ sy, const floa
     float xt = (float)M.m[0], yt = (float)M.m[1], zt = (float)M.m[2];
     const bool finite = isfinite(xt) && isfinite(yt) && isfinite(zt);
     if (!finite) { xt = 0.0f; yt = 0.0f; zt = 0.0f; }   // as k_point_scores: no NaN / Inf reaches the index casts
-    // the classification of k_point_scores (ndt_derivs.hip), operation for operation
-    const float w = g.leaf;
-    const float cx[3] = {xt, xt + w, xt - w}, cy[3] = {yt, yt + w, yt - w}, cz[3] = {zt, zt + w, zt - w};
-    bool inx[3], iny[3], inz[3];
-    unsigned int ix[3], iy[3], iz[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      inx[k] = cx[k] >= g.lo[0] && cx[k] < g.hi[0];
-      iny[k] = cy[k] >= g.lo[1] && cy[k] < g.hi[1];
-      inz[k] = cz[k] >= g.lo[2] && cz[k] < g.hi[2];
-      ix[k] = (unsigned int)(int)(floorf(cx[k] * g.inv_leaf) - (float)g.min_b[0]);
-      iy[k] = (unsigned int)(int)(floorf(cy[k] * g.inv_leaf) - (float)g.min_b[1]) * (unsigned int)g.mul1;
-      iz[k] = (unsigned int)(int)(floorf(cz[k] * g.inv_leaf) - (float)g.min_b[2]) * (unsigned int)g.mul2;
-    }
-    int cell[7];
-    {
-      const int idx0 = (int)(ix[0] + iy[0] + iz[0]);
-      cell[0] = (inx[0] && iny[0] && inz[0] && idx0 >= 0 && idx0 < g.ncells) ? idx0 : -1;
-    }
-#pragma unroll
-    for (int k = 1; k < 3; ++k) {
-      const int ax = (int)(ix[k] + iy[0] + iz[0]), ay = (int)(ix[0] + iy[k] + iz[0]), az = (int)(ix[0] + iy[0] + iz[k]);
-      cell[k] = (D7 && inx[k] && iny[0] && inz[0] && ax >= 0 && ax < g.ncells) ? ax : -1;
-      cell[2 + k] = (D7 && inx[0] && iny[k] && inz[0] && ay >= 0 && ay < g.ncells) ? ay : -1;
-      cell[4 + k] = (D7 && inx[0] && iny[0] && inz[k] && az >= 0 && az < g.ncells) ? az : -1;
-    }
+    int cell[7], slots[7];
+    neighbor_cells7<D7>(xt, yt, zt, g, cell);
+    neighbor_slots7<D7>(cell, finite, cell2leaf, slots);
     double score = 0.0, best = 0.0, fw[3] = {0.0, 0.0, 0.0};
     double Mxx = 0.0, Mxy = 0.0, Mxz = 0.0, Myy = 0.0, Myz = 0.0, Mzz = 0.0;   // sum of f (B - d2 v v^T)
     int npairs = 0;
 #pragma unroll
     for (int k = 0; k < (D7 ? 7 : 1); ++k) {
-      const int slot = (finite && cell[k] >= 0) ? cell2leaf[cell[k]] : -1;
+      const int slot = slots[k];
       if (slot < 0) continue;
       const LeafStats& L = stats[slot];
       const double mu[3] = {M.m[0] - L.mean[0], M.m[1] - L.mean[1], M.m[2] - L.mean[2]};
@@ -214,20 +188,7 @@ k_ct_eval(const float* __restrict__ sx, const float* __restrict__ sy, const floa
     }
   }
   // lane -> wave -> block
-  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
-#pragma unroll
-  for (int k = 0; k < EV_WORDS; ++k) {
-    const bool skip = k == EV_FAIL || (!HESSIAN && k >= EV_H && k < EV_H + 21);
-    const double s = skip ? 0.0 : ct_wave_sum(words[k]);
-    if (lane == 0) s_part[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < EV_WORDS) {
-    double s = s_part[0][threadIdx.x];
-#pragma unroll
-    for (int wv = 1; wv < CT_WAVES; ++wv) s += s_part[wv][threadIdx.x];
-    rows[(size_t)blockIdx.x * EV_WORDS + threadIdx.x] = s;
-  }
+  eval_block_row<CT_WAVES, HESSIAN>(words, s_part, rows);
 }
 
 // The deskewed scan: point i moved by its own pose, in the target's frame (frame 1) or brought back into the END pose's
@@ -294,11 +255,7 @@ int ct_source_ready(ndt_handle* h) {
 // what a CT evaluation can work with: DIRECT1 / DIRECT7 on a single grid, one rank; then target, source and times
 int ct_ready(ndt_handle* h) {
   if (int rc = settle(h)) return rc;
-  if (h->red.mode() != NDT_REDUCE_NONE) return fail(h, NDT_ERR_UNSUPPORTED, "CT: multi-rank evaluation is not supported");
-  if (h->prm.search_method != NDT_DIRECT1 && h->prm.search_method != NDT_DIRECT7)
-    return fail(h, NDT_ERR_UNSUPPORTED, "CT: the search method must be DIRECT1 or DIRECT7");
-  if (h->tgt.is_union()) return fail(h, NDT_ERR_UNSUPPORTED, "CT: a multi-grid union target is not supported");
-  if (!h->tgt.have_grid() || h->tgt.n_valid() <= 0) return fail(h, NDT_ERR_NO_TARGET, "no target voxel grid (setInputTarget first)");
+  if (int rc = lane_eval_supported(h, "CT")) return rc;
   return ct_source_ready(h);
 }
 
@@ -322,51 +279,23 @@ void ct_fit_begin(const double begin6[6], const double ref3[3], double out6[6]) 
 // K end poses -> K x EV_WORDS raw sums in `out`; ct_ready has passed.  fit: the begin pose is fitted to each end pose
 // (the public evaluation); the align hands over the one it fitted to its guess
 int ct_eval_raw(ndt_handle* h, const double begin6[6], const double* poses6, int K, bool need_h, double* out, bool fit) {
-  CtBufs& c = h->ct;
   const int n = (int)h->n_src, nb = ct_blocks(h->n_src);
-  HIP_TRY(h, c.rows.ensure((size_t)K * (size_t)nb * EV_WORDS));
-  HIP_TRY(h, c.out.ensure((size_t)K * EV_WORDS));
-  HIP_TRY(h, c.out_h.ensure((size_t)K * EV_WORDS));
   double d1, d2;
   gauss_constants((double)h->prm.resolution, h->prm.outlier_ratio, &d1, &d2);
   const bool d7 = h->prm.search_method == NDT_DIRECT7;
-  hipStream_t s = h->stream;
   const dim3 grid((unsigned)nb), block(CT_THREADS);
-  for (int k = 0; k < K; ++k) {   // one launch per pose: a pose's rows are what they are alone
+  return lane_eval_rows(h, "CT", nb, K, [&](int k, double* rows) {
     CtPoses P;
     std::memcpy(P.p, poses6 + 6 * (size_t)k, sizeof(P.p));
     if (fit) ct_fit_begin(begin6, P.p + 3, P.b);
     else std::memcpy(P.b, begin6, sizeof(P.b));
-    double* rows = c.rows.p + (size_t)k * (size_t)nb * EV_WORDS;
 #define NDT_CT_LAUNCH(H, D7) \
-  hipLaunchKernelGGL((k_ct_eval<H, D7>), grid, block, 0, s, h->vx, h->vy, h->vz, c.alpha.p, n, h->geom, h->cell2leaf.p, h->stats.p, P, \
-                     d1, d2, rows)
+  hipLaunchKernelGGL((k_ct_eval<H, D7>), grid, block, 0, h->stream, h->vx, h->vy, h->vz, h->ct.alpha.p, n, h->geom, h->cell2leaf.p, \
+                     h->stats.p, P, d1, d2, rows)
     if (need_h) { if (d7) NDT_CT_LAUNCH(true, true); else NDT_CT_LAUNCH(true, false); }
     else { if (d7) NDT_CT_LAUNCH(false, true); else NDT_CT_LAUNCH(false, false); }
 #undef NDT_CT_LAUNCH
-  }
-  d2d_launch_sum(c.rows.p, nb, K, c.out.p, s);
-  HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipMemcpyAsync(c.out_h.h, c.out.p, (size_t)K * EV_WORDS * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_TRY(h, hipStreamSynchronize(s));
-  std::memcpy(out, c.out_h.h, (size_t)K * EV_WORDS * sizeof(double));
-  for (int k = 0; k < K; ++k)
-    if (!std::isfinite(out[(size_t)k * EV_WORDS + EV_SCORE])) return fail(h, NDT_ERR_HIP, "CT evaluation returned a non-finite score");
-  return NDT_OK;
-}
-
-// raw sums -> what ndt_eval_derivatives hands out: ridge / regularisation / guards, repacked
-void ct_finish_words(ndt_handle* h, const double p[6], bool need_h, double* w) {
-  Eval e;
-  unpack_eval(w, &e);
-  finish_eval(h->prm, h->have_reg ? h->reg_pose : nullptr, p, need_h, &e);
-  w[EV_SCORE] = e.score;
-  for (int i = 0; i < 6; ++i) w[EV_G + i] = e.g[i];
-  if (need_h) {
-    int idx = EV_H;
-    for (int i = 0; i < 6; ++i)
-      for (int j = i; j < 6; ++j) w[idx++] = e.H[6 * i + j];
-  }
+  }, out);
 }
 
 int ct_apply(ndt_handle* h, const double begin6[6], const double end6[6], int frame, float* ox, float* oy, float* oz) {
@@ -430,7 +359,7 @@ int ndt_eval_derivatives_ct(ndt_handle* h, const double begin_pose6[6], const do
   if (int rc = bind_device(h)) return rc;
   if (int rc = ct_ready(h)) return rc;
   if (int rc = ct_eval_raw(h, begin_pose6, poses6, K, compute_hessian != 0, out, /*fit=*/true)) return rc;
-  for (int k = 0; k < K; ++k) ct_finish_words(h, poses6 + 6 * (size_t)k, compute_hessian != 0, out + (size_t)k * EV_WORDS);
+  for (int k = 0; k < K; ++k) finish_words(h, poses6 + 6 * (size_t)k, compute_hessian != 0, out + (size_t)k * EV_WORDS);
   return NDT_OK;
 }
 
@@ -447,17 +376,9 @@ int ndt_align_ct(ndt_handle* h, const double begin_pose6[6], const float guess[1
   matrix_to_pose(guess, g6);
   if (ct_finite6(g6)) ct_fit_begin(begin_pose6, g6 + 3, b);
   else std::memcpy(b, begin_pose6, sizeof(b));
-  EvalFn fn = [h, &b](const double* p, const float*, bool need_h, Eval* e) {
-    double words[EV_WORDS];
-    if (int r = ct_eval_raw(h, b, p, 1, need_h, words, /*fit=*/false)) return r;
-    unpack_eval(words, e);
-    finish_eval(h->prm, h->have_reg ? h->reg_pose : nullptr, p, need_h, e);
-    return 0;
-  };
-  // the product path of ndt_align (the Hessian in every trial, the memo on); no iteration history
-  const int rc = newton_align(h->prm, (int64_t)h->n_src, guess, fn, out, /*hessian_in_trials=*/true);
-  h->keepwarm.touch();
-  return rc;
+  return lane_align(h, (int64_t)h->n_src, guess, [h, &b](const double* p, bool need_h, double* words) {
+    return ct_eval_raw(h, b, p, 1, need_h, words, /*fit=*/false);
+  }, out);
 }
 
 int ndt_transform_source_ct_device(ndt_handle* h, const double begin_pose6[6], const double end_pose6[6], int frame, float* ox,

@@ -6,21 +6,23 @@
 //                                   Gaussians {mean 3, cov 6} in input order (ndt_compact_device.h)
 //   ndt_eval_derivatives_d2d        k_d2d_gather_target once per published target (mean 3 + cov 6 per leaf slot, from
 //                                   `stats`), then per pose one launch of k_d2d_eval<HESSIAN> -- one source Gaussian per
-//                                   lane -- and one launch of k_d2d_sum over all poses
+//                                   lane -- and one launch of the fixed-order sum over all poses
 //   ndt_align_d2d                   newton_align over that evaluation
-// Sums: lane -> wave (xor butterfly) -> block (LDS, wave order) -> one row per block -> k_d2d_sum in fixed order.  No
-// float atomics; a pose's launch and its rows do not depend on the other poses of a call, so it gives the bits it gives
-// alone.  The point source, the align state and the iteration history of the handle are not touched.
+// A moved mean's neighbours are found by ndt_neighbors_device.h, as every evaluator's.  Sums: lane -> wave -> block -> one
+// row per block (eval_block_row, ndt_evalrows_device.h) -> k_eval_rows_sum in fixed order; the host side around the
+// launches (lane_eval_rows, finish_words, lane_align) is ndt_eval_rows.hip's, shared with the continuous-time evaluation.
+// The point source, the align state and the iteration history of the handle are not touched.
 #include "ndt_engine.h"
 #include "ndt_compact_device.h"
+#include "ndt_evalrows_device.h"
 #include "ndt_leaf_device.h"
+#include "ndt_neighbors_device.h"
 
 namespace ndt {
 
 namespace {
 
 constexpr int D2D_THREADS = 256, D2D_WAVES = D2D_THREADS / 64;
-constexpr int SUM_SEGS = D2D_THREADS / EV_WORDS;   // k_d2d_sum: threads per word
 
 // R = Rx(roll) Ry(pitch) Rz(yaw) and its first and second angle derivatives, row-major, f64 from exact sin / cos
 struct D2dPose {
@@ -68,12 +70,6 @@ __device__ __forceinline__ Sym3 sym_of(const double M[9]) {
 // sum_ab Z_ab W_ab of two symmetric matrices
 __device__ __forceinline__ double sym_inner(const Sym3& Z, const Sym3& W) {
   return ((Z.xx * W.xx + Z.yy * W.yy) + Z.zz * W.zz) + 2.0 * ((Z.xy * W.xy + Z.xz * W.xz) + Z.yz * W.yz);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
-  return v;   // (a + b and b + a are the same bits: every lane holds the same sum)
 }
 
 // a record of the setters' input that cannot be a voxel: count < 1 or a non-finite sum
@@ -210,8 +206,8 @@ __device__ __forceinline__ void d2d_pair(D2dAcc<HESSIAN>& acc, const double* __r
   }
 }
 
-// One source Gaussian per lane: the moved mean, its neighbours as k_point_scores finds them for the f32-rounded moved
-// mean (DIRECT1 / DIRECT7, the same pair order), the pairs, and the block's row of EV_WORDS sums (word 31 = 0).
+// One source Gaussian per lane: the moved mean, the neighbours of the f32-rounded moved mean (neighbor_cells7: DIRECT1 /
+// DIRECT7, the pair order of every evaluator), the pairs, and the block's row of EV_WORDS sums (word 31 = 0).
 template <bool HESSIAN, bool D7>
 __global__ void __launch_bounds__(D2D_THREADS)
 k_d2d_eval(const double* __restrict__ gauss, int n, GridGeom g, const int* __restrict__ cell2leaf, const double* __restrict__ tleaf,
@@ -237,35 +233,9 @@ k_d2d_eval(const double* __restrict__ gauss, int n, GridGeom g, const int* __res
     for (int a = 0; a < 3; ++a) m[a] = ((P.R[3 * a] * mu[0] + P.R[3 * a + 1] * mu[1]) + P.R[3 * a + 2] * mu[2]) + P.t[a];
     const float xt = (float)m[0], yt = (float)m[1], zt = (float)m[2];
     const bool finite = isfinite(xt) && isfinite(yt) && isfinite(zt);
-    // the classification of k_point_scores (ndt_derivs.hip), operation for operation
-    const float w = g.leaf;
-    const float cx[3] = {xt, xt + w, xt - w}, cy[3] = {yt, yt + w, yt - w}, cz[3] = {zt, zt + w, zt - w};
-    bool inx[3], iny[3], inz[3];
-    unsigned int ix[3], iy[3], iz[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      inx[k] = cx[k] >= g.lo[0] && cx[k] < g.hi[0];
-      iny[k] = cy[k] >= g.lo[1] && cy[k] < g.hi[1];
-      inz[k] = cz[k] >= g.lo[2] && cz[k] < g.hi[2];
-      ix[k] = (unsigned int)(int)(floorf(cx[k] * g.inv_leaf) - (float)g.min_b[0]);
-      iy[k] = (unsigned int)(int)(floorf(cy[k] * g.inv_leaf) - (float)g.min_b[1]) * (unsigned int)g.mul1;
-      iz[k] = (unsigned int)(int)(floorf(cz[k] * g.inv_leaf) - (float)g.min_b[2]) * (unsigned int)g.mul2;
-    }
-    int cell[7];
-    {
-      const int idx0 = (int)(ix[0] + iy[0] + iz[0]);
-      cell[0] = (inx[0] && iny[0] && inz[0] && idx0 >= 0 && idx0 < g.ncells) ? idx0 : -1;
-    }
-#pragma unroll
-    for (int k = 1; k < 3; ++k) {
-      const int ax = (int)(ix[k] + iy[0] + iz[0]), ay = (int)(ix[0] + iy[k] + iz[0]), az = (int)(ix[0] + iy[0] + iz[k]);
-      cell[k] = (D7 && inx[k] && iny[0] && inz[0] && ax >= 0 && ax < g.ncells) ? ax : -1;
-      cell[2 + k] = (D7 && inx[0] && iny[k] && inz[0] && ay >= 0 && ay < g.ncells) ? ay : -1;
-      cell[4 + k] = (D7 && inx[0] && iny[0] && inz[k] && az >= 0 && az < g.ncells) ? az : -1;
-    }
-    int slot[7];
-#pragma unroll
-    for (int k = 0; k < (D7 ? 7 : 1); ++k) slot[k] = (finite && cell[k] >= 0) ? cell2leaf[cell[k]] : -1;
+    int cell[7], slot[7];
+    neighbor_cells7<D7>(xt, yt, zt, g, cell);
+    neighbor_slots7<D7>(cell, finite, cell2leaf, slot);
     bool any = false;
 #pragma unroll
     for (int k = 0; k < (D7 ? 7 : 1); ++k) any = any || slot[k] >= 0;
@@ -320,44 +290,7 @@ k_d2d_eval(const double* __restrict__ gauss, int n, GridGeom g, const int* __res
   words[EV_NWITH] = acc.npairs > 0 ? 1.0 : 0.0;
   words[EV_NPAIRS] = (double)acc.npairs;
   words[EV_FAIL] = 0.0;
-  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
-#pragma unroll
-  for (int k = 0; k < EV_WORDS; ++k) {
-    if (!HESSIAN && k >= EV_H && k < EV_H + 21) continue;
-    if (k == EV_FAIL) continue;
-    const double s = wave_sum(words[k]);
-    if (lane == 0) s_part[wave][k] = s;
-  }
-  if (lane == 0) {
-    s_part[wave][EV_FAIL] = 0.0;
-    if (!HESSIAN)
-#pragma unroll
-      for (int k = 0; k < 21; ++k) s_part[wave][EV_H + k] = 0.0;
-  }
-  __syncthreads();
-  if (threadIdx.x < EV_WORDS) {
-    double s = s_part[0][threadIdx.x];
-#pragma unroll
-    for (int wv = 1; wv < D2D_WAVES; ++wv) s += s_part[wv][threadIdx.x];
-    rows[(size_t)blockIdx.x * EV_WORDS + threadIdx.x] = s;
-  }
-}
-
-// out[k] = the nb rows of pose k added in a fixed order: SUM_SEGS strided partial sums per word, then those in order
-__global__ void __launch_bounds__(D2D_THREADS) k_d2d_sum(const double* __restrict__ rows, int nb, double* __restrict__ out) {
-  __shared__ double s_seg[SUM_SEGS][EV_WORDS];
-  const int word = (int)(threadIdx.x % EV_WORDS), seg = (int)(threadIdx.x / EV_WORDS);
-  const double* r = rows + (size_t)blockIdx.x * (size_t)nb * EV_WORDS;
-  double s = 0.0;
-  for (int b = seg; b < nb; b += SUM_SEGS) s += r[(size_t)b * EV_WORDS + word];
-  s_seg[seg][word] = s;
-  __syncthreads();
-  if (threadIdx.x < EV_WORDS) {
-    double t = s_seg[0][word];
-#pragma unroll
-    for (int k = 1; k < SUM_SEGS; ++k) t += s_seg[k][word];
-    out[(size_t)blockIdx.x * EV_WORDS + word] = t;
-  }
+  eval_block_row<D2D_WAVES, HESSIAN>(words, s_part, rows);
 }
 
 void rot_x(double a, int order, double M[9]) {   // order-th derivative of Rx(a)
@@ -413,11 +346,6 @@ int blocks_for(size_t n) { return (int)((n + D2D_THREADS - 1) / D2D_THREADS); }
 }  // namespace
 
 namespace engine {
-
-void d2d_launch_sum(const double* rows, int nb, int K, double* out, hipStream_t s) {
-  hipLaunchKernelGGL(k_d2d_sum, dim3((unsigned)K), dim3(D2D_THREADS), 0, s, rows, nb, out);
-}
-
 namespace {
 
 int d2d_min_points(const ndt_handle* h) { return std::max(3, h->prm.min_points_per_voxel); }   // the ordinary build's rule (build_begin)
@@ -470,20 +398,10 @@ void d2d_clear(ndt_handle* h) {
 
 bool d2d_too_many(size_t n) { return n > (size_t)std::numeric_limits<int>::max() / 16; }
 
-// what a D2D evaluation can work with: DIRECT1 / DIRECT7 on a single grid, one rank
-int d2d_supported(ndt_handle* h) {
-  if (h->red.mode() != NDT_REDUCE_NONE) return fail(h, NDT_ERR_UNSUPPORTED, "D2D: multi-rank evaluation is not supported");
-  if (h->prm.search_method != NDT_DIRECT1 && h->prm.search_method != NDT_DIRECT7)
-    return fail(h, NDT_ERR_UNSUPPORTED, "D2D: the search method must be DIRECT1 or DIRECT7");
-  if (h->tgt.is_union()) return fail(h, NDT_ERR_UNSUPPORTED, "D2D: a multi-grid union target is not supported");
-  return NDT_OK;
-}
-
 // target, then distribution source: what ndt_align_d2d answers with the guess
 int d2d_ready(ndt_handle* h) {
   if (int rc = settle(h)) return rc;
-  if (int rc = d2d_supported(h)) return rc;
-  if (!h->tgt.have_grid() || h->tgt.n_valid() <= 0) return fail(h, NDT_ERR_NO_TARGET, "no target voxel grid (setInputTarget first)");
+  if (int rc = lane_eval_supported(h, "D2D")) return rc;
   if (int rc = d2d_source_fresh(h)) return rc;
   if (!h->d2d.have || h->d2d.n_accepted == 0)
     return fail(h, NDT_ERR_NO_SOURCE, "no source Gaussians (ndt_set_source_distributions first)");
@@ -504,32 +422,19 @@ int d2d_ready(ndt_handle* h) {
 int d2d_eval_raw(ndt_handle* h, const double* poses6, int K, bool need_h, double* out) {
   D2dBufs& d = h->d2d;
   const int n = (int)d.n_accepted, nb = blocks_for(d.n_accepted);
-  HIP_TRY(h, d.rows.ensure((size_t)K * (size_t)nb * EV_WORDS));
-  HIP_TRY(h, d.out.ensure((size_t)K * EV_WORDS));
-  HIP_TRY(h, d.out_h.ensure((size_t)K * EV_WORDS));
   double d1, d2;
   gauss_constants((double)h->prm.resolution, h->prm.outlier_ratio, &d1, &d2);
   const bool d7 = h->prm.search_method == NDT_DIRECT7;
-  hipStream_t s = h->stream;
   const dim3 grid((unsigned)nb), block(D2D_THREADS);
-  for (int k = 0; k < K; ++k) {   // one launch per pose: a pose's rows are what they are alone
+  return lane_eval_rows(h, "D2D", nb, K, [&](int k, double* rows) {
     D2dPose P;
     fill_d2d_pose(poses6 + 6 * (size_t)k, &P);
-    double* rows = d.rows.p + (size_t)k * (size_t)nb * EV_WORDS;
 #define NDT_D2D_LAUNCH(H, D7) \
-  hipLaunchKernelGGL((k_d2d_eval<H, D7>), grid, block, 0, s, d.gauss.p, n, h->geom, h->cell2leaf.p, d.tleaf.p, P, d1, d2, rows)
+  hipLaunchKernelGGL((k_d2d_eval<H, D7>), grid, block, 0, h->stream, d.gauss.p, n, h->geom, h->cell2leaf.p, d.tleaf.p, P, d1, d2, rows)
     if (need_h) { if (d7) NDT_D2D_LAUNCH(true, true); else NDT_D2D_LAUNCH(true, false); }
     else { if (d7) NDT_D2D_LAUNCH(false, true); else NDT_D2D_LAUNCH(false, false); }
 #undef NDT_D2D_LAUNCH
-  }
-  d2d_launch_sum(d.rows.p, nb, K, d.out.p, s);
-  HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipMemcpyAsync(d.out_h.h, d.out.p, (size_t)K * EV_WORDS * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_TRY(h, hipStreamSynchronize(s));
-  std::memcpy(out, d.out_h.h, (size_t)K * EV_WORDS * sizeof(double));
-  for (int k = 0; k < K; ++k)
-    if (!std::isfinite(out[(size_t)k * EV_WORDS + EV_SCORE])) return fail(h, NDT_ERR_HIP, "D2D evaluation returned a non-finite score");
-  return NDT_OK;
+  }, out);
 }
 
 }  // namespace
@@ -627,20 +532,7 @@ int ndt_eval_derivatives_d2d(ndt_handle* h, const double* poses6, int K, int com
   if (int rc = bind_device(h)) return rc;
   if (int rc = d2d_ready(h)) return rc;
   if (int rc = d2d_eval_raw(h, poses6, K, compute_hessian != 0, out)) return rc;
-  // ridge / regularisation / guards as ndt_eval_derivatives applies them, then repacked
-  for (int k = 0; k < K; ++k) {
-    double* w = out + (size_t)k * EV_WORDS;
-    Eval e;
-    unpack_eval(w, &e);
-    finish_eval(h->prm, h->have_reg ? h->reg_pose : nullptr, poses6 + 6 * (size_t)k, compute_hessian != 0, &e);
-    w[EV_SCORE] = e.score;
-    for (int i = 0; i < 6; ++i) w[EV_G + i] = e.g[i];
-    if (compute_hessian) {
-      int idx = EV_H;
-      for (int i = 0; i < 6; ++i)
-        for (int j = i; j < 6; ++j) w[idx++] = e.H[6 * i + j];
-    }
-  }
+  for (int k = 0; k < K; ++k) finish_words(h, poses6 + 6 * (size_t)k, compute_hessian != 0, out + (size_t)k * EV_WORDS);
   return NDT_OK;
 }
 
@@ -651,17 +543,8 @@ int ndt_align_d2d(ndt_handle* h, const float guess[16], ndt_result* out) {
   if (int rc = bind_device(h)) return rc;
   h->keepwarm.touch();
   if (int rc = d2d_ready(h)) return rc;
-  EvalFn fn = [h](const double* p, const float*, bool need_h, Eval* e) {
-    double words[EV_WORDS];
-    if (int r = d2d_eval_raw(h, p, 1, need_h, words)) return r;
-    unpack_eval(words, e);
-    finish_eval(h->prm, h->have_reg ? h->reg_pose : nullptr, p, need_h, e);
-    return 0;
-  };
-  // the product path of ndt_align (the Hessian in every trial, the memo on); no iteration history
-  const int rc = newton_align(h->prm, (int64_t)h->d2d.n_accepted, guess, fn, out, /*hessian_in_trials=*/true);
-  h->keepwarm.touch();
-  return rc;
+  return lane_align(h, (int64_t)h->d2d.n_accepted, guess,
+                    [h](const double* p, bool need_h, double* words) { return d2d_eval_raw(h, p, 1, need_h, words); }, out);
 }
 
 }  // extern "C"

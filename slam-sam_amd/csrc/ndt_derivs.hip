@@ -20,6 +20,7 @@
 // Compiled with -ffp-contract=off; the transform and the index arithmetic must
 // round exactly as written to classify points into the same voxels as the ref.
 #include "ndt_kernels.h"
+#include "ndt_neighbors_device.h"
 
 #include <hip/hip_ext.h>
 
@@ -33,14 +34,7 @@ namespace {
 
 constexpr int MAX_BLOCK = 1024;  // block size is chosen per launch (derivs_block_threads), <= 16 waves
 
-// Classifying a point into a voxel (ref: voxel_grid_covariance_impl.hpp:46-71 for the f32 bounds
-// test, voxel_grid_covariance.h:297-300 for the index):
-//   in   = lo <= p < hi on every axis (f32);   i_a = (int)(floorf(p_a * inv_leaf) - (float)min_b_a);
-//   idx  = i0 + i1 * mul1 + i2 * mul2.
-// The reference looks idx up in its hash map whatever its value (f32 rounding at an upper face
-// can alias into the next row); an idx outside [0, ncells) can never be a stored key there, so
-// it is a miss here too -- same outcome.  point_pairs() evaluates this for the point and its
-// six face-offset copies with the per-axis pieces shared.
+// (Moving a point and classifying it into voxels: ndt_neighbors_device.h, shared with the other evaluators.)
 
 struct PairAcc {
   double w[3];
@@ -315,51 +309,10 @@ __device__ __forceinline__ void point_pairs(PairAcc& a, float x, float y, float 
 #pragma unroll
   for (int k = 0; k < 6; ++k) a.S[k] = 0.0;
   a.score = 0.0; a.best = 0.0; a.npairs = 0;
-  // x' = r0*x + (r1*y + (r2*z + t)), f32, unfused (transformPointCloud, ref :761)
-  float xt = P.R[0] * x + (P.R[1] * y + (P.R[2] * z + P.t[0]));
-  float yt = P.R[3] * x + (P.R[4] * y + (P.R[5] * z + P.t[1]));
-  float zt = P.R[6] * x + (P.R[7] * y + (P.R[8] * z + P.t[2]));
-  const bool finite = active && isfinite(xt) && isfinite(yt) && isfinite(zt);  // ref :573: such points are skipped
-  if (!finite) { xt = 0.0f; yt = 0.0f; zt = 0.0f; }  // keeps NaN / Inf out of the (masked) pair arithmetic
-
-  // ref: voxel_grid_covariance_impl.hpp:560-600 -- neighbours are found by offsetting the
-  // POINT by +-leaf in f32 and re-classifying it (see above).  The seven classifications share
-  // their per-axis pieces: a probe differs from the centre in one coordinate only, so only that
-  // axis' bounds test, floor and index are recomputed -- same f32 operations on the same
-  // operands as seven independent classifications, a third of the instructions.
-  const float w = g.leaf;
-  const float cx[3] = {xt, xt + w, xt - w}, cy[3] = {yt, yt + w, yt - w}, cz[3] = {zt, zt + w, zt - w};
-  bool inx[3], iny[3], inz[3];
-  unsigned int ix[3], iy[3], iz[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    inx[k] = cx[k] >= g.lo[0] && cx[k] < g.hi[0];
-    iny[k] = cy[k] >= g.lo[1] && cy[k] < g.hi[1];
-    inz[k] = cz[k] >= g.lo[2] && cz[k] < g.hi[2];
-    // (out-of-range coordinates convert to saturated garbage that the bounds flags mask;
-    // unsigned arithmetic so that garbage may wrap)
-    ix[k] = (unsigned int)(int)(floorf(cx[k] * g.inv_leaf) - (float)g.min_b[0]);
-    iy[k] = (unsigned int)(int)(floorf(cy[k] * g.inv_leaf) - (float)g.min_b[1]) * (unsigned int)g.mul1;
-    iz[k] = (unsigned int)(int)(floorf(cz[k] * g.inv_leaf) - (float)g.min_b[2]) * (unsigned int)g.mul2;
-  }
+  float xt, yt, zt;
+  const bool finite = rigid_move(P, x, y, z, active, xt, yt, zt);
   int cell[7];
-  {
-    const int idx0 = (int)(ix[0] + iy[0] + iz[0]);
-    cell[0] = (inx[0] && iny[0] && inz[0] && idx0 >= 0 && idx0 < g.ncells) ? idx0 : -1;
-  }
-  if (D7) {
-#pragma unroll
-    for (int k = 1; k < 3; ++k) {
-      const int ax = (int)(ix[k] + iy[0] + iz[0]), ay = (int)(ix[0] + iy[k] + iz[0]), az = (int)(ix[0] + iy[0] + iz[k]);
-      // an idx outside [0, ncells) can never be a stored key of the reference's hash map: a miss
-      cell[k] = (inx[k] && iny[0] && inz[0] && ax >= 0 && ax < g.ncells) ? ax : -1;
-      cell[2 + k] = (inx[0] && iny[k] && inz[0] && ay >= 0 && ay < g.ncells) ? ay : -1;
-      cell[4 + k] = (inx[0] && iny[0] && inz[k] && az >= 0 && az < g.ncells) ? az : -1;
-    }
-  } else {
-#pragma unroll
-    for (int k = 1; k < 7; ++k) cell[k] = -1;
-  }
+  neighbor_cells7<D7>(xt, yt, zt, g, cell);
   if (!D7) {  // DIRECT1 (ref: getNeighborhoodAtPoint1, voxel_grid_covariance_impl.hpp:604-615)
     const int slot0 = (finite && cell[0] >= 0) ? cell2leaf[cell[0]] : -1;
     __builtin_amdgcn_sched_barrier(0);
@@ -369,7 +322,7 @@ __device__ __forceinline__ void point_pairs(PairAcc& a, float x, float y, float 
     pair_update<MODE>(a, r0, xt, yt, zt, ec, slot0 >= 0);
     return;
   }
-  int slot[7];
+  int slot[7];   // (neighbor_slots7's gather, written out: through the helper the DIRECT7 kernels schedule differently)
 #pragma unroll
   for (int k = 0; k < 7; ++k) slot[k] = (finite && cell[k] >= 0) ? cell2leaf[cell[k]] : -1;
   __builtin_amdgcn_sched_barrier(0);
@@ -449,11 +402,8 @@ __device__ __forceinline__ void point_pairs_kd(PairAcc& a, float x, float y, flo
 #pragma unroll
   for (int k = 0; k < 6; ++k) a.S[k] = 0.0;
   a.score = 0.0; a.best = 0.0; a.npairs = 0;
-  float xt = P.R[0] * x + (P.R[1] * y + (P.R[2] * z + P.t[0]));
-  float yt = P.R[3] * x + (P.R[4] * y + (P.R[5] * z + P.t[1]));
-  float zt = P.R[6] * x + (P.R[7] * y + (P.R[8] * z + P.t[2]));
-  const bool finite = active && isfinite(xt) && isfinite(yt) && isfinite(zt);
-  if (!finite) { xt = 0.0f; yt = 0.0f; zt = 0.0f; }
+  float xt, yt, zt;
+  const bool finite = rigid_move(P, x, y, z, active, xt, yt, zt);
   // the point's own (possibly out-of-box) cell, same f32 arithmetic as the grid build
   const int i0 = finite ? (int)(floorf(xt * g.inv_leaf) - (float)g.min_b[0]) : -4;
   const int i1 = finite ? (int)(floorf(yt * g.inv_leaf) - (float)g.min_b[1]) : -4;
@@ -462,6 +412,7 @@ __device__ __forceinline__ void point_pairs_kd(PairAcc& a, float x, float y, flo
   // 27; round 3).  At the ends of the grid a row starts one or two ints outside it -- the index grid is readable four
   // ints beyond either end (IndexGrid, ndt_engine.h) and those lanes are masked.  Cell n = (dx+1) + 3 (dy+1) + 9 (dz+1),
   // as before: the listing order, hence the summation order, is unchanged.
+  // (This lookup is written out here and in k_point_scores: see the note at the end of ndt_neighbors_device.h.)
   int slot[KD_CELLS];
   {
     // (unsigned compares: one instruction per range test; bitwise `&` on the flags: the short-circuit form compiles to an
@@ -1476,9 +1427,7 @@ __global__ void __launch_bounds__(256) k_transform(const float* __restrict__ sx,
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float x = sx[i], y = sy[i], z = sz[i];
-  out[3 * i + 0] = P.R[0] * x + (P.R[1] * y + (P.R[2] * z + P.t[0]));
-  out[3 * i + 1] = P.R[3] * x + (P.R[4] * y + (P.R[5] * z + P.t[1]));
-  out[3 * i + 2] = P.R[6] * x + (P.R[7] * y + (P.R[8] * z + P.t[2]));
+  rigid_apply(P, x, y, z, out[3 * i + 0], out[3 * i + 1], out[3 * i + 2]);
 }
 
 // ---- per-point scores (ndt_score_points) ------------------------------------------------------------------------
@@ -1524,44 +1473,16 @@ k_point_scores(const float* __restrict__ sx, const float* __restrict__ sy, const
   const bool active = i < n;
   float x = 0.0f, y = 0.0f, z = 0.0f;
   if (active) { x = sx[i]; y = sy[i]; z = sz[i]; }
-  float xt = P.R[0] * x + (P.R[1] * y + (P.R[2] * z + P.t[0]));
-  float yt = P.R[3] * x + (P.R[4] * y + (P.R[5] * z + P.t[1]));
-  float zt = P.R[6] * x + (P.R[7] * y + (P.R[8] * z + P.t[2]));
-  const bool finite = active && isfinite(xt) && isfinite(yt) && isfinite(zt);
-  if (!finite) { xt = 0.0f; yt = 0.0f; zt = 0.0f; }
+  float xt, yt, zt;
+  const bool finite = rigid_move(P, x, y, z, active, xt, yt, zt);
   PointAcc p;
   p.score = 0.0; p.best = 0.0; p.npairs = 0; p.best_cell = -1;
   constexpr bool KD = NB >= 2 && NB <= 4;
   if (!KD) {
     constexpr bool D7 = NB == 1 || NB == 6, PACKED = NB >= 5;
-    const float w = g.leaf;
-    const float cx[3] = {xt, xt + w, xt - w}, cy[3] = {yt, yt + w, yt - w}, cz[3] = {zt, zt + w, zt - w};
-    bool inx[3], iny[3], inz[3];
-    unsigned int ix[3], iy[3], iz[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      inx[k] = cx[k] >= g.lo[0] && cx[k] < g.hi[0];
-      iny[k] = cy[k] >= g.lo[1] && cy[k] < g.hi[1];
-      inz[k] = cz[k] >= g.lo[2] && cz[k] < g.hi[2];
-      ix[k] = (unsigned int)(int)(floorf(cx[k] * g.inv_leaf) - (float)g.min_b[0]);
-      iy[k] = (unsigned int)(int)(floorf(cy[k] * g.inv_leaf) - (float)g.min_b[1]) * (unsigned int)g.mul1;
-      iz[k] = (unsigned int)(int)(floorf(cz[k] * g.inv_leaf) - (float)g.min_b[2]) * (unsigned int)g.mul2;
-    }
-    int cell[7];
-    {
-      const int idx0 = (int)(ix[0] + iy[0] + iz[0]);
-      cell[0] = (inx[0] && iny[0] && inz[0] && idx0 >= 0 && idx0 < g.ncells) ? idx0 : -1;
-    }
-#pragma unroll
-    for (int k = 1; k < 3; ++k) {
-      const int ax = (int)(ix[k] + iy[0] + iz[0]), ay = (int)(ix[0] + iy[k] + iz[0]), az = (int)(ix[0] + iy[0] + iz[k]);
-      cell[k] = (D7 && inx[k] && iny[0] && inz[0] && ax >= 0 && ax < g.ncells) ? ax : -1;
-      cell[2 + k] = (D7 && inx[0] && iny[k] && inz[0] && ay >= 0 && ay < g.ncells) ? ay : -1;
-      cell[4 + k] = (D7 && inx[0] && iny[0] && inz[k] && az >= 0 && az < g.ncells) ? az : -1;
-    }
-    int slot[7];
-#pragma unroll
-    for (int k = 0; k < (D7 ? 7 : 1); ++k) slot[k] = (finite && cell[k] >= 0) ? cell2leaf[cell[k]] : -1;
+    int cell[7], slot[7];
+    neighbor_cells7<D7>(xt, yt, zt, g, cell);
+    neighbor_slots7<D7>(cell, finite, cell2leaf, slot);
 #pragma unroll
     for (int k = 0; k < (D7 ? 7 : 1); ++k) {
       const VoxelRecord r = fetch_record(rec, slot[k] >= 0 ? slot[k] : 0, PACKED);

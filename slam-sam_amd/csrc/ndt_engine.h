@@ -16,6 +16,8 @@
 //                      and align against the target's leaves (k_d2d_* kernels)
 //   ndt_ct.hip         continuous-time registration: per-point times of the point source, the evaluation with one pose per
 //                      point, its align and the deskewed scan under a result (k_ct_* kernels)
+//   ndt_eval_rows.hip  what those two evaluations share behind their kernels: the fixed-order sum of block rows, the host
+//                      driver, the support check, the finished-words repack, the align wrapper
 //   ndt_scan_context.hip  Scan Context place recognition: a scan's rings x sectors descriptor, the descriptor bank beside
 //                      the keyframe archive and the all-shifts match against it (k_sc_* kernels)
 //   ndt_map_carve.hip  free-space carving of the map: voxels that a scan's rays pass through go (k_mapcarve_* kernels)
@@ -288,12 +290,9 @@ struct D2dBufs {
   DevBuf<double> tleaf;              // the target's leaves, 9 doubles per slot
   uint64_t tleaf_gen = 0;            // TargetState::gen() of the target they were gathered from
   bool tleaf_valid = false;
-  DevBuf<double> rows, out;          // per-block rows of K poses, their K x EV_WORDS sums
-  PinBuf<double> out_h;
   void release() {
     rcount.release(); rmom.release(); gauss.release(); gcount.release(); gindex.release(); frec.release(); fcent.release();
-    fstats.release(); fcell.release(); bad.release(); bad_h.release(); tleaf.release(); rows.release(); out.release();
-    out_h.release();
+    fstats.release(); fcell.release(); bad.release(); bad_h.release(); tleaf.release();
     n_records = n_accepted = 0;
     have = tleaf_valid = false;
   }
@@ -304,13 +303,19 @@ struct D2dBufs {
 struct CtBufs {
   DevBuf<float> alpha;               // one factor per source point, in the source's order
   size_t n = 0;                      // times attached (== n_src), 0 = none
-  DevBuf<double> rows, out;          // per-block rows of K poses, their K x EV_WORDS sums
-  PinBuf<double> out_h;
   DevBuf<float> xyz;                 // [x | y | z] of ndt_transform_source_ct's host form
   void release() {
-    alpha.release(); rows.release(); out.release(); out_h.release(); xyz.release();
+    alpha.release(); xyz.release();
     n = 0;
   }
+};
+
+// The rows of a lane-per-item evaluation (lane_eval_rows, ndt_eval_rows.hip).  One instance serves D2D and CT: either
+// evaluation is awaited before it returns.
+struct EvalRowBufs {
+  DevBuf<double> rows, out;          // per-block rows of K poses, their K x EV_WORDS sums
+  PinBuf<double> out_h;
+  void release() { rows.release(); out.release(); out_h.release(); }
 };
 
 // Scan Context (ndt_scan_context.hip): the parameters, the sector table they imply, the scratch of a descriptor call and
@@ -468,6 +473,7 @@ struct ndt_handle {
   ScanContextBufs sc;                // Scan Context: parameters, sector table, descriptor bank (ndt_scan_context.hip)
   D2dBufs d2d;                       // the distribution source of ndt_*_d2d and the target's leaves for it (ndt_d2d.hip)
   CtBufs ct;                         // the source's times and the scratch of ndt_*_ct (ndt_ct.hip)
+  EvalRowBufs evrows;                // the block rows and sums of a D2D or CT evaluation (ndt_eval_rows.hip)
   // the same points in block order of the target grid (see sort_source_by_blocks); valid until
   // the source or the target changes
   DevBuf<float> ox, oy, oz;
@@ -788,9 +794,20 @@ int map_import_checks(ndt_handle* h, float leaf, const double* moments9, size_t 
 int map_import_tail(ndt_handle* h, const int32_t* d_count, const float* d_sums, const double* d_mom, size_t n);
 int map_merge_records(ndt_handle* h, const MapTable& t, unsigned long long* d_nvox, const int32_t* d_count, const float* d_sums,
                       const double* d_mom, size_t n);
-// ndt_d2d.hip: k_d2d_sum on rows of K poses x nb blocks x EV_WORDS -> out (K x EV_WORDS), enqueued on s; the CT evaluation's
-// rows have the same layout and take the same fixed-order sum
-void d2d_launch_sum(const double* rows, int nb, int K, double* out, hipStream_t s);
+// ndt_eval_rows.hip: what the lane-per-item evaluations (D2D, CT) share behind their kernels.  `what` is "D2D" or "CT"
+// and heads the error texts.
+// k_eval_rows_sum on rows of K poses x nb blocks x EV_WORDS -> out (K x EV_WORDS), enqueued on s
+void launch_eval_rows_sum(const double* rows, int nb, int K, double* out, hipStream_t s);
+// what such an evaluation can work with: one rank, DIRECT1 / DIRECT7, a single grid -- and a target to evaluate against
+int lane_eval_supported(ndt_handle* h, const char* what);
+// K poses -> K x EV_WORDS raw sums in `out`: launch(k, rows) enqueues pose k's kernel (nb blocks, one row each) on the
+// engine's stream; then the fixed-order sum, the copy and the wait.  A score that is not finite fails.
+int lane_eval_rows(ndt_handle* h, const char* what, int nb, int K, const std::function<void(int, double*)>& launch, double* out);
+// raw sums -> what ndt_eval_derivatives hands out: ridge / regularisation / guards (finish_eval), repacked in place
+void finish_words(ndt_handle* h, const double pose6[6], bool need_h, double* w);
+// newton_align over an evaluation of n_items items: raw(pose6, need_h, words) fills one pose's raw sums
+using LaneEvalFn = std::function<int(const double*, bool, double*)>;
+int lane_align(ndt_handle* h, int64_t n_items, const float guess[16], const LaneEvalFn& raw, ndt_result* out);
 void fill_pose_consts(const double p[6], const float T[16], PoseConsts* pc);
 unsigned long long process_item_salt();
 EvalConsts make_eval_consts(const ndt_handle* h, bool need_h);

@@ -837,17 +837,7 @@ static int eval_batch(ndt_handle* h, const double* poses6, const float* transfor
   }
   if (score_only) return NDT_OK;
   // ridge / regularisation / guards, then repack so callers see finished values
-  for (int k = 0; k < K; ++k) {
-    double* w = out + (size_t)k * EV_WORDS;
-    Eval e;
-    unpack_eval(w, &e);
-    finish_eval(h->prm, h->have_reg ? h->reg_pose : nullptr, poses6 + 6 * (size_t)k, compute_hessian != 0, &e);
-    w[EV_SCORE] = e.score;
-    for (int i = 0; i < 6; ++i) w[EV_G + i] = e.g[i];
-    int idx = EV_H;
-    for (int i = 0; i < 6; ++i)
-      for (int j = i; j < 6; ++j) w[idx++] = e.H[6 * i + j];
-  }
+  for (int k = 0; k < K; ++k) finish_words(h, poses6 + 6 * (size_t)k, compute_hessian != 0, out + (size_t)k * EV_WORDS);
   return NDT_OK;
 }
 

@@ -1,5 +1,6 @@
 // ndt_point_scores.hip -- per-point NDT scores and the score-based source filter (see ndt_engine.h).
-//   ndt_score_points*        one launch of k_point_scores (ndt_derivs.hip) on the engine's stream
+//   ndt_score_points*        one launch of k_point_scores (ndt_derivs.hip) on the engine's stream; the kernel moves and
+//                            classifies a point through ndt_neighbors_device.h, as the evaluation that scored it does
 //   ndt_filter_source*       k_point_scores for the predicate values, then the stable compaction of
 //                            ndt_compact_device.h in three small launches: k_filter_count, k_filter_scan, k_filter_emit.
 // Integer counters only, no atomics: where a point lands depends on the points in front of it and on nothing else.

@@ -583,4 +583,6 @@ def test_ct_kernels_do_not_spill(tmp_path):
     src = open(path).read()
     assert len(re.findall(r"__global__", src)) == len(kernels)
     assert not re.findall(r"atomic\w*\(", src) and not re.search(r"\basm\b", src)
-    assert "d2d_launch_sum(" in src                                                   # D2D's fixed-order sum, not a copy
+    # the fixed-order sum and its host driver, the neighbour rule and the block row are the shared ones, not copies
+    assert "lane_eval_rows(" in src and "k_eval_rows_sum" not in src.split("namespace ndt")[1]
+    assert "neighbor_cells7<" in src and "floorf(" not in src and "eval_block_row<" in src and "__shfl_xor" not in src

@@ -370,26 +370,34 @@ def test_python_mirror_validates_before_the_library(pkg):
 
 # ---- the kernels --------------------------------------------------------------------------------------------------------
 def test_d2d_kernels_do_not_spill(tmp_path):
-    """The figures tools/kernel_resources.py prints for `ndt_d2d.hip k_d2d_`: every kernel without scratch, the Hessian
+    """The figures tools/kernel_resources.py prints for `ndt_d2d.hip k_d2d_` and for the fixed-order sum it shares with the
+    continuous-time evaluation (`ndt_eval_rows.hip k_eval_rows_`): every kernel without scratch, the Hessian
     instantiations of k_d2d_eval within the 256 architectural VGPRs."""
-    path = os.path.join(ROOT, "slam-sam_amd", "csrc", "ndt_d2d.hip")
-    p = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", path, "-o", str(tmp_path / "k.o")],
-                       capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    usage, name = {}, None
-    for ln in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", ln)
-        if m:
-            name = m.group(1)
-        m = re.search(r"(VGPRs|AGPRs|ScratchSize \[bytes/lane\]): (\d+)", ln)
-        if m and name:
-            usage.setdefault(name, {})[m.group(1).split(" ")[0]] = int(m.group(2))
+    def resources(file_name):
+        path = os.path.join(ROOT, "slam-sam_amd", "csrc", file_name)
+        p = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
+                            "-Rpass-analysis=kernel-resource-usage", "-c", path, "-o", str(tmp_path / "k.o")],
+                           capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-2000:]
+        usage, name = {}, None
+        for ln in p.stderr.splitlines():
+            m = re.search(r"Function Name: (\S+)", ln)
+            if m:
+                name = m.group(1)
+            m = re.search(r"(VGPRs|AGPRs|ScratchSize \[bytes/lane\]): (\d+)", ln)
+            if m and name:
+                usage.setdefault(name, {})[m.group(1).split(" ")[0]] = int(m.group(2))
+        return path, usage
+
+    _, rows_usage = resources("ndt_eval_rows.hip")
+    assert len(rows_usage) == 1 and "k_eval_rows_sum" in next(iter(rows_usage)), sorted(rows_usage)
+    path, usage = resources("ndt_d2d.hip")
     assert usage and all("k_d2d_" in k for k in usage), sorted(usage)                 # the new kernels carry the prefix
     assert not any("k_derivatives" in k for k in usage)
     kernels = {re.search(r"k_d2d_[a-z_]+?(?=I|E)", k).group(0) for k in usage}
-    assert kernels == {"k_d2d_check", "k_d2d_finalize", "k_d2d_emit", "k_d2d_gather_target", "k_d2d_eval", "k_d2d_sum"}, kernels
-    assert len(usage) == 9                                                            # k_d2d_eval: <HESSIAN, D7> four times
+    assert kernels == {"k_d2d_check", "k_d2d_finalize", "k_d2d_emit", "k_d2d_gather_target", "k_d2d_eval"}, kernels
+    assert len(usage) == 8                                                            # k_d2d_eval: <HESSIAN, D7> four times
+    usage.update(rows_usage)
     for k, u in usage.items():
         print(k, u)
         assert u["ScratchSize"] == 0 and u["VGPRs"] <= 256, (k, u)
@@ -400,5 +408,8 @@ def test_d2d_kernels_do_not_spill(tmp_path):
     assert re.findall(r"atomic\w*\(", src) == ["atomicOr("] and not re.search(r"\basm\b", src)
     assert "finalize_leaf(" in src and "jacobi" not in src and '#include "ndt_leaf_device.h"' in src
     assert "compact_ballot(" in src and "compact_position(" in src and "launch_filter_scan(" in src and "compact_total(" in src
+    # the neighbour rule, the block row and the host driver are called, not copied
+    assert "neighbor_cells7<" in src and "floorf(" not in src and "eval_block_row<" in src and "__shfl_xor" not in src
+    assert "lane_eval_rows(" in src and "lane_align(" in src and "finish_words(" in src
     target = open(os.path.join(ROOT, "slam-sam_amd", "csrc", "ndt_target.hip")).read()
     assert '#include "ndt_leaf_device.h"' in target and "bool finalize_leaf(" not in target
