@@ -1083,6 +1083,107 @@ int     ndt_transform_source_ct(ndt_handle* h, const double begin_pose6[6], cons
 int     ndt_transform_source_ct_device(ndt_handle* h, const double begin_pose6[6], const double end_pose6[6], int frame,
                                        float* ox, float* oy, float* oz, size_t cap);
 
+/* Generalised ICP (GICP; Segal, Haehnel & Thrun, RSS 2009) in the plane-to-plane form of PCL / pclomp: the third method of
+ * the registration boundary beside NDT and SVN-NDT, and a cross-check of an NDT result -- same clouds, no voxel grid.  It
+ * registers the current POINT source (ndt_set_source*) to the points the target was built from (a target that keeps no
+ * points -- ndt_set_target_device*, a multi-grid union -- is NDT_ERR_UNSUPPORTED, as for ndt_fitness_score).  Everything
+ * below is IEEE arithmetic rounded as written, no contraction; tests/test_gicp_cpu.py restates it in NumPy.
+ * PARAMETERS ndt_gicp_params (defaults: ndt_gicp_default_params): k_neighbours 20 (PCL's correspondence randomness; 4 ..
+ * 32), max_neighbour_distance +INF (> 0; finite: bounds the neighbour search of isolated points), covariance_epsilon 1e-3
+ * (PCL's gicp_epsilon; in (0, 1]), max_correspondence_distance D = 5.0 (> 0, +INF allowed), transformation_epsilon 1e-4
+ * (finite, >= 0), max_iterations 64 (outer loop, >= 1), max_inner_iterations 20 (>= 1).  ndt_gicp_set_params: a NULL
+ * pointer or a value outside these ranges (NaN included) is NDT_ERR_INVALID_ARG before the handle is looked at, and
+ * nothing changes.  A changed k_neighbours, max_neighbour_distance or covariance_epsilon drops the cached covariances of
+ * both clouds (and the pairs); a changed max_correspondence_distance drops the pairs.
+ * NEIGHBOURS of point i of a cloud (`which`: NDT_GICP_SOURCE or NDT_GICP_TARGET), a point being FINITE when x, y and z are:
+ *    d2(i, j) = (dx*dx + dy*dy) + dz*dz in f32, dx = x_j - x_i and so on, rounded as written.
+ *    The neighbours are the m <= k finite points j of the SAME cloud with the smallest (d2, j) in lexicographic order, i
+ *    itself included (d2 = 0), restricted to d2 <= (float)(cap * cap) when max_neighbour_distance = cap is finite.  The
+ *    search is exact: it does not depend on how the engine indexes the cloud.  A point that is not finite has m = 0.
+ *    A point with m < 4 HAS NO COVARIANCE: it takes no part in anything below and is counted.
+ * COVARIANCE of a point with m >= 4, f64, over its neighbour list in that order (x_j: the f32 coordinates as f64):
+ *    mean_a   = (sum over the list in order, starting from 0) / m
+ *    raw_ab   = (sum over the list in order of (x_ja - mean_a) * (x_jb - mean_b), starting from 0) / m, ab over xx, xy,
+ *               xz, yy, yz, zz
+ *    n        = the unit eigenvector of the smallest eigenvalue of raw, by the target build's cyclic Jacobi in f64
+ *               (columns sorted by ascending eigenvalue; numpy.linalg.eigh agrees to a few ulp where the two smallest
+ *               eigenvalues are apart)
+ *    C_ab     = delta_ab - ((1 - eps) * n_a) * n_b, eps = covariance_epsilon: PCL's U diag(1, 1, eps) U^T, written so that
+ *               it depends on the normal alone (xy, xz, yz are computed once: C is symmetric bit for bit).
+ * The lists and covariances are derived lazily by the first call that needs them and cached: the source's until a call
+ * replaces or re-declares the source (ndt_set_source*, _device, _device_view, ndt_set_source_from_keyframe,
+ * ndt_source_changed), the target's until the target changes.
+ *  - ndt_gicp_export_neighbours: idx (n x k_neighbours int32, row i in (d2, j) order, -1 padded) and n_found (n int32), rows
+ *    in input order; either may be NULL.  Returns n, or < 0 (cap < n: NDT_ERR_INVALID_ARG).
+ *  - ndt_gicp_export_covariances: mean3 (n x 3), raw_cov6 (n x 6), cov6 (n x 6), rows in input order, NaN rows for points
+ *    without a covariance; any may be NULL.  Returns n, or < 0.
+ * PAIRING ndt_gicp_pair(pose6 = [x, y, z, roll, pitch, yaw]): for every source point with a covariance
+ *    rotation    R = Rx(roll) Ry(pitch) Rz(yaw), built on the host in f64 from the sin / cos of pose6, as for
+ *                ndt_eval_derivatives_d2d.
+ *    moved point x'_a = ((R_a0 x_0 + R_a1 x_1) + R_a2 x_2) + t_a in f64 (that rule's moved mean), query = its f32 rounding.
+ *    partner     the finite target point j with the smallest (d2, j), d2 = (dx*dx + dy*dy) + dz*dz in f32 between the
+ *                query and the target point (target - query), found exactly.  It is kept when d2 <= (float)(D * D),
+ *                inclusive, and when j has a covariance.
+ *    Otherwise -- and for a source point without a covariance or a query that is not finite -- the entry is -1 with d2 = +INF.
+ * The pairs are FROZEN in the handle until the next pairing, a source or target change, or a parameter change.
+ * *n_pairs (nullable): the kept pairs.  ndt_gicp_export_pairs: target_index (n int32) and d2 (n floats) in source order,
+ * either may be NULL; returns n, 0 without frozen pairs, or < 0.
+ * THE EVALUATION ndt_eval_derivatives_gicp: K poses -> K x NDT_EVAL_WORDS words in the layout of ndt_eval_derivatives
+ * (ndt_unpack_eval applies; ridge / regularisation as there) over the FROZEN pairs, IEEE f64.  Per pair (i, j), with the
+ * rotation and moved point of the pairing at the evaluated pose:
+ *    mu = x'_i - b_j (b_j: the target point), C = R C_i R^T + C_j, B = C^-1 (by cofactors), q = mu^T B mu;
+ *    score += -q / 2, gradient_a += -q_a / 2, Hessian_ab += -q_ab / 2, q_a and q_ab EXACTLY the expressions of
+ *    ndt_eval_derivatives_d2d with Sigma_i = C_i, Sigma_j = C_j (the same device function with the weight f = -1/2 in
+ *    place of (d1 d2 / 2) e, and without the (d2 / 2) q_a q_b term).  A pair whose q is not finite contributes nothing
+ *    and is not counted.  nvtl_sum = score; n_points_with_neighbors = n_pairs = the counted pairs.
+ * compute_hessian == 0: the Hessian words are zero, score and gradient are the bits of the Hessian call.  Sums are made in
+ * a fixed order without float atomics: the same bits every time, and a pose in a batch of K gets the bits it gets alone.
+ * NDT_ERR_INVALID_ARG, before the handle is looked at, for a NULL pointer, K <= 0 or a non-finite pose entry;
+ * NDT_ERR_UNSUPPORTED with a reducer other than NDT_REDUCE_NONE and for a target that keeps no points; NDT_ERR_NO_TARGET
+ * without a target; NDT_ERR_NO_SOURCE without a source or without frozen pairs.
+ * THE ALIGN ndt_align_gicp, PCL's two-level loop.  p_0 = the pose ndt_newton_align derives from the guess matrix, T_0 = the
+ * guess.  Outer iteration s = 0 .. max_iterations - 1:
+ *    1. ndt_gicp_pair at p_s; zero pairs end the call with NDT_ERR_NO_SOURCE.
+ *    2. ndt_newton_align's loop (the ndt_align product path) from T_s over the evaluation above, with the handle's
+ *       ndt_params except trans_epsilon = transformation_epsilon and max_iterations = max_inner_iterations, n_source_total
+ *       = the source size: result r_s.  p_{s+1} = r_s.final_pose, T_{s+1} = r_s.final_transformation.
+ *    3. stop, converged, when sqrt(sum_c (p_{s+1,c} - p_{s,c})^2) < transformation_epsilon -- the criterion that loop
+ *       applies to the length of a step.  After max_iterations outer iterations the call ends with converged = 0.
+ * `out` is the last inner result as ndt_align_d2d fills it, with converged as above, iterations = the outer iterations,
+ * n_evaluations / n_evaluations_reused summed over the inner loops and ms_total the whole call.  `info` (nullable): outer
+ * iterations, inner iterations summed, evaluations summed, the pairs of the last pairing, the points without a covariance
+ * of either cloud.  On every failure `out` holds the guess with converged = 0.  The handle's align state, iteration history,
+ * pre-launch state, point source and distribution source are left alone, as by ndt_align_d2d: an ndt_align afterwards gives
+ * the bits it gave before, and so do the fitness calls (they share the target's point index). */
+#define NDT_GICP_SOURCE 0
+#define NDT_GICP_TARGET 1
+typedef struct ndt_gicp_params {
+  int k_neighbours;
+  double max_neighbour_distance;
+  double covariance_epsilon;
+  double max_correspondence_distance;
+  double transformation_epsilon;
+  int max_iterations;
+  int max_inner_iterations;
+} ndt_gicp_params;
+typedef struct ndt_gicp_info {
+  int outer_iterations;
+  int inner_iterations;
+  int n_evaluations;
+  int64_t n_pairs;
+  int64_t n_source_without_covariance;
+  int64_t n_target_without_covariance;
+} ndt_gicp_info;
+void    ndt_gicp_default_params(ndt_gicp_params* p);
+int     ndt_gicp_set_params(ndt_handle* h, const ndt_gicp_params* p);
+int     ndt_gicp_get_params(const ndt_handle* h, ndt_gicp_params* p);
+int64_t ndt_gicp_export_neighbours(ndt_handle* h, int which, int32_t* idx, int32_t* n_found, size_t cap);
+int64_t ndt_gicp_export_covariances(ndt_handle* h, int which, double* mean3, double* raw_cov6, double* cov6, size_t cap);
+int     ndt_gicp_pair(ndt_handle* h, const double pose6[6], int64_t* n_pairs);
+int64_t ndt_gicp_export_pairs(ndt_handle* h, int32_t* target_index, float* d2, size_t cap);
+int     ndt_eval_derivatives_gicp(ndt_handle* h, const double* poses6, int K, int compute_hessian, double* out);
+int     ndt_align_gicp(ndt_handle* h, const float guess_colmajor[16], ndt_result* out, ndt_gicp_info* info);
+
 /* Scan Context place recognition (Kim & Kim, IROS 2018) over the device keyframe archive: which archived scan shows this
  * place again, and under which heading -- the question in front of ndt_align_batch / ndt_align_d2d (the relative pose) and
  * ndt_map_transform / ndt_map_import_state_posed (the correction).  A scan becomes an n_rings x n_sectors matrix of

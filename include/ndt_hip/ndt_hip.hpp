@@ -1627,6 +1627,11 @@ class NormalDistributionsTransform
   // only produced (on the device) when asked for
   void setFillOutputCloud(bool on) { fill_output_ = on; }
 
+ protected:
+  // the engine call behind align(): GeneralizedIterativeClosestPoint below substitutes its own
+  virtual int alignEngine(const float* guess, ndt_result* out) { return ndt_align(h_, guess, out); }
+  void setStatus(int s) { status_ = s; }
+
  private:
   void push() { if (h_) status_ = ndt_set_params(h_, &prm_); }
   template <class Cloud>
@@ -1658,7 +1663,7 @@ class NormalDistributionsTransform
     std::memset(&res_, 0, sizeof(res_));
     std::memcpy(res_.final_transformation, guess, sizeof(float) * 16);
     if (!h_) { status_ = NDT_ERR_NO_DEVICE; return; }
-    status_ = ndt_align(h_, guess, &res_);
+    status_ = alignEngine(guess, &res_);
     if (status_ != NDT_OK) {  // the reference returns the prior, not converged
       std::memcpy(res_.final_transformation, guess, sizeof(float) * 16);
       res_.converged = 0;
@@ -1702,6 +1707,68 @@ class NormalDistributionsTransform
   TargetGrid grid_;
   std::map<std::string, int64_t> target_ids_;  // multi-grid: tier4's string ids -> the C-ABI's integers
   int64_t next_target_id_ = 1;
+};
+
+// pclomp::GeneralizedIterativeClosestPoint (ref: include/registercallback.hpp:11-12, config/register_config.json:
+// gicp_corr_dist_threshold, gicp_transform_epsilon) on the engine's GICP (ndt_gicp_*, ndt_align_gicp): PCL's setter names,
+// the clouds, align(), getFinalTransformation(), hasConverged() and getFitnessScore() of the class above -- whose NDT
+// setters stay available: the target's voxel grid is still built, and ndt_align on the same clouds is the cross-check.
+// With PCL visible it is a pcl::Registration like the NDT class, so it can be stored in RegisterCallback::registration.
+template <typename PointSource, typename PointTarget>
+class GeneralizedIterativeClosestPoint : public NormalDistributionsTransform<PointSource, PointTarget> {
+  using Ndt = NormalDistributionsTransform<PointSource, PointTarget>;
+
+ public:
+#if NDT_HIP_WITH_PCL
+  using Ptr = typename std::pointer_traits<typename Ndt::Base::Ptr>::template rebind<GeneralizedIterativeClosestPoint<PointSource, PointTarget>>;
+  using ConstPtr = typename std::pointer_traits<typename Ndt::Base::Ptr>::template rebind<const GeneralizedIterativeClosestPoint<PointSource, PointTarget>>;
+#else
+  using Ptr = std::shared_ptr<GeneralizedIterativeClosestPoint<PointSource, PointTarget>>;
+  using ConstPtr = std::shared_ptr<const GeneralizedIterativeClosestPoint<PointSource, PointTarget>>;
+#endif
+
+  GeneralizedIterativeClosestPoint() {
+    ndt_gicp_default_params(&gp_);
+#if NDT_HIP_WITH_PCL
+    this->reg_name_ = "ndt_hip::GeneralizedIterativeClosestPoint";
+    this->max_iterations_ = gp_.max_iterations;
+    this->transformation_epsilon_ = gp_.transformation_epsilon;
+#endif
+  }
+
+  void setMaxCorrespondenceDistance(double d) { gp_.max_correspondence_distance = d; pushGicp(); }
+  double getMaxCorrespondenceDistance() const { return gp_.max_correspondence_distance; }
+  void setTransformationEpsilon(double e) {
+#if NDT_HIP_WITH_PCL
+    this->transformation_epsilon_ = e;
+#endif
+    gp_.transformation_epsilon = e;
+    pushGicp();
+  }
+  void setCorrespondenceRandomness(int k) { gp_.k_neighbours = k; pushGicp(); }
+  int getCorrespondenceRandomness() const { return gp_.k_neighbours; }
+  void setMaximumIterations(int n) {   // the outer loop
+#if NDT_HIP_WITH_PCL
+    this->max_iterations_ = n;
+#endif
+    gp_.max_iterations = n;
+    pushGicp();
+  }
+  void setMaximumOptimizerIterations(int n) { gp_.max_inner_iterations = n; pushGicp(); }
+  int getMaximumOptimizerIterations() const { return gp_.max_inner_iterations; }
+  // every GICP parameter at once (max_neighbour_distance, covariance_epsilon, ...)
+  const ndt_gicp_params& gicpParams() const { return gp_; }
+  void setGicpParams(const ndt_gicp_params& p) { gp_ = p; pushGicp(); }
+  // outer / inner iterations, evaluations, pairs and points without a covariance of the last align()
+  const ndt_gicp_info& gicpInfo() const { return info_; }
+
+ protected:
+  int alignEngine(const float* guess, ndt_result* out) override { return ndt_align_gicp(this->handle(), guess, out, &info_); }
+
+ private:
+  void pushGicp() { this->setStatus(this->handle() ? ndt_gicp_set_params(this->handle(), &gp_) : NDT_ERR_NO_DEVICE); }
+  ndt_gicp_params gp_{};
+  ndt_gicp_info info_{};
 };
 
 // tier4's class name for the multi-grid face [RECALLED]; here the same engine object carries both faces

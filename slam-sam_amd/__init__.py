@@ -124,6 +124,22 @@ class ScanContextParams(C.Structure):
                 ("lift", C.c_float), ("min_points_per_bin", C.c_int32)]
 
 
+class GicpParams(C.Structure):
+    """ndt_gicp_params (ndt_gicp_default_params: 20, +inf, 1e-3, 5.0, 1e-4, 64, 20)"""
+    _fields_ = [("k_neighbours", C.c_int), ("max_neighbour_distance", C.c_double), ("covariance_epsilon", C.c_double),
+                ("max_correspondence_distance", C.c_double), ("transformation_epsilon", C.c_double),
+                ("max_iterations", C.c_int), ("max_inner_iterations", C.c_int)]
+
+
+class GicpInfo(C.Structure):
+    _fields_ = [("outer_iterations", C.c_int), ("inner_iterations", C.c_int), ("n_evaluations", C.c_int),
+                ("n_pairs", C.c_int64), ("n_source_without_covariance", C.c_int64),
+                ("n_target_without_covariance", C.c_int64)]
+
+
+GICP_SOURCE, GICP_TARGET = 0, 1
+
+
 class MapCarveResult(C.Structure):
     _fields_ = [("n_rays", C.c_int64), ("n_rays_skipped", C.c_int64), ("n_steps", C.c_int64), ("n_voxels_crossed", C.c_int64),
                 ("n_voxels_hit", C.c_int64), ("n_removed", C.c_int64), ("n_points_removed", C.c_int64)]
@@ -328,6 +344,8 @@ ABI_SYMBOLS = [
     "ndt_export_source_distributions", "ndt_eval_derivatives_d2d", "ndt_align_d2d",
     "ndt_set_source_times", "ndt_set_source_times_device", "ndt_source_times_info", "ndt_eval_derivatives_ct", "ndt_align_ct",
     "ndt_transform_source_ct", "ndt_transform_source_ct_device",
+    "ndt_gicp_default_params", "ndt_gicp_set_params", "ndt_gicp_get_params", "ndt_gicp_export_neighbours",
+    "ndt_gicp_export_covariances", "ndt_gicp_pair", "ndt_gicp_export_pairs", "ndt_eval_derivatives_gicp", "ndt_align_gicp",
     "ndt_scan_context_default_params", "ndt_scan_context_set_params", "ndt_scan_context_get_params",
     "ndt_scan_context_sector_table", "ndt_scan_context", "ndt_scan_context_device", "ndt_scan_context_keyframe",
     "ndt_scan_context_bank_put", "ndt_scan_context_bank_get", "ndt_scan_context_bank_erase", "ndt_scan_context_bank_clear",
@@ -482,6 +500,20 @@ def lib():
         L.ndt_align_ct.argtypes = [vp, dp, fp, C.POINTER(Result)]
         L.ndt_transform_source_ct.argtypes = [vp, dp, dp, C.c_int, vp, C.c_size_t]
         L.ndt_transform_source_ct_device.argtypes = [vp, dp, dp, C.c_int, vp, vp, vp, C.c_size_t]
+        gpp = C.POINTER(GicpParams)
+        L.ndt_gicp_default_params.restype = None
+        L.ndt_gicp_default_params.argtypes = [gpp]
+        L.ndt_gicp_set_params.argtypes = [vp, gpp]
+        L.ndt_gicp_get_params.argtypes = [vp, gpp]
+        L.ndt_gicp_export_neighbours.argtypes = [vp, C.c_int, vp, vp, C.c_size_t]
+        L.ndt_gicp_export_neighbours.restype = C.c_int64
+        L.ndt_gicp_export_covariances.argtypes = [vp, C.c_int, dp, dp, dp, C.c_size_t]
+        L.ndt_gicp_export_covariances.restype = C.c_int64
+        L.ndt_gicp_pair.argtypes = [vp, dp, C.POINTER(C.c_int64)]
+        L.ndt_gicp_export_pairs.argtypes = [vp, vp, vp, C.c_size_t]
+        L.ndt_gicp_export_pairs.restype = C.c_int64
+        L.ndt_eval_derivatives_gicp.argtypes = [vp, dp, C.c_int, C.c_int, dp]
+        L.ndt_align_gicp.argtypes = [vp, fp, C.POINTER(Result), C.POINTER(GicpInfo)]
         scp, i64 = C.POINTER(ScanContextParams), C.c_int64
         L.ndt_scan_context_default_params.restype = None
         L.ndt_scan_context_default_params.argtypes = [scp]
@@ -2170,6 +2202,130 @@ def transformSourceCTDevice(ndt, begin, end, d_x, d_y, d_z, cap, frame=0):
     if frame not in (0, 1) or not d_x or not d_y or not d_z or int(cap) < 0:
         raise ValueError("frame must be 0 or 1 and the three device pointers are needed")
     ndt._check(lib().ndt_transform_source_ct_device(ndt._h, _dp(b), _dp(e), int(frame), d_x, d_y, d_z, int(cap)))
+
+
+# --- GICP: the point source registered to the target's kept points, plane to plane (ndt_gicp_*, ndt_eval_derivatives_gicp,
+# ndt_align_gicp).  Functions on an engine, as above; their first parameter is named `engine`, not `ndt`: the API
+# fuzz's vocabulary (tests/test_api_sequences_cpu.py) is every function whose first parameter is `ndt`, and these join it
+# in the change that extends the fuzz.  `which`: "source" / "target" (or GICP_SOURCE / GICP_TARGET). ---
+def _gicp_which(which):
+    w = {"source": GICP_SOURCE, "target": GICP_TARGET, GICP_SOURCE: GICP_SOURCE, GICP_TARGET: GICP_TARGET}.get(which)
+    if w is None:
+        raise ValueError("which must be 'source' or 'target'")
+    return w
+
+
+def _gicp_cloud_size(engine, which):
+    n = lib().ndt_gicp_export_neighbours(engine._h, which, None, None, 1 << 62)   # (no output: the size alone)
+    if n < 0:
+        engine._check(int(n))
+    return int(n)
+
+
+def gicpDefaultParams():
+    p = GicpParams()
+    lib().ndt_gicp_default_params(C.byref(p))
+    return p
+
+
+def gicpGetParams(engine):
+    """dict of the engine's ndt_gicp_params"""
+    p = GicpParams()
+    engine._check(lib().ndt_gicp_get_params(engine._h, C.byref(p)))
+    return {k: getattr(p, k) for k, _ in GicpParams._fields_}
+
+
+def gicpSetParams(engine, **kw):
+    """Changes the named fields of the engine's ndt_gicp_params (k_neighbours, max_neighbour_distance, covariance_epsilon,
+    max_correspondence_distance, transformation_epsilon, max_iterations, max_inner_iterations); returns them all."""
+    names = [k for k, _ in GicpParams._fields_]
+    for k in kw:
+        if k not in names:
+            raise ValueError("unknown GICP parameter %r" % k)
+    ints = ("k_neighbours", "max_iterations", "max_inner_iterations")
+    for k, v in kw.items():
+        if k in ints and (isinstance(v, bool) or int(v) != v):
+            raise ValueError("%s must be an integer" % k)
+        if np.ndim(v) != 0 or np.isnan(float(v)):
+            raise ValueError("%s must be a number" % k)
+    p = GicpParams()
+    if engine._h is None:
+        raise ValueError("the engine has no handle")
+    engine._check(lib().ndt_gicp_get_params(engine._h, C.byref(p)))
+    for k, v in kw.items():
+        setattr(p, k, int(v) if k in ints else float(v))
+    engine._check(lib().ndt_gicp_set_params(engine._h, C.byref(p)))
+    return gicpGetParams(engine)
+
+
+def gicpNeighbours(engine, which="source"):
+    """(idx [n, k] int32 in (d2, index) order, -1 padded; n_found [n] int32) of the source's or the target's points"""
+    w = _gicp_which(which)
+    n, k = _gicp_cloud_size(engine, w), gicpGetParams(engine)["k_neighbours"]
+    idx, found = np.full((n, k), -1, np.int32), np.zeros(n, np.int32)
+    got = lib().ndt_gicp_export_neighbours(engine._h, w, idx.ctypes.data, found.ctypes.data, n)
+    if got < 0:
+        engine._check(int(got))
+    return idx[:got], found[:got]
+
+
+def gicpCovariances(engine, which="source"):
+    """dict(mean [n, 3], raw_cov6 [n, 6], cov6 [n, 6] (xx, xy, xz, yy, yz, zz), cov [n, 3, 3]); NaN rows for points
+    without a covariance"""
+    w = _gicp_which(which)
+    n = _gicp_cloud_size(engine, w)
+    mean, raw, cov6 = np.zeros((n, 3)), np.zeros((n, 6)), np.zeros((n, 6))
+    got = lib().ndt_gicp_export_covariances(engine._h, w, _dp(mean), _dp(raw), _dp(cov6), n)
+    if got < 0:
+        engine._check(int(got))
+    mean, raw, cov6 = mean[:got], raw[:got], cov6[:got]
+    return dict(mean=mean, raw_cov6=raw, cov6=cov6, cov=cov6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, 3, 3))
+
+
+def gicpPair(engine, pose6):
+    """ndt_gicp_pair: freezes the nearest-point pairs at `pose6` [x, y, z, roll, pitch, yaw]; returns their number"""
+    p = _pose6(pose6, "pose6")
+    n = C.c_int64(0)
+    engine._check(lib().ndt_gicp_pair(engine._h, _dp(p), C.byref(n)))
+    return int(n.value)
+
+
+def gicpPairs(engine):
+    """(target_index [n] int32, -1 = none; d2 [n] float32, +inf for none) of the frozen pairs, in source order"""
+    n = engine.sourceSize()
+    idx, d2 = np.full(n, -1, np.int32), np.full(n, np.inf, np.float32)
+    got = lib().ndt_gicp_export_pairs(engine._h, idx.ctypes.data, d2.ctypes.data, n)
+    if got < 0:
+        engine._check(int(got))
+    return idx[:got], d2[:got]
+
+
+def evalDerivativesGICP(engine, poses6, compute_hessian=True, raw=False):
+    """The GICP score (-sum q / 2), gradient and Hessian over the frozen pairs at K poses (K x 6): a list of dicts as
+    evalDerivatives gives them; raw=True: the K x 32 packed words."""
+    p = np.ascontiguousarray(np.atleast_2d(poses6), dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 6 or not np.isfinite(p).all():
+        raise ValueError("poses6 must be K x 6 and finite")
+    K = p.shape[0]
+    out = np.zeros((K, EVAL_WORDS))
+    engine._check(lib().ndt_eval_derivatives_gicp(engine._h, _dp(p), K, int(bool(compute_hessian)), _dp(out)))
+    return out if raw else [unpack_eval(out[k]) for k in range(K)]
+
+
+def alignGICP(engine, guess=None):
+    """ndt_align_gicp from `guess` (4x4, default identity).  Returns (final 4x4, result dict as getResult() gives it with
+    `gicp`: outer / inner iterations, evaluations, pairs, points without a covariance); getResult() keeps reporting the
+    last align()."""
+    g = np.asarray(np.eye(4) if guess is None else guess, dtype=np.float64)
+    if g.shape != (4, 4) or not np.isfinite(g).all():
+        raise ValueError("guess must be a finite 4 x 4 matrix")
+    g = _colmajor(g)
+    r, info = Result(), GicpInfo()
+    engine._check(lib().ndt_align_gicp(engine._h, _fp(g), C.byref(r), C.byref(info)))
+    d = result_to_dict(r)
+    d["iteration_num"] = d["iterations"]
+    d["gicp"] = {k: getattr(info, k) for k, _ in GicpInfo._fields_}
+    return d["T"], d
 
 
 # --- Scan Context place recognition over the keyframe archive (ndt_scan_context*; DESIGN 7m).  Functions on an engine, as

@@ -16,7 +16,10 @@
 //                      and align against the target's leaves (k_d2d_* kernels)
 //   ndt_ct.hip         continuous-time registration: per-point times of the point source, the evaluation with one pose per
 //                      point, its align and the deskewed scan under a result (k_ct_* kernels)
-//   ndt_eval_rows.hip  what those two evaluations share behind their kernels: the fixed-order sum of block rows, the host
+//   ndt_gicp.hip       generalised ICP: the exact k nearest neighbours of every point of a cloud, the point covariances made
+//                      from them, the frozen nearest-point pairs, the plane-to-plane evaluation over them and the two-level
+//                      align (k_gicp_* kernels); the index it searches is the fitness index (ndt_fitness.hip, ndt_fit_device.h)
+//   ndt_eval_rows.hip  what those evaluations share behind their kernels: the fixed-order sum of block rows, the host
 //                      driver, the support check, the finished-words repack, the align wrapper
 //   ndt_scan_context.hip  Scan Context place recognition: a scan's rings x sectors descriptor, the descriptor bank beside
 //                      the keyframe archive and the all-shifts match against it (k_sc_* kernels)
@@ -310,7 +313,38 @@ struct CtBufs {
   }
 };
 
-// The rows of a lane-per-item evaluation (lane_eval_rows, ndt_eval_rows.hip).  One instance serves D2D and CT: either
+// GICP (ndt_gicp.hip).  One cloud's side: the neighbour lists and the covariances derived from them, cached until the cloud
+// or the rule (k, distance cap, epsilon) changes.  The source's go with every call that replaces or re-declares the source
+// (the list the CT times follow), the target's are tagged with TargetState::gen() like FitIndex.
+struct GicpCloud {
+  bool valid = false;
+  uint64_t gen = 0;                  // target side: TargetState::gen() of the target they were derived from
+  size_t n = 0;                      // points of the cloud, rows of everything below (input order)
+  int k = 0;                         // row length of nbr
+  int64_t n_without = 0;             // points without a covariance
+  DevBuf<int32_t> nbr, nfound;       // n x k neighbour indices (-1 padded), neighbours found
+  DevBuf<double> mean, raw;          // n x 3 neighbourhood mean, n x 6 raw covariance (NaN rows without a covariance)
+  DevBuf<double> gauss;              // n x 9 as the evaluation reads it: {the point itself x y z, regularised cov xx xy xz yy yz zz}
+  void release() { nbr.release(); nfound.release(); mean.release(); raw.release(); gauss.release(); valid = false; n = 0; }
+};
+struct GicpBufs {
+  ndt_gicp_params prm{20, INFINITY, 1e-3, 5.0, 1e-4, 64, 20};
+  GicpCloud src, tgt;
+  FitIndex sidx;                     // the source's own point index (the target's is the handle's `fit`)
+  DevBuf<int> work;                  // [0] unresolved queries of a search's pass 1, then their indices; [1 + n]: points without a covariance
+  PinBuf<int> work_h;
+  // the frozen pairs: per source point the target point's input index (-1: none) and the f32 d^2
+  DevBuf<int32_t> pair;
+  DevBuf<float> pd2;
+  bool pairs_valid = false;
+  uint64_t pairs_gen = 0;            // TargetState::gen() of the target they point into
+  int64_t n_pairs = 0;
+  void drop_pairs() { pairs_valid = false; n_pairs = 0; }
+  void drop_source() { src.valid = false; sidx.valid = false; drop_pairs(); }
+  void release() { src.release(); tgt.release(); sidx.release(); work.release(); work_h.release(); pair.release(); pd2.release(); drop_pairs(); }
+};
+
+// The rows of a lane-per-item evaluation (lane_eval_rows, ndt_eval_rows.hip).  One instance serves D2D, CT and GICP: each
 // evaluation is awaited before it returns.
 struct EvalRowBufs {
   DevBuf<double> rows, out;          // per-block rows of K poses, their K x EV_WORDS sums
@@ -473,7 +507,8 @@ struct ndt_handle {
   ScanContextBufs sc;                // Scan Context: parameters, sector table, descriptor bank (ndt_scan_context.hip)
   D2dBufs d2d;                       // the distribution source of ndt_*_d2d and the target's leaves for it (ndt_d2d.hip)
   CtBufs ct;                         // the source's times and the scratch of ndt_*_ct (ndt_ct.hip)
-  EvalRowBufs evrows;                // the block rows and sums of a D2D or CT evaluation (ndt_eval_rows.hip)
+  GicpBufs gicp;                     // GICP's parameters, neighbour lists, covariances and frozen pairs (ndt_gicp.hip)
+  EvalRowBufs evrows;                // the block rows and sums of a D2D, CT or GICP evaluation (ndt_eval_rows.hip)
   // the same points in block order of the target grid (see sort_source_by_blocks); valid until
   // the source or the target changes
   DevBuf<float> ox, oy, oz;
@@ -794,8 +829,13 @@ int map_import_checks(ndt_handle* h, float leaf, const double* moments9, size_t 
 int map_import_tail(ndt_handle* h, const int32_t* d_count, const float* d_sums, const double* d_mom, size_t n);
 int map_merge_records(ndt_handle* h, const MapTable& t, unsigned long long* d_nvox, const int32_t* d_count, const float* d_sums,
                       const double* d_mom, size_t n);
-// ndt_eval_rows.hip: what the lane-per-item evaluations (D2D, CT) share behind their kernels.  `what` is "D2D" or "CT"
-// and heads the error texts.
+// ndt_fitness.hip: the point-level index `f` (re)built over the SoA cloud x / y / z (device memory, n points), enqueued
+// on the engine's stream behind one host wait; `what` heads the error texts.  fit_build: the handle's `fit` over the
+// engine's copy of the target, lazily (the target is settled).
+int fit_build_cloud(ndt_handle* h, FitIndex& f, const float* x, const float* y, const float* z, size_t n, const char* what);
+int fit_build(ndt_handle* h);
+// ndt_eval_rows.hip: what the lane-per-item evaluations (D2D, CT, GICP) share behind their kernels.  `what` is "D2D", "CT"
+// or "GICP" and heads the error texts.
 // k_eval_rows_sum on rows of K poses x nb blocks x EV_WORDS -> out (K x EV_WORDS), enqueued on s
 void launch_eval_rows_sum(const double* rows, int nb, int K, double* out, hipStream_t s);
 // what such an evaluation can work with: one rank, DIRECT1 / DIRECT7, a single grid -- and a target to evaluate against
@@ -807,7 +847,9 @@ int lane_eval_rows(ndt_handle* h, const char* what, int nb, int K, const std::fu
 void finish_words(ndt_handle* h, const double pose6[6], bool need_h, double* w);
 // newton_align over an evaluation of n_items items: raw(pose6, need_h, words) fills one pose's raw sums
 using LaneEvalFn = std::function<int(const double*, bool, double*)>;
-int lane_align(ndt_handle* h, int64_t n_items, const float guess[16], const LaneEvalFn& raw, ndt_result* out);
+// (prm: the parameters of the loop and of finish_eval; null: the handle's)
+int lane_align(ndt_handle* h, int64_t n_items, const float guess[16], const LaneEvalFn& raw, ndt_result* out,
+               const ndt_params* prm = nullptr);
 void fill_pose_consts(const double p[6], const float T[16], PoseConsts* pc);
 unsigned long long process_item_salt();
 EvalConsts make_eval_consts(const ndt_handle* h, bool need_h);

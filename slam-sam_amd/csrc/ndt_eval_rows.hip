@@ -1,5 +1,5 @@
 // ndt_eval_rows.hip -- what the lane-per-item evaluations share behind their kernels (see ndt_engine.h): D2D
-// (ndt_d2d.hip) and continuous time (ndt_ct.hip) each give a lane one item and write one row of EV_WORDS sums per block
+// (ndt_d2d.hip), continuous time (ndt_ct.hip) and GICP (ndt_gicp.hip) each give a lane one item and write one row of EV_WORDS sums per block
 // (eval_block_row, ndt_evalrows_device.h).  Here:
 //   k_eval_rows_sum        a pose's rows added in a fixed order, one block per pose
 //   lane_eval_rows         the host driver: buffers, one launch per pose through the caller's callback, the sum, the copy
@@ -80,16 +80,18 @@ void finish_words(ndt_handle* h, const double pose6[6], bool need_h, double* w) 
   }
 }
 
-int lane_align(ndt_handle* h, int64_t n_items, const float guess[16], const LaneEvalFn& raw, ndt_result* out) {
-  EvalFn fn = [h, &raw](const double* p, const float*, bool need_h, Eval* e) {
+int lane_align(ndt_handle* h, int64_t n_items, const float guess[16], const LaneEvalFn& raw, ndt_result* out,
+               const ndt_params* prm) {
+  const ndt_params& pr = prm ? *prm : h->prm;
+  EvalFn fn = [h, &raw, &pr](const double* p, const float*, bool need_h, Eval* e) {
     double words[EV_WORDS];
     if (int r = raw(p, need_h, words)) return r;
     unpack_eval(words, e);
-    finish_eval(h->prm, h->have_reg ? h->reg_pose : nullptr, p, need_h, e);
+    finish_eval(pr, h->have_reg ? h->reg_pose : nullptr, p, need_h, e);
     return 0;
   };
   // the product path of ndt_align (the Hessian in every trial, the memo on); no iteration history
-  const int rc = newton_align(h->prm, n_items, guess, fn, out, /*hessian_in_trials=*/true);
+  const int rc = newton_align(pr, n_items, guess, fn, out, /*hessian_in_trials=*/true);
   h->keepwarm.touch();
   return rc;
 }

@@ -13,6 +13,7 @@
 // fixed-order f64 reduction per pose (per-block partial sums in a slab, added on the host in block order): no float
 // atomics, bit-reproducible.
 #include "ndt_engine.h"
+#include "ndt_fit_device.h"
 
 namespace ndt {
 namespace engine {
@@ -22,17 +23,6 @@ constexpr int FIT_THREADS = 256;
 constexpr int FIT_BOUNDS_BLOCKS = 256;
 constexpr int FIT_REDUCE_CHUNK = 2048;       // points per reduction block (8 per lane)
 constexpr int FIT_SHELL_BLOCKS = 1024;       // pass 2: grid-stride over the compacted entries
-constexpr uint32_t FIT_EMPTY = 0xffffffffu;
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-  return isfinite(x) && isfinite(y) && isfinite(z);
-}
-
-// (murmur3's finaliser: neighbouring cells -- keys that differ by 1, dims0 or dims0 * dims1 -- land far apart)
-__device__ __forceinline__ uint32_t fit_hash(uint32_t key, uint32_t mask) {
-  key ^= key >> 16; key *= 0x85ebca6bu; key ^= key >> 13; key *= 0xc2b2ae35u; key ^= key >> 16;
-  return key & mask;
-}
 
 __global__ void __launch_bounds__(FIT_THREADS) k_fit_bounds(const float* __restrict__ x, const float* __restrict__ y,
                                                             const float* __restrict__ z, int n, float* __restrict__ bslab,
@@ -70,13 +60,6 @@ __global__ void __launch_bounds__(FIT_THREADS) k_fit_bounds(const float* __restr
   }
 }
 
-// cell coordinate of u = (p - lo) * inv_c on one axis, clamped to [-1, dims] (a point outside the box searches from
-// the box's face; the lower bounds below use u itself, so the clamp never costs exactness)
-__device__ __forceinline__ int fit_cell(float u, int dims) {
-  const float f = fminf(fmaxf(floorf(u), -1.0f), (float)dims);
-  return (int)f;
-}
-
 __global__ void __launch_bounds__(FIT_THREADS) k_fit_keys(const float* __restrict__ x, const float* __restrict__ y,
                                                           const float* __restrict__ z, int n, FitGeom g,
                                                           uint32_t* __restrict__ keys) {
@@ -88,12 +71,13 @@ __global__ void __launch_bounds__(FIT_THREADS) k_fit_keys(const float* __restric
     const int cx = min(max(fit_cell((px - g.lo[0]) * g.inv_c, g.dims[0]), 0), g.dims[0] - 1);
     const int cy = min(max(fit_cell((py - g.lo[1]) * g.inv_c, g.dims[1]), 0), g.dims[1] - 1);
     const int cz = min(max(fit_cell((pz - g.lo[2]) * g.inv_c, g.dims[2]), 0), g.dims[2] - 1);
-    key = (uint32_t)cx + (uint32_t)g.dims[0] * ((uint32_t)cy + (uint32_t)g.dims[1] * (uint32_t)cz);
+    key = fit_key(g, cx, cy, cz);
   }
   keys[i] = key;
 }
 
-// the finite points in cell order as float4; the first point of every cell claims a hash slot and records itself
+// the finite points in cell order as float4, w = the point's input index (its bits); the first point of every cell claims
+// a hash slot and records itself
 __global__ void __launch_bounds__(FIT_THREADS) k_fit_gather(const float* __restrict__ x, const float* __restrict__ y,
                                                             const float* __restrict__ z, const uint32_t* __restrict__ sorted_keys,
                                                             const uint32_t* __restrict__ sorted_vals, int nf, uint32_t mask,
@@ -101,22 +85,11 @@ __global__ void __launch_bounds__(FIT_THREADS) k_fit_gather(const float* __restr
   const int i = blockIdx.x * FIT_THREADS + threadIdx.x;
   if (i >= nf) return;
   const uint32_t key = sorted_keys[i], idx = sorted_vals[i];
-  pts[i] = make_float4(x[idx], y[idx], z[idx], 0.0f);
+  pts[i] = make_float4(x[idx], y[idx], z[idx], __int_as_float((int)idx));
   if (i > 0 && sorted_keys[i - 1] == key) return;
   uint32_t slot = fit_hash(key, mask);
   for (;;) {   // (the table has at least twice as many slots as there are cells)
     if (atomicCAS(&tab[4 * (size_t)slot], FIT_EMPTY, key) == FIT_EMPTY) { tab[4 * (size_t)slot + 1] = (uint32_t)i; return; }
-    slot = (slot + 1) & mask;
-  }
-}
-
-__device__ __forceinline__ int fit_find(const uint4* __restrict__ tab, uint32_t mask, uint32_t key, uint32_t* first,
-                                        uint32_t* end) {
-  uint32_t slot = fit_hash(key, mask);
-  for (;;) {
-    const uint4 e = tab[slot];
-    if (e.x == key) { *first = e.y; *end = e.z; return 1; }
-    if (e.x == FIT_EMPTY) return 0;
     slot = (slot + 1) & mask;
   }
 }
@@ -133,12 +106,6 @@ __global__ void __launch_bounds__(FIT_THREADS) k_fit_ends(const uint32_t* __rest
   tab[4 * (size_t)slot + 2] = (uint32_t)(i + 1);
 }
 
-struct FitQuery {
-  float qx, qy, qz;    // the transformed point (ndt_transform_source's arithmetic)
-  float u[3];          // (q - lo) * inv_c
-  int k[3];            // its cell, clamped to [-1, dims]
-};
-
 __device__ __forceinline__ bool fit_transform(const float* __restrict__ P, float x, float y, float z, const FitGeom& g,
                                               FitQuery* q) {
   // exactly k_transform (ndt_derivs.hip): same operations, same order, -ffp-contract=off
@@ -146,19 +113,14 @@ __device__ __forceinline__ bool fit_transform(const float* __restrict__ P, float
   q->qy = P[3] * x + (P[4] * y + (P[5] * z + P[10]));
   q->qz = P[6] * x + (P[7] * y + (P[8] * z + P[11]));
   if (!finite3(q->qx, q->qy, q->qz)) return false;
-  q->u[0] = (q->qx - g.lo[0]) * g.inv_c;
-  q->u[1] = (q->qy - g.lo[1]) * g.inv_c;
-  q->u[2] = (q->qz - g.lo[2]) * g.inv_c;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) q->k[a] = fit_cell(q->u[a], g.dims[a]);
+  fit_locate(g, q);
   return true;
 }
 
 __device__ __forceinline__ void fit_scan_cell(const float4* __restrict__ pts, const uint4* __restrict__ tab,
                                               const FitGeom& g, int cx, int cy, int cz, const FitQuery& q, float* best) {
-  const uint32_t key = (uint32_t)cx + (uint32_t)g.dims[0] * ((uint32_t)cy + (uint32_t)g.dims[1] * (uint32_t)cz);
   uint32_t first, end;
-  if (!fit_find(tab, g.hash_mask, key, &first, &end)) return;
+  if (!fit_find(tab, g.hash_mask, fit_key(g, cx, cy, cz), &first, &end)) return;
   float b = *best;
   for (uint32_t j = first; j < end; ++j) {
     const float4 p = pts[j];
@@ -167,37 +129,6 @@ __device__ __forceinline__ void fit_scan_cell(const float4* __restrict__ pts, co
     b = fminf(b, d2);
   }
   *best = b;
-}
-
-// Squared lower bound on the distance from q to any target point in a cell OUTSIDE the scanned box
-// [k - r, k + r]^3 (clipped to the grid); +INF when the scanned box covers the grid.  A point of such a cell lies
-// beyond one face of the scanned box on some axis a (gap_a) and inside the bounding box on every axis (dG_b), so its
-// distance is at least sqrt(max(gap_a, dG_a)^2 + sum_{b != a} dG_b^2); the bound is the minimum over the faces that
-// still have cells behind them.  Everything is in cell units, shrunk by a slack that covers the f32 rounding of the
-// cell classification (relative ~1.2e-7 of |u|, on the target's side and on the query's) and of d^2 itself, so a
-// closer point can never hide behind a mis-classified cell at km-scale coordinates.
-__device__ __forceinline__ float fit_lower_bound2(const FitQuery& q, const FitGeom& g, int r) {
-  float dG[3], slack[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    slack[a] = 1e-6f * (fabsf(q.u[a]) + (float)g.dims[a] + (float)r + 2.0f);
-    dG[a] = fmaxf(fmaxf(-q.u[a], q.u[a] - (float)g.dims[a]) - slack[a], 0.0f);
-  }
-  const float s2 = dG[0] * dG[0] + dG[1] * dG[1] + dG[2] * dG[2];
-  float lb2 = INFINITY;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float rest = s2 - dG[a] * dG[a];
-    if (q.k[a] - r > 0) {
-      const float gap = fmaxf(fmaxf(q.u[a] - (float)(q.k[a] - r) - slack[a], dG[a]), 0.0f);
-      lb2 = fminf(lb2, fmaxf(rest, 0.0f) + gap * gap);
-    }
-    if (q.k[a] + r < g.dims[a] - 1) {
-      const float gap = fmaxf(fmaxf((float)(q.k[a] + r + 1) - q.u[a] - slack[a], dG[a]), 0.0f);
-      lb2 = fminf(lb2, fmaxf(rest, 0.0f) + gap * gap);
-    }
-  }
-  return lb2 * (g.c * g.c) * (1.0f - 4e-6f);
 }
 
 // verdict of a point after its box of radius r: 1 = done (d2 final), 0 = search on
@@ -220,12 +151,7 @@ __global__ void __launch_bounds__(FIT_THREADS) k_fit_query(const float* __restri
   FitQuery q;
   if (!fit_transform(poses + 12 * blockIdx.y, sx[i], sy[i], sz[i], g, &q)) { dist[e] = NAN; return; }
   float best = INFINITY;
-  const int z0 = max(q.k[2] - 1, 0), z1 = min(q.k[2] + 1, g.dims[2] - 1);
-  const int y0 = max(q.k[1] - 1, 0), y1 = min(q.k[1] + 1, g.dims[1] - 1);
-  const int x0 = max(q.k[0] - 1, 0), x1 = min(q.k[0] + 1, g.dims[0] - 1);
-  for (int cz = z0; cz <= z1; ++cz)
-    for (int cy = y0; cy <= y1; ++cy)
-      for (int cx = x0; cx <= x1; ++cx) fit_scan_cell(pts, tab, g, cx, cy, cz, q, &best);
+  fit_walk_box(q, g, [&](int cx, int cy, int cz) { fit_scan_cell(pts, tab, g, cx, cy, cz, q, &best); });
   float d2;
   if (fit_settle(best, fit_lower_bound2(q, g, 1), max_range, &d2)) { dist[e] = d2; return; }
   dist[e] = best;                      // (the best so far; pass 2 goes on from it)
@@ -246,22 +172,9 @@ __global__ void __launch_bounds__(FIT_THREADS) k_fit_shells(const float* __restr
     FitQuery q;
     fit_transform(poses + 12 * k, sx[i], sy[i], sz[i], g, &q);   // (finite: pass 1 queued it)
     float best = dist[e], d2 = best;
-    const int rmax = max(g.dims[0], max(g.dims[1], g.dims[2])) + 1;
+    const int rmax = fit_rmax(g);
     for (int r = 2; r <= rmax; ++r) {
-      const int z0 = max(q.k[2] - r, 0), z1 = min(q.k[2] + r, g.dims[2] - 1);
-      const int y0 = max(q.k[1] - r, 0), y1 = min(q.k[1] + r, g.dims[1] - 1);
-      const int x0 = max(q.k[0] - r, 0), x1 = min(q.k[0] + r, g.dims[0] - 1);
-      for (int cz = z0; cz <= z1; ++cz) {
-        const bool zface = cz == q.k[2] - r || cz == q.k[2] + r;
-        for (int cy = y0; cy <= y1; ++cy) {
-          if (zface || cy == q.k[1] - r || cy == q.k[1] + r) {
-            for (int cx = x0; cx <= x1; ++cx) fit_scan_cell(pts, tab, g, cx, cy, cz, q, &best);
-          } else {
-            if (q.k[0] - r >= 0) fit_scan_cell(pts, tab, g, q.k[0] - r, cy, cz, q, &best);
-            if (q.k[0] + r <= g.dims[0] - 1) fit_scan_cell(pts, tab, g, q.k[0] + r, cy, cz, q, &best);
-          }
-        }
-      }
+      fit_walk_shell(q, g, r, [&](int cx, int cy, int cz) { fit_scan_cell(pts, tab, g, cx, cy, cz, q, &best); });
       if (fit_settle(best, fit_lower_bound2(q, g, r), max_range, &d2)) break;
     }
     dist[e] = d2;
@@ -302,14 +215,13 @@ __global__ void __launch_bounds__(FIT_THREADS) k_fit_reduce(const float* __restr
 
 unsigned grid1(size_t n) { return (unsigned)((n + FIT_THREADS - 1) / FIT_THREADS); }
 
-// Lazily (re)builds the index over the engine's copy of the target.  Called with the target settled.
-int fit_build(ndt_handle* h) {
-  FitIndex& f = h->fit;
-  if (f.valid && f.gen == h->tgt.gen()) return NDT_OK;
+}  // namespace
+
+// (Re)builds the index `f` over the SoA cloud x / y / z (device memory, n points) on the engine's stream; `what` heads
+// the error texts.  The caller tags the index (gen) when that is how it is kept fresh.
+int fit_build_cloud(ndt_handle* h, FitIndex& f, const float* x, const float* y, const float* z, size_t n, const char* what) {
   f.valid = false;
   hipStream_t s = h->stream;
-  const size_t n = h->tgt.cloud_n();
-  const float *x = h->tx.p, *y = h->ty.p, *z = h->tz.p;
   // bounds of the finite points: per-block rows, finished on the host (one wait: the geometry sizes everything else)
   const int nb = (int)std::min<size_t>(FIT_BOUNDS_BLOCKS, grid1(n));
   HIP_TRY(h, f.bslab.ensure(6 * (size_t)nb));
@@ -331,12 +243,12 @@ int fit_build(ndt_handle* h) {
       hi[a] = std::max(hi[a], f.bslab_h.h[6 * b + 3 + a]);
     }
   }
-  if (nf == 0) return fail(h, NDT_ERR_NO_TARGET, "fitness: the target has no finite point");
+  if (nf == 0) return fail(h, NDT_ERR_NO_TARGET, std::string(what) + " has no finite point");
   // cell edge: the grid resolution (a cell then holds about what a voxel holds), grown until the bounding box has
   // fewer than 2^30 cells (the keys are 32-bit and the radix sort sorts 32-bit keys; the table never sees empty cells)
   FitGeom g{};
   for (int a = 0; a < 3; ++a)
-    if (!std::isfinite(hi[a] - lo[a])) return fail(h, NDT_ERR_UNSUPPORTED, "fitness: the target's extent overflows f32");
+    if (!std::isfinite(hi[a] - lo[a])) return fail(h, NDT_ERR_UNSUPPORTED, std::string(what) + "'s extent overflows f32");
   float c = h->prm.resolution;
   for (;;) {
     const float inv_c = 1.0f / c;
@@ -375,10 +287,20 @@ int fit_build(ndt_handle* h) {
   hipLaunchKernelGGL(k_fit_ends, dim3(grid1((size_t)nf)), dim3(FIT_THREADS), 0, s, sk, (int)nf, g.hash_mask, f.tab.p);
   HIP_TRY(h, hipGetLastError());
   f.g = g;
-  f.gen = h->tgt.gen();
   f.valid = true;
   return NDT_OK;
 }
+
+// Lazily (re)builds the index over the engine's copy of the target.  Called with the target settled.
+int fit_build(ndt_handle* h) {
+  FitIndex& f = h->fit;
+  if (f.valid && f.gen == h->tgt.gen()) return NDT_OK;
+  if (int rc = fit_build_cloud(h, f, h->tx.p, h->ty.p, h->tz.p, h->tgt.cloud_n(), "fitness: the target")) return rc;
+  f.gen = h->tgt.gen();
+  return NDT_OK;
+}
+
+namespace {
 
 // argument checks that need no device, then the state checks of the C-ABI's table
 int fit_ready(ndt_handle* h) {

@@ -164,6 +164,7 @@ int ndt_destroy(ndt_handle* h) {
   h->fit.release();
   h->d2d.release();
   h->ct.release();
+  h->gicp.release();
   h->evrows.release();
   h->sc.release();
   h->compact.release(); h->knots.release();

@@ -580,6 +580,7 @@ int ndt_set_source(ndt_handle* h, const float* xyz, size_t n, size_t stride_byte
   h->vx = h->vy = h->vz = nullptr;
   h->n_src = 0;
   h->ct.n = 0;   // the times go with the source they were set for
+  h->gicp.drop_source();
   // asynchronous hand-off: on the source lane's own stream, so that its copies run beside the target's build; the
   // engine's streams are ordered behind it by the first call that evaluates (settle_source)
   const bool async = h->handoff_mode == NDT_HANDOFF_ASYNC;
@@ -601,6 +602,7 @@ int ndt_set_source_soa(ndt_handle* h, const float* x, const float* y, const floa
   h->vx = h->vy = h->vz = nullptr;
   h->n_src = 0;
   h->ct.n = 0;   // the times go with the source they were set for
+  h->gicp.drop_source();
   const bool async = h->handoff_mode == NDT_HANDOFF_ASYNC;
   rc = source_behind_target_transfer(h, async);
   if (rc) return rc;
@@ -631,6 +633,7 @@ int ndt_set_source_device(ndt_handle* h, const float* dx, const float* dy, const
   h->n_src = n;
   h->src_sorted = false;
   h->ct.n = 0;
+  h->gicp.drop_source();
   return NDT_OK;
 }
 
@@ -644,6 +647,7 @@ int ndt_set_source_device_view(ndt_handle* h, const float* dx, const float* dy, 
   h->n_src = n;
   h->src_sorted = false;
   h->ct.n = 0;
+  h->gicp.drop_source();
   return NDT_OK;
 }
 
@@ -653,6 +657,7 @@ int ndt_source_changed(ndt_handle* h) {
   if (!h) return NDT_ERR_INVALID_ARG;
   h->src_sorted = false;
   h->ct.n = 0;   // rewritten points: the times of the previous ones do not describe them
+  h->gicp.drop_source();
   return NDT_OK;
 }
 

@@ -19,6 +19,7 @@ ndt_handle::Keyframe& keyframe_claim(ndt_handle* h, int64_t id, size_t n) {
     h->vx = h->vy = h->vz = nullptr;
     h->n_src = 0;
     h->ct.n = 0;
+    h->gicp.drop_source();
   }
   return kf;
 }
@@ -206,6 +207,7 @@ int ndt_keyframe_erase(ndt_handle* h, int64_t id) {
     h->vx = h->vy = h->vz = nullptr;
     h->n_src = 0;
     h->ct.n = 0;
+    h->gicp.drop_source();
   }
   if (h->keyframe_pool.size() < 4 && it->second.x.p) {
     // (whatever still reads these arrays was enqueued on the engine's stream before this call; the next put writes
