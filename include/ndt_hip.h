@@ -1184,6 +1184,69 @@ int64_t ndt_gicp_export_pairs(ndt_handle* h, int32_t* target_index, float* d2, s
 int     ndt_eval_derivatives_gicp(ndt_handle* h, const double* poses6, int K, int compute_hessian, double* out);
 int     ndt_align_gicp(ndt_handle* h, const float guess_colmajor[16], ndt_result* out, ndt_gicp_info* info);
 
+/* Voxelised GICP (VGICP; Koide, Yokozuka, Oishi & Banno, ICRA 2021): GICP's plane-to-plane cost with ONE AGGREGATE PER
+ * TARGET VOXEL as the partner of a source point -- the mean of the voxel's points and the mean of their GICP covariances,
+ * found by a voxel lookup.  There is no nearest-point search at evaluation time, there are no frozen pairs and there is no
+ * outer re-pairing loop: the align is one Newton loop, as for NDT.  The point covariances of both clouds are GICP's, under
+ * the handle's ndt_gicp_params (of which only k_neighbours, max_neighbour_distance and covariance_epsilon are read here).
+ * Everything below is IEEE arithmetic rounded as written, no contraction; tests/test_vgicp_cpu.py restates it in NumPy.
+ * VOXELS.  A VGICP voxel is a leaf of the built NDT target: one row per leaf in the order of ndt_export_leaves.  The
+ * handle's resolution, min_points_per_voxel and leaf rule (eigenvalue checks included) decide which voxels exist: a caller
+ * who wants sparse voxels lowers min_points_per_voxel, whose floor is 3.  Target point j CONTRIBUTES to leaf l when it is
+ * finite, has a covariance (m >= 4 neighbours under the GICP rule above) and the f32 classification of the target build --
+ * in = lo <= p < hi per axis, i_a = (int)(floorf(p_a * inv_leaf) - (float)min_b_a), the classification ndt_score_points
+ * gives the unmoved point -- puts it into the cell of leaf l.  The aggregates, f64, over the contributing points in
+ * ascending input index:
+ *    N_l      = their number
+ *    mean_a   = (sum of (double)x_ja, starting from 0) / N_l
+ *    cov_ab   = (sum of C_j,ab, starting from 0) / N_l, ab over xx, xy, xz, yy, yz, zz; C_j: the regularised covariance
+ *               ndt_gicp_export_covariances shows
+ * A leaf with N_l = 0 has NaN rows and never pairs.  The sums are made in a fixed order without float atomics.  The table
+ * is derived lazily by the first call that needs it and cached; it is dropped when the target changes, when
+ * ndt_set_params rebuilds the grid and when ndt_gicp_set_params changes k_neighbours, max_neighbour_distance or
+ * covariance_epsilon.
+ *  - ndt_vgicp_export_voxels: count (n_leaves int32), mean3 (n_leaves x 3), cov6 (n_leaves x 6); any may be NULL.  Returns
+ *    n_leaves, or < 0 (cap < n_leaves: NDT_ERR_INVALID_ARG).
+ *  - ndt_vgicp_get_info: derives the table if needed (and the source's covariances when a source is set); the pair fields
+ *    are 0.
+ * THE EVALUATION ndt_eval_derivatives_vgicp: K poses -> K x NDT_EVAL_WORDS words in the layout of ndt_eval_derivatives
+ * (ndt_unpack_eval applies; ridge / regularisation as there), IEEE f64.  Per source point i with a covariance:
+ *    rotation, moved point x' and its f32 query: exactly those of ndt_gicp_pair / ndt_eval_derivatives_d2d.
+ *    partners    the leaves ndt_score_points gives a point at that query: DIRECT1 or DIRECT7 by the handle's search
+ *                method, in the same pair order.
+ *    pair (i, l) with N_l >= 1: mu = x' - mean_l, C = R C_i R^T + cov_l, B = C^-1 (by cofactors), q = mu^T B mu,
+ *                f = -0.5 * (double)N_l; score += f * q, gradient_a += f * q_a, Hessian_ab += f * q_ab, q_a and q_ab
+ *                EXACTLY the expressions of ndt_eval_derivatives_d2d (the same device function), without the q_a q_b
+ *                term.  A pair whose q is not finite contributes nothing and is not counted.
+ *    nvtl_sum = score; n_points_with_neighbors = the source points with a counted pair; n_pairs = the counted pairs.
+ * compute_hessian == 0: the Hessian words are zero, score and gradient are the bits of the Hessian call.  The same bits
+ * every time, and a pose in a batch of K gets the bits it gets alone.
+ * DIRECT7 is the wider and the LESS EXACT neighbourhood: the cost is quadratic (no exponential cuts a far partner off),
+ * so the neighbouring voxels of other surfaces pull on a point.  It pairs almost every source point and tolerates a
+ * worse guess; DIRECT1 ends closer to the true pose (DESIGN 7q has the figures).
+ * NDT_ERR_INVALID_ARG, before the handle is looked at, for a NULL pointer, K <= 0 or a non-finite pose entry;
+ * NDT_ERR_UNSUPPORTED for a target that keeps no points (ndt_set_target_device*), a multi-grid union, NDT_KDTREE /
+ * NDT_DIRECT26 and a reducer other than NDT_REDUCE_NONE; NDT_ERR_NO_TARGET without a target; NDT_ERR_NO_SOURCE without a
+ * source or without a source point that has a covariance.
+ * THE ALIGN ndt_align_vgicp: ONE run of ndt_newton_align's loop (the ndt_align product path) over that evaluation with the
+ * handle's ndt_params and regularisation pose, n_source_total = the source size; `out` as ndt_align_d2d fills it.  There is
+ * no outer loop.  `info` (nullable): the table's counters, the points without a covariance of either cloud, and the pairs
+ * of the last evaluation of the loop.  On every failure `out` holds the guess with converged = 0.  The handle's align
+ * state, iteration history, pre-launch state, point source, distribution source and frozen GICP pairs are left alone: an
+ * ndt_align, an ndt_align_gicp and the fitness calls afterwards give the bits they gave before. */
+typedef struct ndt_vgicp_info {
+  int64_t n_voxels;                    /* leaves with N_l >= 1 */
+  int64_t n_leaves;                    /* rows of the table */
+  int64_t n_target_points_in_voxels;   /* sum of N_l */
+  int64_t n_target_without_covariance;
+  int64_t n_source_without_covariance;
+  int64_t n_pairs, n_source_with_pairs;   /* of the last evaluation of the align */
+} ndt_vgicp_info;
+int64_t ndt_vgicp_export_voxels(ndt_handle* h, int32_t* count, double* mean3, double* cov6, size_t cap);
+int     ndt_vgicp_get_info(ndt_handle* h, ndt_vgicp_info* out);
+int     ndt_eval_derivatives_vgicp(ndt_handle* h, const double* poses6, int K, int compute_hessian, double* out);
+int     ndt_align_vgicp(ndt_handle* h, const float guess_colmajor[16], ndt_result* out, ndt_vgicp_info* info_or_null);
+
 /* Scan Context place recognition (Kim & Kim, IROS 2018) over the device keyframe archive: which archived scan shows this
  * place again, and under which heading -- the question in front of ndt_align_batch / ndt_align_d2d (the relative pose) and
  * ndt_map_transform / ndt_map_import_state_posed (the correction).  A scan becomes an n_rings x n_sectors matrix of

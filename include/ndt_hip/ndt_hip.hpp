@@ -1771,6 +1771,46 @@ class GeneralizedIterativeClosestPoint : public NormalDistributionsTransform<Poi
   ndt_gicp_info info_{};
 };
 
+// Voxelised GICP (ndt_vgicp_*, ndt_align_vgicp): the GICP class above whose align() registers the source to one aggregate
+// per target leaf -- no nearest-point pairing, ONE Newton loop.  That loop is the NDT loop and reads the handle's
+// ndt_params, so setTransformationEpsilon and setMaximumIterations are the NDT class's again here (the GICP class's set
+// its two-level loop, which this method does not have), beside setStepSize, setResolution and the rest; of the GICP
+// parameters only those that decide the covariances matter (setCorrespondenceRandomness, setGicpParams).  The voxels are
+// the target's NDT leaves: setResolution and setMinPointPerVoxel decide them.  The reference names no such class: there is
+// no compat header.
+template <typename PointSource, typename PointTarget>
+class VoxelizedGeneralizedIterativeClosestPoint : public GeneralizedIterativeClosestPoint<PointSource, PointTarget> {
+  using Ndt = NormalDistributionsTransform<PointSource, PointTarget>;
+
+ public:
+#if NDT_HIP_WITH_PCL
+  using Ptr = typename std::pointer_traits<typename Ndt::Base::Ptr>::template rebind<VoxelizedGeneralizedIterativeClosestPoint<PointSource, PointTarget>>;
+  using ConstPtr = typename std::pointer_traits<typename Ndt::Base::Ptr>::template rebind<const VoxelizedGeneralizedIterativeClosestPoint<PointSource, PointTarget>>;
+#else
+  using Ptr = std::shared_ptr<VoxelizedGeneralizedIterativeClosestPoint<PointSource, PointTarget>>;
+  using ConstPtr = std::shared_ptr<const VoxelizedGeneralizedIterativeClosestPoint<PointSource, PointTarget>>;
+#endif
+
+  VoxelizedGeneralizedIterativeClosestPoint() {
+#if NDT_HIP_WITH_PCL
+    this->reg_name_ = "ndt_hip::VoxelizedGeneralizedIterativeClosestPoint";
+    this->max_iterations_ = this->params().max_iterations;
+    this->transformation_epsilon_ = this->params().trans_epsilon;
+#endif
+  }
+
+  void setTransformationEpsilon(double e) { Ndt::setTransformationEpsilon(e); }
+  void setMaximumIterations(int n) { Ndt::setMaximumIterations(n); }
+  // the table's counters, the points without a covariance and the pairs of the last evaluation of the last align()
+  const ndt_vgicp_info& vgicpInfo() const { return vinfo_; }
+
+ protected:
+  int alignEngine(const float* guess, ndt_result* out) override { return ndt_align_vgicp(this->handle(), guess, out, &vinfo_); }
+
+ private:
+  ndt_vgicp_info vinfo_{};
+};
+
 // tier4's class name for the multi-grid face [RECALLED]; here the same engine object carries both faces
 template <typename PointSource, typename PointTarget>
 using MultiGridNormalDistributionsTransform = NormalDistributionsTransform<PointSource, PointTarget>;

@@ -140,6 +140,12 @@ class GicpInfo(C.Structure):
 GICP_SOURCE, GICP_TARGET = 0, 1
 
 
+class VgicpInfo(C.Structure):
+    _fields_ = [("n_voxels", C.c_int64), ("n_leaves", C.c_int64), ("n_target_points_in_voxels", C.c_int64),
+                ("n_target_without_covariance", C.c_int64), ("n_source_without_covariance", C.c_int64),
+                ("n_pairs", C.c_int64), ("n_source_with_pairs", C.c_int64)]
+
+
 class MapCarveResult(C.Structure):
     _fields_ = [("n_rays", C.c_int64), ("n_rays_skipped", C.c_int64), ("n_steps", C.c_int64), ("n_voxels_crossed", C.c_int64),
                 ("n_voxels_hit", C.c_int64), ("n_removed", C.c_int64), ("n_points_removed", C.c_int64)]
@@ -346,6 +352,7 @@ ABI_SYMBOLS = [
     "ndt_transform_source_ct", "ndt_transform_source_ct_device",
     "ndt_gicp_default_params", "ndt_gicp_set_params", "ndt_gicp_get_params", "ndt_gicp_export_neighbours",
     "ndt_gicp_export_covariances", "ndt_gicp_pair", "ndt_gicp_export_pairs", "ndt_eval_derivatives_gicp", "ndt_align_gicp",
+    "ndt_vgicp_export_voxels", "ndt_vgicp_get_info", "ndt_eval_derivatives_vgicp", "ndt_align_vgicp",
     "ndt_scan_context_default_params", "ndt_scan_context_set_params", "ndt_scan_context_get_params",
     "ndt_scan_context_sector_table", "ndt_scan_context", "ndt_scan_context_device", "ndt_scan_context_keyframe",
     "ndt_scan_context_bank_put", "ndt_scan_context_bank_get", "ndt_scan_context_bank_erase", "ndt_scan_context_bank_clear",
@@ -514,6 +521,11 @@ def lib():
         L.ndt_gicp_export_pairs.restype = C.c_int64
         L.ndt_eval_derivatives_gicp.argtypes = [vp, dp, C.c_int, C.c_int, dp]
         L.ndt_align_gicp.argtypes = [vp, fp, C.POINTER(Result), C.POINTER(GicpInfo)]
+        L.ndt_vgicp_export_voxels.argtypes = [vp, vp, dp, dp, C.c_size_t]
+        L.ndt_vgicp_export_voxels.restype = C.c_int64
+        L.ndt_vgicp_get_info.argtypes = [vp, C.POINTER(VgicpInfo)]
+        L.ndt_eval_derivatives_vgicp.argtypes = [vp, dp, C.c_int, C.c_int, dp]
+        L.ndt_align_vgicp.argtypes = [vp, fp, C.POINTER(Result), C.POINTER(VgicpInfo)]
         scp, i64 = C.POINTER(ScanContextParams), C.c_int64
         L.ndt_scan_context_default_params.restype = None
         L.ndt_scan_context_default_params.argtypes = [scp]
@@ -2325,6 +2337,58 @@ def alignGICP(engine, guess=None):
     d = result_to_dict(r)
     d["iteration_num"] = d["iterations"]
     d["gicp"] = {k: getattr(info, k) for k, _ in GicpInfo._fields_}
+    return d["T"], d
+
+
+# --- Voxelised GICP: the point source against one aggregate per target leaf (ndt_vgicp_*, ndt_eval_derivatives_vgicp,
+# ndt_align_vgicp).  Functions on an engine with `engine` as their first parameter, as GICP's and for the same
+# reason.  The covariance rule is GICP's (gicpSetParams). ---
+def vgicpVoxels(engine):
+    """dict(count [L] int32, mean [L, 3], cov6 [L, 6] (xx, xy, xz, yy, yz, zz), cov [L, 3, 3]) of the target's leaves in
+    getLeaves() order; NaN rows with count 0 for a leaf none of whose points contributes"""
+    n = lib().ndt_vgicp_export_voxels(engine._h, None, None, None, 1 << 62)   # (no output: the size alone)
+    if n < 0:
+        engine._check(int(n))
+    n = int(n)
+    count, mean, cov6 = np.zeros(n, np.int32), np.zeros((n, 3)), np.zeros((n, 6))
+    got = lib().ndt_vgicp_export_voxels(engine._h, count.ctypes.data, _dp(mean), _dp(cov6), n)
+    if got < 0:
+        engine._check(int(got))
+    count, mean, cov6 = count[:got], mean[:got], cov6[:got]
+    return dict(count=count, mean=mean, cov6=cov6, cov=cov6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, 3, 3))
+
+
+def vgicpInfo(engine):
+    """dict of ndt_vgicp_info (the table is derived if needed; the pair fields are 0)"""
+    info = VgicpInfo()
+    engine._check(lib().ndt_vgicp_get_info(engine._h, C.byref(info)))
+    return {k: getattr(info, k) for k, _ in VgicpInfo._fields_}
+
+
+def evalDerivativesVGICP(engine, poses6, compute_hessian=True, raw=False):
+    """The VGICP score (-sum N q / 2 over the voxels of every source point), gradient and Hessian at K poses (K x 6): a list
+    of dicts as evalDerivatives gives them; raw=True: the K x 32 packed words."""
+    p = np.ascontiguousarray(np.atleast_2d(poses6), dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 6 or not np.isfinite(p).all():
+        raise ValueError("poses6 must be K x 6 and finite")
+    K = p.shape[0]
+    out = np.zeros((K, EVAL_WORDS))
+    engine._check(lib().ndt_eval_derivatives_vgicp(engine._h, _dp(p), K, int(bool(compute_hessian)), _dp(out)))
+    return out if raw else [unpack_eval(out[k]) for k in range(K)]
+
+
+def alignVGICP(engine, guess=None):
+    """ndt_align_vgicp from `guess` (4x4, default identity).  Returns (final 4x4, result dict as getResult() gives it with
+    `vgicp`: the fields of ndt_vgicp_info); getResult() keeps reporting the last align()."""
+    g = np.asarray(np.eye(4) if guess is None else guess, dtype=np.float64)
+    if g.shape != (4, 4) or not np.isfinite(g).all():
+        raise ValueError("guess must be a finite 4 x 4 matrix")
+    g = _colmajor(g)
+    r, info = Result(), VgicpInfo()
+    engine._check(lib().ndt_align_vgicp(engine._h, _fp(g), C.byref(r), C.byref(info)))
+    d = result_to_dict(r)
+    d["iteration_num"] = d["iterations"]
+    d["vgicp"] = {k: getattr(info, k) for k, _ in VgicpInfo._fields_}
     return d["T"], d
 
 

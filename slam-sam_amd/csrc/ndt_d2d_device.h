@@ -1,8 +1,9 @@
 // ndt_d2d_device.h -- one pair of Gaussians under a pose (internal; HIP): q = mu^T (R Sigma_i R^T + Sigma_j)^-1 mu and
 // its exact first and second derivatives by the six pose parameters, as include/ndt_hip.h states them for
-// ndt_eval_derivatives_d2d.  Two evaluations share it and differ only in the WEIGHT a pair's q enters the sums with:
+// ndt_eval_derivatives_d2d.  Three evaluations share it and differ only in the WEIGHT a pair's q enters the sums with:
 //   D2dNdtWeight   distribution-to-distribution NDT (ndt_d2d.hip): score -d1 exp(-d2 q / 2), f = (d1 d2 / 2) e
 //   D2dHalfWeight  GICP's plane-to-plane cost (ndt_gicp.hip): score -q / 2, f = -1/2, no q_a q_b term
+//   D2dCountWeight voxelised GICP (ndt_vgicp.hip): the partner is a voxel of N points, score -N q / 2, f = -N / 2, no q_a q_b term
 // Also here: the pose's rotation with its angle derivatives (host side) and the small symmetric-matrix helpers.
 // Whoever includes it is compiled with -ffp-contract=off like the rest of the engine.
 #pragma once
@@ -82,6 +83,18 @@ struct D2dHalfWeight {
     if (!isfinite(q)) return false;
     *sc = -0.5 * q;
     *f = -0.5;
+    return true;
+  }
+  __device__ __forceinline__ double qq() const { return 0.0; }
+};
+
+struct D2dCountWeight {
+  double n;   // (double)N of the voxel
+  static constexpr bool QQ = false;
+  __device__ __forceinline__ bool weigh(double q, double* sc, double* f) const {
+    if (!isfinite(q)) return false;
+    *f = -0.5 * n;
+    *sc = *f * q;
     return true;
   }
   __device__ __forceinline__ double qq() const { return 0.0; }

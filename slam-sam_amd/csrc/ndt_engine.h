@@ -19,6 +19,8 @@
 //   ndt_gicp.hip       generalised ICP: the exact k nearest neighbours of every point of a cloud, the point covariances made
 //                      from them, the frozen nearest-point pairs, the plane-to-plane evaluation over them and the two-level
 //                      align (k_gicp_* kernels); the index it searches is the fitness index (ndt_fitness.hip, ndt_fit_device.h)
+//   ndt_vgicp.hip      voxelised GICP: the target's point covariances aggregated into the target's leaves, the evaluation
+//                      of a source point against up to seven of those voxels and the one-level align (k_vgicp_* kernels)
 //   ndt_eval_rows.hip  what those evaluations share behind their kernels: the fixed-order sum of block rows, the host
 //                      driver, the support check, the finished-words repack, the align wrapper
 //   ndt_scan_context.hip  Scan Context place recognition: a scan's rings x sectors descriptor, the descriptor bank beside
@@ -344,7 +346,22 @@ struct GicpBufs {
   void release() { src.release(); tgt.release(); sidx.release(); work.release(); work_h.release(); pair.release(); pd2.release(); drop_pairs(); }
 };
 
-// The rows of a lane-per-item evaluation (lane_eval_rows, ndt_eval_rows.hip).  One instance serves D2D, CT and GICP: each
+// Voxelised GICP (ndt_vgicp.hip): per leaf slot of the target the mean of its points and the mean of their GICP
+// covariances, derived lazily from GicpBufs::tgt and cached until the target (gen, target_retire / target_drop) or the
+// covariance rule (ndt_gicp_set_params) changes.  The source side is GicpBufs::src.
+struct VgicpBufs {
+  bool valid = false;
+  uint64_t gen = 0;                  // TargetState::gen() of the target the table was derived from
+  int n_slots = 0;                   // rows of the table (leaf slots, rejected leaves included: those never pair)
+  int64_t n_voxels = 0, n_points = 0;   // leaves with N >= 1, sum of N
+  DevBuf<double> table;              // n_slots x 9 in d2d_pair's target layout {mean 3, cov xx xy xz yy yz zz}; NaN rows for N = 0
+  DevBuf<int32_t> count;             // N per slot
+  SortScratch sort;                  // (leaf slot, point index) pairs of the derivation ...
+  DevBuf<BuildGeom> plan;            // ... and their sort plan
+  void release() { table.release(); count.release(); sort.release(); plan.release(); valid = false; }
+};
+
+// The rows of a lane-per-item evaluation (lane_eval_rows, ndt_eval_rows.hip).  One instance serves D2D, CT, GICP and VGICP: each
 // evaluation is awaited before it returns.
 struct EvalRowBufs {
   DevBuf<double> rows, out;          // per-block rows of K poses, their K x EV_WORDS sums
@@ -508,6 +525,7 @@ struct ndt_handle {
   D2dBufs d2d;                       // the distribution source of ndt_*_d2d and the target's leaves for it (ndt_d2d.hip)
   CtBufs ct;                         // the source's times and the scratch of ndt_*_ct (ndt_ct.hip)
   GicpBufs gicp;                     // GICP's parameters, neighbour lists, covariances and frozen pairs (ndt_gicp.hip)
+  VgicpBufs vgicp;                   // voxelised GICP's table of per-leaf aggregates (ndt_vgicp.hip)
   EvalRowBufs evrows;                // the block rows and sums of a D2D, CT or GICP evaluation (ndt_eval_rows.hip)
   // the same points in block order of the target grid (see sort_source_by_blocks); valid until
   // the source or the target changes
@@ -834,7 +852,13 @@ int map_merge_records(ndt_handle* h, const MapTable& t, unsigned long long* d_nv
 // engine's copy of the target, lazily (the target is settled).
 int fit_build_cloud(ndt_handle* h, FitIndex& f, const float* x, const float* y, const float* z, size_t n, const char* what);
 int fit_build(ndt_handle* h);
-// ndt_eval_rows.hip: what the lane-per-item evaluations (D2D, CT, GICP) share behind their kernels.  `what` is "D2D", "CT"
+// ndt_gicp.hip's host side as ndt_vgicp.hip uses it: one rank and the streams settled; what a target / a source must be;
+// the target's and the source's neighbour lists and covariances (h->gicp.tgt / h->gicp.src), derived if they are not fresh
+int gicp_settle(ndt_handle* h);
+int gicp_target_state(ndt_handle* h);
+int gicp_target_ready(ndt_handle* h);
+int gicp_source_ready(ndt_handle* h);
+// ndt_eval_rows.hip: what the lane-per-item evaluations (D2D, CT, GICP, VGICP) share behind their kernels.  `what` is "D2D", "CT"
 // or "GICP" and heads the error texts.
 // k_eval_rows_sum on rows of K poses x nb blocks x EV_WORDS -> out (K x EV_WORDS), enqueued on s
 void launch_eval_rows_sum(const double* rows, int nb, int K, double* out, hipStream_t s);

@@ -345,6 +345,9 @@ int gicp_derive(ndt_handle* h, GicpCloud& c, const FitIndex& f, const float* x, 
   return NDT_OK;
 }
 
+}  // namespace
+
+// (declared in ndt_engine.h: voxelised GICP shares them)
 // what every GICP call checks first: one rank, and the streams ordered behind whatever is in flight
 int gicp_settle(ndt_handle* h) {
   if (int rc = settle(h)) return rc;
@@ -389,6 +392,8 @@ int gicp_source_ready(ndt_handle* h) {
   }
   return gicp_derive(h, b.src, b.sidx, h->vx, h->vy, h->vz, h->n_src);
 }
+
+namespace {
 
 int gicp_cloud_ready(ndt_handle* h, int which) {
   if (int rc = gicp_settle(h)) return rc;
@@ -472,6 +477,7 @@ int ndt_gicp_set_params(ndt_handle* h, const ndt_gicp_params* p) {
   if (p->k_neighbours != o.k_neighbours || p->max_neighbour_distance != o.max_neighbour_distance ||
       p->covariance_epsilon != o.covariance_epsilon) {
     b.src.valid = b.tgt.valid = false;
+    h->vgicp.valid = false;   // (the voxel table is made of the target's covariances)
     b.drop_pairs();
   }
   if (p->max_correspondence_distance != o.max_correspondence_distance) b.drop_pairs();

@@ -165,6 +165,7 @@ int ndt_destroy(ndt_handle* h) {
   h->d2d.release();
   h->ct.release();
   h->gicp.release();
+  h->vgicp.release();
   h->evrows.release();
   h->sc.release();
   h->compact.release(); h->knots.release();

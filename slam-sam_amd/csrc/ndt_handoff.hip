@@ -102,6 +102,7 @@ IndexReuse target_retire(ndt_handle* h, size_t kept_cloud_n) {
   h->src_sorted = false;
   h->prec_valid = false;
   h->d2d.tleaf_valid = false;   // (the D2D evaluation's copy of the leaves goes with the target)
+  h->vgicp.valid = false;       // (... and voxelised GICP's table of them)
   h->build_pending = false;
   h->deferred_rc = 0;
   h->deferred_msg.clear();
@@ -129,6 +130,7 @@ int target_publish(ndt_handle* h, TargetKind kind, const GridGeom& geom, const i
 void target_drop(ndt_handle* h) {
   h->tgt.drop();
   h->d2d.tleaf_valid = false;
+  h->vgicp.valid = false;
 }
 
 // everything of a build that does not depend on the attempt: state reset, allocations, constants

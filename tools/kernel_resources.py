@@ -1,12 +1,13 @@
 """VGPRs / SGPRs / scratch / LDS of the evaluators' kernels (hipcc cross-compiles; no GPU).
-python tools/kernel_resources.py                    every k_derivatives instantiation, k_point_scores, k_d2d_eval, k_ct_eval
-                                                    and the fixed-order row sum they share
+python tools/kernel_resources.py                    every k_derivatives instantiation, k_point_scores, k_d2d_eval, k_ct_eval,
+                                                    k_vgicp_eval and the fixed-order row sum they share
 python tools/kernel_resources.py FILE PATTERN ...   the kernels of csrc/FILE whose name matches PATTERN (extra hipcc arguments follow)"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "slam-sam_amd", "csrc")
 # (a file that a tree does not have is skipped: the row sum was k_d2d_sum in ndt_d2d.hip before ndt_eval_rows.hip)
 EVALUATORS = (("ndt_derivs.hip", "k_derivatives|k_point_scores"), ("ndt_d2d.hip", "k_d2d_eval|k_d2d_sum"), ("ndt_ct.hip", "k_ct_eval"),
+              ("ndt_vgicp.hip", "k_vgicp_eval"),
               ("ndt_eval_rows.hip", "k_eval_rows_sum"))
 
 
@@ -30,7 +31,7 @@ def tag_of(nm):
     if t: return "batch%s mode%s nb%s mbox%s" % t.groups()
     t = re.search(r"(k_point_scores)ILi(\d)E", nm)
     if t: return "%s<%s>" % t.groups()
-    t = re.search(r"(k_d2d_eval|k_ct_eval)ILb(\d)ELb(\d)E", nm)
+    t = re.search(r"(k_d2d_eval|k_ct_eval|k_vgicp_eval)ILb(\d)ELb(\d)E", nm)
     if t: return "%s<hessian %s, d7 %s>" % t.groups()
     t = re.search(r"\d+(k_[a-z0-9_]+?)(?=[EIP])", nm)
     return t.group(1) if t else nm[:60]
