@@ -53,7 +53,8 @@ typedef enum ndt_status {
   NDT_ERR_GRID_OVERFLOW = -6, /* dx*dy*dz > INT32_MAX (ref: voxel_grid_covariance_impl.hpp:108-125) */
   NDT_ERR_ALLOC = -7,
   NDT_ERR_COMM = -8,        /* RCCL / shared-memory reduction failure */
-  NDT_ERR_UNSUPPORTED = -9
+  NDT_ERR_UNSUPPORTED = -9,
+  NDT_ERR_INTERNAL = -10    /* a bounded device loop ran out of its bound (ndt_map_components*): a defect, never a wait */
 } ndt_status;
 
 /* same order as pclomp::NeighborSearchMethod (ref: run/pipeline.cpp:471-480) */
@@ -837,6 +838,102 @@ int ndt_map_carve(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes
                   ndt_map_carve_result* out_or_null);
 int ndt_map_carve_keyframe(ndt_handle* h, int64_t id, const float origin[3], const double pose16_colmajor[16],
                            const ndt_map_carve_params* params, ndt_map_carve_result* out_or_null);
+
+/* Connected components of the map: which voxels belong together.  ndt_map_crop removes by position and ndt_map_carve by
+ * a later scan's rays; these calls label the occupied voxels by adjacency on the device (a lock-free union-find over the
+ * table's slots), report the components, label the points of a cloud by the voxel they fall in, and remove the
+ * components a filter rejects: floating speckle, the scraps a carve leaves, the disconnected pieces of a bad merge
+ * (pcl::EuclideanClusterExtraction / RadiusOutlierRemoval on a map that keeps no points).  Every output is an integer.
+ *  1. Eligible voxels.  An occupied voxel with count >= min_count is eligible; one with count < min_count takes no part:
+ *     it joins nothing and bridges nothing.
+ *  2. Adjacency.  Two eligible voxels are adjacent when their ijk differ by at most 1 on every axis and the sum s of the
+ *     absolute differences is 1 (connectivity 6: faces), 1 <= s <= 2 (18: faces and edges) or 1 <= s <= 3 (26: faces,
+ *     edges and corners).
+ *  3. No neighbours beyond the range.  A neighbour coordinate with |ijk| >= 2^20 on an axis does not exist (no key is
+ *     ever formed from it): (2^20 - 1, 0, 0) and (-(2^20 - 1), 1, 0) are not adjacent.
+ *  4. Components.  A component is a class of the transitive closure of adjacency.  Its root is its first voxel in
+ *     ascending (k, j, i) order -- ndt_map_export_state's order.
+ *  5. Numbering.  Components are numbered 0 .. C - 1 in ascending (k, j, i) order of their roots.  The label of an
+ *     eligible voxel is its component's number, the label of an ineligible voxel is -1.
+ *  6. Slot independence.  Labels and component records depend on the set of (ijk, count) alone: not on the table's
+ *     capacity, not on the order of the adds, not on the slot a voxel sits in.
+ * Calls.  Every call takes the params and stands for the map as it is when it is called (the engine may keep a labelling
+ * until the map changes; a result after any change of the map is fresh).
+ *  - ndt_map_components: labels the map; *info_or_null receives the counts: n_components, the eligible (labelled) and
+ *    ineligible (unlabelled) voxels, `largest` = the index of the first component with the most voxels (-1 without one)
+ *    and its n_voxels / n_points.  An empty map is NDT_OK with zero components and largest = -1.
+ *  - ndt_map_export_components: the C records in index order: root_ijk, n_voxels, n_points (the sum of the voxels'
+ *    counts) and the tight ijk box.  Size protocol of ndt_map_export (*n_out = C; at most cap records are written; C > cap
+ *    is NDT_ERR_INVALID_ARG behind the write).
+ *  - ndt_map_export_labels / _device: every OCCUPIED voxel of the whole map in ndt_map_export_state(NULL, NULL, ...)'s
+ *    order -- row r of one is row r of the other -- ijk 3 x int32 and label int32; each may be NULL.  Same size protocol.
+ *  - ndt_map_label_points / _device: label_out[p] for the n points of a strided host cloud / SoA device arrays.  A point
+ *    is moved by the pose (NULL: none) exactly as ndt_map_add moves it (f64 products summed left to right, one f32
+ *    rounding), its voxel is floor(p * inv_leaf) in f32 as for ndt_map_add, its label is that voxel's label; -1 for a
+ *    point that is not finite (before or after the pose), beyond the coordinate range, in a voxel the map does not hold
+ *    or in an ineligible voxel.  *n_labelled_or_null: the points with a label >= 0.  n == 0 is a no-op (0 labelled).
+ *  - ndt_map_remove_components: a component SURVIVES when n_voxels >= min_voxels and n_points >= min_points and
+ *    (keep_largest == 0 or its position among ALL components ordered by (n_voxels descending, index ascending) is below
+ *    keep_largest).  The eligible voxels of the components that do not survive go; the ineligible voxels go iff
+ *    remove_unlabelled != 0.  *out_or_null: n_components, n_components_removed, n_removed (voxels) and
+ *    n_points_removed.  Everything else is ndt_map_crop's contract: nothing to remove is NDT_OK with the table untouched;
+ *    otherwise the survivors move bit for bit, moments included, into a fresh table of crop's capacity;
+ *    ndt_map_get_info reports the kept voxels and points and their tight ijk box; n_points_dropped, n_adds and n_grows
+ *    are unchanged; an emptied map still exists; an allocation failure is NDT_ERR_ALLOC and leaves the map as it was.
+ *    With dry_run the counts are reported and the map is untouched in every case.
+ * Refusals, NDT_ERR_INVALID_ARG with nothing changed: no map; NULL params or filter; a connectivity other than 6, 18, 26;
+ * min_count < 1; a non-zero reserved word; min_voxels < 1, min_points < 0 or keep_largest < 0; a non-finite pose; a NULL
+ * cloud pointer or a NULL label output with n > 0; a stride below 12 or no multiple of 4; a NULL n_out.  The argument
+ * checks come before the handle is looked at.  A bounded loop of the labelling that ran out of its bound is
+ * NDT_ERR_INTERNAL (no loop of it waits for another thread).  Target, source, align state, iteration history, evaluation
+ * counters and the keyframe archive are left untouched by all calls; the cached levels are left alone except that a
+ * removal, as every change of the map, makes them stale.  The calls work on the map itself (also one coarsened by
+ * ndt_map_coarsen); components of a cached level or of a box, and clustering the points of a scan without a map, are
+ * out of scope.  Complete when they return. */
+typedef struct ndt_map_components_params {
+  int connectivity;   /* 6 (faces), 18 (faces + edges) or 26 (faces + edges + corners) */
+  int min_count;      /* >= 1: a voxel with count < min_count takes no part: it joins nothing and bridges nothing */
+  int reserved[2];    /* zero */
+} ndt_map_components_params;
+typedef struct ndt_map_component {
+  int32_t root_ijk[3];                  /* the component's first voxel in ascending (k, j, i) order */
+  int32_t n_voxels;
+  int64_t n_points;                     /* sum of the voxels' counts */
+  int32_t min_ijk[3], max_ijk[3];       /* tight box */
+} ndt_map_component;
+typedef struct ndt_map_components_info {
+  int64_t n_components, n_voxels_labelled, n_voxels_unlabelled;
+  int64_t largest;                      /* index of the first component with the most voxels; -1 without one */
+  int64_t largest_n_voxels, largest_n_points;
+} ndt_map_components_info;
+typedef struct ndt_map_component_filter {
+  int32_t min_voxels;        /* >= 1 */
+  int64_t min_points;        /* >= 0 */
+  int32_t keep_largest;      /* 0: off; N > 0: only the N first components in (n_voxels descending, index ascending) order survive */
+  int32_t remove_unlabelled; /* != 0: the voxels with count < min_count go as well */
+  int32_t dry_run;
+  int32_t reserved[3];       /* zero */
+} ndt_map_component_filter;
+typedef struct ndt_map_remove_components_result {
+  int64_t n_components, n_components_removed, n_removed, n_points_removed;
+} ndt_map_remove_components_result;
+void ndt_map_components_default_params(ndt_map_components_params* p);        /* 26, 1 */
+void ndt_map_component_filter_default_params(ndt_map_component_filter* f);   /* 1, 0, 0, 0, 0: removes nothing */
+int ndt_map_components(ndt_handle* h, const ndt_map_components_params* params, ndt_map_components_info* info_or_null);
+int ndt_map_export_components(ndt_handle* h, const ndt_map_components_params* params, ndt_map_component* comps,
+                              size_t cap, size_t* n_out);
+int ndt_map_export_labels(ndt_handle* h, const ndt_map_components_params* params, int32_t* ijk, int32_t* label,
+                          size_t cap, size_t* n_out);
+int ndt_map_export_labels_device(ndt_handle* h, const ndt_map_components_params* params, int32_t* ijk, int32_t* label,
+                                 size_t cap, size_t* n_out);
+int ndt_map_label_points(ndt_handle* h, const ndt_map_components_params* params, const float* xyz, size_t n,
+                         size_t stride_bytes, const double* pose16_colmajor_or_null, int32_t* label_out,
+                         int64_t* n_labelled_or_null);
+int ndt_map_label_points_device(ndt_handle* h, const ndt_map_components_params* params, const float* dx,
+                                const float* dy, const float* dz, size_t n, const double* pose16_colmajor_or_null,
+                                int32_t* d_label_out, int64_t* n_labelled_or_null);
+int ndt_map_remove_components(ndt_handle* h, const ndt_map_components_params* params,
+                              const ndt_map_component_filter* filter, ndt_map_remove_components_result* out_or_null);
 
 /* Re-pose the map: after a pose-graph correction or a loop closure the frame a map was accumulated in moves.  The map
  * has no points to move, but it keeps exactly the sums that move exactly: with p' = R p + t, sum p' and sum p' p'^T are

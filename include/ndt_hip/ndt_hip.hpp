@@ -797,6 +797,91 @@ class NormalDistributionsTransform
     status_ = ndt_map_carve_keyframe(h_, id, origin, pose_colmajor, params ? params : &def, &r);
     return status_ == NDT_OK ? r : ndt_map_carve_result{};
   }
+  // ---- connected components (ndt_map_components*): which voxels belong together under 6 / 18 / 26 adjacency; voxels with
+  // fewer than min_count points take no part.  params null: ndt_map_components_default_params (26, 1).  On error the
+  // outputs are empty / zero and lastStatus() says why. ----
+  ndt_map_components_info mapComponents(const ndt_map_components_params* params = nullptr) {
+    ndt_map_components_info info{};
+    info.largest = -1;
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return info; }
+    ndt_map_components_params def;
+    ndt_map_components_default_params(&def);
+    status_ = ndt_map_components(h_, params ? params : &def, &info);
+    return info;
+  }
+  // the component table in index order
+  void mapExportComponents(std::vector<ndt_map_component>& comps, const ndt_map_components_params* params = nullptr) {
+    comps.clear();
+    const ndt_map_components_info info = mapComponents(params);
+    if (status_ != NDT_OK) return;
+    ndt_map_components_params def;
+    ndt_map_components_default_params(&def);
+    comps.resize((size_t)info.n_components);
+    size_t m = 0;
+    status_ = ndt_map_export_components(h_, params ? params : &def, comps.data(), comps.size(), &m);
+    comps.resize(status_ == NDT_OK ? m : 0);
+  }
+  // every occupied voxel in mapExportState's order: ijk (3 per voxel) and label (-1: fewer than min_count points)
+  void mapExportLabels(std::vector<int32_t>& ijk, std::vector<int32_t>& labels, const ndt_map_components_params* params = nullptr) {
+    ijk.clear(); labels.clear();
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return; }
+    ndt_map_info mi{};
+    status_ = ndt_map_get_info(h_, &mi);
+    if (status_ != NDT_OK) return;
+    ndt_map_components_params def;
+    ndt_map_components_default_params(&def);
+    const size_t cap = (size_t)mi.n_voxels;
+    ijk.resize(3 * cap); labels.resize(cap);
+    size_t m = 0;
+    status_ = ndt_map_export_labels(h_, params ? params : &def, ijk.data(), labels.data(), cap, &m);
+    if (status_ != NDT_OK) m = 0;
+    ijk.resize(3 * m); labels.resize(m);
+  }
+  // into device arrays of cap rows (either may be null); returns the number of voxels
+  size_t mapExportLabelsDevice(int32_t* d_ijk, int32_t* d_label, size_t cap, const ndt_map_components_params* params = nullptr) {
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return 0; }
+    ndt_map_components_params def;
+    ndt_map_components_default_params(&def);
+    size_t m = 0;
+    status_ = ndt_map_export_labels_device(h_, params ? params : &def, d_ijk, d_label, cap, &m);
+    return m;
+  }
+  // the label of the map voxel each point falls in once moved by the pose (as mapAdd moves it), -1 where there is none;
+  // returns the number of points with a label
+  template <class Cloud>
+  int64_t mapLabelPoints(const Cloud& cloud, std::vector<int32_t>& labels, const double* pose_colmajor = nullptr,
+                         const ndt_map_components_params* params = nullptr) {
+    labels.assign(cloud.points.size(), -1);
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return 0; }
+    ndt_map_components_params def;
+    ndt_map_components_default_params(&def);
+    int64_t k = 0;
+    if (cloud.points.empty()) status_ = ndt_map_label_points(h_, params ? params : &def, nullptr, 0, 12, pose_colmajor, nullptr, &k);
+    else status_ = ndt_map_label_points(h_, params ? params : &def, &cloud.points[0].x, cloud.points.size(), sizeof(cloud.points[0]),
+                                        pose_colmajor, labels.data(), &k);
+    return status_ == NDT_OK ? k : 0;
+  }
+  int64_t mapLabelPointsDevice(const float* dx, const float* dy, const float* dz, size_t n, int32_t* d_label,
+                               const double* pose_colmajor = nullptr, const ndt_map_components_params* params = nullptr) {
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return 0; }
+    ndt_map_components_params def;
+    ndt_map_components_default_params(&def);
+    int64_t k = 0;
+    status_ = ndt_map_label_points_device(h_, params ? params : &def, dx, dy, dz, n, pose_colmajor, d_label, &k);
+    return status_ == NDT_OK ? k : 0;
+  }
+  // removes the components the filter rejects (filter null: ndt_map_component_filter_default_params, which removes nothing)
+  ndt_map_remove_components_result mapRemoveComponents(const ndt_map_component_filter* filter,
+                                                       const ndt_map_components_params* params = nullptr) {
+    ndt_map_remove_components_result r{};
+    if (!h_) { status_ = NDT_ERR_NO_DEVICE; return r; }
+    ndt_map_components_params def;
+    ndt_map_components_default_params(&def);
+    ndt_map_component_filter fdef;
+    ndt_map_component_filter_default_params(&fdef);
+    status_ = ndt_map_remove_components(h_, params ? params : &def, filter ? filter : &fdef, &r);
+    return status_ == NDT_OK ? r : ndt_map_remove_components_result{};
+  }
 
   // box_min / box_max: three floats each, or both null for the whole map
   void mapExportState(MapState& out, const float* box_min = nullptr, const float* box_max = nullptr) {

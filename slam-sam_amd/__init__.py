@@ -151,6 +151,33 @@ class MapCarveResult(C.Structure):
                 ("n_voxels_hit", C.c_int64), ("n_removed", C.c_int64), ("n_points_removed", C.c_int64)]
 
 
+class MapComponentsParams(C.Structure):
+    """ndt_map_components_params (ndt_map_components_default_params: 26, 1)"""
+    _fields_ = [("connectivity", C.c_int), ("min_count", C.c_int), ("reserved", C.c_int * 2)]
+
+
+class MapComponent(C.Structure):
+    """ndt_map_component: one record of ndt_map_export_components (48 bytes)"""
+    _fields_ = [("root_ijk", C.c_int32 * 3), ("n_voxels", C.c_int32), ("n_points", C.c_int64), ("min_ijk", C.c_int32 * 3),
+                ("max_ijk", C.c_int32 * 3)]
+
+
+class MapComponentsInfo(C.Structure):
+    _fields_ = [("n_components", C.c_int64), ("n_voxels_labelled", C.c_int64), ("n_voxels_unlabelled", C.c_int64),
+                ("largest", C.c_int64), ("largest_n_voxels", C.c_int64), ("largest_n_points", C.c_int64)]
+
+
+class MapComponentFilter(C.Structure):
+    """ndt_map_component_filter (ndt_map_component_filter_default_params: 1, 0, 0, 0, 0 -- removes nothing)"""
+    _fields_ = [("min_voxels", C.c_int32), ("min_points", C.c_int64), ("keep_largest", C.c_int32),
+                ("remove_unlabelled", C.c_int32), ("dry_run", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class MapRemoveComponentsResult(C.Structure):
+    _fields_ = [("n_components", C.c_int64), ("n_components_removed", C.c_int64), ("n_removed", C.c_int64),
+                ("n_points_removed", C.c_int64)]
+
+
 DESKEW_MAX_KNOTS = 64
 
 
@@ -343,6 +370,9 @@ ABI_SYMBOLS = [
     "ndt_unproject_packet_frame_device", "ndt_unproject_packet_frame", "ndt_keyframe_put_from_packets",
     "ndt_map_crop", "ndt_map_export_state", "ndt_map_export_state_device", "ndt_map_import_state", "ndt_map_import_state_device",
     "ndt_map_carve_default_params", "ndt_map_carve_device", "ndt_map_carve", "ndt_map_carve_keyframe",
+    "ndt_map_components_default_params", "ndt_map_component_filter_default_params", "ndt_map_components",
+    "ndt_map_export_components", "ndt_map_export_labels", "ndt_map_export_labels_device", "ndt_map_label_points",
+    "ndt_map_label_points_device", "ndt_map_remove_components",
     "ndt_map_transform", "ndt_map_import_state_posed", "ndt_map_import_state_posed_device",
     "ndt_map_level_info", "ndt_map_export_state_level", "ndt_map_export_state_level_device", "ndt_set_target_from_map_level",
     "ndt_map_coarsen", "ndt_map_levels_drop", "ndt_align_map_levels",
@@ -552,6 +582,18 @@ def lib():
         L.ndt_map_carve.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, dp, C.POINTER(MapCarveParams),
                                     C.POINTER(MapCarveResult)]
         L.ndt_map_carve_keyframe.argtypes = [vp, C.c_int64, fp, dp, C.POINTER(MapCarveParams), C.POINTER(MapCarveResult)]
+        ccp, szp = C.POINTER(MapComponentsParams), C.POINTER(C.c_size_t)
+        L.ndt_map_components_default_params.restype = None
+        L.ndt_map_components_default_params.argtypes = [ccp]
+        L.ndt_map_component_filter_default_params.restype = None
+        L.ndt_map_component_filter_default_params.argtypes = [C.POINTER(MapComponentFilter)]
+        L.ndt_map_components.argtypes = [vp, ccp, C.POINTER(MapComponentsInfo)]
+        L.ndt_map_export_components.argtypes = [vp, ccp, C.POINTER(MapComponent), C.c_size_t, szp]
+        L.ndt_map_export_labels.argtypes = [vp, ccp, vp, vp, C.c_size_t, szp]
+        L.ndt_map_export_labels_device.argtypes = [vp, ccp, vp, vp, C.c_size_t, szp]
+        L.ndt_map_label_points.argtypes = [vp, ccp, vp, C.c_size_t, C.c_size_t, dp, vp, C.POINTER(C.c_int64)]
+        L.ndt_map_label_points_device.argtypes = [vp, ccp, vp, vp, vp, C.c_size_t, dp, vp, C.POINTER(C.c_int64)]
+        L.ndt_map_remove_components.argtypes = [vp, ccp, C.POINTER(MapComponentFilter), C.POINTER(MapRemoveComponentsResult)]
         L.ndt_trajectory_pose.argtypes = [dp, dp, C.c_int, dp, C.c_double, dp]
         traj = [dp, dp, C.c_int, dp, C.POINTER(ScanFilter)]
         L.ndt_deskew_device.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t] + traj + [vp, vp, vp, vp, vp, C.c_size_t,
@@ -1956,6 +1998,117 @@ def mapImportStatePosedDevice(ndt, leaf, d_ijk, d_count, d_sums, d_moments, n, p
     """As mapImportStatePosed, from device arrays (integer addresses; d_moments None for a map without moments)."""
     p = _finite_pose16(pose)
     ndt._check(lib().ndt_map_import_state_posed_device(ndt._h, float(leaf), d_ijk, d_count, d_sums, d_moments, int(n), _dp(p)))
+
+
+# --- connected components of the map: which voxels belong together (ndt_map_components*, ndt_map_export_labels*,
+# ndt_map_label_points*, ndt_map_remove_components; DESIGN 7r).  Functions on an engine, as above; `engine` is a
+# NormalDistributionsTransform that holds a map. ---
+def _components_params(connectivity, min_count):
+    """MapComponentsParams; ValueError on what the library would refuse.  None: the library's default (26, 1)."""
+    prm = MapComponentsParams()
+    lib().ndt_map_components_default_params(C.byref(prm))
+    if connectivity is not None:
+        prm.connectivity = int(connectivity)
+    if min_count is not None:
+        prm.min_count = int(min_count)
+    if prm.connectivity not in (6, 18, 26) or prm.min_count < 1:
+        raise ValueError("connectivity is 6, 18 or 26 and min_count >= 1")
+    return prm
+
+
+def _finite_pose16_or_none(pose):
+    return None if pose is None else _finite_pose16(pose)
+
+
+def mapComponents(engine, connectivity=None, min_count=None):
+    """Label the map of `engine`: dict(n_components, n_voxels_labelled, n_voxels_unlabelled, largest, largest_n_voxels,
+    largest_n_points).  Voxels with fewer than min_count points take no part; connectivity is 6, 18 or 26."""
+    prm = _components_params(connectivity, min_count)
+    info = MapComponentsInfo()
+    engine._check(lib().ndt_map_components(engine._h, C.byref(prm), C.byref(info)))
+    return {name: int(getattr(info, name)) for name, _ in MapComponentsInfo._fields_}
+
+
+def mapExportComponents(engine, connectivity=None, min_count=None):
+    """The component table in index order: dict(root_ijk [C, 3], n_voxels [C], n_points [C] int64, min_ijk [C, 3],
+    max_ijk [C, 3]), int32 unless said otherwise."""
+    prm = _components_params(connectivity, min_count)
+    cap = mapComponents(engine, prm.connectivity, prm.min_count)["n_components"]
+    rec = (MapComponent * max(cap, 1))()
+    m = C.c_size_t(0)
+    engine._check(lib().ndt_map_export_components(engine._h, C.byref(prm), rec if cap else None, cap, C.byref(m)))
+    dt = np.dtype([("root_ijk", np.int32, 3), ("n_voxels", np.int32), ("n_points", np.int64), ("min_ijk", np.int32, 3),
+                   ("max_ijk", np.int32, 3)])
+    a = np.frombuffer(rec, dtype=dt, count=max(cap, 1))[:m.value].copy()
+    return {k: a[k] for k in dt.names}
+
+
+def mapExportLabels(engine, connectivity=None, min_count=None):
+    """Every occupied voxel of the map in mapExportState()'s order: dict(ijk [m, 3] int32, label [m] int32; -1 for a
+    voxel with fewer than min_count points)."""
+    prm = _components_params(connectivity, min_count)
+    cap = engine.mapInfo()["n_voxels"]
+    ijk = np.zeros((cap, 3), dtype=np.int32)
+    label = np.zeros(cap, dtype=np.int32)
+    m = C.c_size_t(0)
+    engine._check(lib().ndt_map_export_labels(engine._h, C.byref(prm), ijk.ctypes.data if cap else None,
+                                           label.ctypes.data if cap else None, cap, C.byref(m)))
+    return dict(ijk=ijk[:m.value], label=label[:m.value])
+
+
+def mapExportLabelsDevice(engine, d_ijk, d_label, cap, connectivity=None, min_count=None):
+    """Into device arrays of `cap` rows (integer addresses, either may be None); returns the number of voxels."""
+    prm = _components_params(connectivity, min_count)
+    m = C.c_size_t(0)
+    engine._check(lib().ndt_map_export_labels_device(engine._h, C.byref(prm), d_ijk, d_label, int(cap), C.byref(m)))
+    return int(m.value)
+
+
+def mapLabelPoints(engine, cloud, pose=None, connectivity=None, min_count=None):
+    """The label of the map voxel each point of a host cloud (N x >= 3 float32) falls in once moved by `pose` (4x4 double,
+    as mapAdd moves it): int32 [N], -1 where there is none.  Returns (labels, n_labelled)."""
+    prm = _components_params(connectivity, min_count)
+    a = np.ascontiguousarray(cloud, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] < 3:
+        raise ValueError("cloud must be N x >=3 float32")
+    p = _finite_pose16_or_none(pose)
+    stride = a.strides[0] if len(a) else a.itemsize * a.shape[1]
+    out = np.full(len(a), -1, dtype=np.int32)
+    k = C.c_int64(0)
+    engine._check(lib().ndt_map_label_points(engine._h, C.byref(prm), a.ctypes.data if len(a) else None, len(a), stride,
+                                          None if p is None else _dp(p), out.ctypes.data if len(a) else None, C.byref(k)))
+    return out, int(k.value)
+
+
+def mapLabelPointsDevice(engine, dx, dy, dz, n, d_label, pose=None, connectivity=None, min_count=None):
+    """SoA float32 arrays and an int32 output in device memory (integer addresses), as mapLabelPoints; returns n_labelled."""
+    prm = _components_params(connectivity, min_count)
+    p = _finite_pose16_or_none(pose)
+    if int(n) > 0 and not (dx and dy and dz and d_label):
+        raise ValueError("the cloud and the label output are needed")
+    k = C.c_int64(0)
+    engine._check(lib().ndt_map_label_points_device(engine._h, C.byref(prm), dx, dy, dz, int(n), None if p is None else _dp(p),
+                                                 d_label, C.byref(k)))
+    return int(k.value)
+
+
+def mapRemoveComponents(engine, connectivity=None, min_count=None, min_voxels=1, min_points=0, keep_largest=0,
+                        remove_unlabelled=False, dry_run=False):
+    """Remove the components that do not survive: fewer than min_voxels voxels, fewer than min_points points, or not
+    among the keep_largest largest (0: off); remove_unlabelled also takes the voxels with fewer than min_count points;
+    dry_run only counts.  Returns dict(n_components, n_components_removed, n_removed, n_points_removed)."""
+    prm = _components_params(connectivity, min_count)
+    f = MapComponentFilter()
+    lib().ndt_map_component_filter_default_params(C.byref(f))
+    if int(min_voxels) < 1 or int(min_points) < 0 or int(keep_largest) < 0:
+        raise ValueError("min_voxels >= 1, min_points >= 0, keep_largest >= 0")
+    if int(min_voxels) > 2 ** 31 - 1 or int(keep_largest) > 2 ** 31 - 1 or int(min_points) > 2 ** 63 - 1:
+        raise ValueError("a filter field is out of range")
+    f.min_voxels, f.min_points, f.keep_largest = int(min_voxels), int(min_points), int(keep_largest)
+    f.remove_unlabelled, f.dry_run = int(bool(remove_unlabelled)), int(bool(dry_run))
+    r = MapRemoveComponentsResult()
+    engine._check(lib().ndt_map_remove_components(engine._h, C.byref(prm), C.byref(f), C.byref(r)))
+    return {name: int(getattr(r, name)) for name, _ in MapRemoveComponentsResult._fields_}
 
 
 # --- levels: the map at leaf * 2^L made from its own sums, and coarse-to-fine alignment over them (ndt_map_level_*,

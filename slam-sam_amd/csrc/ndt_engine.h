@@ -446,6 +446,18 @@ struct VoxelMap {
   DevBuf<unsigned int> cmarks;         // carve (ndt_map_carve.hip): one call's mark word per slot, `capacity` of them
   DevBuf<unsigned long long> cstat;    // ... and its counters
   PinBuf<unsigned long long> cstat_h;
+  // Components (ndt_map_components.hip): the union-find's parent word and the label per slot, `capacity` of each, the
+  // component table on the device and on the host, the survivor flag per component of a removal.  The labelling is
+  // cached: it stands while the map's `change`, the connectivity and min_count are those it was made under.
+  DevBuf<uint32_t> ccparent;
+  DevBuf<int32_t> cclabel;
+  DevBuf<ndt_map_component> cccomps;
+  DevBuf<int32_t> ccsurvive;
+  std::vector<ndt_map_component> cccomps_h;
+  ndt_map_components_info ccinfo{};
+  bool cc_valid = false;
+  uint64_t cc_change = 0;
+  int cc_connectivity = 0, cc_min_count = 0;
   void release() {
     map_free_table(tab);
     moments = false;
@@ -453,6 +465,9 @@ struct VoxelMap {
     stats.release(); nvox.release(); stats_h.release(); nvox_h.release(); xcounts.release();
     xslot.release(); xslot2.release(); xhi.release(); xout.release(); xcnt.release(); xijk.release(); xmom.release();
     tsel.release(); tsel_h.release(); cmarks.release(); cstat.release(); cstat_h.release(); lchild.release();
+    ccparent.release(); cclabel.release(); cccomps.release(); ccsurvive.release();
+    cccomps_h.clear(); cccomps_h.shrink_to_fit();
+    cc_valid = false;
   }
 };
 
