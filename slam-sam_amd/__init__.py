@@ -833,6 +833,18 @@ def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _host_cloud(cloud, intensity_column=None):
+    """A host cloud as the C ABI takes it: (the N x >= 3 contiguous float32 array, stride_bytes, intensity_offset_bytes;
+    -1: none).  NumPy reports strides of 0 for an empty array, and the calls that accept n = 0 still check the stride."""
+    a = np.ascontiguousarray(cloud, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] < 3:
+        raise ValueError("cloud must be N x >=3 float32")
+    if intensity_column is not None and not 3 <= int(intensity_column) < a.shape[1]:
+        raise ValueError("intensity_column outside the cloud's columns")
+    off = -1 if intensity_column is None else 4 * int(intensity_column)
+    return a, (a.strides[0] if len(a) else a.itemsize * a.shape[1]), off
+
+
 def unpack_eval(words):
     """32 packed doubles -> dict(score, gradient[6], hessian[6,6], nvtl_sum, n_with, n_pairs)."""
     w = np.ascontiguousarray(words, dtype=np.float64)
@@ -917,10 +929,7 @@ class NormalDistributionsTransform:
     # --- clouds ---
     @staticmethod
     def _xyz(a):
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] < 3:
-            raise ValueError("cloud must be N x >=3 float32")
-        return a
+        return _host_cloud(a)[0]
 
     def debugSortPairs(self, keys, end_bit):
         """Test seam: the voxel build's stable radix sort on caller keys -> (sorted keys, permutation)."""
@@ -999,8 +1008,8 @@ class NormalDistributionsTransform:
     # --- multi-grid target [RECALLED: tier4 MultiGridNormalDistributionsTransform] ---
     def addTarget(self, cloud, target_id):
         """Voxelises `cloud` on its own and keeps its leaves under `target_id`."""
-        a = self._xyz(cloud)
-        self._check(lib().ndt_multigrid_add_target(self._h, int(target_id), a.ctypes.data, len(a), a.strides[0]))
+        a, stride, _ = _host_cloud(cloud)
+        self._check(lib().ndt_multigrid_add_target(self._h, int(target_id), a.ctypes.data, len(a), stride))
 
     def removeTarget(self, target_id):
         self._check(lib().ndt_multigrid_remove_target(self._h, int(target_id)))
@@ -1014,9 +1023,7 @@ class NormalDistributionsTransform:
 
     # --- device-resident keyframe archive (ref: run/pipeline.cpp:784, run/pipeline_ligo_tc.cpp:519-529) ---
     def putKeyframe(self, kf_id, cloud):
-        a = self._xyz(cloud)
-        # (NumPy reports strides of 0 for an empty array; ndt_keyframe_put accepts n = 0 but checks the stride)
-        stride = a.strides[0] if len(a) else a.itemsize * a.shape[1]
+        a, stride, _ = _host_cloud(cloud)
         self._check(lib().ndt_keyframe_put(self._h, int(kf_id), a.ctypes.data, len(a), stride))
 
     # --- deskew: per-point times + a pose trajectory, the acquisition filter in the same pass ---
@@ -1030,16 +1037,10 @@ class NormalDistributionsTransform:
 
     @staticmethod
     def _scan(cloud, t, intensity_column):
-        a = np.ascontiguousarray(cloud, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] < 3:
-            raise ValueError("cloud must be N x >=3 float32")
+        a, stride, off = _host_cloud(cloud, intensity_column)
         tt = np.ascontiguousarray(t, dtype=np.float32).ravel()
         if len(tt) != len(a):
             raise ValueError("t must hold one time per point")
-        if intensity_column is not None and not 3 <= int(intensity_column) < a.shape[1]:
-            raise ValueError("intensity_column outside the cloud's columns")
-        off = -1 if intensity_column is None else 4 * int(intensity_column)
-        stride = a.strides[0] if len(a) else a.itemsize * a.shape[1]
         return a, tt, stride, off
 
     def deskew(self, cloud, t, knot_t, knot_poses, ref_pose=None, filter=None, intensity_column=None, with_index=False):
@@ -1282,15 +1283,12 @@ class NormalDistributionsTransform:
     def voxelDownsample(self, cloud, leaf, intensity_column=None):
         """Host cloud (N x >= 3 float32; intensity_column: index of the intensity field, 4 for pcl::PointXYZI's
         8-float layout) -> the filtered cloud in the same layout (other columns zero)."""
-        a = np.ascontiguousarray(cloud, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] < 3:
-            raise ValueError("cloud must be N x >=3 float32")
+        a, stride, off = _host_cloud(cloud, intensity_column)
         out = np.zeros_like(a)
         if len(a) == 0:
             return out
         m = C.c_size_t(0)
-        off = -1 if intensity_column is None else 4 * int(intensity_column)
-        self._check(lib().ndt_voxel_downsample(self._h, a.ctypes.data, len(a), a.strides[0], off, float(leaf),
+        self._check(lib().ndt_voxel_downsample(self._h, a.ctypes.data, len(a), stride, off, float(leaf),
                                                out.ctypes.data, len(out), C.byref(m)))
         return out[:m.value]
 
@@ -1314,12 +1312,8 @@ class NormalDistributionsTransform:
     def mapAdd(self, cloud, intensity_column=None, pose=None):
         """Host cloud (N x >= 3 float32; intensity_column as for voxelDownsample), moved by the 4x4 double `pose` if
         one is given, accumulated into the map."""
-        a = np.ascontiguousarray(cloud, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] < 3:
-            raise ValueError("cloud must be N x >=3 float32")
+        a, stride, off = _host_cloud(cloud, intensity_column)
         p = self._pose16_or_none(pose)
-        off = -1 if intensity_column is None else 4 * int(intensity_column)
-        stride = a.strides[0] if len(a) else a.itemsize * a.shape[1]
         self._check(lib().ndt_map_add(self._h, a.ctypes.data, len(a), stride, off, None if p is None else _dp(p)))
 
     def mapAddDevice(self, dx, dy, dz, n, d_intensity=None, pose=None):
@@ -1521,11 +1515,8 @@ class NormalDistributionsTransform:
         protect_min_count points or more stays (0: off), dry_run only counts.  None: the library's default.  Returns
         dict(n_rays, n_rays_skipped, n_steps, n_voxels_crossed, n_voxels_hit, n_removed, n_points_removed)."""
         o, prm = self._carve_args(origin, min_misses, keep_last, max_steps, protect_min_count, dry_run)
-        a = np.ascontiguousarray(cloud, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] < 3:
-            raise ValueError("cloud must be N x >=3 float32")
+        a, stride, _ = _host_cloud(cloud)
         p = self._pose16_or_none(pose)
-        stride = a.strides[0] if len(a) else a.itemsize * a.shape[1]
         r = MapCarveResult()
         self._check(lib().ndt_map_carve(self._h, a.ctypes.data if len(a) else None, len(a), stride, _fp(o),
                                         None if p is None else _dp(p), C.byref(prm), C.byref(r)))
@@ -2068,11 +2059,8 @@ def mapLabelPoints(engine, cloud, pose=None, connectivity=None, min_count=None):
     """The label of the map voxel each point of a host cloud (N x >= 3 float32) falls in once moved by `pose` (4x4 double,
     as mapAdd moves it): int32 [N], -1 where there is none.  Returns (labels, n_labelled)."""
     prm = _components_params(connectivity, min_count)
-    a = np.ascontiguousarray(cloud, dtype=np.float32)
-    if a.ndim != 2 or a.shape[1] < 3:
-        raise ValueError("cloud must be N x >=3 float32")
+    a, stride, _ = _host_cloud(cloud)
     p = _finite_pose16_or_none(pose)
-    stride = a.strides[0] if len(a) else a.itemsize * a.shape[1]
     out = np.full(len(a), -1, dtype=np.int32)
     k = C.c_int64(0)
     engine._check(lib().ndt_map_label_points(engine._h, C.byref(prm), a.ctypes.data if len(a) else None, len(a), stride,
@@ -2610,10 +2598,9 @@ def _sc_desc(ndt, desc):
 def scanContext(ndt, cloud, with_count=False):
     """The Scan Context descriptor of a host cloud (N x >= 3 float32, the sensor at the origin): desc [R, S] float32, with
     with_count also the points per bin [R, S] int32."""
-    a = ndt._xyz(cloud)
+    a, stride, _ = _host_cloud(cloud)
     R, S = _sc_shape(ndt)
     desc, count = np.zeros((R, S), np.float32), np.zeros((R, S), np.int32)
-    stride = a.strides[0] if len(a) else a.itemsize * a.shape[1]
     ndt._check(lib().ndt_scan_context(ndt._h, a.ctypes.data if len(a) else None, len(a), stride, _fp(desc),
                                       count.ctypes.data if with_count else None))
     return (desc, count) if with_count else desc

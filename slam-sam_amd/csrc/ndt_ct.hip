@@ -233,12 +233,6 @@ k_ct_apply(const float* __restrict__ sx, const float* __restrict__ sy, const flo
 
 int ct_blocks(size_t n) { return (int)((n + CT_THREADS - 1) / CT_THREADS); }
 
-bool ct_finite6(const double* p) {
-  for (int i = 0; i < 6; ++i)
-    if (!std::isfinite(p[i])) return false;
-  return true;
-}
-
 }  // namespace
 
 namespace engine {
@@ -353,9 +347,9 @@ int64_t ndt_source_times_info(const ndt_handle* h) { return h ? (int64_t)h->ct.n
 
 int ndt_eval_derivatives_ct(ndt_handle* h, const double begin_pose6[6], const double* poses6, int K, int compute_hessian,
                             double* out) {
-  if (!h || !begin_pose6 || !poses6 || !out || K <= 0 || !ct_finite6(begin_pose6)) return NDT_ERR_INVALID_ARG;
+  if (!h || !begin_pose6 || !poses6 || !out || K <= 0 || !all_finite(begin_pose6, 6)) return NDT_ERR_INVALID_ARG;
   for (int k = 0; k < K; ++k)
-    if (!ct_finite6(poses6 + 6 * (size_t)k)) return NDT_ERR_INVALID_ARG;
+    if (!all_finite(poses6 + 6 * (size_t)k, 6)) return NDT_ERR_INVALID_ARG;
   if (int rc = bind_device(h)) return rc;
   if (int rc = ct_ready(h)) return rc;
   if (int rc = ct_eval_raw(h, begin_pose6, poses6, K, compute_hessian != 0, out, /*fit=*/true)) return rc;
@@ -364,7 +358,7 @@ int ndt_eval_derivatives_ct(ndt_handle* h, const double begin_pose6[6], const do
 }
 
 int ndt_align_ct(ndt_handle* h, const double begin_pose6[6], const float guess[16], ndt_result* out) {
-  if (!h || !begin_pose6 || !guess || !out || !ct_finite6(begin_pose6)) return NDT_ERR_INVALID_ARG;
+  if (!h || !begin_pose6 || !guess || !out || !all_finite(begin_pose6, 6)) return NDT_ERR_INVALID_ARG;
   std::memset(out, 0, sizeof(*out));   // what every failure before the loop leaves: the guess, not converged
   std::memcpy(out->final_transformation, guess, sizeof(float) * 16);
   if (int rc = bind_device(h)) return rc;
@@ -374,7 +368,7 @@ int ndt_align_ct(ndt_handle* h, const double begin_pose6[6], const float guess[1
   // with a slightly negative roll starts on the other triple): the objective does not change under the loop
   double b[6], g6[6];
   matrix_to_pose(guess, g6);
-  if (ct_finite6(g6)) ct_fit_begin(begin_pose6, g6 + 3, b);
+  if (all_finite(g6, 6)) ct_fit_begin(begin_pose6, g6 + 3, b);
   else std::memcpy(b, begin_pose6, sizeof(b));
   return lane_align(h, (int64_t)h->n_src, guess, [h, &b](const double* p, bool need_h, double* words) {
     return ct_eval_raw(h, b, p, 1, need_h, words, /*fit=*/false);
@@ -383,8 +377,8 @@ int ndt_align_ct(ndt_handle* h, const double begin_pose6[6], const float guess[1
 
 int ndt_transform_source_ct_device(ndt_handle* h, const double begin_pose6[6], const double end_pose6[6], int frame, float* ox,
                                    float* oy, float* oz, size_t cap) {
-  if (!h || !begin_pose6 || !end_pose6 || !ox || !oy || !oz || (frame != 0 && frame != 1) || !ct_finite6(begin_pose6) ||
-      !ct_finite6(end_pose6))
+  if (!h || !begin_pose6 || !end_pose6 || !ox || !oy || !oz || (frame != 0 && frame != 1) || !all_finite(begin_pose6, 6) ||
+      !all_finite(end_pose6, 6))
     return NDT_ERR_INVALID_ARG;
   if (int rc = bind_device(h)) return rc;
   if (int rc = ct_source_ready(h)) return rc;
@@ -394,8 +388,8 @@ int ndt_transform_source_ct_device(ndt_handle* h, const double begin_pose6[6], c
 
 int ndt_transform_source_ct(ndt_handle* h, const double begin_pose6[6], const double end_pose6[6], int frame, float* out_xyz,
                             size_t cap_points) {
-  if (!h || !begin_pose6 || !end_pose6 || !out_xyz || (frame != 0 && frame != 1) || !ct_finite6(begin_pose6) ||
-      !ct_finite6(end_pose6))
+  if (!h || !begin_pose6 || !end_pose6 || !out_xyz || (frame != 0 && frame != 1) || !all_finite(begin_pose6, 6) ||
+      !all_finite(end_pose6, 6))
     return NDT_ERR_INVALID_ARG;
   if (int rc = bind_device(h)) return rc;
   if (int rc = ct_source_ready(h)) return rc;
@@ -404,14 +398,7 @@ int ndt_transform_source_ct(ndt_handle* h, const double begin_pose6[6], const do
   HIP_TRY(h, h->ct.xyz.ensure(3 * n));
   float* d = h->ct.xyz.p;
   if (int rc = ct_apply(h, begin_pose6, end_pose6, frame, d, d + n, d + 2 * n)) return rc;
-  std::vector<float> soa(3 * n);
-  HIP_TRY(h, hipMemcpy(soa.data(), d, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < n; ++i) {
-    out_xyz[3 * i] = soa[i];
-    out_xyz[3 * i + 1] = soa[n + i];
-    out_xyz[3 * i + 2] = soa[2 * n + i];
-  }
-  return NDT_OK;
+  return download_strided(h, d, n, n, cap_points, out_xyz, 3 * sizeof(float), -1);
 }
 
 }  // extern "C"

@@ -276,9 +276,7 @@ extern "C" {
 int ndt_set_source_distributions(ndt_handle* h, const int32_t* count, const double* moments9, size_t n) {
   if (!h || (n && (!count || !moments9)) || d2d_too_many(n)) return NDT_ERR_INVALID_ARG;
   for (size_t r = 0; r < n; ++r) {   // (before the handle is looked at: a refused call leaves the previous source)
-    if (count[r] < 1) return NDT_ERR_INVALID_ARG;
-    for (int a = 0; a < 9; ++a)
-      if (!std::isfinite(moments9[9 * r + a])) return NDT_ERR_INVALID_ARG;
+    if (count[r] < 1 || !all_finite(moments9 + 9 * r, 9)) return NDT_ERR_INVALID_ARG;
   }
   if (n == 0) { d2d_clear(h); return NDT_OK; }
   if (int rc = bind_device(h)) return rc;
@@ -357,8 +355,7 @@ int64_t ndt_export_source_distributions(ndt_handle* h, double* mean3, double* co
 
 int ndt_eval_derivatives_d2d(ndt_handle* h, const double* poses6, int K, int compute_hessian, double* out) {
   if (!h || !poses6 || !out || K <= 0) return NDT_ERR_INVALID_ARG;
-  for (int i = 0; i < 6 * K; ++i)
-    if (!std::isfinite(poses6[i])) return NDT_ERR_INVALID_ARG;
+  if (!all_finite(poses6, 6 * (size_t)K)) return NDT_ERR_INVALID_ARG;
   if (int rc = bind_device(h)) return rc;
   if (int rc = d2d_ready(h)) return rc;
   if (int rc = d2d_eval_raw(h, poses6, K, compute_hessian != 0, out)) return rc;

@@ -7,7 +7,8 @@
 // and the segment is a binary search in it.  Integer offsets only, no atomics.  Everything on the engine's stream;
 // the target, the source, the align state, the history and the counters of the handle are not touched.
 // The predicate (dsk_keep), the knot table's LDS copy and the motion (dsk_move) live in ndt_deskew_device.h, shared with
-// ndt_unproject.hip; so do the host's upload of the knot table and the strided download of a result (this file).
+// ndt_unproject.hip; the host's upload of the knot table is in this file, the strided download of a result with the
+// rest of the host-cloud boundary (ndt_host_cloud.h, ndt_handoff.hip).
 #include "ndt_engine.h"
 #include "ndt_compact_device.h"
 #include "ndt_deskew_device.h"
@@ -98,28 +99,6 @@ int knots_upload(ndt_handle* h, const traj::KnotRow* rows, int n_knots) {
   return NDT_OK;
 }
 
-int download_strided(ndt_handle* h, const float* d_cols, size_t col_stride, const float* d_t, const int32_t* d_index, size_t m,
-                     size_t cap, float* back, float* out, size_t stride_bytes, long intensity_offset_bytes, float* t_out,
-                     int32_t* index_out) {
-  if (m > cap) return over_capacity(h, m);
-  if (m == 0) return NDT_OK;
-  const bool has_i = intensity_offset_bytes >= 0;
-  const int cols = has_i ? 4 : 3;
-  for (int a = 0; a < cols; ++a)
-    HIP_TRY(h, hipMemcpyAsync(back + (size_t)a * m, d_cols + (size_t)a * col_stride, m * sizeof(float), hipMemcpyDeviceToHost,
-                              h->stream));
-  if (t_out) HIP_TRY(h, hipMemcpyAsync(t_out, d_t, m * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (index_out) HIP_TRY(h, hipMemcpyAsync(index_out, d_index, m * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  char* ob = reinterpret_cast<char*>(out);
-  for (size_t i = 0; i < m; ++i) {
-    float* p = reinterpret_cast<float*>(ob + i * stride_bytes);
-    p[0] = back[i]; p[1] = back[m + i]; p[2] = back[2 * m + i];
-    if (has_i) *reinterpret_cast<float*>(ob + i * stride_bytes + intensity_offset_bytes) = back[3 * m + i];
-  }
-  return NDT_OK;
-}
-
 namespace {
 
 // The trajectory's table to the device (knots_upload), then the launches; awaited.  dx .. dt (and di, ox .. o_index) are
@@ -173,12 +152,8 @@ int deskew_upload(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes
   if (words > b.stage.cap) HIP_TRY(h, b.stage.ensure(5 * n + (5 * n) / 8 + 4096));
   HIP_TRY(h, b.in.ensure(5 * n));
   float* sx = b.stage.h, *sy = sx + n, *sz = sy + n, *st = sz + n, *si = st + n;
-  const char* base = reinterpret_cast<const char*>(xyz);
-  for (size_t i = 0; i < n; ++i) {
-    const float* p = reinterpret_cast<const float*>(base + i * stride_bytes);
-    sx[i] = p[0]; sy[i] = p[1]; sz[i] = p[2];
-    if (has_i) si[i] = *reinterpret_cast<const float*>(base + i * stride_bytes + intensity_offset_bytes);
-  }
+  gather_xyz(xyz, n, stride_bytes, sx, sy, sz);
+  if (has_i) gather_column(xyz, n, stride_bytes, (size_t)intensity_offset_bytes, si);
   std::memcpy(st, t, n * sizeof(float));
   HIP_TRY(h, hipMemcpyAsync(b.in.p, b.stage.h, words * sizeof(float), hipMemcpyHostToDevice, h->stream));
   return NDT_OK;
@@ -250,8 +225,10 @@ int ndt_deskew(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, l
                      o + 2 * n, has_i ? o + 3 * n : nullptr, index_out ? b.index.p : nullptr, n, n_out);
   if (rc) return rc;
   // (the staging is free again: the upload out of it has been awaited)
-  return download_strided(h, o, n, nullptr, b.index.p, *n_out, cap, b.stage.h, out, stride_bytes, intensity_offset_bytes, nullptr,
-                          index_out);
+  SideColumns side;
+  side.d_i32 = b.index.p;
+  side.i32_out = index_out;
+  return download_strided(h, o, n, *n_out, cap, out, stride_bytes, intensity_offset_bytes, b.stage.h, side);
 }
 
 int ndt_keyframe_put_deskewed(ndt_handle* h, int64_t id, const float* xyz, size_t n, size_t stride_bytes,

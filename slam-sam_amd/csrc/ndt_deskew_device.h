@@ -1,7 +1,7 @@
 // ndt_deskew_device.h -- what the kernels of ndt_deskew.hip and ndt_unproject.hip share (internal; HIP): the acquisition
-// filter's predicate, the block's copy of the knot table and the motion of one point, plus the two argument checks
-// their host sides have in common.  One definition each: the unprojection's contract is bit equality with
-// ndt_deskew_device on the same points.
+// filter's predicate, the block's copy of the knot table and the motion of one point, plus the overlap check their host
+// sides have in common.  One definition each: the unprojection's contract is bit equality with ndt_deskew_device on the
+// same points.  The layout rule of a host cloud is in ndt_host_cloud.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -55,13 +55,6 @@ inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
   if (!a || !b || na == 0 || nb == 0) return false;
   const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
   return pa < pb + nb && pb < pa + na;
-}
-
-// a strided host cloud: x, y, z at the start of every point, the intensity (offset < 0: none) behind them
-inline bool layout_valid(size_t stride_bytes, long intensity_offset_bytes) {
-  if (stride_bytes < 12 || stride_bytes % 4) return false;
-  return intensity_offset_bytes < 0 || (intensity_offset_bytes % 4 == 0 && intensity_offset_bytes >= 12 &&
-                                        (size_t)intensity_offset_bytes + 4 <= stride_bytes);
 }
 
 }  // namespace engine

@@ -55,6 +55,7 @@
 
 #include "../../include/ndt_hip.h"
 #include "ndt_comm.h"
+#include "ndt_host_cloud.h"
 #include "ndt_keepwarm.h"
 #include "ndt_kernels.h"
 #include "ndt_newton.h"
@@ -800,13 +801,23 @@ int compact_total(ndt_handle* h, int nb, size_t cap, size_t* n_out);
 // ndt_deskew.hip: rows[0 .. n_knots) -> h->knots through its pinned staging, enqueued on the engine's stream (n_knots = 0:
 // the table is only allocated)
 int knots_upload(ndt_handle* h, const traj::KnotRow* rows, int n_knots);
-// ndt_deskew.hip, for the host forms of filter, deskew and unprojection: the first m points of a device result -- columns
-// [x | y | z | intensity] col_stride floats apart at d_cols, d_t and d_index beside them -- to a strided host cloud
-// (layout_valid) through the host staging `back` (m floats per column), t_out and index_out (null: not wanted) directly;
-// awaited.  m > cap is refused, m = 0 copies nothing.
-int download_strided(ndt_handle* h, const float* d_cols, size_t col_stride, const float* d_t, const int32_t* d_index, size_t m,
-                     size_t cap, float* back, float* out, size_t stride_bytes, long intensity_offset_bytes, float* t_out,
-                     int32_t* index_out);
+// ---- the host-cloud boundary's engine half (ndt_handoff.hip; the pure host half and the layout rule: ndt_host_cloud.h) ----
+// upload_column: the float byte_offset into every point of a strided host cloud -> dst[0 .. n), gathered into pageable
+// memory and copied with a blocking copy (the intensity column of the host forms that take one)
+int upload_column(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, size_t byte_offset, DevBuf<float>& dst);
+// the tight arrays of a device result that go down beside its cloud, m elements each: one of floats (the points' times)
+// and one of int32 (the points' indices; ndt_map_export's per-voxel counts).  A null host pointer: not wanted.
+struct SideColumns {
+  const float* d_f32 = nullptr;
+  float* f32_out = nullptr;
+  const int32_t* d_i32 = nullptr;
+  int32_t* i32_out = nullptr;
+};
+// download_strided: the first m points of a device result -- columns [x | y | z | intensity] col_stride floats apart at
+// d_cols -- to a strided host cloud (layout_valid) through the host staging `back` (m floats per column; null: a vector
+// of this call), the side columns directly; awaited.  m > cap is refused with nothing written, m = 0 copies nothing.
+int download_strided(ndt_handle* h, const float* d_cols, size_t col_stride, size_t m, size_t cap, float* out, size_t stride_bytes,
+                     long intensity_offset_bytes, float* back = nullptr, const SideColumns& side = SideColumns());
 // ndt_unproject.hip, for the packet forms (ndt_packets.hip): what every unprojection checks before anything is written
 // (the model, the gate, the trajectory into rows), and the launches on device arrays whose arguments have been checked
 int unproject_check(ndt_handle* h, const ndt_range_gate* gate, const double* knot_t, const double* knot_poses16, int n_knots,

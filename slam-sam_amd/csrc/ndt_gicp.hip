@@ -281,12 +281,6 @@ k_gicp_eval(const double* __restrict__ sgauss, const int32_t* __restrict__ pair,
 
 unsigned blocks_of(size_t n, int threads) { return (unsigned)((n + threads - 1) / threads); }
 
-bool finite6(const double* p) {
-  for (int i = 0; i < 6; ++i)
-    if (!std::isfinite(p[i])) return false;
-  return true;
-}
-
 bool gicp_params_valid(const ndt_gicp_params* p) {
   return p && p->k_neighbours >= GICP_MIN_NEIGHBOURS && p->k_neighbours <= 32 && p->max_neighbour_distance > 0.0 &&
          p->covariance_epsilon > 0.0 && p->covariance_epsilon <= 1.0 && p->max_correspondence_distance > 0.0 &&
@@ -520,7 +514,7 @@ int64_t ndt_gicp_export_covariances(ndt_handle* h, int which, double* mean3, dou
 }
 
 int ndt_gicp_pair(ndt_handle* h, const double pose6[6], int64_t* n_pairs) {
-  if (!h || !pose6 || !finite6(pose6)) return NDT_ERR_INVALID_ARG;
+  if (!h || !pose6 || !all_finite(pose6, 6)) return NDT_ERR_INVALID_ARG;
   if (int rc = bind_device(h)) return rc;
   if (int rc = gicp_settle(h)) return rc;
   if (int rc = gicp_target_ready(h)) return rc;
@@ -546,7 +540,7 @@ int64_t ndt_gicp_export_pairs(ndt_handle* h, int32_t* target_index, float* d2, s
 int ndt_eval_derivatives_gicp(ndt_handle* h, const double* poses6, int K, int compute_hessian, double* out) {
   if (!h || !poses6 || !out || K <= 0) return NDT_ERR_INVALID_ARG;
   for (int k = 0; k < K; ++k)
-    if (!finite6(poses6 + 6 * (size_t)k)) return NDT_ERR_INVALID_ARG;
+    if (!all_finite(poses6 + 6 * (size_t)k, 6)) return NDT_ERR_INVALID_ARG;
   if (int rc = bind_device(h)) return rc;
   if (int rc = gicp_eval_ready(h)) return rc;
   if (int rc = gicp_eval_raw(h, poses6, K, compute_hessian != 0, out)) return rc;
@@ -576,7 +570,7 @@ int ndt_align_gicp(ndt_handle* h, const float guess[16], ndt_result* out, ndt_gi
   std::memcpy(T, guess, sizeof(T));
   double p[6];
   matrix_to_pose(T, p);
-  if (!finite6(p)) return fail(h, NDT_ERR_INVALID_ARG, "GICP: the guess is not a finite pose");
+  if (!all_finite(p, 6)) return fail(h, NDT_ERR_INVALID_ARG, "GICP: the guess is not a finite pose");
   ndt_result r;
   int outer = 0, inner = 0, evals = 0, reused = 0;
   bool converged = false;

@@ -79,6 +79,43 @@ int upload_soa(ndt_handle* h, ndt_handle::UploadLane& lane, hipStream_t stream, 
   return NDT_OK;
 }
 
+// ---- the rest of the host-cloud boundary (ndt_host_cloud.h holds the layout rule and the host loops) ----------------
+int upload_column(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, size_t byte_offset, DevBuf<float>& dst) {
+  std::vector<float> tmp(n);
+  gather_column(xyz, n, stride_bytes, byte_offset, tmp.data());
+  HIP_TRY(h, dst.ensure(n));
+  HIP_TRY(h, hipMemcpy(dst.p, tmp.data(), n * sizeof(float), hipMemcpyHostToDevice));
+  return NDT_OK;
+}
+
+int download_strided(ndt_handle* h, const float* d_cols, size_t col_stride, size_t m, size_t cap, float* out, size_t stride_bytes,
+                     long intensity_offset_bytes, float* back, const SideColumns& side) {
+  if (m > cap) return over_capacity(h, m);
+  if (m == 0) return NDT_OK;
+  const size_t cols = intensity_offset_bytes >= 0 ? 4 : 3;
+  // with the caller's pinned staging the copies are enqueued and awaited once; without one they go into a vector of this
+  // call by blocking copies (the result has been awaited by then) -- each as the host forms made them before they met here
+  const bool pinned = back != nullptr;
+  std::vector<float> local;
+  if (!pinned) {
+    local.resize(cols * m);
+    back = local.data();
+  }
+  auto copy = [&](void* dst, const void* src, size_t bytes) {
+    return pinned ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+  };
+  if (!pinned && col_stride == m) {   // one block of columns: the one blocking copy of ndt_map_export and ndt_transform_source_ct
+    HIP_TRY(h, copy(back, d_cols, cols * m * sizeof(float)));
+  } else {
+    for (size_t a = 0; a < cols; ++a) HIP_TRY(h, copy(back + a * m, d_cols + a * col_stride, m * sizeof(float)));
+  }
+  if (side.f32_out) HIP_TRY(h, copy(side.f32_out, side.d_f32, m * sizeof(float)));
+  if (side.i32_out) HIP_TRY(h, copy(side.i32_out, side.d_i32, m * sizeof(int32_t)));
+  if (pinned) HIP_TRY(h, hipStreamSynchronize(h->stream));
+  scatter_cloud(back, m, m, out, stride_bytes, intensity_offset_bytes);
+  return NDT_OK;
+}
+
 // The voxel-grid build proper; x/y/z are device pointers.
 //
 // Steady state ("optimistic"): the dense grid and every scratch buffer exist from an earlier
@@ -531,7 +568,7 @@ void settle_discard(ndt_handle* h) {
 extern "C" {
 
 int ndt_set_target(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes) {
-  if (!h || (!xyz && n) || stride_bytes < 12 || stride_bytes % 4) return NDT_ERR_INVALID_ARG;
+  if (!h || (!xyz && n) || !layout_valid(stride_bytes, -1)) return NDT_ERR_INVALID_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
   settle_discard(h);
@@ -576,7 +613,7 @@ int ndt_set_target_device_deferred(ndt_handle* h, const float* dx, const float* 
 }
 
 int ndt_set_source(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes) {
-  if (!h || (!xyz && n) || stride_bytes < 12 || stride_bytes % 4) return NDT_ERR_INVALID_ARG;
+  if (!h || (!xyz && n) || !layout_valid(stride_bytes, -1)) return NDT_ERR_INVALID_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
   h->vx = h->vy = h->vz = nullptr;

@@ -34,7 +34,7 @@ extern "C" {
 // addTarget(cloud, id): the cloud is voxelised ON ITS OWN by the ordinary build (same kernels, same
 // leaf statistics as setInputTarget) and its valid leaves are kept under `id`.
 int ndt_multigrid_add_target(ndt_handle* h, int64_t id, const float* xyz, size_t n, size_t stride_bytes) {
-  if (!h || !xyz || n == 0 || stride_bytes < 12 || stride_bytes % 4) return NDT_ERR_INVALID_ARG;
+  if (!h || !xyz || n == 0 || !layout_valid(stride_bytes, -1)) return NDT_ERR_INVALID_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
   settle_discard(h);
@@ -175,7 +175,7 @@ int ndt_multigrid_create_kdtree(ndt_handle* h) {
 }
 
 int ndt_keyframe_put(ndt_handle* h, int64_t id, const float* xyz, size_t n, size_t stride_bytes) {
-  if (!h || (!xyz && n) || stride_bytes < 12 || stride_bytes % 4) return NDT_ERR_INVALID_ARG;
+  if (!h || (!xyz && n) || !layout_valid(stride_bytes, -1)) return NDT_ERR_INVALID_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
   ndt_handle::Keyframe& kf = keyframe_claim(h, id, n);
@@ -301,9 +301,7 @@ int ndt_voxel_downsample_device(ndt_handle* h, const float* dx, const float* dy,
 
 int ndt_voxel_downsample(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, long intensity_offset_bytes,
                          float leaf, float* out, size_t cap, size_t* n_out) {
-  if (!h || !n_out || (!xyz && n) || (!out && cap) || stride_bytes < 12 || stride_bytes % 4 || !(leaf > 1e-6f) ||
-      (intensity_offset_bytes >= 0 && (intensity_offset_bytes % 4 || (size_t)intensity_offset_bytes + 4 > stride_bytes ||
-                                       intensity_offset_bytes < 12)))
+  if (!h || !n_out || (!xyz && n) || (!out && cap) || !layout_valid(stride_bytes, intensity_offset_bytes) || !(leaf > 1e-6f))
     return NDT_ERR_INVALID_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
@@ -314,14 +312,9 @@ int ndt_voxel_downsample(ndt_handle* h, const float* xyz, size_t n, size_t strid
   auto done = [&](int code) { x.release(); y.release(); z.release(); in_i.release(); o.release(); return code; };
   rc = upload_soa(h, h->lane_t, h->stream, xyz, nullptr, nullptr, nullptr, n, stride_bytes, x, y, z, true);
   if (rc) return done(rc);
-  std::vector<float> tmp;
   if (has_i) {
-    tmp.resize(n);
-    const char* base = reinterpret_cast<const char*>(xyz) + intensity_offset_bytes;
-    for (size_t i = 0; i < n; ++i) tmp[i] = *reinterpret_cast<const float*>(base + i * stride_bytes);
-    hipError_t e = in_i.ensure(n);
-    if (e == hipSuccess) e = hipMemcpy(in_i.p, tmp.data(), n * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return done(fail(h, NDT_ERR_HIP, hipGetErrorString(e)));
+    rc = upload_column(h, xyz, n, stride_bytes, (size_t)intensity_offset_bytes, in_i);
+    if (rc) return done(rc);
   }
   const size_t ocap = std::min(cap, n);
   hipError_t e = o.ensure(4 * std::max<size_t>(ocap, 1));
@@ -329,18 +322,8 @@ int ndt_voxel_downsample(ndt_handle* h, const float* xyz, size_t n, size_t strid
   float* ox = o.p, *oy = o.p + ocap, *oz = o.p + 2 * ocap, *oi = o.p + 3 * ocap;
   rc = voxel_downsample_device_impl(h, x.p, y.p, z.p, has_i ? in_i.p : nullptr, n, leaf, ox, oy, oz, has_i ? oi : nullptr, ocap, n_out);
   if (rc) return done(rc);
-  const size_t m = *n_out;
-  std::vector<float> back(4 * ocap);
-  e = hipMemcpy(back.data(), o.p, (has_i ? 4 : 3) * ocap * sizeof(float), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return done(fail(h, NDT_ERR_HIP, hipGetErrorString(e)));
-  char* ob = reinterpret_cast<char*>(out);
-  for (size_t i = 0; i < m; ++i) {
-    float* p = reinterpret_cast<float*>(ob + i * stride_bytes);
-    p[0] = back[i]; p[1] = back[ocap + i]; p[2] = back[2 * ocap + i];
-    if (has_i) *reinterpret_cast<float*>(ob + i * stride_bytes + intensity_offset_bytes) = back[3 * ocap + i];
-  }
-  return done(NDT_OK);
+  // (a result above the capacity has been refused by the device form: nothing is written then)
+  return done(download_strided(h, o.p, ocap, *n_out, ocap, out, stride_bytes, intensity_offset_bytes));
 }
-
 
 }  // extern "C"

@@ -651,13 +651,9 @@ int map_box_floor(float v, float inv_leaf) {
   return f <= -MAP_LIMIT ? -MAP_BIAS : f >= MAP_LIMIT ? MAP_BIAS : (int)f;
 }
 
-bool pose_finite(const double p[16]) {
-  for (int i = 0; i < 16; ++i)
-    if (!std::isfinite(p[i])) return false;
-  return true;
-}
+bool pose_finite(const double p[16]) { return all_finite(p, 16); }
 
-bool finite3(const float v[3]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+bool finite3(const float v[3]) { return all_finite(v, 3); }
 
 int no_moments(ndt_handle* h) { return fail(h, NDT_ERR_INVALID_ARG, "the map keeps no moments (ndt_map_enable_moments right after ndt_map_reset)"); }
 
@@ -793,10 +789,7 @@ int ndt_map_add_device(ndt_handle* h, const float* dx, const float* dy, const fl
 }
 
 int ndt_map_add(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, long intensity_offset_bytes, const double* pose16) {
-  if (!h || (!xyz && n) || stride_bytes < 12 || stride_bytes % 4 ||
-      (intensity_offset_bytes >= 0 && (intensity_offset_bytes % 4 || (size_t)intensity_offset_bytes + 4 > stride_bytes ||
-                                       intensity_offset_bytes < 12)))
-    return NDT_ERR_INVALID_ARG;
+  if (!h || (!xyz && n) || !layout_valid(stride_bytes, intensity_offset_bytes)) return NDT_ERR_INVALID_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
   if (!h->map) return no_map(h);
@@ -809,11 +802,8 @@ int ndt_map_add(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, 
   rc = upload_soa(h, h->lane_t, h->stream, xyz, nullptr, nullptr, nullptr, n, stride_bytes, m.ux, m.uy, m.uz, true);
   if (rc) return rc;
   if (has_i) {
-    std::vector<float> tmp(n);
-    const char* base = reinterpret_cast<const char*>(xyz) + intensity_offset_bytes;
-    for (size_t i = 0; i < n; ++i) tmp[i] = *reinterpret_cast<const float*>(base + i * stride_bytes);
-    HIP_TRY(h, m.ui.ensure(n));
-    HIP_TRY(h, hipMemcpy(m.ui.p, tmp.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    rc = upload_column(h, xyz, n, stride_bytes, (size_t)intensity_offset_bytes, m.ui);
+    if (rc) return rc;
   }
   return map_add_device(h, m.ux.p, m.uy.p, m.uz.p, has_i ? m.ui.p : nullptr, n, pose16);
 }
@@ -874,10 +864,7 @@ int ndt_map_export_device(ndt_handle* h, int min_points, float* ox, float* oy, f
 
 int ndt_map_export(ndt_handle* h, int min_points, float* out, size_t stride_bytes, long intensity_offset_bytes, int32_t* count_out,
                    size_t cap, size_t* n_out) {
-  if (!h || !n_out || (!out && cap) || stride_bytes < 12 || stride_bytes % 4 ||
-      (intensity_offset_bytes >= 0 && (intensity_offset_bytes % 4 || (size_t)intensity_offset_bytes + 4 > stride_bytes ||
-                                       intensity_offset_bytes < 12)))
-    return NDT_ERR_INVALID_ARG;
+  if (!h || !n_out || (!out && cap) || !layout_valid(stride_bytes, intensity_offset_bytes)) return NDT_ERR_INVALID_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
   if (!h->map) return no_map(h);
@@ -888,23 +875,18 @@ int ndt_map_export(ndt_handle* h, int min_points, float* out, size_t stride_byte
   if (rc) return rc;
   *n_out = total;
   if (total == 0) return NDT_OK;
-  const size_t w = std::min(total, cap);
+  const size_t w = std::min(total, cap);   // the voxels that fit are written, a shortfall is reported behind them
   if (w) {
-    const bool has_i = intensity_offset_bytes >= 0;
     HIP_TRY(h, m.xout.ensure(4 * w));
     HIP_TRY(h, m.xcnt.ensure(w));
     float* o = m.xout.p;
-    rc = map_export_write(h, min_points, total, o, o + w, o + 2 * w, has_i ? o + 3 * w : nullptr, m.xcnt.p, w);
+    rc = map_export_write(h, min_points, total, o, o + w, o + 2 * w, intensity_offset_bytes >= 0 ? o + 3 * w : nullptr, m.xcnt.p, w);
     if (rc) return rc;
-    std::vector<float> back(4 * w);
-    HIP_TRY(h, hipMemcpy(back.data(), o, (has_i ? 4 : 3) * w * sizeof(float), hipMemcpyDeviceToHost));
-    if (count_out) HIP_TRY(h, hipMemcpy(count_out, m.xcnt.p, w * sizeof(int32_t), hipMemcpyDeviceToHost));
-    char* ob = reinterpret_cast<char*>(out);
-    for (size_t i = 0; i < w; ++i) {
-      float* p = reinterpret_cast<float*>(ob + i * stride_bytes);
-      p[0] = back[i]; p[1] = back[w + i]; p[2] = back[2 * w + i];
-      if (has_i) *reinterpret_cast<float*>(ob + i * stride_bytes + intensity_offset_bytes) = back[3 * w + i];
-    }
+    SideColumns counts;
+    counts.d_i32 = m.xcnt.p;
+    counts.i32_out = count_out;
+    rc = download_strided(h, o, w, w, w, out, stride_bytes, intensity_offset_bytes, nullptr, counts);
+    if (rc) return rc;
   }
   if (total > cap) return fail(h, NDT_ERR_INVALID_ARG, "output capacity too small: " + std::to_string(total) + " voxels");
   return NDT_OK;

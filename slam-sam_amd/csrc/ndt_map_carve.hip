@@ -279,7 +279,7 @@ int ndt_map_carve_device(ndt_handle* h, const float* dx, const float* dy, const 
 
 int ndt_map_carve(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, const float origin[3], const double* pose16,
                   const ndt_map_carve_params* prm, ndt_map_carve_result* out) {
-  if (!h || (!xyz && n) || stride_bytes < 12 || stride_bytes % 4 || !carve_args_ok(origin, prm)) return NDT_ERR_INVALID_ARG;
+  if (!h || (!xyz && n) || !layout_valid(stride_bytes, -1) || !carve_args_ok(origin, prm)) return NDT_ERR_INVALID_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
   if (!h->map) return no_map(h);

@@ -625,7 +625,7 @@ int ndt_map_label_points_device(ndt_handle* h, const ndt_map_components_params* 
 
 int ndt_map_label_points(ndt_handle* h, const ndt_map_components_params* prm, const float* xyz, size_t n, size_t stride_bytes,
                          const double* pose16, int32_t* label_out, int64_t* n_labelled) {
-  if (!h || !cc_params_valid(prm) || ((!xyz || !label_out) && n) || stride_bytes < 12 || stride_bytes % 4 ||
+  if (!h || !cc_params_valid(prm) || ((!xyz || !label_out) && n) || !layout_valid(stride_bytes, -1) ||
       (pose16 && !pose_finite(pose16)))
     return NDT_ERR_INVALID_ARG;
   int rc = cc_enter(h);

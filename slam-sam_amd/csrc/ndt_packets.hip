@@ -348,8 +348,12 @@ int ndt_unproject_packet_frame(ndt_handle* h, const ndt_range_gate* gate_or_null
   if (*n_out > cap) return over_capacity(h, *n_out);
   rc = download_extras(h, filter_or_null ? b.index.p : nullptr, *n_out, signal_out, nir_out);
   if (rc) return rc;
-  return download_strided(h, o, n, o + 4 * n, b.index.p, *n_out, cap, reinterpret_cast<float*>(b.stage.h), out, stride_bytes,
-                          intensity_offset_bytes, t_out, index_out);
+  SideColumns side;
+  side.d_f32 = o + 4 * n;
+  side.f32_out = t_out;
+  side.d_i32 = b.index.p;
+  side.i32_out = index_out;
+  return download_strided(h, o, n, *n_out, cap, out, stride_bytes, intensity_offset_bytes, reinterpret_cast<float*>(b.stage.h), side);
 }
 
 int ndt_keyframe_put_from_packets(ndt_handle* h, int64_t id, const ndt_range_gate* gate_or_null, const double* knot_t,

@@ -225,9 +225,11 @@ int ndt_filter_source(ndt_handle* h, const float T[16], double min_score, int ke
   HIP_TRY(h, ps.index.ensure(n));
   rc = filter_device(h, T, min_score, keep_below, ps.out.p, ps.out.p + n, ps.out.p + 2 * n, ps.index.p, n, n_out);
   if (rc) return rc;
-  std::vector<float> back(3 * *n_out);   // the staging; a tight cloud is a stride of 12 bytes without intensity
-  return download_strided(h, ps.out.p, n, nullptr, ps.index.p, *n_out, cap_points, back.data(), out_xyz, 3 * sizeof(float), -1,
-                          nullptr, index_out);
+  // (a tight cloud is a stride of 12 bytes without intensity)
+  SideColumns side;
+  side.d_i32 = ps.index.p;
+  side.i32_out = index_out;
+  return download_strided(h, ps.out.p, n, *n_out, cap_points, out_xyz, 3 * sizeof(float), -1, nullptr, side);
 }
 
 }  // extern "C"

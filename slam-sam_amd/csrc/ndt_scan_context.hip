@@ -354,7 +354,7 @@ int ndt_scan_context_device(ndt_handle* h, const float* dx, const float* dy, con
 }
 
 int ndt_scan_context(ndt_handle* h, const float* xyz, size_t n, size_t stride_bytes, float* desc, int32_t* count_or_null) {
-  if (!h || !desc || (!xyz && n) || stride_bytes < 12 || stride_bytes % 4) return NDT_ERR_INVALID_ARG;
+  if (!h || !desc || (!xyz && n) || !layout_valid(stride_bytes, -1)) return NDT_ERR_INVALID_ARG;
   int rc = bind_device(h);
   if (rc) return rc;
   ScanContextBufs& sc = h->sc;

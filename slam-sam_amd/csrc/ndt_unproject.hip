@@ -351,8 +351,12 @@ int ndt_unproject(ndt_handle* h, const uint32_t* range_mm, const uint8_t* reflec
                         has_i ? o + 3 * n : nullptr, t_out ? o + 4 * n : nullptr, index_out ? b.index.p : nullptr, n, n_out);
   if (rc) return rc;
   // (the staging is free again: the upload out of it has been awaited)
-  return download_strided(h, o, n, o + 4 * n, b.index.p, *n_out, cap, reinterpret_cast<float*>(b.stage.h), out, stride_bytes,
-                          intensity_offset_bytes, t_out, index_out);
+  SideColumns side;
+  side.d_f32 = o + 4 * n;
+  side.f32_out = t_out;
+  side.d_i32 = b.index.p;
+  side.i32_out = index_out;
+  return download_strided(h, o, n, *n_out, cap, out, stride_bytes, intensity_offset_bytes, reinterpret_cast<float*>(b.stage.h), side);
 }
 
 int ndt_keyframe_put_from_ranges(ndt_handle* h, int64_t id, const uint32_t* range_mm, const uint8_t* reflectivity, const float* col_t,

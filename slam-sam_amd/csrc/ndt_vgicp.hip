@@ -143,12 +143,6 @@ k_vgicp_eval(const double* __restrict__ sgauss, int n, GridGeom g, const int* __
 
 unsigned blocks_of(size_t n) { return (unsigned)((n + VGICP_THREADS - 1) / VGICP_THREADS); }
 
-bool finite6(const double* p) {
-  for (int i = 0; i < 6; ++i)
-    if (!std::isfinite(p[i])) return false;
-  return true;
-}
-
 // the table of the published target, fresh; the target's covariances are ready
 int vgicp_derive(ndt_handle* h) {
   VgicpBufs& v = h->vgicp;
@@ -281,7 +275,7 @@ int ndt_vgicp_get_info(ndt_handle* h, ndt_vgicp_info* out) {
 int ndt_eval_derivatives_vgicp(ndt_handle* h, const double* poses6, int K, int compute_hessian, double* out) {
   if (!h || !poses6 || !out || K <= 0) return NDT_ERR_INVALID_ARG;
   for (int k = 0; k < K; ++k)
-    if (!finite6(poses6 + 6 * (size_t)k)) return NDT_ERR_INVALID_ARG;
+    if (!all_finite(poses6 + 6 * (size_t)k, 6)) return NDT_ERR_INVALID_ARG;
   if (int rc = bind_device(h)) return rc;
   if (int rc = vgicp_ready(h)) return rc;
   if (int rc = vgicp_eval_raw(h, poses6, K, compute_hessian != 0, out)) return rc;
@@ -302,7 +296,7 @@ int ndt_align_vgicp(ndt_handle* h, const float guess[16], ndt_result* out, ndt_v
   if (int rc = vgicp_ready(h)) return rc;
   double p[6];
   matrix_to_pose(guess, p);
-  if (!finite6(p)) return fail(h, NDT_ERR_INVALID_ARG, "VGICP: the guess is not a finite pose");
+  if (!all_finite(p, 6)) return fail(h, NDT_ERR_INVALID_ARG, "VGICP: the guess is not a finite pose");
   double last_pairs = 0.0, last_with = 0.0;
   const int rc = lane_align(h, (int64_t)h->n_src, guess, [&](const double* q, bool need_h, double* words) {
     const int r = vgicp_eval_raw(h, q, 1, need_h, words);

@@ -13,6 +13,9 @@
 //     that is overwritten and freed THE MOMENT the call returns -- the staging copy must already be complete.
 //   * the radix sort's plan rule (ndt_sort_plan.h): key bits of a range, and the split of 1 .. 32 bits into digits with
 //     derived and with planned pass counts, against the rule's properties and a recorded table.
+//   * the host-cloud boundary (ndt_host_cloud.h): the layout rule over a grid of strides and offsets, the gathers and the
+//     scatter against scalar restatements on exactly-sized heap blocks (no byte behind the last used field is read or
+//     written, no byte between the fields is written), all_finite at every position of a pose.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <unistd.h>
@@ -31,6 +34,7 @@
 #include <vector>
 
 #include "../../slam-sam_amd/csrc/ndt_comm.h"
+#include "../../slam-sam_amd/csrc/ndt_host_cloud.h"
 #include "../../slam-sam_amd/csrc/ndt_newton.h"
 #include "../../slam-sam_amd/csrc/ndt_repack_pool.h"
 #include "../../slam-sam_amd/csrc/ndt_se3.h"
@@ -415,6 +419,104 @@ int main() {
     CHECK(ndt::sort_key_bits(0) == 0 && ndt::sort_key_bits(-1) == 0);
     CHECK(std::max(1, ndt::sort_key_bits(0)) == 1);
     CHECK(ndt::sort_key_bits((1ll << 31) - 1) == 31 && ndt::sort_key_bits(1ll << 31) == 32 && ndt::sort_key_bits(1ll << 61) == 62);
+  }
+
+  // ---- the host-cloud boundary (ndt_host_cloud.h) ----------------------------------------------------
+  {
+    namespace hc = ndt::engine;
+    // the layout rule against the five-clause expression the host forms spelled out before it had one home
+    for (size_t stride_bytes = 0; stride_bytes <= 40; ++stride_bytes)
+      for (long intensity_offset_bytes = -1; intensity_offset_bytes <= 40; ++intensity_offset_bytes) {
+        const bool refused = stride_bytes < 12 || stride_bytes % 4 ||
+                             (intensity_offset_bytes >= 0 && (intensity_offset_bytes % 4 || (size_t)intensity_offset_bytes + 4 > stride_bytes ||
+                                                              intensity_offset_bytes < 12));
+        CHECK(hc::layout_valid(stride_bytes, intensity_offset_bytes) == !refused);
+      }
+    CHECK(hc::layout_valid(16, -4));   // (any negative offset means "no intensity")
+    std::uniform_real_distribution<float> U(-100.f, 100.f);
+    const unsigned char SENTINEL = 0xA5;
+    for (size_t stride : {(size_t)12, (size_t)16, (size_t)32})
+      for (long off : {-1L, 12L, 28L}) {
+        if (!hc::layout_valid(stride, off)) continue;
+        for (size_t n : {(size_t)0, (size_t)1, (size_t)2, (size_t)65}) {
+          const bool has_i = off >= 0;
+          // exactly the bytes a cloud of n points owns: up to the last used field of the last point
+          const size_t last_used = has_i ? (size_t)off + 4 : 12, bytes = n ? (n - 1) * stride + last_used : 0;
+          const size_t pad = 3;   // the columns lie col_stride = n + pad floats apart; the block ends with the last used element
+          const size_t ncols = has_i ? 4 : 3, col_stride = n + pad, col_floats = n ? (ncols - 1) * col_stride + n : 0;
+          // gathers: the input block is exactly `bytes` long
+          char* in = static_cast<char*>(std::malloc(bytes ? bytes : 1));
+          std::vector<float> wx(n), wy(n), wz(n), wi(n);
+          std::memset(in, 0x3c, bytes);
+          for (size_t i = 0; i < n; ++i) {
+            wx[i] = U(rng); wy[i] = U(rng); wz[i] = U(rng); wi[i] = U(rng);
+            std::memcpy(in + i * stride, &wx[i], 4);
+            std::memcpy(in + i * stride + 4, &wy[i], 4);
+            std::memcpy(in + i * stride + 8, &wz[i], 4);
+            if (has_i) std::memcpy(in + i * stride + off, &wi[i], 4);
+          }
+          float* g = static_cast<float*>(std::malloc(4 * n * sizeof(float) + 1));   // [x | y | z | i], exactly n each
+          hc::gather_xyz(n ? in : nullptr, n, stride, g, g + n, g + 2 * n);
+          if (has_i) hc::gather_column(in, n, stride, (size_t)off, g + 3 * n);
+          bool same = true;
+          for (size_t i = 0; i < n; ++i)
+            same = same && g[i] == wx[i] && g[n + i] == wy[i] && g[2 * n + i] == wz[i] && (!has_i || g[3 * n + i] == wi[i]);
+          CHECK(same);
+          for (size_t c = 0; c < 3; ++c) {   // one coordinate as a column
+            hc::gather_column(in, n, stride, 4 * c, g);
+            const std::vector<float>& w = c == 0 ? wx : c == 1 ? wy : wz;
+            CHECK(n == 0 || std::memcmp(g, w.data(), n * sizeof(float)) == 0);
+          }
+          std::free(g);
+          std::free(in);
+          // scatter: the columns end with the last used element, the output block is exactly `bytes` long
+          float* cols = static_cast<float*>(std::malloc(col_floats * sizeof(float) + 1));
+          for (size_t i = 0; i < col_floats; ++i) cols[i] = -7.0f;
+          for (size_t i = 0; i < n; ++i) {
+            cols[i] = wx[i]; cols[col_stride + i] = wy[i]; cols[2 * col_stride + i] = wz[i];
+            if (has_i) cols[3 * col_stride + i] = wi[i];
+          }
+          unsigned char* out = static_cast<unsigned char*>(std::malloc(bytes ? bytes : 1));
+          std::memset(out, SENTINEL, bytes);
+          hc::scatter_cloud(cols, col_stride, n, out, stride, off);
+          std::vector<unsigned char> want(bytes, SENTINEL);   // the scalar restatement
+          for (size_t i = 0; i < n; ++i) {
+            std::memcpy(&want[i * stride], &wx[i], 4);
+            std::memcpy(&want[i * stride + 4], &wy[i], 4);
+            std::memcpy(&want[i * stride + 8], &wz[i], 4);
+            if (has_i) std::memcpy(&want[i * stride + (size_t)off], &wi[i], 4);
+          }
+          CHECK(bytes == 0 || std::memcmp(out, want.data(), bytes) == 0);
+          // the first m < n points only: the rest of the block keeps the sentinel
+          if (n > 1) {
+            std::memset(out, SENTINEL, bytes);
+            hc::scatter_cloud(cols, col_stride, n - 1, out, stride, off);
+            const size_t written = (n - 2) * stride + last_used;
+            bool ok = std::memcmp(out, want.data(), written) == 0;
+            for (size_t b = written; b < bytes; ++b) ok = ok && out[b] == SENTINEL;
+            CHECK(ok);
+          }
+          std::free(out);
+          std::free(cols);
+        }
+      }
+    // all_finite: one NaN / +Inf / -Inf at every position of a 6- and a 16-word pose, in a block that ends with the pose
+    for (size_t words : {(size_t)6, (size_t)16}) {
+      double* pose = static_cast<double*>(std::malloc(words * sizeof(double)));
+      float* posef = static_cast<float*>(std::malloc(words * sizeof(float)));
+      for (size_t i = 0; i < words; ++i) { pose[i] = N(rng) * 1e3; posef[i] = (float)pose[i]; }
+      CHECK(hc::all_finite(pose, words) && hc::all_finite(posef, words) && hc::all_finite(pose, 0));
+      for (size_t at = 0; at < words; ++at)
+        for (double bad : {(double)NAN, (double)INFINITY, -(double)INFINITY}) {
+          const double keep = pose[at];
+          pose[at] = bad; posef[at] = (float)bad;
+          CHECK(!hc::all_finite(pose, words) && !hc::all_finite(posef, words));
+          CHECK(hc::all_finite(pose, at) && hc::all_finite(pose + at + 1, words - at - 1));   // (only that word)
+          pose[at] = keep; posef[at] = (float)keep;
+        }
+      std::free(pose);
+      std::free(posef);
+    }
   }
 
   // ---- SE(3) ---------------------------------------------------------------------------------------
